@@ -180,6 +180,64 @@ def self_check(batch, stream, ref):
             "true_peak_rel_err": tp_rel, "decimation_bit_exact": wave_ok, "ok": bool(ok)}
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+DUMP_STREAMS = 64
+# bytes per kind; a kind that would exceed its share keeps a seeded sample of its rows (windows, decimation bins, sub-blocks, streams)
+DUMP_BUDGET = {"spectrum": 32 * 10**6, "waveform": 12 * 10**6, "subblocks": 8 * 10**6, "results": 4 * 10**6}
+
+
+def dump_outputs(b, first, corpus, path):
+    """--dump-outputs: what the last timed step left in the batch, as a caller of the path receives it, written as float32 /
+    float64 .npy files under `path` (this rank's shard).  The sample is drawn with a fixed seed from the shapes alone, so the
+    same arguments select the same rows in every run and every build.  Files (the *_index / streams arrays hold positions):
+      streams            [S]                 global ids of the sampled streams (at most 64)
+      spectrum           [S, w, 2, bins] f32 dB rows of the sampled windows (Batch.fft), spectrum_windows [w]
+      waveform           [S, p, 2] f32       (min, max) of the sampled decimation bins (Batch.waveform), waveform_bins [p]
+      subblocks          [S, q, channels] f64 K-weighted 100 ms sub-block energies (Batch.subblocks), subblocks_index [q]
+      results            [r, 8] f64          per stream: integrated LUFS, LRA, true peak L/R, sample peak L/R, gating blocks,
+                                             short-term blocks (Batch.results), results_streams [r] global ids
+      histograms         [2, 1000] f64       the corpus histograms (block, short-term) the gate read
+      corpus_gate        [2] f64             corpus integrated LUFS and LRA"""
+    rng = np.random.default_rng(0x5EED)
+    lay, count = b.layout, int(b.cfg.n_streams)
+
+    def pick(n, k):                                    # sorted seeded sample of k of range(n), or all of it
+        return np.arange(n) if k >= n else np.sort(rng.choice(n, k, replace=False))
+
+    def rows(kind, row_bytes):                         # rows that fit the kind's budget, each with its f64 index entry
+        return max(1, DUMP_BUDGET[kind] // (row_bytes + 8))
+
+    streams = pick(count, DUMP_STREAMS)
+    S = streams.size
+    win = pick(lay.n_windows, rows("spectrum", S * lay.fft_channels * lay.n_bins * 4))
+    wbin = pick(lay.n_wave_points // 2, rows("waveform", S * 2 * 4))
+    sub = pick(lay.n_subblocks, rows("subblocks", S * int(b.cfg.channels) * 8))
+    rstreams = pick(count, rows("results", 8 * 8))
+    res = b.results()
+    out = {
+        "streams": (first + streams).astype(np.float64),
+        "spectrum": np.stack([b.fft(int(s))[win] for s in streams]).astype(np.float32),
+        "spectrum_windows": win.astype(np.float64),
+        "waveform": np.stack([b.waveform(int(s))[wbin] for s in streams]).astype(np.float32),
+        "waveform_bins": wbin.astype(np.float64),
+        "subblocks": np.stack([b.subblocks(int(s))[sub] for s in streams]).astype(np.float64),
+        "subblocks_index": sub.astype(np.float64),
+        "results": np.array([[res[s].integrated_lufs, res[s].loudness_range, res[s].true_peak[0], res[s].true_peak[1],
+                              res[s].sample_peak[0], res[s].sample_peak[1], res[s].n_gating_blocks, res[s].n_st_blocks]
+                             for s in rstreams], np.float64).reshape(-1, 8),
+        "results_streams": (first + rstreams).astype(np.float64),
+        "histograms": np.stack(b.histograms()).astype(np.float64),
+        "corpus_gate": np.array(corpus, np.float64),
+    }
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte cap")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return len(out), total
+
+
 def reference_tick_workload(ssa, L, rate=48000, secs=12, cpu_ticks=60):
     """The reference's OWN workload, one file and one tick at a time, beside the CPU oracle driven the same way:
       tick  = analyze_audio_file_samples (tui.rs:1482-1552): get_fft(mid) + get_fft(side) on the last 16384 frames, add_samples of the
@@ -368,7 +426,12 @@ def main():
                          "(the JSON says which transport ran).  Without this flag a failed RCCL setup ends the run non-zero.")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (and its parity check)")
     ap.add_argument("--no-extra", action="store_true", help="skip the config 2 / config 5 lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed seeded sample, at most 64 MB) as "
+                         "DIR/<name>.npy, float32 / float64 (rank 0's shard); see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line (the JSON): native libraries print to file descriptor 1 on their own (RCCL's
     # version banner at communicator creation), so everything but the final line is sent to stderr
@@ -494,6 +557,10 @@ def main():
     host_i, host_lra = corpus_gate(hist[0])                     # the same gate on the host copy of the histograms
     if abs(corpus_i - host_i) > 1e-9 or abs(corpus_lra - host_lra) > 1e-9:
         raise SystemExit(f"device corpus gate {corpus_i, corpus_lra} != host {host_i, host_lra}")
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the batch: the sustained and f16x3 passes below overwrite its results
+        n_files, n_bytes = dump_outputs(b, first, (corpus_i, corpus_lra), args.dump_outputs)
+        print(f"[bench] wrote {n_files} arrays ({n_bytes / 1e6:.1f} MB) to {args.dump_outputs}", file=sys.stderr, flush=True)
 
     # The reference's true-peak arithmetic is an f32 FIR (ebur128's interpolator: f32 taps, f32 accumulation; analyzer.rs:139-141,
     # 159-164).  The timed step above runs it at that width (SS_TP_ARITH_F32, the library's default: an f32 fma chain per output —
