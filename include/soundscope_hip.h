@@ -216,7 +216,12 @@ enum {
      * instead of 6.49 GB of rows), the second pass over the rows gone, and 10.6x less to download over PCIe.  The kernel itself is
      * no faster than the full-row one (3.0-3.2 ms against 2.9): the spectrum kernel is bound by VALU issue, not by its stores, and
      * folding 1705 bins into columns costs about as many instructions as storing them saves waiting. */
-    SS_BATCH_FFT_COLUMNS = 16u
+    SS_BATCH_FFT_COLUMNS = 16u,
+    /* with SS_BATCH_LUFS (SS_ERR_INVALID_ARG otherwise): the momentary and short-term loudness series of every stream and their
+     * maxima, formed on the device behind the gating pass (ss_batch_download_loudness_series, ss_batch_loudness_extremes below).
+     * Allocates [n_streams][n_subblocks][2] f64 plus one ss_loudness_extremes per stream; a pass with the flag off launches
+     * nothing more. */
+    SS_BATCH_LOUDNESS_SERIES = 32u
 };
 
 typedef struct ss_batch_config {
@@ -390,6 +395,26 @@ int ss_batch_bin_tables(const ss_batch *b, double *chart_x, double *freq, double
 int ss_batch_download_waveform(ss_batch *b, uint32_t stream, float *out, size_t cap_floats);
 /* K-weighted energy of the 100 ms sub-blocks of one stream: [n_subblocks][channels] f64 */
 int ss_batch_download_subblocks(ss_batch *b, uint32_t stream, double *out, size_t cap_doubles);
+/* Loudness over time (SS_BATCH_LOUDNESS_SERIES batches; SS_ERR_INVALID_MODE otherwise).  Entry j of a stream's series is what
+ * EbuR128::loudness_momentary() / loudness_shortterm() returns after the stream's first (j + 1) * s100 frames
+ * (s100 = (rate + 5) / 10):  10 log10(E) - 0.691,  E = sum_c w_c (sum of the sub-block energies j - N + 1 ... j) / (N s100),
+ * N = 4 (momentary) or 30 (short-term), w_c the meter's channel weights (weight-0 channels are never read).  Sub-blocks in front
+ * of the stream count as zero (the crate's ring starts zeroed): entries j < N - 1 are its partial readings; E = 0 reads -inf.
+ * A non-finite sample poisons the meter like the crate's: every window that ends behind the first sub-block holding one reads
+ * NaN, the window that ends with it holds what the recurrence produced.  At rates whose thirty sub-blocks exceed the crate's
+ * 3 s ring (loudness_shortterm fails there) the short-term entries are NaN.
+ * ss_batch_download_loudness_series writes the stream's own n_subblocks entries (ss_batch_stream_shape for ragged batches) into
+ * either array (either may be NULL); cap < n_subblocks: SS_ERR_CAPACITY. */
+int ss_batch_download_loudness_series(ss_batch *b, uint32_t stream, double *momentary, double *shortterm, size_t cap);
+/* the maxima of the series over the FULL windows only (j >= 3 momentary, j >= 29 short-term): NaN entries are skipped, an
+ * infinity counts as a value, ties go to the lowest j; no such entry: -inf at 0xFFFFFFFF.  Waits for the batch's stream; cap_streams < n_streams: SS_ERR_CAPACITY. */
+typedef struct ss_loudness_extremes {
+    double max_momentary;       /* LUFS; -inf if the stream has no full 400 ms window                        */
+    double max_shortterm;       /* LUFS; -inf if the stream has no full 3 s window                           */
+    uint32_t max_momentary_at;  /* sub-block index j of the window that attains it first; 0xFFFFFFFF if none */
+    uint32_t max_shortterm_at;
+} ss_loudness_extremes;         /* 24 bytes */
+int ss_batch_loudness_extremes(ss_batch *b, ss_loudness_extremes *out, uint32_t cap_streams);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

@@ -43,6 +43,7 @@ SYMBOLS = [
     "ss_batch_corpus_gate_enqueue", "ss_batch_corpus_gate_read", "ss_batch_checksums", "ss_inspect_filter_state", "ss_batch_set_true_peak_arith", "ss_batch_get_true_peak_arith", "ss_batch_set_time_domain_mode", "ss_batch_set_columns_gain",
     "ss_release_caches", "ss_batch_geometry_get_sized",
     "ss_inspect_kweight", "ss_inspect_true_peak", "ss_inspect_hann", "ss_inspect_bins", "ss_inspect_histogram",
+    "ss_batch_download_loudness_series", "ss_batch_loudness_extremes",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -53,6 +54,7 @@ SS_ERR_CAPACITY, SS_ERR_UNSUPPORTED, SS_ERR_INVALID_ARG, SS_ERR_DEVICE = 20, 21,
 
 SS_BATCH_FFT, SS_BATCH_LUFS, SS_BATCH_TRUE_PEAK, SS_BATCH_WAVEFORM, SS_BATCH_ALL = 1, 2, 4, 8, 15
 SS_BATCH_FFT_COLUMNS = 16
+SS_BATCH_LOUDNESS_SERIES = 32
 SS_PCM_U8, SS_PCM_S16, SS_PCM_S24, SS_PCM_S32, SS_PCM_F32, SS_PCM_F64 = 1, 2, 3, 4, 5, 6
 SS_GAIN_FIXED, SS_GAIN_REFERENCE = 0, 1
 SS_COMM_RCCL, SS_COMM_HOST_TCP = 0, 1
@@ -97,6 +99,11 @@ class BatchGeometry(C.Structure):
                 ("td_segment_subblocks", C.c_uint32), ("td_warm_subblocks", C.c_uint32),
                 ("td_true_peak_factor", C.c_uint32), ("waveform_fused", C.c_uint32), ("overlap", C.c_uint32),
                 ("td_split", C.c_uint32), ("td_fixup_subblocks", C.c_uint32)]
+
+
+class LoudnessExtremes(C.Structure):
+    _fields_ = [("max_momentary", C.c_double), ("max_shortterm", C.c_double),
+                ("max_momentary_at", C.c_uint32), ("max_shortterm_at", C.c_uint32)]
 
 
 class BatchLayout(C.Structure):
@@ -226,6 +233,8 @@ def _bind(lib):
         "ss_inspect_hann": (C.c_int, [C.c_uint32, f32p]),
         "ss_inspect_bins": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_inspect_histogram": (C.c_int, [f64p, f64p]),
+        "ss_batch_download_loudness_series": (C.c_int, [vp, C.c_uint32, f64p, f64p, C.c_size_t]),
+        "ss_batch_loudness_extremes": (C.c_int, [vp, C.POINTER(LoudnessExtremes), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -207,6 +207,24 @@ class Batch:
         _check(L.lib().ss_batch_download_subblocks(self._h, stream, out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
         return out
 
+    def loudness_series(self, stream):
+        """(momentary, shortterm): the stream's loudness after every 100 ms sub-block, LUFS, two f64 arrays of its own
+        n_subblocks entries — entry j is what EbuR128::loudness_momentary() / loudness_shortterm() returns after the first
+        (j + 1) sub-blocks (batches made with L.SS_BATCH_LOUDNESS_SERIES)."""
+        n = int(self.stream_shape(stream).n_subblocks)
+        m, s = np.empty(n, np.float64), np.empty(n, np.float64)
+        dp = C.POINTER(C.c_double)
+        _check(L.lib().ss_batch_download_loudness_series(self._h, stream, m.ctypes.data_as(dp), s.ctypes.data_as(dp), n))
+        return m, s
+
+    def loudness_extremes(self):
+        """Per stream: L.LoudnessExtremes (max_momentary, max_shortterm, max_momentary_at, max_shortterm_at) over the full
+        windows of its series; -inf at 0xFFFFFFFF where there is none."""
+        n = int(self.cfg.n_streams)
+        arr = (L.LoudnessExtremes * n)()
+        _check(L.lib().ss_batch_loudness_extremes(self._h, arr, n))
+        return list(arr)
+
     def histograms(self):
         out = np.empty(2000, np.uint64)
         _check(L.lib().ss_batch_histograms(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))

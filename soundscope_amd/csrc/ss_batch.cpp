@@ -39,6 +39,9 @@ struct ss_batch {
     DevBuf<uint32_t> counts;
     DevBuf<unsigned char> raw;      // device staging of raw PCM for the asynchronous ingest
     DevBuf<uint64_t> checks;        // ss_batch_checksums: [stream][3]
+    // SS_BATCH_LOUDNESS_SERIES: [stream][n_subblocks][2] (momentary, short-term) LUFS and the per-stream maxima
+    DevBuf<double> series;
+    DevBuf<ssk::LoudnessExtremes> extremes;
     // ragged batches (ss_batch_set_lengths): per-stream frames / windows / sub-blocks / decimation bins
     bool ragged = false;
     std::vector<uint64_t> frames_h, wave_samples_h;
@@ -206,6 +209,7 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
     if ((cfg->flags & SS_BATCH_ALL) == 0) return SS_ERR_INVALID_ARG;
     const bool columns_only = (cfg->flags & SS_BATCH_FFT_COLUMNS) != 0;
     if (columns_only && (!(cfg->flags & SS_BATCH_FFT) || cfg->spectrum_columns == 0 || cfg->spectrum_columns > 512)) return SS_ERR_INVALID_ARG;
+    if ((cfg->flags & SS_BATCH_LOUDNESS_SERIES) && !(cfg->flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_ARG;      // the series reads the gating pass
     // destroyed (streams and events included) on every early return
     std::unique_ptr<ss_batch, decltype(&ss_batch_destroy)> b(new ss_batch(), &ss_batch_destroy);
     b->device = current_device();
@@ -341,6 +345,10 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
         std::vector<double> w(C);
         sst::channel_weights(C, w.data());
         HIPCHK(b->weights.upload(w));
+        if (cfg->flags & SS_BATCH_LOUDNESS_SERIES) {
+            HIPCHK(b->series.alloc((size_t)cfg->n_streams * (L.n_subblocks ? L.n_subblocks : 1) * 2));
+            HIPCHK(b->extremes.alloc(cfg->n_streams));
+        }
     }
     if (cfg->flags & SS_BATCH_WAVEFORM) {
         const double win = cfg->waveform_window > 0.0 ? cfg->waveform_window : (double)F / (double)cfg->sample_rate;
@@ -724,6 +732,9 @@ int ss_batch_run(ss_batch *b)
         f.out_integrated = b->integrated.p; f.out_lra = b->lra.p; f.out_counts = b->counts.p;
         f.state = b->state.p;
         HIPCHK(ssk::launch_finalize(f, b->stream));
+        // the series behind the gating pass, on the same stream: behind the hand-over's fix-up launch like it (exact segment
+        // heads), inside the FINALIZE timing slot
+        if (b->series.p) HIPCHK(ssk::launch_loudness_series(f, b->series.p, L.n_subblocks ? L.n_subblocks : 1, b->extremes.p, b->stream));
     }
     HIPCHK(rec(2 * SS_KERNEL_FINALIZE + 1));
 
@@ -993,6 +1004,40 @@ int ss_batch_download_subblocks(ss_batch *b, uint32_t stream, double *out, size_
     if (cap < per) return SS_ERR_CAPACITY;
     if (!per) return SS_OK;
     HIPCHK(hipMemcpyAsync(out, b->sub.p + (size_t)stream * per, per * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return SS_OK;
+}
+
+static_assert(sizeof(ss_loudness_extremes) == 24 && sizeof(ssk::LoudnessExtremes) == sizeof(ss_loudness_extremes) &&
+              offsetof(ssk::LoudnessExtremes, at_m) == offsetof(ss_loudness_extremes, max_momentary_at), "extremes layout");
+
+int ss_batch_download_loudness_series(ss_batch *b, uint32_t stream, double *momentary, double *shortterm, size_t cap)
+{
+    SS_ON_DEVICE(b);
+    if (!b || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+    if (!b->series.p) return SS_ERR_INVALID_MODE;                // the batch was made without SS_BATCH_LOUDNESS_SERIES
+    const size_t n = b->ragged ? b->sub_h[stream] : b->lay.n_subblocks;
+    if (cap < n) return SS_ERR_CAPACITY;
+    if (!n || (!momentary && !shortterm)) return SS_OK;
+    const size_t stride = b->lay.n_subblocks ? b->lay.n_subblocks : 1;
+    std::vector<double> ms(2 * n);
+    HIPCHK(hipMemcpyAsync(ms.data(), b->series.p + (size_t)stream * stride * 2, 2 * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (size_t j = 0; j < n; j++) {
+        if (momentary) momentary[j] = ms[2 * j];
+        if (shortterm) shortterm[j] = ms[2 * j + 1];
+    }
+    return SS_OK;
+}
+
+int ss_batch_loudness_extremes(ss_batch *b, ss_loudness_extremes *out, uint32_t cap_streams)
+{
+    SS_ON_DEVICE(b);
+    if (!b || !out) return SS_ERR_INVALID_ARG;
+    if (!b->extremes.p) return SS_ERR_INVALID_MODE;
+    const uint32_t n = b->cfg.n_streams;
+    if (cap_streams < n) return SS_ERR_CAPACITY;
+    HIPCHK(hipMemcpyAsync(out, b->extremes.p, n * sizeof(ss_loudness_extremes), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return SS_OK;
 }

@@ -212,6 +212,12 @@ struct FinalizeParams {
     const float *readings_peaks_src; float *readings_peaks_dst; uint32_t *readings_flag; uint32_t readings_seq;
 };
 hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s);
+// Momentary / short-term loudness series of every stream of a batch and their maxima (SS_BATCH_LOUDNESS_SERIES), behind
+// launch_finalize on the same stream: p as given there (batches: slot == sub-block index); series[stream][series_stride][2]
+// (momentary, short-term) LUFS, extremes[stream] laid out as ss_loudness_extremes.
+struct LoudnessExtremes { double max_m, max_s; uint32_t at_m, at_s; };
+hipError_t launch_loudness_series(const FinalizeParams &p, double *series, uint64_t series_stride, LoudnessExtremes *extremes,
+                                  hipStream_t s);
 // gate + LRA on explicit histograms (corpus gate after the all-reduce; handle getters)
 // `peaks` (optional): a handle's readings in one launch — 2 * kMaxChannels floats copied from peaks_src to peaks_dst beside the
 // evaluation, then `seq` stored into *flag (host-visible memory: whoever sees the flag sees out2 and the peaks)

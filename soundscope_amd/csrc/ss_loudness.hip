@@ -369,6 +369,108 @@ hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s)
     return hipGetLastError();
 }
 
+// ============================================================================
+//  Loudness series (SS_BATCH_LOUDNESS_SERIES): EbuR128::loudness_momentary / loudness_shortterm after every sub-block, and maxima
+// ============================================================================
+// The crate's partial reading (j < N - 1): its ring starts zeroed, so the window holds sub-blocks 0 ... j only.  The same additions
+// as window_energy with the missing leading terms taken as zero (0 + 0 = 0: the first real term lands on an exact zero).
+template <int N>
+__device__ __forceinline__ double window_energy_head(const double *__restrict__ P, uint32_t j, uint32_t C,
+                                                     const double *__restrict__ weights)
+{
+    double sum = 0.0;
+    for (uint32_t c = 0; c < C; c++) {
+        const double w = weights[c];
+        if (w == 0.0) continue;
+        double cs = 0.0;
+        for (uint32_t q = 0; q <= j; q++) cs += P[(size_t)q * C + c];
+        sum += w * cs;
+    }
+    return sum;
+}
+
+__device__ __forceinline__ double energy_to_lufs(double e) { return e <= 0.0 ? -INFINITY : 10.0 * log10(e) - 0.691; }
+
+// (value, j) maximum: a NaN never wins, ties go to the lower j; (-inf, 0xFFFFFFFF) is "none yet" and loses to any value
+__device__ __forceinline__ void max_at(double &v, uint32_t &at, double v2, uint32_t at2)
+{
+    if (v2 > v || (v2 == v && at2 < at)) { v = v2; at = at2; }
+}
+
+// One workgroup per stream, a thread per sub-block j (long streams loop).  Every full window's energy is formed by the very
+// window_energy form and additions k_finalize used for its histograms (the momentary energy at j >= 3 is that gating block's,
+// the short-term energy at j = 29 + 10 m that short-term block's), and the first-bad-sub-block rule is k_finalize's.  The
+// maxima are a wave / LDS reduction in the same launch.  Batches only: slot == sub-block index.
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? 256 : 1024) void k_loudness_series(FinalizeParams p, double *series, uint64_t series_stride,
+                                                                         LoudnessExtremes *extremes)
+{
+    __shared__ uint32_t bad_from_s;
+    __shared__ double red_v[2][16];
+    __shared__ uint32_t red_at[2][16];
+    const uint32_t stream = blockIdx.x;
+    const int tid = threadIdx.x, nthr = (int)blockDim.x;
+    if (tid < 64) {
+        const uint32_t bf = first_bad_subblock(p.state ? p.state + stream : nullptr, p.channels, p.weights, (uint32_t)tid);
+        if (tid == 0) bad_from_s = bf;
+    }
+    const uint32_t n = (uint32_t)(p.sub_end_of ? p.sub_end_of[stream] : p.sub_end);
+    __syncthreads();
+    const uint32_t C = p.channels, cap = p.sub_cap;
+    const double S = (double)p.k->s100;
+    const bool st_on = !p.k->st_off;
+    const double *P = p.subblocks + (size_t)stream * p.sub_stride;
+    double2 *out = reinterpret_cast<double2 *>(series) + (size_t)stream * series_stride;
+    const uint32_t bad_from = bad_from_s;
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    double bm = -INFINITY, bs = -INFINITY;
+    uint32_t am = kNone, as = kNone;
+    for (uint32_t j = (uint32_t)tid; j < n; j += (uint32_t)nthr) {
+        double em, es = __builtin_nan("");
+        if (j >= 3) em = SMALL ? window_energy_eager<4, true>(P, j, cap, C, p.weights) : window_energy<4, true>(P, j, cap, C, p.weights);
+        else em = window_energy_head<4>(P, j, C, p.weights);
+        em /= 4.0 * S;
+        if (st_on) {
+            if (j >= 29) es = SMALL ? window_energy_eager<30, true>(P, j, cap, C, p.weights) : window_energy<30, true>(P, j, cap, C, p.weights);
+            else es = window_energy_head<30>(P, j, C, p.weights);
+            es /= 30.0 * S;
+        }
+        if (j > bad_from) { em = __builtin_nan(""); es = __builtin_nan(""); }
+        const double lm = energy_to_lufs(em), ls = energy_to_lufs(es);
+        out[j] = make_double2(lm, ls);
+        if (j >= 3) max_at(bm, am, lm, j);
+        if (j >= 29) max_at(bs, as, ls, j);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        max_at(bm, am, __shfl_xor(bm, o, 64), (uint32_t)__shfl_xor((int)am, o, 64));
+        max_at(bs, as, __shfl_xor(bs, o, 64), (uint32_t)__shfl_xor((int)as, o, 64));
+    }
+    const int wave = tid >> 6;
+    if ((tid & 63) == 0) { red_v[0][wave] = bm; red_at[0][wave] = am; red_v[1][wave] = bs; red_at[1][wave] = as; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < (nthr >> 6); w++) { max_at(bm, am, red_v[0][w], red_at[0][w]); max_at(bs, as, red_v[1][w], red_at[1][w]); }
+        extremes[stream] = LoudnessExtremes{bm, bs, am, as};
+    }
+}
+
+hipError_t launch_loudness_series(const FinalizeParams &p, double *series, uint64_t series_stride, LoudnessExtremes *extremes,
+                                  hipStream_t s)
+{
+    if (p.n_streams == 0) return hipSuccess;
+    if (p.sub_begin != 0 || p.sub_end > p.sub_cap || p.sub_end > series_stride || p.sub_end > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    // a thread per sub-block, whole waves (a 10 s stream: two waves, not four mostly idle ones); the SMALL form where k_finalize takes it
+    const uint64_t nsub = p.sub_end;
+    const bool small = p.n_streams <= SS_FINALIZE_SMALL_MAX && nsub <= 2048;
+    const uint64_t most = small ? 256u : 1024u;
+    uint64_t threads = (nsub + 63u) & ~63ull;
+    threads = threads < 64u ? 64u : (threads > most ? most : threads);
+    if (small) hipLaunchKernelGGL(k_loudness_series<true>, dim3(p.n_streams), dim3((uint32_t)threads), 0, s, p, series, series_stride, extremes);
+    else hipLaunchKernelGGL(k_loudness_series<false>, dim3(p.n_streams), dim3((uint32_t)threads), 0, s, p, series, series_stride, extremes);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(64) void k_hist_eval(const unsigned long long *hist2000, const double *en,
                                                   const double *bd, double *out2, ReadingsExtra x)
 {
