@@ -21,10 +21,12 @@ struct ss_batch {
     uint64_t first_start = 0;
     uint32_t wave_window = 0;
     uint32_t windows_per_block = 16;
-    uint32_t td_nseg = 1, td_seg_sub = 0;
+    struct {                        // how the time-domain launch cuts the streams (choose_td_geometry): TdParams' fields of these names
+        uint32_t nseg = 1, seg_sub = 0, warm_sub = 0, fix_sub = 0;
+        uint32_t split_batch = ssk::kTdSplitNone;       // (ragged lengths: one wave per stream / segment)
+        bool fixup = false;                             // segments > 0 hand over exactly: the fix-up launch re-runs their first fix_sub
+    } td_plan;
     uint32_t td_nsub_hint = 0;      // ragged batches: sub-blocks of the LONGEST stream (the geometry follows the lengths, not the slot size)
-    bool td_split = false;          // whole-stream workgroups (choose_td_geometry)
-    bool td_split_segments = false; // the same per time segment, eight waves each (a handful of streams)
     int td_mode = 0;                // ss_batch_set_time_domain_mode
     bool wave_fused = false;     // decimation runs inside the time-domain kernel
     uint32_t wave_halo = 0;
@@ -114,12 +116,21 @@ int batch_collect_timing(ss_batch *b)
     return SS_OK;
 }
 
+// N = 16384 with hop 1024 and at least eight windows: k_fft16k_run (runs of windows per workgroup), otherwise k_fft16k
+static bool fft16k_runs(const ss_batch *b)
+{
+#ifdef SS_TUNING
+    if (std::getenv("SS_FFT16K_SINGLE")) return false;
+#endif
+    return b->cfg.fft_n == 16384 && !b->fft_fast && !b->fft_pairw && b->cfg.hop_frames == 1024 && b->lay.n_windows >= 8;
+}
+
 }  // namespace
 
 extern "C" {
 
 // How the time-domain kernel walks a stream.
-//  * whole-stream workgroups (td_split): a stream is ONE segment, its tiles dealt to the four waves of a workgroup, the filter state
+//  * whole-stream workgroups (kTdSplitStreams): a stream is ONE segment, its tiles dealt to the four waves of a workgroup, the filter state
 //    and the lanes' energy shares handed from tile to tile through LDS — the whole recurrence, nothing truncated.  Needs enough
 //    streams to fill the chip with one workgroup each (n_streams x 4 waves against the W0 the chip holds); stereo and eight
 //    channels, equal lengths.
@@ -179,24 +190,29 @@ static void choose_td_geometry(ss_batch *b)
     const double split_score = split_ok ? wsplit / (std::ceil(wsplit / W0) * W0) : 0.0;
     // (measured at the bench shape: the coupled waves of a workgroup run 16 % behind independent segment waves — the chain makes a
     // workgroup as slow as its slowest wave, tile by tile — so the automatic choice wants a clear win in fill)
-    b->td_split = split_ok && (b->td_mode == 2 || (b->td_mode == 0 && 0.8 * split_score > best));
-    b->td_split_segments = false;
-    if (b->td_split) {
-        b->td_nseg = 1; b->td_seg_sub = 0;
-    } else if (best_seg >= min_seg && best_seg < nsub) {
-        b->td_seg_sub = best_seg;
-        b->td_nseg = (nsub + best_seg - 1) / best_seg;
-    } else {
-        b->td_nseg = 1; b->td_seg_sub = 0;
-    }
+    auto &plan = b->td_plan;
+    plan = {};
+    uint32_t split = ssk::kTdSplitNone;
+    if (split_ok && (b->td_mode == 2 || (b->td_mode == 0 && 0.8 * split_score > best))) split = ssk::kTdSplitStreams;
+    else if (best_seg >= min_seg && best_seg < nsub) { plan.seg_sub = best_seg; plan.nseg = (nsub + best_seg - 1) / best_seg; }
     // A handful of streams (one file): even the shortest segments leave most of the chip idle, and a pass takes as long as ONE
     // wave needs for its segment's tiles, one after the other.  There a segment's tiles are dealt to the eight waves of a
     // workgroup instead (the whole-stream form, per segment): if eight waves per shortest segment still fit the chip at once.
     const uint32_t nseg_min = (nsub + min_seg - 1) / min_seg;
-    if (forgets && split_ok && b->td_mode == 0 && !b->td_split && nsub > min_seg && 8.0 * cfg->n_streams * nseg_min <= W0) {
-        b->td_split_segments = true;
-        b->td_seg_sub = min_seg;
-        b->td_nseg = nseg_min;
+    if (forgets && split_ok && b->td_mode == 0 && split == ssk::kTdSplitNone && nsub > min_seg && 8.0 * cfg->n_streams * nseg_min <= W0) {
+        split = ssk::kTdSplitSegments; plan.seg_sub = min_seg; plan.nseg = nseg_min;
+    }
+    plan.split_batch = b->ragged ? ssk::kTdSplitNone : split;
+    // How segments > 0 start.  The exact hand-over: no run-in, their first kTdFixSub sub-blocks re-run from the true state by a
+    // second launch (launch_time_domain_fixup).  Mode 1: the 0.1 s run-in from a zero state of rounds 1-4.  Segments of eight
+    // waves (the pass is a latency chain, and a second launch is a fifth of it): every segment runs the FILTER over the kTdFixSub
+    // sub-blocks in front of it, from zero, inside the one launch — the state it starts its own frames with is what the second
+    // launch would have started from (a zero-state run over 0.2 s: 1.6e-21 of the true state's response left), the run-in tiles
+    // cost the filter passes only, no second launch.
+    if (plan.nseg > 1) {
+        if (split == ssk::kTdSplitSegments && SS_TD_SPLIT_LONG_RUN_IN) plan.warm_sub = kTdFixSub;
+        else if (b->td_mode == 1) plan.warm_sub = kTdWarmSub;
+        else { plan.fixup = true; plan.fix_sub = plan.seg_sub < kTdFixSub ? plan.seg_sub : kTdFixSub; }
     }
 }
 
@@ -647,11 +663,7 @@ int ss_batch_run(ss_batch *b)
             p.db_offset = (float)(20.0 * std::log10(4.0 / (double)c.fft_n));
             if (c.fft_n == 16384) {
                 p.tw_core = b->ft->core_tw4096; p.tw_256 = b->ft->core_tw256;
-                bool run_kernel = (c.hop_frames == 1024 && L.n_windows >= 8);
-#ifdef SS_TUNING
-                if (std::getenv("SS_FFT16K_SINGLE")) run_kernel = false;
-#endif
-                if (run_kernel)
+                if (fft16k_runs(b))
                     HIPCHK(ssk::launch_fft16k_run(p, b->fft_mode, fft_stream));
                 else
                     HIPCHK(ssk::launch_fft16k(p, b->fft_mode, fft_stream));
@@ -680,25 +692,16 @@ int ss_batch_run(ss_batch *b)
         p.n_streams = c.n_streams; p.channels = C; p.k = b->td->dev.p; p.state = b->state.p;
         p.subblocks = b->sub.p; p.sub_cap = L.n_subblocks ? L.n_subblocks : 1;
         p.sub_stride = (uint64_t)p.sub_cap * C; p.ring = nullptr; p.ring_frames = 0; p.tp_factor = b->tp_factor;
-        p.s100 = b->td->host.s100; p.nseg = b->td_nseg; p.seg_sub = b->td_seg_sub;
-        // segments > 0: exact hand-over (no run-in; their first kTdFixSub sub-blocks re-run from the true state by the second launch
-        // below), or — mode 1 — the 0.1 s run-in from a zero state of rounds 1-4
-        // ... or, a handful of streams cut into the shortest segments (td_split_segments: the pass is a latency chain, and a second
-        // launch is a fifth of it): every segment runs the FILTER over the kTdFixSub sub-blocks in front of it, from zero, inside the
-        // one launch — the state it starts its own frames with is what the second launch would have started from (a zero-state run
-        // over 0.2 s: 1.6e-21 of the true state's response left), the run-in tiles cost the filter passes only, no second launch
-        const bool long_run_in = b->td_nseg > 1 && b->td_mode == 0 && b->td_split_segments && SS_TD_SPLIT_LONG_RUN_IN;
-        const bool exact_segments = b->td_nseg > 1 && b->td_mode != 1 && !long_run_in;
-        p.warm_sub = long_run_in ? kTdFixSub : (exact_segments ? 0u : kTdWarmSub);
-        if (exact_segments) {
-            const size_t need = (size_t)c.n_streams * b->td_nseg * C * 4;
+        const auto &plan = b->td_plan;
+        p.s100 = b->td->host.s100; p.nseg = plan.nseg; p.seg_sub = plan.seg_sub;
+        p.warm_sub = plan.warm_sub; p.fix_sub = plan.fix_sub; p.split_batch = plan.split_batch;
+        if (plan.fixup) {
+            const size_t need = (size_t)c.n_streams * plan.nseg * C * 4;
             if (b->seg_state.n < need) HIPCHK(b->seg_state.alloc(need));
             p.seg_state = b->seg_state.p;
-            p.fix_sub = b->td_seg_sub < kTdFixSub ? b->td_seg_sub : kTdFixSub;
         }
         p.frames_of = b->ragged ? b->frames_d.p : nullptr;
         p.tp_f32 = b->tp_arith == SS_TP_ARITH_F32 ? 1u : 0u;
-        p.split_batch = b->ragged ? 0u : (b->td_split ? 1u : (b->td_split_segments ? 2u : 0u));      // (ragged lengths: one wave per stream / segment)
         if (b->wave_fused && !b->ragged) { p.wave_out = b->wave.p; p.wave_stride = (uint64_t)2 * b->wave_window; p.wave_window = b->wave_window; p.halo_frames = b->wave_halo; }
         HIPCHK(ssk::launch_time_domain(p, b->stream));
         if (mode == 2) {
@@ -709,7 +712,7 @@ int ss_batch_run(ss_batch *b)
             HIPCHK(hipStreamWaitEvent(b->stream2, b->ev_fork, 0));
             rc = launch_spectrum(); if (rc) return rc;
         }
-        if (exact_segments) HIPCHK(ssk::launch_time_domain_fixup(p, b->stream));
+        if (plan.fixup) HIPCHK(ssk::launch_time_domain_fixup(p, b->stream));
     } else if (mode == 2) {                                  // (no time-domain work at all: the spectrum kernel is the pass)
         HIPCHK(hipEventRecord(b->ev_fork, b->stream));
         HIPCHK(hipStreamWaitEvent(b->stream2, b->ev_fork, 0));
@@ -853,13 +856,12 @@ int ss_batch_geometry_get(const ss_batch *b, ss_batch_geometry *out)
     const ss_batch_layout &L = b->lay;
     if ((b->cfg.flags & SS_BATCH_FFT) && L.n_windows) {
         out->fft_windows_per_block = b->windows_per_block;
-        const bool run16k = b->cfg.fft_n == 16384 && b->cfg.hop_frames == 1024 && L.n_windows >= 8 && !b->fft_fast && !b->fft_pairw;
         if (b->fft_fast) {
             out->fft_blocks = b->cfg.n_streams * ((L.n_windows + b->windows_per_block - 1) / b->windows_per_block);
         } else if (b->fft_pairw) {
             const uint32_t ppb = b->windows_per_block >> 1, np = (L.n_windows + 1) >> 1;
             out->fft_blocks = b->cfg.n_streams * L.fft_channels * ((np + ppb - 1) / ppb);
-        } else if (run16k) {
+        } else if (fft16k_runs(b)) {
             uint32_t wpb = 0, groups = 0;
             ssk::fft16k_run_geometry(b->cfg.n_streams, L.fft_channels, L.n_windows, &wpb, &groups);
             out->fft_windows_per_block = wpb;
@@ -870,14 +872,11 @@ int ss_batch_geometry_get(const ss_batch *b, ss_batch_geometry *out)
         }
     }
     if (b->td) {
-        out->td_segments = b->td_nseg;
-        out->td_segment_subblocks = b->td_seg_sub;
-        out->td_warm_subblocks = (b->td_nseg > 1 && b->td_mode == 1) ? kTdWarmSub : 0;
-        // (ragged lengths: one wave per stream / segment whatever the shape would have allowed — ss_batch_run)
-        out->td_split = b->ragged ? 0u : (b->td_split ? 1u : (b->td_split_segments ? 2u : 0u));
-        const bool long_run_in = b->td_nseg > 1 && b->td_mode == 0 && b->td_split_segments && SS_TD_SPLIT_LONG_RUN_IN;
-        out->td_fixup_subblocks = (b->td_nseg > 1 && b->td_mode != 1 && !long_run_in) ? (b->td_seg_sub < kTdFixSub ? b->td_seg_sub : kTdFixSub) : 0;
-        if (long_run_in) out->td_warm_subblocks = kTdFixSub;
+        out->td_segments = b->td_plan.nseg;
+        out->td_segment_subblocks = b->td_plan.seg_sub;
+        out->td_warm_subblocks = b->td_plan.warm_sub;
+        out->td_split = b->td_plan.split_batch;
+        out->td_fixup_subblocks = b->td_plan.fix_sub;
         out->td_true_peak_factor = (uint32_t)b->tp_factor;
     }
     out->waveform_fused = (b->wave_fused && !b->ragged) ? 1u : 0u;
@@ -1218,7 +1217,7 @@ const char *ss_batch_kernel_name(const ss_batch *b, int kernel)
         return hop == 1024 ? "k_fft4096_ms1" : ((hop == 512 || hop == 2048) ? "k_fft4096_ms" : "k_fft4096_ms_anyhop");
     }
     if (b->cfg.fft_n == 16384)
-        return (b->cfg.hop_frames == 1024 && b->lay.n_windows >= 8) ? "k_fft16k_run" : "k_fft16k";
+        return fft16k_runs(b) ? "k_fft16k_run" : "k_fft16k";
     return "k_fft_generic";
 }
 

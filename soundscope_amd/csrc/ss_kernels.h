@@ -135,6 +135,8 @@ struct TdState {                 // per stream / per handle, device resident
     uint32_t bad_key[kMaxChannels];
 };
 
+enum TdSplitBatch : uint32_t { kTdSplitNone = 0, kTdSplitStreams = 1, kTdSplitSegments = 2 };    // TdParams::split_batch
+
 struct TdParams {
     const float *pcm;            // [stream][frame][channels]
     uint64_t stream_stride;      // floats between consecutive streams
@@ -165,11 +167,11 @@ struct TdParams {
     // fix_sub sub-blocks of every segment > 0 from the state the segment in front of it left, and overwrites their energies.
     double *seg_state;
     uint32_t fixup, fix_sub;
-    uint32_t split_batch;         // 2: the same with eight waves per (stream, SEGMENT) — a handful of streams cut into short segments,
-                                  // where the length of the chain of tiles is what a pass takes.
-                                  // 1 (batches, nseg == 1): a stream is ONE segment walked by the four waves of a workgroup, the filter
-                                  // state handed from tile to tile through LDS (SPLIT with the batch's chunk length) — no run-in, nothing
-                                  // of the recurrence truncated
+    uint32_t split_batch;         // TdSplitBatch.  kTdSplitNone: one wave per stream / segment.  kTdSplitStreams (batches, nseg == 1):
+                                  // a stream is ONE segment walked by the four waves of a workgroup, the filter state handed from tile to
+                                  // tile through LDS (SPLIT with the batch's chunk length) — no run-in, nothing of the recurrence truncated.
+                                  // kTdSplitSegments: the same with eight waves per (stream, SEGMENT) — a handful of streams cut into
+                                  // short segments, where the length of the chain of tiles is what a pass takes
     // a tick's short-term reading inside the same launch (k_tick only; st_out == nullptr: off).  The window of st_frames frames
     // ends with this call; the st_old_total ring elements from st_begin_elem on are the part in front of the call.
     double *st_out;               // (energy, loudness): device or mapped host memory

@@ -531,49 +531,69 @@ __global__ __launch_bounds__(64 * kTdSplitWaves, 3) void k_tick(TdParams p, uint
 #include "ss_td_body.inc"
 }
 
-uint32_t td_lds_blocks(uint32_t C, uint32_t tile_len);       // (ss_time_domain.hip: the chunk-length model)
+constexpr uint32_t kTdLdsBytes = 160u * 1024u;      // LDS of a CU (gfx950): the most one workgroup may take
+
+// How a launch of chunk length L tiles a sub-block of S frames: `pieces` equal tiles of tile_len frames, none longer than the
+// 64 / C chunks one wave scans at once (pieces x cap >= S, so ceil(S / pieces) <= cap), and the dynamic LDS of a workgroup of
+// nwb waves: per wave halo + tile + slack + 64 peak slots, whole float4s, plus TdShare where the waves share the tiles (SPLIT)
+struct TdTile { uint32_t pieces, tile_len, wave_floats; size_t lds; };
+static inline TdTile td_tile(uint32_t C, uint32_t S, uint32_t L, uint32_t halo, uint32_t nwb, bool split)
+{
+    const uint32_t cap = (64u / C) * L;
+    TdTile t;
+    t.pieces = (S + cap - 1) / cap;
+    t.tile_len = (S + t.pieces - 1) / t.pieces;
+    t.wave_floats = ((halo + t.tile_len) * C + td_slack_floats(C) + kMaxChannels + 3u) & ~3u;
+    t.lds = (size_t)t.wave_floats * 4 * nwb + (split ? sizeof(TdShare) : 0);
+    return t;
+}
+
+// Whether a launch's tiles are shared by the eight waves of a workgroup with the chunk length made for that: one streaming call
+// (SPLIT on the ring) or one short segment of a handful of streams (split_batch == kTdSplitSegments).  Whole-stream workgroups
+// (kTdSplitStreams) and one wave per segment take the batch's td_chunk_frames.  Two mirrors must agree with this rule: the
+// kernel's choice of K.m_pow_split over K.m_pow (ss_td_body.inc, `mpow`) and the tables get_td_tables (ss_host.cpp) builds for
+// each length — a launch whose L differs from its tables' computes wrong energies.
+static inline bool td_eight_wave_tiles(bool split, bool ring, uint32_t split_batch) { return split && (ring || split_batch == kTdSplitSegments); }
+static inline uint32_t td_launch_chunk_frames(bool split, bool ring, uint32_t split_batch, uint32_t C, uint32_t S)
+{
+    return td_eight_wave_tiles(split, ring, split_batch) ? td_split_chunk_frames(C, S) : td_chunk_frames(C, S);
+}
+
+// waves (SPLIT: workgroups) of a launch: one per (stream, segment), the fix-up's without segment 0
+static inline uint64_t td_launch_units(const TdParams &p) { return (uint64_t)p.n_streams * (p.fixup ? p.nseg - 1u : p.nseg); }
 
 template <int FACTOR, bool RING, int CT, int WAVE, int WPS, bool SPLIT = false, bool LATE = false>
 static hipError_t td_launch_w(const TdParams &p, hipStream_t s)
 {
     const uint32_t C = p.channels;
     const uint32_t S = p.s100;
-    // chunk length: the batch's (whole tiles of whole chunks, occupancy) — or, where one call / one short segment is shared by eight
-    // waves (streaming calls; split_batch == 2), the one that lets eight tiles cover it in ONE round
-    const uint32_t L = (SPLIT && p.split_batch != 1u) ? td_split_chunk_frames(C, S) : td_chunk_frames(C, S);
-    const uint32_t nch = 64u / C;
-    const uint32_t cap = nch * L;                                   // frames one wave can scan at once
-    const uint32_t pieces = (S + cap - 1) / cap;                    // equal tiles per sub-block
-    uint32_t tile_len = (S + pieces - 1) / pieces;
-    if (tile_len > cap) tile_len = cap;
-    // per-wave LDS: halo + tile + slack + 64 peak slots
+    const bool eight = td_eight_wave_tiles(SPLIT, RING, p.split_batch);
+    const uint32_t L = td_launch_chunk_frames(SPLIT, RING, p.split_batch, C, S);
     const uint32_t halo = WAVE ? p.halo_frames : (uint32_t)kTdHaloFrames;
-    uint32_t wave_floats = (halo + tile_len) * C + td_slack_floats(C) + kMaxChannels;
-    wave_floats = (wave_floats + 3u) & ~3u;
     // SPLIT: eight waves share the call where eight slices fit the LDS (up to 16 channels or so), four otherwise
     // (a batch's streams: four waves each — the grid is n_streams workgroups, and sixteen waves per CU are what the LDS slices allow;
-    // split_batch == 2, a handful of streams cut into short segments: eight, latency is what counts there)
-    uint32_t nwb = (SPLIT && p.split_batch != 1u) ? (uint32_t)kTdSplitWaves : (uint32_t)kTdWavesPerBlock;
-    if (SPLIT && (size_t)wave_floats * 4 * nwb + sizeof(TdShare) > 160 * 1024) nwb = (uint32_t)kTdWavesPerBlock;
-    const size_t lds = (size_t)wave_floats * 4 * nwb + (SPLIT ? sizeof(TdShare) : 0);
+    // split_batch == kTdSplitSegments, a handful of streams cut into short segments: eight, latency is what counts there)
+    uint32_t nwb = eight ? (uint32_t)kTdSplitWaves : (uint32_t)kTdWavesPerBlock;
+    TdTile t = td_tile(C, S, L, halo, nwb, SPLIT);
+    if (SPLIT && t.lds > kTdLdsBytes) t = td_tile(C, S, L, halo, nwb = (uint32_t)kTdWavesPerBlock, SPLIT);
     auto fn = k_time_domain<FACTOR, RING, CT, WAVE, WPS, SPLIT, LATE>;
     static DevicePrep prepared;                     // one per kernel instantiation
     const hipError_t pe = prepare_on_device(prepared, [fn] {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTdLdsBytes);
     });
     if (pe != hipSuccess) return pe;
-    const uint32_t waves = p.n_streams * (p.fixup ? p.nseg - 1u : p.nseg);
+    const uint32_t waves = (uint32_t)td_launch_units(p);
     const uint32_t blocks = SPLIT ? waves : (waves + kTdWavesPerBlock - 1) / kTdWavesPerBlock;      // SPLIT: a workgroup per (stream, segment)
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (t.lds > kTdLdsBytes) return hipErrorInvalidValue;
 #ifdef SS_TUNING        // development builds only: name the instantiation a launch takes (tools/probe_td_wps.py)
     if (std::getenv("SS_TD_VERBOSE")) {
         hipFuncAttributes a{};
         (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(fn));
         std::fprintf(stderr, "k_time_domain<%d,%d,%d,%d,%d,%d,%d> grid %u x %u lds %zu scratch %zu B/lane vgpr %d\n", FACTOR, (int)RING, CT, WAVE, WPS,
-                     (int)SPLIT, (int)LATE, blocks, 64 * nwb, lds, (size_t)a.localSizeBytes, a.numRegs);
+                     (int)SPLIT, (int)LATE, blocks, 64 * nwb, t.lds, (size_t)a.localSizeBytes, a.numRegs);
     }
 #endif
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * nwb), lds, s, p, L, tile_len, wave_floats, halo);
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * nwb), t.lds, s, p, L, t.tile_len, t.wave_floats, halo);
     return hipGetLastError();
 }
 
@@ -585,16 +605,10 @@ static hipError_t td_launch_tick(const TdParams &p, const FftBatchParams &fp, hi
     *fused = false;
     const uint32_t C = p.channels;
     const uint32_t S = p.s100;
-    const uint32_t L = td_split_chunk_frames(C, S);
-    const uint32_t cap = (64u / C) * L;
-    const uint32_t pieces = (S + cap - 1) / cap;
-    uint32_t tile_len = (S + pieces - 1) / pieces;
-    if (tile_len > cap) tile_len = cap;
+    const uint32_t L = td_launch_chunk_frames(true, true, p.split_batch, C, S);
     const uint32_t halo = (uint32_t)kTdHaloFrames;
-    uint32_t wave_floats = (halo + tile_len) * C + td_slack_floats(C) + kMaxChannels;
-    wave_floats = (wave_floats + 3u) & ~3u;
-    size_t lds = (size_t)wave_floats * 4 * kTdSplitWaves + sizeof(TdShare);
-    if (lds < (size_t)kFft16kLdsBytes) lds = kFft16kLdsBytes;           // (the spectrum's workgroups use the same dynamic block)
+    const TdTile t = td_tile(C, S, L, halo, kTdSplitWaves, true);
+    const size_t lds = t.lds < (size_t)kFft16kLdsBytes ? (size_t)kFft16kLdsBytes : t.lds;     // (the spectrum's workgroups use the same dynamic block)
     auto fn = k_tick<FACTOR, CT>;
     static DevicePrep prepared;
     static std::atomic<size_t> static_lds{0};
@@ -604,12 +618,12 @@ static hipError_t td_launch_tick(const TdParams &p, const FftBatchParams &fp, hi
         if (e != hipSuccess) return e;
         static_lds.store(a.sharedSizeBytes, std::memory_order_relaxed);
         return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(160 * 1024 - a.sharedSizeBytes));
+                                   (int)(kTdLdsBytes - a.sharedSizeBytes));
     });
     if (pe != hipSuccess) return pe;
-    if (lds + static_lds.load(std::memory_order_relaxed) > 160 * 1024) return hipSuccess;     // not fused: the caller launches both
+    if (lds + static_lds.load(std::memory_order_relaxed) > kTdLdsBytes) return hipSuccess;     // not fused: the caller launches both
     const uint32_t fft_blocks = 2;                                      // mid, side
-    hipLaunchKernelGGL(fn, dim3(fft_blocks + 1 + (p.st_out ? p.st_blocks : 0u)), dim3(64 * kTdSplitWaves), lds, s, p, L, tile_len, wave_floats,
+    hipLaunchKernelGGL(fn, dim3(fft_blocks + 1 + (p.st_out ? p.st_blocks : 0u)), dim3(64 * kTdSplitWaves), lds, s, p, L, t.tile_len, t.wave_floats,
                        halo, fp, fft_blocks);
     *fused = true;
     return hipGetLastError();
@@ -629,41 +643,42 @@ static inline uint32_t td_device_cus()
     return n;
 }
 
-// batches whose streams are walked by a whole workgroup (TdParams::split_batch): the same two register builds by grid size
-template <int FACTOR, int CT, int WAVE>
-static hipError_t td_launch_split_batch(const TdParams &p, hipStream_t s)
+// register build of a grid of `blocks` four-wave workgroups: the spill-free three-waves-per-SIMD build where three workgroups per CU
+// hold the whole grid, the SS_TD_WAVES build otherwise
+static inline bool td_three_waves(uint64_t blocks)
 {
-    const uint64_t blocks = (uint64_t)p.n_streams * (p.fixup ? p.nseg - 1u : p.nseg);
-    // a handful of streams cut into short segments: eight waves per segment, the state applied behind the scan (LATE) — the chain
-    // of a segment's tiles is what the launch takes
-    if (p.split_batch == 2u) return td_launch_w<FACTOR, false, CT, WAVE, 2, true, true>(p, s);      // (two waves per SIMD: nothing spilled; the grid is small by definition)
     bool three = SS_TD_WAVES == 4 && blocks <= 3ull * td_device_cus();
 #ifdef SS_TUNING        // development builds only: SS_TD_WPS=3|4 forces a register build
     if (const char *e = std::getenv("SS_TD_WPS")) three = SS_TD_WAVES == 4 && std::atoi(e) == 3;
 #endif
-    if (three) return td_launch_w<FACTOR, false, CT, WAVE, 3, true>(p, s);
+    return three;
+}
+
+// batches whose streams are walked by a whole workgroup (TdParams::split_batch): the same two register builds by grid size
+template <int FACTOR, int CT, int WAVE>
+static hipError_t td_launch_split_batch(const TdParams &p, hipStream_t s)
+{
+    // a handful of streams cut into short segments: eight waves per segment, the state applied behind the scan (LATE) — the chain
+    // of a segment's tiles is what the launch takes
+    if (p.split_batch == kTdSplitSegments) return td_launch_w<FACTOR, false, CT, WAVE, 2, true, true>(p, s);      // (two waves per SIMD: nothing spilled; the grid is small by definition)
+    if (td_three_waves(td_launch_units(p))) return td_launch_w<FACTOR, false, CT, WAVE, 3, true>(p, s);
     return td_launch_w<FACTOR, false, CT, WAVE, SS_TD_WAVES, true>(p, s);
 }
 
 template <int FACTOR, bool RING, int CT, int WAVE>
 static hipError_t td_launch(const TdParams &p, hipStream_t s)
 {
-    // a workgroup is four waves, one per SIMD: three workgroups per CU hold the whole grid -> the spill-free build
+    // a workgroup is four waves, one per SIMD
     if constexpr (RING) return td_launch_w<FACTOR, RING, CT, WAVE, 3>(p, s);      // a streaming call is one stream: one workgroup
     else {                                             // (else: the four-waves build of a streaming form is never instantiated)
-        const uint64_t waves = (uint64_t)p.n_streams * (p.fixup ? p.nseg - 1u : p.nseg);
-        const uint64_t blocks = (waves + kTdWavesPerBlock - 1) / kTdWavesPerBlock;
-        bool three = SS_TD_WAVES == 4 && blocks <= 3ull * td_device_cus();
-#ifdef SS_TUNING        // development builds only: SS_TD_WPS=3|4 forces a register build
-        if (const char *e = std::getenv("SS_TD_WPS")) three = SS_TD_WAVES == 4 && std::atoi(e) == 3;
-#endif
-        if (three) return td_launch_w<FACTOR, RING, CT, WAVE, 3>(p, s);
+        if (td_three_waves((td_launch_units(p) + kTdWavesPerBlock - 1) / kTdWavesPerBlock)) return td_launch_w<FACTOR, RING, CT, WAVE, 3>(p, s);
         return td_launch_w<FACTOR, RING, CT, WAVE, SS_TD_WAVES>(p, s);
     }
 }
 
 // Decimation fast path (WAVE = 2): samples per bin spp = len / W is an exact integer multiple of four (<= 128), so
 // floor(i spp) / ceil((i+1) spp) are the integer products, and every tile starts on a multiple of four floats.
+// (batch launches only: SPLIT exactly where split_batch is set)
 static inline int td_wave_int4(const TdParams &p)
 {
     const uint64_t len = p.n_frames * p.channels;
@@ -671,11 +686,8 @@ static inline int td_wave_int4(const TdParams &p)
     const uint64_t spp = len / p.wave_window;
     if (spp < 4 || spp > 1000 || (spp & 3u)) return 0;         // the fused path itself stops at 1000 samples per bin
     const uint32_t C = p.channels, S = p.s100;
-    const uint32_t L = p.split_batch == 2u ? td_split_chunk_frames(C, S) : td_chunk_frames(C, S);
-    const uint32_t cap = (64u / C) * L;
-    const uint32_t pieces = (S + cap - 1) / cap;
-    uint32_t tile_len = (S + pieces - 1) / pieces;
-    if (tile_len > cap) tile_len = cap;
+    const uint32_t L = td_launch_chunk_frames(p.split_batch != kTdSplitNone, false, p.split_batch, C, S);
+    const uint32_t tile_len = td_tile(C, S, L, p.halo_frames, kTdWavesPerBlock, false).tile_len;
     if (!(((uint64_t)S * C) % 4u == 0 && ((uint64_t)tile_len * C) % 4u == 0 && (p.halo_frames * C) % 4u == 0)) return 0;
     return spp <= 128 ? 2 : 3;
 }
@@ -715,12 +727,10 @@ static hipError_t td_launch_c(const TdParams &p, hipStream_t s, const FftBatchPa
     if (const char *e = std::getenv("SS_TD_SPLIT")) split = split && std::atoi(e) != 0;
 #endif
     if constexpr (RING) if (split) {            // (constexpr: the batch side never instantiates these forms)
+        // "longer than one tile" is measured with the BATCH's chunk length, not the split launch's own (td_split_chunk_frames)
         const uint32_t C = p.channels, S = p.s100;
-        const uint32_t cap = (64u / C) * td_chunk_frames(C, S);
-        const uint32_t pieces = (S + cap - 1) / cap;
-        uint32_t tile_len = (S + pieces - 1) / pieces;
-        if (tile_len > cap) tile_len = cap;
-        if (p.n_frames > tile_len) {
+        const uint32_t batch_tile_len = td_tile(C, S, td_chunk_frames(C, S), kTdHaloFrames, kTdWavesPerBlock, false).tile_len;
+        if (p.n_frames > batch_tile_len) {
             if (RING && tick_fft && p.n_streams == 1) {                 // a tick: the spectrum's workgroups ride the same launch
                 const hipError_t e = p.channels == 2 ? td_launch_tick<FACTOR, 2>(p, *tick_fft, s, fused)
                                                      : td_launch_tick<FACTOR, 0>(p, *tick_fft, s, fused);

@@ -23,12 +23,10 @@ namespace ssk {
 // 48 kHz stereo 4800 = 5 x 32 x 30 — k_time_domain 2.14 -> 1.98 ms against L = 33 (5 tiles of 29 chunks + 3 frames)
 // although the walk of an even L is 2-way bank conflicted; 96 kHz stereo 2.91 -> 2.17 ms (was L = 65); BASELINE
 // config 5 (96 kHz, 8 channels) 3.02 -> 2.08 ms (was L = 65: 19 tiles of 7 chunks + 51 frames; now 40 tiles of 8 x 30).
-uint32_t td_lds_blocks(uint32_t C, uint32_t tile_len)
+// four-wave workgroups of `lds` bytes one CU holds at once (the launch bound allows SS_TD_WAVES waves per SIMD)
+static uint32_t td_lds_blocks(size_t lds)
 {
-    uint32_t wave_floats = ((uint32_t)kTdHaloFrames + tile_len) * C + td_slack_floats(C) + kMaxChannels;
-    wave_floats = (wave_floats + 3u) & ~3u;
-    const size_t lds = (size_t)wave_floats * 4 * kTdWavesPerBlock;
-    uint32_t blocks = (uint32_t)((160u * 1024u) / lds);
+    const uint32_t blocks = (uint32_t)(kTdLdsBytes / lds);
     const uint32_t max_blocks = (4u * SS_TD_WAVES) / kTdWavesPerBlock;
     return blocks > max_blocks ? max_blocks : blocks;
 }
@@ -43,11 +41,9 @@ uint32_t td_chunk_frames(uint32_t C, uint32_t s100)
     static const double occupancy[5] = {8.0, 3.0, 1.6, 1.25, 1.0};
     uint32_t best = 33; double best_cost = 1e300;
     for (uint32_t L : {20u, 25u, 30u, 33u, 35u, 40u, 45u, 49u, 50u, 55u, 60u, 65u}) {
-        const uint32_t cap = nch * L;
-        const uint32_t pieces = (s100 + cap - 1) / cap;
-        uint32_t tile_len = (s100 + pieces - 1) / pieces;
-        if (tile_len > cap) tile_len = cap;
-        const uint32_t blocks = td_lds_blocks(C, tile_len);
+        const TdTile t = td_tile(C, s100, L, kTdHaloFrames, kTdWavesPerBlock, false);
+        const uint32_t pieces = t.pieces, tile_len = t.tile_len;
+        const uint32_t blocks = td_lds_blocks(t.lds);
         if (blocks == 0) continue;
         const uint32_t rem = tile_len % L;
         uint32_t ways = 1;                                    // bank conflicts of one pass read, per half wave
@@ -85,17 +81,12 @@ uint32_t td_split_chunk_frames(uint32_t C, uint32_t s100)
     // (48 kHz stereo: 40 -> tiles of 1200 frames, at most eight per tick, 16.4 us for the call where L = 30 — nine or ten tiles
     // of 960, wave 0 taking a second one behind its first one's true-peak product — takes 22.7; partial chunks are poison: a
     // tile that ends inside a chunk runs the unbatched loops, L = 35 / 38 / 45: 84-98 us, tools/sweep_tick_lsplit.sh.)
-    const uint32_t nch = 64u / C;
     const uint32_t n_tick = 16384u / C;
     for (uint32_t L : {25u, 30u, 33u, 35u, 40u, 45u, 49u, 50u, 55u, 60u, 65u}) {
-        const uint32_t cap = nch * L;
-        const uint32_t pieces = (s100 + cap - 1) / cap;
-        const uint32_t tile_len = (s100 + pieces - 1) / pieces;
-        if (tile_len > cap || tile_len * pieces != s100 || tile_len % L) continue;
-        if ((n_tick - 1u) / tile_len + 2u > (uint32_t)kTdSplitWaves) continue;
-        uint32_t wave_floats = ((uint32_t)kTdHaloFrames + tile_len) * C + td_slack_floats(C) + kMaxChannels;
-        wave_floats = (wave_floats + 3u) & ~3u;
-        if ((size_t)wave_floats * 4 * kTdSplitWaves + sizeof(TdShare) > 160 * 1024) continue;
+        const TdTile t = td_tile(C, s100, L, kTdHaloFrames, kTdSplitWaves, true);
+        if (t.tile_len * t.pieces != s100 || t.tile_len % L) continue;
+        if ((n_tick - 1u) / t.tile_len + 2u > (uint32_t)kTdSplitWaves) continue;
+        if (t.lds > kTdLdsBytes) continue;
         return L;
     }
     return td_chunk_frames(C, s100);
@@ -104,20 +95,9 @@ uint32_t td_split_chunk_frames(uint32_t C, uint32_t s100)
 // waves of k_time_domain one CU holds at once (LDS per wave grows with the channel count and the decimation halo)
 uint32_t td_resident_waves_per_cu(uint32_t C, uint32_t s100, uint32_t halo_frames)
 {
-    const uint32_t L = td_chunk_frames(C, s100);
-    const uint32_t cap = (64u / C) * L;
-    const uint32_t pieces = (s100 + cap - 1) / cap;
-    uint32_t tile_len = (s100 + pieces - 1) / pieces;
-    if (tile_len > cap) tile_len = cap;
     const uint32_t halo = halo_frames ? halo_frames : (uint32_t)kTdHaloFrames;
-    uint32_t wave_floats = (halo + tile_len) * C + td_slack_floats(C) + kMaxChannels;
-    wave_floats = (wave_floats + 3u) & ~3u;
-    const size_t lds = (size_t)wave_floats * 4 * kTdWavesPerBlock;
-    uint32_t blocks = lds ? (uint32_t)((160u * 1024u) / lds) : 4u;
-    const uint32_t max_blocks = (4u * SS_TD_WAVES) / kTdWavesPerBlock;      // launch bound: SS_TD_WAVES waves per SIMD
-    if (blocks > max_blocks) blocks = max_blocks;
-    if (blocks < 1) blocks = 1;
-    return blocks * kTdWavesPerBlock;
+    const uint32_t blocks = td_lds_blocks(td_tile(C, s100, td_chunk_frames(C, s100), halo, kTdWavesPerBlock, false).lds);
+    return (blocks ? blocks : 1u) * kTdWavesPerBlock;
 }
 
 hipError_t launch_time_domain(const TdParams &p, hipStream_t s, const FftBatchParams *tick_fft, bool *tick_fused)
