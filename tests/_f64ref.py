@@ -1,0 +1,146 @@
+"""Plain f64 restatements, from the published definitions, that the time-domain tests hold the device path to (a helper
+module, not a test file): none of it calls the product or the oracle.
+
+  * K-weighting: libebur128's design (ebur128_init_filter: a high shelf, then the 38 Hz high-pass, each by bilinear transform,
+    numerators and denominators convolved into one 4th-order section) for any rate, run as a sequential f64 filter;
+  * the crate's true-peak interpolator: 49 Hann-windowed sinc taps rounded to f32, a zero-stuffed polyphase convolution in f64;
+  * ebur128's channel weights, and the momentary / short-term series as `loudness_momentary()` / `loudness_shortterm()` return
+    them after every 100 ms sub-block (zeros before the start);
+  * get_waveform's min-max decimation (analyzer.rs:107-137).
+"""
+import numpy as np
+from scipy import signal
+
+
+def subblock_frames(rate):
+    return (rate + 5) // 10
+
+
+def kweight_coeffs(rate):
+    """(b[5], a[5]) of the K-weighting filter at `rate` (libebur128 ebur128_init_filter)."""
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = np.tan(np.pi * f0 / rate)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    pb = np.array([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0])
+    pa = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = np.tan(np.pi * f0 / rate)
+    rb = np.array([1.0, -2.0, 1.0])
+    ra = np.array([1.0, 2.0 * (K * K - 1.0) / (1.0 + K / Q + K * K), (1.0 - K / Q + K * K) / (1.0 + K / Q + K * K)])
+    return np.convolve(pb, rb), np.convolve(pa, ra)
+
+
+def kweighted_subblocks(x, rate, channels, frames=None):
+    """[sub-block][channel] sums of y^2 of a sequential f64 K-weighting of interleaved `x` (its first `frames` frames), over the
+    whole sub-blocks of (rate + 5) // 10 frames."""
+    b, a = kweight_coeffs(rate)
+    x = np.asarray(x).reshape(-1, channels)
+    if frames is not None:
+        x = x[:frames]
+    S = subblock_frames(rate)
+    n = x.shape[0] // S
+    y = signal.lfilter(b, a, x[:n * S].astype(np.float64), axis=0)
+    return (y * y).reshape(n, S, channels).sum(axis=1)
+
+
+def channel_weights(channels):
+    """ebur128's default channel map as weights: L / R / C 1.0, LFE (the fourth of five and more) 0, the surrounds 1.41,
+    channels past the sixth unused; four channels are L R Ls Rs, five L R C Ls Rs."""
+    if channels == 4:
+        return np.array([1.0, 1.0, 1.41, 1.41])
+    if channels == 5:
+        return np.array([1.0, 1.0, 1.0, 1.41, 1.41])
+    w = np.zeros(channels)
+    for i, v in enumerate((1.0, 1.0, 1.0, 0.0, 1.41, 1.41)):
+        if i < channels:
+            w[i] = v
+    return w
+
+
+def _window_loudness(e, k, S):
+    """-0.691 + 10 log10 of the mean square over the last k sub-blocks after each sub-block (zeros before the start)."""
+    c = np.concatenate([np.zeros(k), np.cumsum(e)])
+    win = (c[k:] - c[:-k]) / (k * S)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(win > 0.0, 10.0 * np.log10(np.where(win > 0.0, win, 1.0)) - 0.691, -np.inf)
+
+
+def loudness_series(sub, rate, channels):
+    """(momentary, short-term) after every sub-block from [sub-block][channel] energies: 4 and 30 sub-blocks, channel-weighted."""
+    S = subblock_frames(rate)
+    e = sub @ channel_weights(channels)
+    return _window_loudness(e, 4, S), _window_loudness(e, 30, S)
+
+
+def interpolator_taps(factor):
+    """The 49 taps of the crate's interpolator (sinc at 1/factor, Hann over 48 intervals), rounded to f32 like the crate's."""
+    j = np.arange(49, dtype=np.float64)
+    m = j - 24.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = np.where(np.abs(m) > 1e-6, np.sin(m * np.pi / factor) / (m * np.pi / factor), 1.0)
+    c *= 0.5 * (1.0 - np.cos(2.0 * np.pi * j / 48.0))
+    c[np.abs(c) <= 1e-6] = 0.0                          # the crate keeps only taps above 1e-6
+    return c.astype(np.float32).astype(np.float64)
+
+
+def true_peak(ch, factor):
+    """One channel's true peak in f64: max(|upfirdn(taps, x, factor)|[:factor n], |x|); the sample peak at factor 0."""
+    ch = np.asarray(ch, np.float64)
+    if factor == 0:
+        return float(np.abs(ch).max())
+    up = signal.upfirdn(interpolator_taps(factor), ch, up=factor)
+    return float(max(np.abs(up[:factor * ch.size]).max(), np.abs(ch).max()))
+
+
+def tap_bound(factor):
+    """max over the phases of sum |taps|: no interpolated output exceeds this times the largest |sample| it reads"""
+    t = np.abs(interpolator_taps(factor))
+    return float(max(t[p::factor].sum() for p in range(factor)))
+
+
+def event_windows(x, starts, span, pad=40):
+    """frames [start - pad, start + span + pad) of every row of x ([k][n]), zeros outside [0, n)"""
+    x = np.asarray(x)
+    k, n = x.shape
+    idx = np.asarray(starts, np.int64)[:, None] - pad + np.arange(span + 2 * pad)[None, :]
+    return np.where((idx >= 0) & (idx < n), x[np.arange(k)[:, None], np.clip(idx, 0, n - 1)], 0).astype(np.float64)
+
+
+def event_true_peak(win, starts, n, span, factor, pad=40):
+    """True peaks of many channels of n frames, each holding one event at frames [start, start + span), from the frames around
+    it alone (win = event_windows(...)).  The outputs whose taps reach into the event read only frames of the window
+    (pad >= 48 / factor) and are computed exactly; every other output reads only background and is at most
+    tap_bound(factor) * max|background|.  Returns the event's peak, [k], its own samples included: the channel's true peak is
+    max(that, its sample peak) wherever the caller's background bound lies below it.  (An event in the last 48 / factor frames
+    rings past the end of the stream: the outputs there are never made.)"""
+    k, W = win.shape
+    starts = np.asarray(starts, np.int64)
+    span = W - 2 * pad
+    taps = interpolator_taps(factor)
+    up = np.zeros((k, W * factor))
+    up[:, ::factor] = win
+    y = np.zeros_like(up)
+    for j in np.nonzero(taps)[0]:                       # y[m] = sum_j taps[j] up[m - j]
+        y[:, j:] += taps[j] * up[:, :up.shape[1] - j]
+    m = (starts[:, None] - pad) * factor + np.arange(W * factor)[None, :]   # the outputs' positions in the whole stream
+    exact = (np.arange(W * factor)[None, :] >= 48) & (m >= 0) & (m < factor * np.reshape(n, (-1, 1)))
+    return np.maximum(np.where(exact, np.abs(y), 0.0).max(axis=1), np.abs(win[:, pad:pad + span]).max(axis=1))
+
+
+def waveform_numpy(x, window_s):
+    """analyzer.rs:107-137 with numpy: W = window_s * 1000 bins, spp = len / W in f64, bin i = [floor(i spp),
+    min(ceil((i + 1) spp), len)), points (i, min), (i, max); stops at the first bin that starts past the end."""
+    w = int(window_s * 1000.0)
+    spp = len(x) / w
+    out = []
+    for i in range(w):
+        bs = int(np.floor(i * spp))
+        be = min(int(np.ceil((i + 1) * spp)), len(x))
+        if bs >= len(x):
+            break
+        seg = x[bs:be]
+        out += [np.nanmin(seg) if seg.size and not np.all(np.isnan(seg)) else (np.nan if seg.size else 0.0),
+                np.nanmax(seg) if seg.size and not np.all(np.isnan(seg)) else (np.nan if seg.size else 0.0)]
+    return np.array(out, np.float32)

@@ -13,6 +13,7 @@ from scipy import signal
 import soundscope_amd as ssa
 from soundscope_amd import _lib as L
 from conftest import db_close, db_report, make_stereo
+from _f64ref import interpolator_taps, waveform_numpy
 
 pytestmark = pytest.mark.gpu
 
@@ -77,15 +78,6 @@ def test_integrated_loudness_against_exact_f64_gating(oracle, rate):
     coeffs = oracle.Meter(2, rate).coeffs()            # the design is pinned separately (tests/test_product_tables.py)
     for i, x in enumerate(xs):
         assert abs(b.results()[i].integrated_lufs - lufs_f64(x, rate, 2, coeffs)) <= 0.05, i
-
-
-def interpolator_taps(factor):
-    j = np.arange(49, dtype=np.float64)
-    m = j - 24.0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        c = np.where(np.abs(m) > 1e-6, np.sin(m * np.pi / factor) / (m * np.pi / factor), 1.0)
-    c *= 0.5 * (1.0 - np.cos(2.0 * np.pi * j / 48.0))
-    return c.astype(np.float32).astype(np.float64)      # the crate keeps f32 taps
 
 
 @pytest.mark.parametrize("rate,factor", [(48000, 4), (44100, 4), (96000, 2)])
@@ -171,23 +163,6 @@ def test_streaming_shortterm_and_momentary_against_f64_windows(oracle, rate, sli
             want = -np.inf if e <= 0 else 10.0 * np.log10(e) - 0.691
             assert abs(got - want) <= 1e-6, (fed, win, got, want)
     a.close()
-
-
-def waveform_numpy(x, window_s):
-    """analyzer.rs:107-137 with numpy: W = window_s * 1000 bins, spp = len / W in f64, bin i = [floor(i spp),
-    min(ceil((i + 1) spp), len)), points (i, min), (i, max); stops at the first bin that starts past the end."""
-    w = int(window_s * 1000.0)
-    spp = len(x) / w
-    out = []
-    for i in range(w):
-        bs = int(np.floor(i * spp))
-        be = min(int(np.ceil((i + 1) * spp)), len(x))
-        if bs >= len(x):
-            break
-        seg = x[bs:be]
-        out += [np.nanmin(seg) if seg.size and not np.all(np.isnan(seg)) else (np.nan if seg.size else 0.0),
-                np.nanmax(seg) if seg.size and not np.all(np.isnan(seg)) else (np.nan if seg.size else 0.0)]
-    return np.array(out, np.float32)
 
 
 @pytest.mark.parametrize("rate,channels,seconds", [(48000, 2, 2.0), (44100, 2, 2.0), (96000, 8, 1.0), (48000, 1, 0.0294), (22050, 2, 3.7)])
