@@ -77,6 +77,9 @@ int ss_inspect_kweight(uint32_t rate, double b5[5], double a5[5]);
 /* true-peak interpolator (49-tap Hann-windowed sinc, `factor` 2 or 4): taps[(f - 1) * len + t] = coefficient of x[n - t] in
  * polyphase branch f = 1 .. factor - 1 (branch 0 is the identity tap); *len = taps per branch (12 or 24) */
 int ss_inspect_true_peak(int factor, float *taps, uint32_t cap, uint32_t *len);
+/* the factor-4 branches folded about their centre, as the VALU true-peak forms hold them: fold18[0..5] = (a[k] + c[k]) / 2,
+ * [6..11] = (a[k] - c[k]) / 2, [12..17] = b[k], k = 0 .. 5, for branches a = 1, b = 2, c = 3 of ss_inspect_true_peak */
+int ss_inspect_true_peak_fold(float fold18[18]);
 /* spectrum-analyzer's periodic Hann window in f32 (n values) */
 int ss_inspect_hann(uint32_t n, float *w);
 /* retained bins of FrequencyLimit::Range(20, 20000) for (rate, n): FFT index of the first one and their number */

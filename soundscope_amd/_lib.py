@@ -42,7 +42,7 @@ SYMBOLS = [
     "ss_batch_allreduce_histograms", "ss_batch_traffic_floor",
     "ss_batch_corpus_gate_enqueue", "ss_batch_corpus_gate_read", "ss_batch_checksums", "ss_inspect_filter_state", "ss_batch_set_true_peak_arith", "ss_batch_get_true_peak_arith", "ss_batch_set_time_domain_mode", "ss_batch_set_columns_gain",
     "ss_release_caches", "ss_batch_geometry_get_sized",
-    "ss_inspect_kweight", "ss_inspect_true_peak", "ss_inspect_hann", "ss_inspect_bins", "ss_inspect_histogram",
+    "ss_inspect_kweight", "ss_inspect_true_peak", "ss_inspect_true_peak_fold", "ss_inspect_hann", "ss_inspect_bins", "ss_inspect_histogram",
     "ss_batch_download_loudness_series", "ss_batch_loudness_extremes",
 ]
 
@@ -230,6 +230,7 @@ def _bind(lib):
         "ss_batch_geometry_get_sized": (C.c_int, [vp, vp, C.c_size_t]),
         "ss_inspect_kweight": (C.c_int, [C.c_uint32, f64p, f64p]),
         "ss_inspect_true_peak": (C.c_int, [C.c_int, f32p, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "ss_inspect_true_peak_fold": (C.c_int, [f32p]),
         "ss_inspect_hann": (C.c_int, [C.c_uint32, f32p]),
         "ss_inspect_bins": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_inspect_histogram": (C.c_int, [f64p, f64p]),

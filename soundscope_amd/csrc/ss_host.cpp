@@ -208,6 +208,7 @@ int get_td_tables(uint32_t rate, int factor, uint32_t channels, TdTables **out)
         k.tp_len = factor == 4 ? 12 : 24;
         for (int f = 1; f < factor; f++)
             for (const auto &tap : ph[f]) k.tp[f - 1][tap.delay] = tap.coeff;
+        if (factor == 4) sst::true_peak_fold4(k.tp_fold);
     }
     k.s100 = (rate + 5) / 10;
     {
@@ -316,6 +317,14 @@ int ss_inspect_true_peak(int factor, float *taps, uint32_t cap, uint32_t *len)
         for (int f = 1; f < factor; f++)
             for (const auto &tap : ph[f]) if ((uint32_t)tap.delay < n) taps[(size_t)(f - 1) * n + tap.delay] = tap.coeff;
     }
+    return SS_OK;
+}
+
+int ss_inspect_true_peak_fold(float fold18[18])
+{
+    float f[3][6];
+    sst::true_peak_fold4(f);
+    if (fold18) std::memcpy(fold18, f, sizeof f);
     return SS_OK;
 }
 

@@ -112,6 +112,7 @@ struct TdConst {                 // one per (rate, true-peak factor), device res
                                  // behind chunk c — applied when that state arrives, behind a scan that ran without it
     double m_chunk[64][16];      // the same for L = td_chunk_frames(C): batches whose streams are walked by a whole workgroup (split_batch)
     float tp[3][kTpHistMax];     // polyphase branches 1..factor-1, coefficient of x[n - t]
+    float tp_fold[3][6];         // factor 4: the branches folded about their centre (sst::true_peak_fold4), the VALU forms' taps
     int32_t tp_factor;           // 0, 2, 4
     int32_t tp_len;              // taps per branch (12 or 24)
     uint32_t s100;               // frames per 100 ms sub-block = (rate + 5) / 10

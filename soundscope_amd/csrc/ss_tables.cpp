@@ -170,6 +170,21 @@ void true_peak_design(int factor, std::vector<std::vector<PolyTap>> &phases, int
     }
 }
 
+void true_peak_fold4(float fold[3][6])
+{
+    std::vector<std::vector<PolyTap>> ph;
+    int delay = 0;
+    true_peak_design(4, ph, &delay);
+    float br[3][12] = {};
+    for (int f = 1; f < 4; f++)
+        for (const auto &tap : ph[f]) br[f - 1][tap.delay] = tap.coeff;
+    for (int k = 0; k < 6; k++) {
+        fold[0][k] = 0.5f * (br[0][k] + br[2][k]);
+        fold[1][k] = 0.5f * (br[0][k] - br[2][k]);
+        fold[2][k] = br[1][k];
+    }
+}
+
 int true_peak_factor_for_rate(uint32_t rate)
 {
     return rate < 96000 ? 4 : (rate < 192000 ? 2 : 0);

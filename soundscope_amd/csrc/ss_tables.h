@@ -36,6 +36,12 @@ void kweight_transition_pow(const double a[5], uint64_t steps, double out[16]);
 // (delay index, coefficient) in ascending delay; coefficient kept in f32.
 struct PolyTap { int delay; float coeff; };
 void true_peak_design(int factor, std::vector<std::vector<PolyTap>> &phases, int *delay_len);
+// The factor-4 branches folded about their centre.  The 49 taps are symmetric, so branch 3 is branch 1 reversed
+// (a[k], c[k] = a[11 - k]) and branch 2 is its own reverse (b[k] = b[11 - k]).  With u_k = x[n - k] + x[n - 11 + k] and
+// v_k = x[n - k] - x[n - 11 + k] (k < 6): (y1 + y3) / 2 = sum fold[0][k] u_k, (y1 - y3) / 2 = sum fold[1][k] v_k,
+// y2 = sum fold[2][k] u_k, and max(|y1|, |y3|) = |(y1 + y3) / 2| + |(y1 - y3) / 2|.  fold[0][k] = (a[k] + c[k]) / 2,
+// fold[1][k] = (a[k] - c[k]) / 2 (one f32 rounding, an exact halving), fold[2][k] = b[k].
+void true_peak_fold4(float fold[3][6]);
 // oversampling rule of the crate: <96 kHz: 4, <192 kHz: 2, else 0 (off)
 int true_peak_factor_for_rate(uint32_t rate);
 

@@ -1043,22 +1043,21 @@
                 // SIMD for 3072 clocks per 960-frame stereo tile and lets no other wave's VALU work issue meanwhile; here a lane takes
                 // FIFTEEN consecutive frames of BOTH channels of a pair — a frame of interleaved stereo is an aligned register pair
                 // (L, R), which is exactly a packed operand — reads its 26-frame window once (ds_read_b64, lane stride 30 dwords:
-                // conflict-free) and runs 3 phases x 12 taps as 36 v_pk_fma_f32 per frame with the tap broadcast from an SGPR pair
-                // through op_sel: 540 packed FMAs (5.2 issue clocks each at four waves per SIMD) + 60 maxima per tile, 2800 clocks,
-                // none wasted — measured -9 % kernel time (profiles/r06_ab_tp_packed_valu.txt).  The tile's frames are dealt
+                // conflict-free) and runs the 3 phases x 12 taps folded about their centre (SS_TP_VALU_FOLD1) as 30 packed
+                // instructions per frame with the taps broadcast from SGPR pairs through op_sel: 450 packed (5.2 issue clocks each at
+                // four waves per SIMD) + 60 plain per tile, 2500 clocks — the unfolded 540 FMAs measured -9 % kernel time against the
+                // matrix pipe (profiles/r06_ab_tp_packed_valu.txt), the fold -5 % more.  The tile's frames are dealt
                 // 15 to a lane; the last lane of a tile that is no multiple of 15 takes the tile's LAST fifteen frames (its first ones
                 // a second time: a maximum does not mind), and a tile of fewer than fifteen frames takes the crate's loop.
                 if (seg < kTpValuFrames) tp_exact_range(0u, seg);
                 else {
                     uint32_t lane_v = lane;
                     asm volatile("" : "+v"(lane_v));
-                    const_f64_ptr cp = (const_f64_ptr)(uintptr_t)&K.tp[0][0];        // tap pairs (c[2 m], c[2 m + 1]): scalar loads
+                    const_f64_ptr cp = (const_f64_ptr)(uintptr_t)&K.tp_fold[0][0];   // folded tap pairs (f[2 m], f[2 m + 1]): scalar loads
                     asm volatile("" : "+s"(cp));
-                    double tc[3][6];
+                    double tf[9];
 #pragma unroll
-                    for (int f = 0; f < 3; f++)
-#pragma unroll
-                        for (int m = 0; m < 6; m++) tc[f][m] = cp[f * (kTpHistMax / 2) + m];
+                    for (int m = 0; m < 9; m++) tf[m] = cp[m];
                     // (more channels: a lane takes fifteen frames of ONE pair of adjacent channels, the pairs of a run of frames side
                     // by side in neighbouring lanes — eight channels: lane stride 120 dwords per run, 2 per pair: conflict-free too)
                     const uint32_t nl = (seg + (uint32_t)kTpValuFrames - 1u) / (uint32_t)kTpValuFrames * kTpPairs;
@@ -1070,34 +1069,25 @@
                             uint32_t first = run * (uint32_t)kTpValuFrames;
                             first = first + (uint32_t)kTpValuFrames <= seg ? first : seg - (uint32_t)kTpValuFrames;
                             const v2f_td *wp = reinterpret_cast<const v2f_td *>(tile) + ((int)first - 11) * (int)kTpPairs + (int)pair;
-                            // (the window slides through the registers three frames at a time: fourteen frames live, not twenty-six —
+                            // (the window slides through the registers a frame at a time: thirteen frames live, not twenty-six —
                             // the four-waves build has 128 registers and the next tile's prefetch is in 32 of them)
                             v2f_td W[kTpValuFrames + 11];                             // frames first - 11 .. first + 14
 #pragma unroll
-                            for (int j = 0; j < 14; j++) W[j] = wp[j * (int)kTpPairs];
+                            for (int j = 0; j < 13; j++) W[j] = wp[j * (int)kTpPairs];
 #pragma unroll
-                            for (int g = 0; g < kTpValuFrames / 3; g++) {
+                            for (int j = 0; j < kTpValuFrames; j++) {                 // (L, R) at frame first + j
 #if defined(__HIP_DEVICE_COMPILE__)
                                 __builtin_amdgcn_sched_barrier(0);
 #endif
                                 {
-#pragma unroll
-                                    for (int f = 0; f < 3; f++) {                    // (L, R) of phase f + 1 at frames first + 3 g + 0 .. 2
-                                        v2f_td a[3];
-                                        SS_TP_VALU_PHASE3(a[0], a[1], a[2], W, g, tc[f]);
-                                        asm("v_max3_f32 %0, %0, |%2|, |%3|\n\tv_max3_f32 %1, %1, |%4|, |%5|\n\t"
-                                            "v_max_f32_e64 %0, %0, |%6|\n\tv_max_f32_e64 %1, %1, |%7|"
-                                            : "+v"(mL), "+v"(mR)
-                                            : "v"(a[0].x), "v"(a[1].x), "v"(a[0].y), "v"(a[1].y), "v"(a[2].x), "v"(a[2].y));
-                                    }
+                                    v2f_td sv, yv, dv;
+                                    SS_TP_VALU_FOLD1(sv, yv, dv, W, j, tf);
+                                    SS_TP_VALU_FOLD1_MAX(mL, mR, sv, yv, dv);
                                 }
 #if defined(__HIP_DEVICE_COMPILE__)
                                 __builtin_amdgcn_sched_barrier(0);
 #endif
-                                if (g + 1 < kTpValuFrames / 3) {             // (requested a group ahead: measured, spills in the four-waves build)
-#pragma unroll
-                                    for (int j = 14 + 3 * g; j < 17 + 3 * g; j++) W[j] = wp[j * (int)kTpPairs];
-                                }
+                                if (j + 13 < kTpValuFrames + 11) W[j + 13] = wp[(j + 13) * (int)kTpPairs];    // (for frame j + 2)
                             }
                             if (CT != 2) {                                           // (a lane's pair changes from round to round)
                                 atomicMax(&tpk[2u * pair], __float_as_uint(mL));
@@ -1189,14 +1179,14 @@
                 else {
                     uint32_t lane_v = lane;
                     asm volatile("" : "+v"(lane_v));
-                    const_f32_ptr tapp = (const_f32_ptr)(uintptr_t)&K.tp[0][0];       // scalar loads
+                    // scalar loads: factor 4 the three branches folded (18 taps), factor 2 its one branch of 24
+                    const_f32_ptr tapp = (const_f32_ptr)(uintptr_t)(FACTOR == 4 ? &K.tp_fold[0][0] : &K.tp[0][0]);
                     asm volatile("" : "+s"(tapp));
-                    constexpr int NT = Cfg::HIST;                                      // 12 taps x 3 branches, or 24 x 1
-                    float tcf[Cfg::NPH > 0 ? Cfg::NPH : 1][NT];
+                    constexpr int NT = Cfg::HIST;                                      // window reach: 12 or 24 frames
+                    constexpr int NTAPS = FACTOR == 4 ? 18 : NT;
+                    float tcf[NTAPS];
 #pragma unroll
-                    for (int f = 0; f < Cfg::NPH; f++)
-#pragma unroll
-                        for (int t = 0; t < NT; t++) tcf[f][t] = tapp[f * kTpHistMax + t];
+                    for (int t = 0; t < NTAPS; t++) tcf[t] = tapp[t];
                     const uint32_t nl = (seg + (uint32_t)kTpValuFrames - 1u) / (uint32_t)kTpValuFrames * C;
                     float mC = 0.0f;
                     for (uint32_t l0 = 0; l0 < nl; l0 += 64u) {
@@ -1214,14 +1204,11 @@
 #if defined(__HIP_DEVICE_COMPILE__)
                                 __builtin_amdgcn_sched_barrier(0);
 #endif
-#pragma unroll
-                                for (int f = 0; f < Cfg::NPH; f++) {
+                                if constexpr (FACTOR == 4) SS_TP_VALU_FOLD3_PLAIN(mC, W, g, tcf);
+                                else {
                                     float a0, a1, a2;
-                                    if (FACTOR == 4) SS_TP_VALU_PLAIN3(a0, a1, a2, W, g, tcf[f]);
-                                    else {
-                                        SS_TP_VALU_PLAIN3(a0, a1, a2, W + 12, g, tcf[f]);              // taps 0 .. 11 over frames n - 11 .. n
-                                        SS_TP_VALU_PLAIN3_ACC(a0, a1, a2, W, g, tcf[f] + 12);          // taps 12 .. 23 over frames n - 23 .. n - 12
-                                    }
+                                    SS_TP_VALU_PLAIN3(a0, a1, a2, W + 12, g, tcf);              // taps 0 .. 11 over frames n - 11 .. n
+                                    SS_TP_VALU_PLAIN3_ACC(a0, a1, a2, W, g, tcf + 12);          // taps 12 .. 23 over frames n - 23 .. n - 12
                                     asm("v_max3_f32 %0, %0, |%1|, |%2|\n\tv_max_f32_e64 %0, %0, |%3|" : "+v"(mC) : "v"(a0), "v"(a1), "v"(a2));
                                 }
 #if defined(__HIP_DEVICE_COMPILE__)

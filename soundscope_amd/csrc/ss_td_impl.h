@@ -53,10 +53,11 @@ namespace ssk {
 //  * True peak at the crate's f32 width, the polyphase FIR  y_f[n] = sum_t c_f[t] x[n-t]  (an f32 fma chain per output), in the
 //    form that measured fastest for the shape (round 6):
 //      - 2 / 6 / 8 channels: on the packed-f32 VALU — a frame's pair of adjacent channels is one packed operand, a lane takes
-//        fifteen frames of one pair, taps broadcast from SGPR pairs through op_sel (SS_TP_VALU_PHASE3); factor 2 in the
-//        three-waves builds: the 24-tap branch's halves on neighbouring lanes, taps as per-lane VGPR pairs, one DPP add per result;
+//        fifteen frames of one pair, the three factor-4 branches folded about their centre, taps broadcast from SGPR pairs through
+//        op_sel (SS_TP_VALU_FOLD1); factor 2 in the three-waves builds: the 24-tap branch's halves on neighbouring lanes, taps as
+//        per-lane VGPR pairs, one DPP add per result (SS_TP_VALU_PHASE3V);
 //      - channel counts that do not divide sixteen, and factor 2 in the four-waves builds: plain v_fma_f32, a lane takes fifteen
-//        frames of ONE channel (SS_TP_VALU_PLAIN3);
+//        frames of ONE channel (SS_TP_VALU_FOLD3_PLAIN at factor 4, SS_TP_VALU_PLAIN3 at factor 2);
 //      - mono, 4 and 16 channels (and the four-waves builds of whole-stream workgroups): a banded-Toeplitz product on the f32
 //        matrix pipe over a block of BLK consecutive outputs,
 //          D[(f,r), col] = sum_k A[(f,r), k] * B[k, col],  A[(f,r), k] = c_f[HIST-1 + r - k],  B[k, col] = x[start_col - (HIST-1) + k],
@@ -120,15 +121,14 @@ static __device__ unsigned long long g_td_trace[32][16];
 #endif
 
 // packed-f32 forms of the true-peak interpolator (stereo: a frame (L, R) is one packed operand): acc += c x with the tap c broadcast
-// from the low / high half of an SGPR pair
+// from the low / high half of a register pair
 typedef float v2f_td __attribute__((ext_vector_type(2)));
 // One polyphase branch over THREE consecutive frames, both channels: out0..2 = sum over k of c[k] (L, R)[n - k], k ascending, as
 // three interleaved chains of twelve packed operations (a multiply, eleven FMAs) in ONE asm statement — between separate statements
 // the compiler keeps a wait state for hazards it cannot rule out for inline asm (an s_nop per three instructions).  Operands:
 // %0..%2 the three results (frames n, n + 1, n + 2), %3..%16 the window's fourteen frames (n - 11 .. n + 2), %17..%22 the taps as
-// six register pairs (c[2 m], c[2 m + 1]), broadcast through op_sel — SGPR pairs where the taps are the wave's, VGPR pairs where
-// neighbouring lanes run different halves of a longer branch (factor 2).
-#define SS_TP_VALU_PHASE3_(CK, o0, o1, o2, W, g, tc)                                                                        \
+// six VGPR pairs (c[2 m], c[2 m + 1]), broadcast through op_sel: neighbouring lanes run different halves of the factor-2 branch.
+#define SS_TP_VALU_PHASE3V(o0, o1, o2, W, g, tc)                                                                            \
     asm("v_pk_mul_f32 %0, %17, %14 op_sel:[0,0] op_sel_hi:[0,1]\n\t" \
         "v_pk_mul_f32 %1, %17, %15 op_sel:[0,0] op_sel_hi:[0,1]\n\t" \
         "v_pk_mul_f32 %2, %17, %16 op_sel:[0,0] op_sel_hi:[0,1]\n\t" \
@@ -169,9 +169,63 @@ typedef float v2f_td __attribute__((ext_vector_type(2)));
         : "v"(W[3 * (g) + 0]), "v"(W[3 * (g) + 1]), "v"(W[3 * (g) + 2]), "v"(W[3 * (g) + 3]), "v"(W[3 * (g) + 4]),       \
           "v"(W[3 * (g) + 5]), "v"(W[3 * (g) + 6]), "v"(W[3 * (g) + 7]), "v"(W[3 * (g) + 8]), "v"(W[3 * (g) + 9]),       \
           "v"(W[3 * (g) + 10]), "v"(W[3 * (g) + 11]), "v"(W[3 * (g) + 12]), "v"(W[3 * (g) + 13]),                        \
-          CK(tc[0]), CK(tc[1]), CK(tc[2]), CK(tc[3]), CK(tc[4]), CK(tc[5]))
-#define SS_TP_VALU_PHASE3(o0, o1, o2, W, g, tc) SS_TP_VALU_PHASE3_("s", o0, o1, o2, W, g, tc)       /* taps wave-uniform: SGPR pairs */
-#define SS_TP_VALU_PHASE3V(o0, o1, o2, W, g, tc) SS_TP_VALU_PHASE3_("v", o0, o1, o2, W, g, tc)      /* taps per lane: VGPR pairs */
+          "v"(tc[0]), "v"(tc[1]), "v"(tc[2]), "v"(tc[3]), "v"(tc[4]), "v"(tc[5]))
+
+// Factor 4, all three branches at once, folded about their centre (sst::true_peak_fold4: branch 3 is branch 1 reversed, branch 2
+// is its own reverse): for frame n and k < 6, u = x[n - k] + x[n - 11 + k] and v = x[n - k] - x[n - 11 + k] feed
+// s = (y1 + y3) / 2 += f0[k] u, y2 += f2[k] u and d = (y1 - y3) / 2 += f1[k] v, and max(|y1|, |y3|) = |s| + |d|: 12 additions and 18
+// products per frame where the three branches take 36.  ONE frame per statement, u and v in one temporary: interleaving three
+// frames as the unfolded form did needs 24 more registers than the four-waves builds have, and even a second temporary spills
+// the general-bins four-waves builds.  Packed, both channels of a pair: %0 u then v, %1..%3 s, y2, d; the frames n - 11 .. n as
+// %4..%15 (W[j] = frame n - 11), the taps (f0, f1, f2) as nine SGPR pairs %16..%24 broadcast through op_sel.  SS_TP_VALU_FOLD1_MAX then takes |s| + |d| and |y2| into the
+// running maxima of the two channels.
+#define SS_TP_VALU_FOLD1(S, Y, D, W, j, tf)                                                                                      \
+    do {                                                                                                                          \
+        v2f_td t_;                                                                                                                \
+        asm(                                                                                                                      \
+        "v_pk_add_f32 %0, %15, %4\n\t"                                                                                            \
+        "v_pk_mul_f32 %1, %16, %0 op_sel:[0,0] op_sel_hi:[0,1]\n\t"                                                               \
+        "v_pk_mul_f32 %2, %22, %0 op_sel:[0,0] op_sel_hi:[0,1]\n\t"                                                               \
+        "v_pk_add_f32 %0, %15, %4 neg_lo:[0,1] neg_hi:[0,1]\n\t"                                                                  \
+        "v_pk_mul_f32 %3, %19, %0 op_sel:[0,0] op_sel_hi:[0,1]\n\t"                                                               \
+        "v_pk_add_f32 %0, %14, %5\n\t"                                                                                            \
+        "v_pk_fma_f32 %1, %16, %0, %1 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_fma_f32 %2, %22, %0, %2 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %14, %5 neg_lo:[0,1] neg_hi:[0,1]\n\t"                                                                  \
+        "v_pk_fma_f32 %3, %19, %0, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %13, %6\n\t"                                                                                            \
+        "v_pk_fma_f32 %1, %17, %0, %1 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                       \
+        "v_pk_fma_f32 %2, %23, %0, %2 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %13, %6 neg_lo:[0,1] neg_hi:[0,1]\n\t"                                                                  \
+        "v_pk_fma_f32 %3, %20, %0, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %12, %7\n\t"                                                                                            \
+        "v_pk_fma_f32 %1, %17, %0, %1 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_fma_f32 %2, %23, %0, %2 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %12, %7 neg_lo:[0,1] neg_hi:[0,1]\n\t"                                                                  \
+        "v_pk_fma_f32 %3, %20, %0, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %11, %8\n\t"                                                                                            \
+        "v_pk_fma_f32 %1, %18, %0, %1 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                       \
+        "v_pk_fma_f32 %2, %24, %0, %2 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %11, %8 neg_lo:[0,1] neg_hi:[0,1]\n\t"                                                                  \
+        "v_pk_fma_f32 %3, %21, %0, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %10, %9\n\t"                                                                                            \
+        "v_pk_fma_f32 %1, %18, %0, %1 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_fma_f32 %2, %24, %0, %2 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"                                                       \
+        "v_pk_add_f32 %0, %10, %9 neg_lo:[0,1] neg_hi:[0,1]\n\t"                                                                  \
+        "v_pk_fma_f32 %3, %21, %0, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]"                                                           \
+            : "=&v"(t_), "=&v"(S), "=&v"(Y), "=&v"(D)                                                                            \
+            : "v"(W[(j) + 0]), "v"(W[(j) + 1]), "v"(W[(j) + 2]), "v"(W[(j) + 3]), "v"(W[(j) + 4]), "v"(W[(j) + 5]),              \
+              "v"(W[(j) + 6]), "v"(W[(j) + 7]), "v"(W[(j) + 8]), "v"(W[(j) + 9]), "v"(W[(j) + 10]), "v"(W[(j) + 11]),            \
+              "s"(tf[0]), "s"(tf[1]), "s"(tf[2]), "s"(tf[3]), "s"(tf[4]), "s"(tf[5]), "s"(tf[6]), "s"(tf[7]), "s"(tf[8]));       \
+    } while (0)
+#define SS_TP_VALU_FOLD1_MAX(mL, mR, S, Y, D)                                                                                    \
+    do {                                                                                                                          \
+        float sx_ = S.x, sy_ = S.y;                                                                                               \
+        asm("v_add_f32_e64 %2, |%2|, |%4|\n\tv_add_f32_e64 %3, |%3|, |%5|\n\t"                                                   \
+            "v_max3_f32 %0, %0, |%6|, %2\n\tv_max3_f32 %1, %1, |%7|, %3"                                                           \
+            : "+v"(mL), "+v"(mR), "+v"(sx_), "+v"(sy_)                                                                            \
+            : "v"(D.x), "v"(D.y), "v"(Y.x), "v"(Y.y));                                                                            \
+    } while (0)
 
 // The same over ONE channel with plain f32 FMAs (any channel count: a lane takes fifteen frames of one channel; on gfx950 a wave's
 // v_fma_f32 issues in 2.8 cycles against 5.2 for v_pk_fma_f32, so per MAC this is within a tenth of the packed form): twelve taps
@@ -263,6 +317,119 @@ typedef float v2f_td __attribute__((ext_vector_type(2)));
           "v"((W)[3 * (g) + 10]), "v"((W)[3 * (g) + 11]), "v"((W)[3 * (g) + 12]), "v"((W)[3 * (g) + 13]),                        \
           "s"((tc)[0]), "s"((tc)[1]), "s"((tc)[2]), "s"((tc)[3]), "s"((tc)[4]), "s"((tc)[5]),                                    \
           "s"((tc)[6]), "s"((tc)[7]), "s"((tc)[8]), "s"((tc)[9]), "s"((tc)[10]), "s"((tc)[11]))
+
+// The folded factor-4 form (SS_TP_VALU_FOLD1) over ONE channel with plain f32 instructions, three frames n .. n + 2 one after the
+// other in one statement, the maxima included: %0 the running maximum, %1 / %2 u / v, %3..%5 s, y2, d; window %6..%19 = frames
+// n - 11 .. n + 2, taps f0 / f1 / f2 as eighteen SGPRs %20..%37.
+#define SS_TP_VALU_FOLD3_PLAIN(m, W, g, tf)                                                                                      \
+    do {                                                                                                                          \
+        float u_, v_, s_, y_, d_;                                                                                                 \
+        asm(                                                                                                                      \
+        "v_add_f32 %1, %17, %6\n\t"                                                                                               \
+        "v_sub_f32 %2, %17, %6\n\t"                                                                                               \
+        "v_mul_f32 %3, %20, %1\n\t"                                                                                               \
+        "v_mul_f32 %4, %32, %1\n\t"                                                                                               \
+        "v_mul_f32 %5, %26, %2\n\t"                                                                                               \
+        "v_add_f32 %1, %16, %7\n\t"                                                                                               \
+        "v_sub_f32 %2, %16, %7\n\t"                                                                                               \
+        "v_fma_f32 %3, %21, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %33, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %27, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %15, %8\n\t"                                                                                               \
+        "v_sub_f32 %2, %15, %8\n\t"                                                                                               \
+        "v_fma_f32 %3, %22, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %34, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %28, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %14, %9\n\t"                                                                                               \
+        "v_sub_f32 %2, %14, %9\n\t"                                                                                               \
+        "v_fma_f32 %3, %23, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %35, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %29, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %13, %10\n\t"                                                                                              \
+        "v_sub_f32 %2, %13, %10\n\t"                                                                                              \
+        "v_fma_f32 %3, %24, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %36, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %30, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %12, %11\n\t"                                                                                              \
+        "v_sub_f32 %2, %12, %11\n\t"                                                                                              \
+        "v_fma_f32 %3, %25, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %37, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %31, %2, %5\n\t"                                                                                           \
+        "v_add_f32_e64 %3, |%3|, |%5|\n\t"                                                                                        \
+        "v_max3_f32 %0, %0, |%4|, %3\n\t"                                                                                         \
+        "v_add_f32 %1, %18, %7\n\t"                                                                                               \
+        "v_sub_f32 %2, %18, %7\n\t"                                                                                               \
+        "v_mul_f32 %3, %20, %1\n\t"                                                                                               \
+        "v_mul_f32 %4, %32, %1\n\t"                                                                                               \
+        "v_mul_f32 %5, %26, %2\n\t"                                                                                               \
+        "v_add_f32 %1, %17, %8\n\t"                                                                                               \
+        "v_sub_f32 %2, %17, %8\n\t"                                                                                               \
+        "v_fma_f32 %3, %21, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %33, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %27, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %16, %9\n\t"                                                                                               \
+        "v_sub_f32 %2, %16, %9\n\t"                                                                                               \
+        "v_fma_f32 %3, %22, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %34, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %28, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %15, %10\n\t"                                                                                              \
+        "v_sub_f32 %2, %15, %10\n\t"                                                                                              \
+        "v_fma_f32 %3, %23, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %35, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %29, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %14, %11\n\t"                                                                                              \
+        "v_sub_f32 %2, %14, %11\n\t"                                                                                              \
+        "v_fma_f32 %3, %24, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %36, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %30, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %13, %12\n\t"                                                                                              \
+        "v_sub_f32 %2, %13, %12\n\t"                                                                                              \
+        "v_fma_f32 %3, %25, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %37, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %31, %2, %5\n\t"                                                                                           \
+        "v_add_f32_e64 %3, |%3|, |%5|\n\t"                                                                                        \
+        "v_max3_f32 %0, %0, |%4|, %3\n\t"                                                                                         \
+        "v_add_f32 %1, %19, %8\n\t"                                                                                               \
+        "v_sub_f32 %2, %19, %8\n\t"                                                                                               \
+        "v_mul_f32 %3, %20, %1\n\t"                                                                                               \
+        "v_mul_f32 %4, %32, %1\n\t"                                                                                               \
+        "v_mul_f32 %5, %26, %2\n\t"                                                                                               \
+        "v_add_f32 %1, %18, %9\n\t"                                                                                               \
+        "v_sub_f32 %2, %18, %9\n\t"                                                                                               \
+        "v_fma_f32 %3, %21, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %33, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %27, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %17, %10\n\t"                                                                                              \
+        "v_sub_f32 %2, %17, %10\n\t"                                                                                              \
+        "v_fma_f32 %3, %22, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %34, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %28, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %16, %11\n\t"                                                                                              \
+        "v_sub_f32 %2, %16, %11\n\t"                                                                                              \
+        "v_fma_f32 %3, %23, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %35, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %29, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %15, %12\n\t"                                                                                              \
+        "v_sub_f32 %2, %15, %12\n\t"                                                                                              \
+        "v_fma_f32 %3, %24, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %36, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %30, %2, %5\n\t"                                                                                           \
+        "v_add_f32 %1, %14, %13\n\t"                                                                                              \
+        "v_sub_f32 %2, %14, %13\n\t"                                                                                              \
+        "v_fma_f32 %3, %25, %1, %3\n\t"                                                                                           \
+        "v_fma_f32 %4, %37, %1, %4\n\t"                                                                                           \
+        "v_fma_f32 %5, %31, %2, %5\n\t"                                                                                           \
+        "v_add_f32_e64 %3, |%3|, |%5|\n\t"                                                                                        \
+        "v_max3_f32 %0, %0, |%4|, %3"                                                                                             \
+            : "+v"(m), "=&v"(u_), "=&v"(v_), "=&v"(s_), "=&v"(y_), "=&v"(d_)                                                     \
+            : "v"((W)[3 * (g) + 0]), "v"((W)[3 * (g) + 1]), "v"((W)[3 * (g) + 2]), "v"((W)[3 * (g) + 3]),                        \
+              "v"((W)[3 * (g) + 4]), "v"((W)[3 * (g) + 5]), "v"((W)[3 * (g) + 6]), "v"((W)[3 * (g) + 7]),                        \
+              "v"((W)[3 * (g) + 8]), "v"((W)[3 * (g) + 9]), "v"((W)[3 * (g) + 10]), "v"((W)[3 * (g) + 11]),                      \
+              "v"((W)[3 * (g) + 12]), "v"((W)[3 * (g) + 13]),                                                                     \
+              "s"((tf)[0]), "s"((tf)[1]), "s"((tf)[2]), "s"((tf)[3]), "s"((tf)[4]), "s"((tf)[5]),                                \
+              "s"((tf)[6]), "s"((tf)[7]), "s"((tf)[8]), "s"((tf)[9]), "s"((tf)[10]), "s"((tf)[11]),                              \
+              "s"((tf)[12]), "s"((tf)[13]), "s"((tf)[14]), "s"((tf)[15]), "s"((tf)[16]), "s"((tf)[17]));                         \
+    } while (0)
 
 template <int FACTOR>
 struct TpCfg {
