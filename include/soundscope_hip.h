@@ -429,6 +429,46 @@ double ss_corpus_integrated_lufs(const uint64_t *block_hist1000);
 double ss_corpus_loudness_range(const uint64_t *st_hist1000);
 
 /* ------------------------------------------------------------------------- *
+ *  Meter banks: N independent live EBU R128 meters (one channel count, rate and true-peak rule) advanced together.  Stream s
+ *  of a bank behaves exactly like an ss_analyzer fed the same blocks (true peak in SS_TP_ARITH_F32, the handle's default); a
+ *  call costs a time-domain launch and a gating launch for ALL streams (calls longer than 32 sub-blocks are cut into pieces,
+ *  as ss_add_samples cuts them), a read one launch and one copy.  A non-finite sample poisons its own stream only.
+ *  Device memory per stream, laid out as a handle holds its meter: the filter state (9.3 KB), a 96-slot sub-block ring, the
+ *  filtered-sample ring of 3 s (rounded up to a whole 100 ms sub-block) x channels f64, two 1000-bin u64 histograms:
+ *  about 2.33 MB at 48 kHz stereo — 2.4 GB for 1024 streams.
+ *  Status codes: channels / rate outside EbuR128::new's range SS_ERR_NOMEM; a bad pointer, stream index, stride or format
+ *  SS_ERR_INVALID_ARG; a `cap` too small SS_ERR_CAPACITY; no device SS_ERR_DEVICE.  frames == 0 is a no-op.
+ * ------------------------------------------------------------------------- */
+typedef struct ss_meter_bank ss_meter_bank;
+typedef struct ss_meter_reading {
+    double momentary;        /* loudness_momentary(), LUFS (-inf for silence)                                      */
+    double shortterm;        /* loudness_shortterm(); NaN at rates where the crate's call fails (3 s < 30 sub-blocks) */
+    double integrated;       /* loudness_global()                                                                  */
+    double loudness_range;   /* loudness_range()                                                                   */
+    double true_peak[2];     /* channels 0, 1: max(true, sample) like ss_get_true_peak; [1] NaN if mono           */
+    double sample_peak[2];
+    uint64_t frames;         /* frames fed since this stream's last reset                                          */
+} ss_meter_reading;          /* 72 bytes */
+/* true_peak_factor: 0 the crate's rule for the rate, 2 or 4 forced (ss_analyzer_set_true_peak_factor) */
+int ss_meter_bank_create(uint32_t n_streams, uint32_t channels, uint32_t rate, int32_t true_peak_factor, ss_meter_bank **out);
+void ss_meter_bank_destroy(ss_meter_bank *m);
+/* every stream gets `frames` frames: pcm is [stream][frame][channel] f32, copied before the call returns */
+int ss_meter_bank_add(ss_meter_bank *m, const float *pcm, uint64_t frames);
+/* producers already on the GPU: stream s starts at pcm_device + s * stream_stride_floats (>= frames * channels); only
+ * queued — the buffer must stay unchanged until the next call that waits (ss_meter_bank_read, _peaks, _histograms) */
+int ss_meter_bank_add_device(ss_meter_bank *m, const float *pcm_device, uint64_t frames, uint64_t stream_stride_floats);
+/* raw little-endian interleaved PCM of an ss_pcm_format, [stream][frame][channel], converted on the device */
+int ss_meter_bank_add_pcm(ss_meter_bank *m, const void *pcm, uint64_t frames, int format);
+/* resets the listed streams (streams == NULL: all of them), as EbuR128::reset; the others are untouched */
+int ss_meter_bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count);
+/* one record per stream for the state after the last add; waits; one device-to-host copy */
+int ss_meter_bank_read(ss_meter_bank *m, ss_meter_reading *out, uint32_t cap_streams);
+/* every channel of one stream: true_pk[c] = max(true, sample) peak, sample_pk[c] (either may be NULL); cap < channels: SS_ERR_CAPACITY */
+int ss_meter_bank_peaks(ss_meter_bank *m, uint32_t stream, double *true_pk, double *sample_pk, uint32_t cap_channels);
+/* one stream's histograms: 1000 block-energy bins followed by 1000 short-term bins */
+int ss_meter_bank_histograms(ss_meter_bank *m, uint32_t stream, uint64_t *out2000);
+
+/* ------------------------------------------------------------------------- *
  *  Multi-GPU: one process per GPU, streams sharded over the ranks, and exactly ONE exchange —
  *  the SUM all-reduce of the two 1000-bin u64 histograms for the corpus-level integrated-LUFS gate
  *  (ebur128 loudness_global_multiple semantics; the reference app has no collective).  The library talks to

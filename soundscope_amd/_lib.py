@@ -44,6 +44,8 @@ SYMBOLS = [
     "ss_release_caches", "ss_batch_geometry_get_sized",
     "ss_inspect_kweight", "ss_inspect_true_peak", "ss_inspect_true_peak_fold", "ss_inspect_hann", "ss_inspect_bins", "ss_inspect_histogram",
     "ss_batch_download_loudness_series", "ss_batch_loudness_extremes",
+    "ss_meter_bank_create", "ss_meter_bank_destroy", "ss_meter_bank_add", "ss_meter_bank_add_device", "ss_meter_bank_add_pcm",
+    "ss_meter_bank_reset", "ss_meter_bank_read", "ss_meter_bank_peaks", "ss_meter_bank_histograms",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -104,6 +106,12 @@ class BatchGeometry(C.Structure):
 class LoudnessExtremes(C.Structure):
     _fields_ = [("max_momentary", C.c_double), ("max_shortterm", C.c_double),
                 ("max_momentary_at", C.c_uint32), ("max_shortterm_at", C.c_uint32)]
+
+
+class MeterReading(C.Structure):
+    _fields_ = [("momentary", C.c_double), ("shortterm", C.c_double), ("integrated", C.c_double),
+                ("loudness_range", C.c_double), ("true_peak", C.c_double * 2), ("sample_peak", C.c_double * 2),
+                ("frames", C.c_uint64)]
 
 
 class BatchLayout(C.Structure):
@@ -236,6 +244,15 @@ def _bind(lib):
         "ss_inspect_histogram": (C.c_int, [f64p, f64p]),
         "ss_batch_download_loudness_series": (C.c_int, [vp, C.c_uint32, f64p, f64p, C.c_size_t]),
         "ss_batch_loudness_extremes": (C.c_int, [vp, C.POINTER(LoudnessExtremes), C.c_uint32]),
+        "ss_meter_bank_create": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(vp)]),
+        "ss_meter_bank_destroy": (None, [vp]),
+        "ss_meter_bank_add": (C.c_int, [vp, f32p, C.c_uint64]),
+        "ss_meter_bank_add_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
+        "ss_meter_bank_add_pcm": (C.c_int, [vp, vp, C.c_uint64, C.c_int]),
+        "ss_meter_bank_reset": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_uint32]),
+        "ss_meter_bank_read": (C.c_int, [vp, vp, C.c_uint32]),
+        "ss_meter_bank_peaks": (C.c_int, [vp, C.c_uint32, f64p, f64p, C.c_uint32]),
+        "ss_meter_bank_histograms": (C.c_int, [vp, C.c_uint32, u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

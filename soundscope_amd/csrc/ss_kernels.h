@@ -149,8 +149,9 @@ struct TdParams {
     double *subblocks;           // [stream][slot][channels] f64, slot = sub-block index % sub_cap
     uint64_t sub_stride;         // doubles between streams
     uint32_t sub_cap;            // ring capacity in sub-blocks
-    double *ring;                // optional filtered-sample ring [ring_frames][channels] (handle API)
+    double *ring;                // optional filtered-sample ring [stream][ring_frames][channels] (handle API, meter banks)
     uint64_t ring_frames;
+    uint64_t ring_stride;        // doubles between the rings of consecutive streams (0: one stream, the handle)
     int32_t tp_factor;           // must equal k->tp_factor (selects the kernel instantiation)
     uint32_t s100;               // must equal k->s100
     uint32_t nseg;               // time segments per stream (1 for streaming calls)
@@ -236,6 +237,36 @@ hipError_t launch_ring_energy(const double *ring, uint64_t ring_frames, uint32_t
                               double *out2 /* energy, loudness: device or mapped host memory */,
                               double *scratch /* kRingScratchDoubles, zero before the first launch */,
                               hipStream_t s);
+
+// ---- meter banks (ss_meter_bank_*): N independent streaming meters advanced together --------------------------------------------
+// Per stream, laid out as a handle holds its meter: TdState, a sub-block ring [sub_cap][C], the filtered-sample ring
+// [ring_frames][C], histograms [2][1000], gating counts [2].
+struct MeterBankParams {
+    const TdConst *k;
+    TdState *state;                  // [stream]
+    double *subblocks; uint64_t sub_stride; uint32_t sub_cap;
+    double *ring; uint64_t ring_stride; uint64_t ring_frames;
+    const double *weights;           // [channels]
+    uint64_t *hist;                  // [stream][2][1000]
+    uint32_t *counts;                // [stream][2]
+    const double *hist_energies;     // 1000
+    const double *hist_bounds;       // 1001
+    uint32_t n_streams, channels;
+    uint32_t st_on;                  // 0: thirty sub-blocks are more than the crate's 3 s ring (the short-term reading is NaN)
+};
+// one record per stream, laid out as ss_meter_reading (include/soundscope_hip.h)
+struct MeterReading {
+    double momentary, shortterm, integrated, loudness_range;
+    double true_peak[2], sample_peak[2];
+    uint64_t frames;
+};
+// gating behind a time-domain launch of `frames` frames per stream: stream s's new sub-blocks are
+// [(fed - frames) / S, fed / S), fed = state[s].frames_fed (the streams' phases differ after a selective reset)
+hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, hipStream_t s);
+// every stream's readings into out[stream] (device or mapped host memory)
+hipError_t launch_meter_bank_readings(const MeterBankParams &p, MeterReading *out, hipStream_t s);
+// clears the listed streams' meters (streams == nullptr: streams 0 .. count - 1)
+hipError_t launch_meter_bank_reset(const MeterBankParams &p, const uint32_t *streams, uint32_t count, hipStream_t s);
 
 // ---- waveform ---------------------------------------------------------------
 struct WaveParams {

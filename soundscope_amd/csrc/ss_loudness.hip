@@ -284,6 +284,39 @@ __global__ __launch_bounds__(SMALL ? 256 : 1024) void k_finalize(FinalizeParams 
                   p.out_lra ? &p.out_lra[stream] : nullptr);
 }
 
+// The gating and short-term blocks of ONE stream that end with its sub-blocks [sub_begin, sub_end), by one wave: histogram
+// increments by global atomics into gh (block ++ short-term), the block counts into out_counts (nullable).  `bd`: the bin
+// boundaries (an LDS copy or the table itself: the same bins either way).  The streaming gating launches (a handle, a meter bank).
+__device__ __forceinline__ void gate_stream_range(const double *__restrict__ P, uint32_t cap, uint32_t C, const double *__restrict__ weights,
+                                                  const TdConst &K, const double *__restrict__ bd, double bd0, uint64_t sub_begin,
+                                                  uint64_t sub_end, uint64_t bad_from, unsigned long long *gh, uint32_t *out_counts,
+                                                  uint32_t lane)
+{
+    const double S = (double)K.s100;
+    uint32_t nb = 0, ns = 0;
+    for (uint64_t j = (sub_begin > 3 ? sub_begin : 3) + lane; j < sub_end; j += 64) {
+        double sum = window_energy_eager<4, false>(P, (uint32_t)(j % cap), cap, C, weights) / (4.0 * S);
+        if (j > bad_from) sum = __builtin_nan("");
+        nb++;
+        if (sum >= bd0) atomicAdd(&gh[hist_index(bd, sum)], 1ull);
+    }
+    if (!K.st_off) {
+        const uint64_t m_begin = sub_begin > 29 ? (sub_begin - 29 + 9) / 10 : 0;
+        for (uint64_t m = m_begin + lane;; m += 64) {
+            const uint64_t j = 29 + 10 * m;
+            if (j >= sub_end) break;
+            double sum = window_energy_eager<30, false>(P, (uint32_t)(j % cap), cap, C, weights) / (30.0 * S);
+            if (j > bad_from) sum = __builtin_nan("");
+            ns++;
+            if (sum >= bd0) atomicAdd(&gh[kHistBins + hist_index(bd, sum)], 1ull);
+        }
+    }
+    if (out_counts) {
+        if (nb) atomicAdd(&out_counts[0], nb);
+        if (ns) atomicAdd(&out_counts[1], ns);
+    }
+}
+
 // Streaming form (one handle, a few new sub-blocks per call, no per-call read-out): the same gating rules
 // with the histogram updated in place by global atomics instead of a 16 KB round trip through LDS.
 __global__ __launch_bounds__(64) void k_finalize_stream(FinalizeParams p)
@@ -299,32 +332,8 @@ __global__ __launch_bounds__(64) void k_finalize_stream(FinalizeParams p)
     const uint64_t bad_from = first_bad_subblock(p.state, p.channels, p.weights, (uint32_t)lane);
     __syncthreads();
     unsigned long long *gh = reinterpret_cast<unsigned long long *>(p.hist);
-    const uint32_t C = p.channels;
-    const double S = (double)p.k->s100;
-    const double *P = p.subblocks;
-    uint32_t nb = 0, ns = 0;
-    const uint32_t cap = p.sub_cap;
-    for (uint64_t j = (p.sub_begin > 3 ? p.sub_begin : 3) + lane; j < p.sub_end; j += 64) {
-        double sum = window_energy_eager<4, false>(P, (uint32_t)(j % cap), cap, C, p.weights) / (4.0 * S);
-        if (j > bad_from) sum = __builtin_nan("");
-        nb++;
-        if (sum >= bd0) atomicAdd(&gh[hist_index(bd, sum)], 1ull);
-    }
-    if (!p.k->st_off) {
-        const uint64_t m_begin = p.sub_begin > 29 ? (p.sub_begin - 29 + 9) / 10 : 0;
-        for (uint64_t m = m_begin + lane;; m += 64) {
-            const uint64_t j = 29 + 10 * m;
-            if (j >= p.sub_end) break;
-            double sum = window_energy_eager<30, false>(P, (uint32_t)(j % cap), cap, C, p.weights) / (30.0 * S);
-            if (j > bad_from) sum = __builtin_nan("");
-            ns++;
-            if (sum >= bd0) atomicAdd(&gh[kHistBins + hist_index(bd, sum)], 1ull);
-        }
-    }
-    if (p.out_counts) {
-        if (nb) atomicAdd(&p.out_counts[0], nb);
-        if (ns) atomicAdd(&p.out_counts[1], ns);
-    }
+    gate_stream_range(p.subblocks, p.sub_cap, p.channels, p.weights, *p.k, bd, bd0, p.sub_begin, p.sub_end, bad_from, gh, p.out_counts,
+                      (uint32_t)lane);
     // the handle's readings behind the update (what the reference's render loop asks for on its next frame): the same wave
     // evaluates the histograms it has just touched — no launch of its own inside a tick
     if (p.readings_out) {
@@ -584,6 +593,164 @@ hipError_t launch_ring_energy(const double *ring, uint64_t ring_frames, uint32_t
     const uint64_t begin = (end_frame % ring_frames + ring_frames - frames) % ring_frames;
     hipLaunchKernelGGL(k_ring_energy, dim3(kRingBlocks), dim3(256), 0, s, ring, (uint32_t)(ring_frames * channels), channels,
                        (uint32_t)(begin * channels), (uint32_t)(frames * channels), (double)frames, weights, scratch, out);
+    return hipGetLastError();
+}
+
+// ============================================================================
+//  Meter banks: N streaming meters advanced by one launch per stage
+// ============================================================================
+// Gating of every stream's new sub-blocks behind a bank's time-domain launch: one wave per stream, k_finalize_stream's gating
+// (the same window form, hence a handle's histograms bit for bit) over the stream's own range, derived from its frame count.
+// Streams that completed no sub-block leave at once.  The tables are read where they are (L2): a wave has a few blocks to gate.
+__global__ __launch_bounds__(64) void k_meter_bank_gate(MeterBankParams p, uint64_t frames)
+{
+    const uint32_t stream = blockIdx.x, lane = threadIdx.x;
+    const TdState *st = p.state + stream;
+    const uint64_t S = p.k->s100;
+    const uint64_t fed = st->frames_fed;
+    const uint64_t sb0 = (fed - frames) / S, sb1 = fed / S;
+    if (sb1 == sb0) return;
+    const uint64_t bad_from = first_bad_subblock(st, p.channels, p.weights, lane);
+    unsigned long long *gh = reinterpret_cast<unsigned long long *>(p.hist) + (size_t)stream * 2 * kHistBins;
+    gate_stream_range(p.subblocks + (size_t)stream * p.sub_stride, p.sub_cap, p.channels, p.weights, *p.k, p.hist_bounds,
+                      p.hist_bounds[0], sb0, sb1, bad_from, gh, p.counts + 2 * (size_t)stream, lane);
+}
+
+hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, hipStream_t s)
+{
+    if (p.n_streams == 0 || frames == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_meter_bank_gate, dim3(p.n_streams), dim3(64), 0, s, p, frames);
+    return hipGetLastError();
+}
+
+// Weighted energy of the N sub-blocks' worth of frames in front of frame F = k S + r of one stream (one wave; every lane gets it):
+// the tail of sub-block k - N from offset r (S - r frames of the filtered-sample ring; when r = 0 that sub-block is whole and comes
+// from the sub-block ring), the complete sub-blocks k - N + 1 ... k - 1 (sub-block ring) and the current partial sub-block
+// (TdState::acc).  What lies in front of frame 0 is zero, as in the crate's zeroed ring.  At most S C ring loads, where summing
+// the window itself would take N S C.
+template <int N>
+__device__ __forceinline__ double bank_window_energy(const MeterBankParams &p, const TdState &st, const double *__restrict__ P,
+                                                     const double *__restrict__ R, uint64_t F, uint32_t lane)
+{
+    const uint32_t C = p.channels, cap = p.sub_cap;
+    const uint64_t S = p.k->s100;
+    const uint64_t k = F / S;
+    const uint32_t r = (uint32_t)(F - k * S);
+    double e = 0.0;
+    for (uint32_t c = lane; c < C; c += 64u) {
+        const double w = p.weights[c];
+        if (w != 0.0) e += w * st.acc[c];
+    }
+    const uint32_t nq = r == 0u ? (uint32_t)N : (uint32_t)(N - 1);     // r = 0: sub-block k - N is whole, from the sub-block ring
+    for (uint32_t i = lane; i < nq * C; i += 64u) {
+        const uint32_t q = 1u + i / C, c = i - (q - 1u) * C;           // sub-block k - q, channel c
+        const double w = p.weights[c];
+        if (k >= q && w != 0.0) e += w * P[(size_t)((k - q) % cap) * C + c];
+    }
+    if (k >= (uint64_t)N && r != 0u) {
+        // one run of ring elements with at most one wrap (S - r <= ring_frames): an add and a compare per element, the channel
+        // advancing by a constant step; four loads in flight per lane
+        const uint32_t ring_elems = (uint32_t)(p.ring_frames * C);
+        const uint32_t begin = (uint32_t)((((k - N) * S + r) % p.ring_frames) * C);
+        const uint32_t total = (uint32_t)((S - r) * C);
+        const uint32_t cstep = 64u % C;
+        uint32_t c = lane % C, i = lane;
+        for (; i + 3u * 64u < total; i += 4u * 64u) {
+            double y[4], w[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                uint32_t el = begin + i + 64u * (uint32_t)q;
+                if (el >= ring_elems) el -= ring_elems;
+                y[q] = R[el];
+                w[q] = p.weights[c];
+                c += cstep; if (c >= C) c -= C;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) e = w[q] != 0.0 ? fma(w[q] * y[q], y[q], e) : e;
+        }
+        for (; i < total; i += 64u) {
+            uint32_t el = begin + i;
+            if (el >= ring_elems) el -= ring_elems;
+            const double y = R[el], w = p.weights[c];
+            e = w != 0.0 ? fma(w * y, y, e) : e;
+            c += cstep; if (c >= C) c -= C;
+        }
+    }
+    return wave_sum(e);
+}
+
+// One wave per stream: momentary and short-term loudness by the window decomposition above, integrated loudness and range by
+// eval_hist on the stream's histograms (a handle's evaluation: the same bits), the peaks of channels 0 and 1, the frame count.
+__global__ __launch_bounds__(64) void k_meter_bank_readings(MeterBankParams p, MeterReading *out)
+{
+    __shared__ unsigned long long hb[kHistBins];
+    __shared__ unsigned long long hs[kHistBins];
+    __shared__ double ev[2];
+    const uint32_t stream = blockIdx.x, lane = threadIdx.x;
+    const unsigned long long *gh = reinterpret_cast<const unsigned long long *>(p.hist) + (size_t)stream * 2 * kHistBins;
+    for (uint32_t i = lane; i < (uint32_t)kHistBins; i += 64u) { hb[i] = gh[i]; hs[i] = gh[kHistBins + i]; }
+    const TdState &st = p.state[stream];
+    const uint64_t F = st.frames_fed;
+    const double *P = p.subblocks + (size_t)stream * p.sub_stride;
+    const double *R = p.ring + (size_t)stream * p.ring_stride;
+    const double S = (double)p.k->s100;
+    const double em = bank_window_energy<4>(p, st, P, R, F, lane) / (4.0 * S);
+    const double es = p.st_on ? bank_window_energy<30>(p, st, P, R, F, lane) / (30.0 * S) : __builtin_nan("");
+    __syncthreads();
+    eval_hist(hb, hs, p.hist_energies, p.hist_bounds, &ev[0], &ev[1]);
+    if (lane == 0) {
+        MeterReading m;
+        m.momentary = energy_to_lufs(em);
+        m.shortterm = p.st_on ? energy_to_lufs(es) : __builtin_nan("");
+        m.integrated = ev[0];
+        m.loudness_range = ev[1];
+        for (uint32_t c = 0; c < 2u; c++) {
+            if (c < p.channels) {
+                const float sp = st.sample_peak[c], tp = st.true_peak[c];
+                m.sample_peak[c] = (double)sp;
+                m.true_peak[c] = (double)(tp > sp ? tp : sp);              // true_peak(): max(true, sample)
+            } else {
+                m.sample_peak[c] = m.true_peak[c] = __builtin_nan("");
+            }
+        }
+        m.frames = F;
+        out[stream] = m;
+    }
+}
+
+hipError_t launch_meter_bank_readings(const MeterBankParams &p, MeterReading *out, hipStream_t s)
+{
+    if (p.n_streams == 0) return hipSuccess;
+    if (p.ring_frames * p.channels >= (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_meter_bank_readings, dim3(p.n_streams), dim3(64), 0, s, p, out);
+    return hipGetLastError();
+}
+
+// Clears listed streams' meters: kResetBlocks workgroups per listed stream share its five regions (state, sub-block ring,
+// sample ring, histograms, counts), 64-bit stores.
+constexpr uint32_t kResetBlocks = 32;
+static_assert(sizeof(TdState) % 8 == 0, "TdState is cleared in 64-bit words");
+__global__ __launch_bounds__(256) void k_meter_bank_reset(MeterBankParams p, const uint32_t *streams)
+{
+    const uint32_t item = blockIdx.x / kResetBlocks, part = blockIdx.x - item * kResetBlocks;
+    const uint32_t s = streams ? streams[item] : item;
+    const uint64_t t0 = (uint64_t)part * 256u + threadIdx.x, stride = (uint64_t)kResetBlocks * 256u;
+    auto zero = [&](void *base, uint64_t words) {
+        uint64_t *w = static_cast<uint64_t *>(base);
+        for (uint64_t i = t0; i < words; i += stride) w[i] = 0ull;
+    };
+    zero(p.state + s, sizeof(TdState) / 8);
+    zero(p.subblocks + (size_t)s * p.sub_stride, (uint64_t)p.sub_cap * p.channels);
+    zero(p.ring + (size_t)s * p.ring_stride, p.ring_frames * p.channels);
+    zero(p.hist + (size_t)s * 2 * kHistBins, 2 * kHistBins);
+    zero(p.counts + 2 * (size_t)s, 1);
+}
+
+hipError_t launch_meter_bank_reset(const MeterBankParams &p, const uint32_t *streams, uint32_t count, hipStream_t s)
+{
+    if (count == 0) return hipSuccess;
+    if ((uint64_t)count * kResetBlocks > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_meter_bank_reset, dim3(count * kResetBlocks), dim3(256), 0, s, p, streams);
     return hipGetLastError();
 }
 

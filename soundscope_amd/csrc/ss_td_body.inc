@@ -829,12 +829,13 @@
             // tile's 3.8 us inside a tick (tools/probe_tick_tiles.py)
             const uint32_t rf32 = (uint32_t)p.ring_frames;
             uint32_t rpos = 0u;
+            double *const ring = RING ? p.ring + (size_t)stream * p.ring_stride : nullptr;     // (wave-uniform: a scalar base)
             if (RING) {
                 const uint32_t tile_rbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((fed0 + pos) % p.ring_frames));
                 rpos = tile_rbase + chunk * L;
                 if (rpos >= rf32) rpos -= rf32;
             }
-#define SS_RING_PUT(v_) do { if (RING) { p.ring[(size_t)rpos * C + ch] = (v_); rpos = rpos + 1u == rf32 ? 0u : rpos + 1u; } } while (0)
+#define SS_RING_PUT(v_) do { if (RING) { ring[(size_t)rpos * C + ch] = (v_); rpos = rpos + 1u == rf32 ? 0u : rpos + 1u; } } while (0)
             if (len == L) {
                 // sample peak over x[0 .. L+2]: the three look-ahead samples are the next chunk's (or the
                 // zeroed slack behind the tile), so including them cannot change the channel's maximum

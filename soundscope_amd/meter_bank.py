@@ -1,0 +1,79 @@
+"""Meter banks (include/soundscope_hip.h, "Meter banks"): N live EBU R128 meters of one shape, advanced together.
+
+Stream s of a bank behaves exactly like an `Analyzer` loudness meter fed the same blocks; a call advances every stream with a
+time-domain launch and a gating launch, and `read()` returns every stream's readings behind one launch and one copy.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .analyzer import _check
+
+READING_DTYPE = np.dtype([("momentary", "<f8"), ("shortterm", "<f8"), ("integrated", "<f8"), ("loudness_range", "<f8"),
+                          ("true_peak", "<f8", (2,)), ("sample_peak", "<f8", (2,)), ("frames", "<u8")])
+assert READING_DTYPE.itemsize == C.sizeof(L.MeterReading) == 72
+
+
+class MeterBank:
+    """`n_streams` meters of `channels` channels at `rate`; true_peak_factor 0 = the crate's rule for the rate, or 2 / 4."""
+
+    def __init__(self, n_streams, channels, rate, true_peak_factor=0):
+        self._h = C.c_void_p()
+        _check(L.lib().ss_meter_bank_create(n_streams, channels, rate, true_peak_factor, C.byref(self._h)))
+        self.n_streams, self.channels, self.rate = int(n_streams), int(channels), int(rate)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            L.lib().ss_meter_bank_destroy(self._h)
+            self._h = None
+
+    def _frames(self, size, per_sample=1):
+        per = self.n_streams * self.channels * per_sample
+        if size % per:
+            raise ValueError(f"{size} values are not whole frames of {self.n_streams} streams x {self.channels} channels")
+        return size // per
+
+    def add(self, pcm):
+        """pcm: [n_streams][frames * channels] f32 (any shape with that many values, stream-major)."""
+        a = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        _check(L.lib().ss_meter_bank_add(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), self._frames(a.size)))
+
+    def add_device(self, ptr, frames, stream_stride_floats):
+        """Device-resident f32 input: stream s at `ptr` + s * stream_stride_floats (an int device address, e.g. a tensor's
+        data_ptr()).  Only queued: the buffer must stay unchanged until the next read."""
+        _check(L.lib().ss_meter_bank_add_device(self._h, C.c_void_p(int(ptr)), int(frames), int(stream_stride_floats)))
+
+    def add_pcm(self, raw, fmt):
+        """Raw little-endian interleaved samples of an ss_pcm_format (bytes or a numpy array), [stream][frame][channel]."""
+        b = np.frombuffer(raw, np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+        sb = int(L.lib().ss_pcm_sample_bytes(int(fmt))) or 1
+        frames = self._frames(b.size, sb)
+        _check(L.lib().ss_meter_bank_add_pcm(self._h, b.ctypes.data_as(C.c_void_p), frames, int(fmt)))
+
+    def reset(self, streams=None):
+        """Reset the listed streams (None: all), as EbuR128::reset; the others are untouched."""
+        if streams is None:
+            _check(L.lib().ss_meter_bank_reset(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+        _check(L.lib().ss_meter_bank_reset(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+
+    def read(self):
+        """Every stream's readings: a structured array [n_streams] of READING_DTYPE (fields as ss_meter_reading)."""
+        out = np.empty(self.n_streams, READING_DTYPE)
+        _check(L.lib().ss_meter_bank_read(self._h, out.ctypes.data_as(C.c_void_p), self.n_streams))
+        return out
+
+    def peaks(self, stream):
+        """Every channel's (true_peak, sample_peak) of one stream, linear: arrays [channels] f64."""
+        tp, sp = np.empty(self.channels, np.float64), np.empty(self.channels, np.float64)
+        dp = C.POINTER(C.c_double)
+        _check(L.lib().ss_meter_bank_peaks(self._h, stream, tp.ctypes.data_as(dp), sp.ctypes.data_as(dp), self.channels))
+        return tp, sp
+
+    def histograms(self, stream):
+        """(block, short-term) histograms of one stream: two arrays [1000] u64."""
+        out = np.empty(2000, np.uint64)
+        _check(L.lib().ss_meter_bank_histograms(self._h, stream, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[:1000].copy(), out[1000:].copy()
