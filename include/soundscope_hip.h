@@ -468,6 +468,39 @@ int ss_meter_bank_peaks(ss_meter_bank *m, uint32_t stream, double *true_pk, doub
 /* one stream's histograms: 1000 block-energy bins followed by 1000 short-term bins */
 int ss_meter_bank_histograms(ss_meter_bank *m, uint32_t stream, uint64_t *out2000);
 
+/* Spectra of a bank: get_fft of every stream's newest SS_BANK_SPECTRUM_N frames, mid and side for stereo banks
+ * (the reference's microphone tick, tui.rs:1427-1445), one row per channel otherwise (as ss_batch does; the reference's mono
+ * device is a stereo bank fed a zero right channel, audio_capture.rs).  One launch transforms every row of every stream.
+ *  - The history is the raw input, not the meter: ss_meter_bank_reset leaves it alone (so does the reference's
+ *    analyzer.reset()), and a non-finite sample refuses a row only while it lies inside that row's window.  Every stream gets
+ *    the same frames per call, so one bank-wide frame counter places the window; a call longer than the window keeps its newest
+ *    SS_BANK_SPECTRUM_N frames.  The window starts full of zeros, as the reference's capture ring does (tui.rs:1783-1784).
+ *  - Refusals follow the crate's order on the windowed signal (for stereo the f32 mid / side values): a windowed NaN (an
+ *    infinite sample under a zero window weight included; +inf in L with -inf in R is a NaN mid) SS_ERR_NAN, else a windowed
+ *    infinity (two finite samples near FLT_MAX overflow the mid) SS_ERR_INFINITY, else a non-finite dB value (the magnitude's
+ *    square overflowed) SS_ERR_SCALING — each exactly what ss_get_fft returns for that window.  A refused row is all NaN.
+ *  - Not enabled SS_ERR_INVALID_MODE; a `cap` too small SS_ERR_CAPACITY; bad cols / gain mode SS_ERR_INVALID_ARG. */
+#define SS_BANK_SPECTRUM_N SS_TICK_WINDOW   /* 16384 frames: tui.rs:1431 / :1488 */
+/* enable != 0: a zeroed history of the newest SS_BANK_SPECTRUM_N frames of every stream (4 * channels * 16384 bytes per
+ * stream); frames added from now on enter it.  Enabling again starts from zeros; enable == 0 frees it.  SS_ERR_FREQ_LIMIT
+ * where get_fft would refuse (20000 > rate / 2 as f32), before anything is allocated.  A bank without the spectrum launches
+ * exactly what it did before. */
+int ss_meter_bank_spectrum_enable(ss_meter_bank *m, int enable);
+/* rows per stream (2 = mid, side for stereo banks, otherwise one per channel), retained bins, and per bin the chart x (the
+ * first element of get_fft's pairs) and the f64 pink compensation (either array may be NULL) */
+int ss_meter_bank_spectrum_layout(const ss_meter_bank *m, uint32_t *rows_per_stream, uint32_t *n_bins,
+                                  double *chart_x, double *pink, uint32_t cap_bins);
+/* the window [fed - 16384, fed) of every stream after the last add: rows [stream][row][n_bins] f32 = the dBFS value BEFORE pink
+ * compensation, so that (double)row[i] + pink[i] is, bit for bit, the second element of the pair ss_get_fft returns for the same
+ * samples; status[stream * rows + row] = SS_OK or the refusal above.  Waits; one launch and one copy. */
+int ss_meter_bank_spectrum(ss_meter_bank *m, float *rows, size_t cap_floats, int32_t *status, uint32_t cap_rows);
+/* the same windows reduced on the device to `cols` chart columns (1 .. 512) by ss_batch_render_spectrum's rule applied to
+ * v[i] = (float)((double)row[i] + pink[i]): max over the column of clamp(v + gain, -100, 0) in f32, NaN for a column without
+ * a bin or a refused row; gain_mode SS_GAIN_FIXED (gain_db) or SS_GAIN_REFERENCE (-13 - (float)integrated of each stream's
+ * meter after the last add, as ss_meter_bank_read returns it).  out is [stream][row][cols]; the rows are never stored. */
+int ss_meter_bank_spectrum_columns(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db,
+                                   float *out, size_t cap_floats, int32_t *status, uint32_t cap_rows);
+
 /* ------------------------------------------------------------------------- *
  *  Multi-GPU: one process per GPU, streams sharded over the ranks, and exactly ONE exchange —
  *  the SUM all-reduce of the two 1000-bin u64 histograms for the corpus-level integrated-LUFS gate

@@ -46,6 +46,7 @@ SYMBOLS = [
     "ss_batch_download_loudness_series", "ss_batch_loudness_extremes",
     "ss_meter_bank_create", "ss_meter_bank_destroy", "ss_meter_bank_add", "ss_meter_bank_add_device", "ss_meter_bank_add_pcm",
     "ss_meter_bank_reset", "ss_meter_bank_read", "ss_meter_bank_peaks", "ss_meter_bank_histograms",
+    "ss_meter_bank_spectrum_enable", "ss_meter_bank_spectrum_layout", "ss_meter_bank_spectrum", "ss_meter_bank_spectrum_columns",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -253,6 +254,10 @@ def _bind(lib):
         "ss_meter_bank_read": (C.c_int, [vp, vp, C.c_uint32]),
         "ss_meter_bank_peaks": (C.c_int, [vp, C.c_uint32, f64p, f64p, C.c_uint32]),
         "ss_meter_bank_histograms": (C.c_int, [vp, C.c_uint32, u64p]),
+        "ss_meter_bank_spectrum_enable": (C.c_int, [vp, C.c_int]),
+        "ss_meter_bank_spectrum_layout": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f64p, f64p, C.c_uint32]),
+        "ss_meter_bank_spectrum": (C.c_int, [vp, f32p, C.c_size_t, C.POINTER(C.c_int32), C.c_uint32]),
+        "ss_meter_bank_spectrum_columns": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_float, f32p, C.c_size_t, C.POINTER(C.c_int32), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

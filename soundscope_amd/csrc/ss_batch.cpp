@@ -89,13 +89,6 @@ bool &batch_corpus_reduced(ss_batch *b) { return b->corpus_reduced; }
 
 namespace {
 
-// chart column of a bin: floor(chart_x / 100 * cols), the last column closed on the right (include/soundscope_hip.h)
-uint32_t spectrum_column_of(double chart_x, uint32_t cols)
-{
-    double f = std::floor(chart_x / 100.0 * (double)cols);
-    if (f < 0) f = 0;
-    return f >= (double)cols ? cols - 1 : (uint32_t)f;
-}
 
 int batch_collect_timing(ss_batch *b)
 {

@@ -1674,6 +1674,145 @@ hipError_t launch_fft_generic(const FftBatchParams &p, int mode, hipStream_t s)
     return hipGetLastError();
 }
 
+// ============================================================================
+//  Meter-bank spectra (include/soundscope_hip.h, "Meter banks"): the window [fed - 16384, fed) of every row of every stream of a
+//  bank, one 512-thread workgroup per (stream, row), running fft16k_transform — the arithmetic of k_fft16k, so a row is the same
+//  bits ss_get_fft reads back for the same samples.  The window lives in a per-stream ring of the newest 16384 frames (slot =
+//  frame & 16383), so every frame index of the loader is masked: any window start, odd or wrapping.
+//  Refusals, in the crate's order, from the windowed values the loader forms: a NaN (an infinity under a zero window weight
+//  included) -> SS_ERR_NAN, else an infinity -> SS_ERR_INFINITY, else a non-finite dB value (the magnitude's square overflowed)
+//  -> SS_ERR_SCALING.  The loader's two flags are folded per wave into LDS ahead of the transform's first barrier and read behind
+//  the workgroup's last one, which the SS_ERR_SCALING flag and the column flush need anyway.  A refused row is all NaN.
+//  COLS: the rows are never stored.  v = (float)((double)dB + pink) is folded into its chart column (LDS ds_max_f32, like
+//  k_fft4096_ms1's columns) and gain and clamp are applied once per column at the flush: max(clamp(v + g)) == clamp(max(v) + g).
+// ============================================================================
+constexpr int32_t kBankStNan = 11, kBankStInf = 12, kBankStScaling = 15;   // SS_ERR_NAN, SS_ERR_INFINITY, SS_ERR_SCALING
+constexpr uint32_t kBankSpecMask = kBankSpecN - 1u;
+
+template <bool COLS>
+struct BankWindow {
+    const BankSpectrumParams &q;
+    lds_f32 *acc;                    // COLS: the row's column accumulators
+    uint32_t *wave_flags;            // [8]: each wave's non-finite flags
+    uint32_t stream, sig;                 // sig: the row's signal (mid / side, or a channel)
+    const float *ring = nullptr;
+    uint32_t nf = 0;                 // bit 0: a windowed NaN, bit 1: a windowed infinity
+    uint32_t bad = 0;                // a non-finite dB value
+    __device__ __forceinline__ bool begin()
+    {
+        ring = q.hist + (size_t)stream * kBankSpecN * q.channels;
+        return true;
+    }
+    __device__ __forceinline__ v2f load(uint32_t i)
+    {
+        const uint32_t f0 = (q.start + 2u * i) & kBankSpecMask, f1 = (q.start + 2u * i + 1u) & kBankSpecMask;
+        float x0, x1;
+        if (q.channels == 2) {                                             // mid / side (audio_player.rs:400-419)
+            const float2 va = reinterpret_cast<const float2 *>(ring)[f0], vb = reinterpret_cast<const float2 *>(ring)[f1];
+            x0 = sig == 0 ? (va.x + va.y) * 0.5f : (va.x - va.y) * 0.5f;
+            x1 = sig == 0 ? (vb.x + vb.y) * 0.5f : (vb.x - vb.y) * 0.5f;
+        } else {
+            x0 = ring[(size_t)f0 * q.channels + sig];
+            x1 = ring[(size_t)f1 * q.channels + sig];
+        }
+        const float2 hw = *reinterpret_cast<const float2 *>(q.f.window + 2 * (size_t)i);
+        const float a = x0 * hw.x, b = x1 * hw.y;
+        nf |= (a != a || b != b) ? 1u : 0u;
+        nf |= (__builtin_fabsf(a) == __builtin_inff() || __builtin_fabsf(b) == __builtin_inff()) ? 2u : 0u;
+        return v2f{a, b};
+    }
+    __device__ __forceinline__ void loaded() const
+    {
+        const uint32_t w = (__ballot(nf & 1u) ? 1u : 0u) | (__ballot(nf & 2u) ? 2u : 0u);
+        if ((threadIdx.x & 63u) == 0) wave_flags[threadIdx.x >> 6] = w;
+    }
+    __device__ __forceinline__ auto row()
+    {
+        BankWindow *self = this;
+        float *o = q.out + ((size_t)stream * q.rows + sig) * q.f.n_bins;
+        return [self, o](uint32_t idx, float r, float pk) {
+            const float v = r + pk;                                        // (pk = 0: the value k_fft16k stores for ss_get_fft)
+            self->bad |= (__builtin_fabsf(v) <= 3.402823466e38f) ? 0u : 1u;
+            if (COLS) lds_fmax(self->acc + self->q.bin_col[idx], (float)((double)v + self->q.pink[idx]));
+            else o[idx] = v;
+        };
+    }
+    __device__ __forceinline__ void done() const {}
+};
+
+template <bool COLS>
+__global__ __launch_bounds__(512, 2) void k_meter_bank_spectrum(BankSpectrumParams q)
+{
+    constexpr int kAccBytes = COLS ? 512 * 4 : 0;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kFft16kLdsBytes + kAccBytes + 64];
+    static_assert(sizeof(lds) <= 80 * 1024, "two workgroups per CU");
+    lds_f32 *acc = (lds_f32 *)(lds_char *)(lds + kFft16kLdsBytes);
+    uint32_t *flags = reinterpret_cast<uint32_t *>(lds + kFft16kLdsBytes + kAccBytes);      // [0, 8): loads, [8, 16): dB values
+    const uint32_t stream = blockIdx.x / q.rows, row = blockIdx.x % q.rows;
+    if (COLS)
+        for (uint32_t c = threadIdx.x; c < q.cols; c += 512u) acc[c] = q.col_init[c];   // (ordered by the transform's barriers)
+    BankWindow<COLS> src{q, acc, flags, stream, row};
+    fft16k_transform(q.f, src, lds);
+    if (__ballot(src.bad) && (threadIdx.x & 63u) == 0) flags[8 + (threadIdx.x >> 6)] = 1u;
+    else if ((threadIdx.x & 63u) == 0) flags[8 + (threadIdx.x >> 6)] = 0u;
+    __syncthreads();
+    uint32_t nf = 0, sc = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) { nf |= flags[w]; sc |= flags[8 + w]; }
+    const int32_t st = (nf & 1u) ? kBankStNan : (nf & 2u) ? kBankStInf : sc ? kBankStScaling : 0;
+    if (threadIdx.x == 0) q.status[blockIdx.x] = st;
+    if (COLS) {
+        const float gain = q.integrated ? -13.0f - (float)q.integrated[(size_t)stream * q.integrated_stride] : q.gain_db;   // tui.rs:1234
+        float *oc = q.out + (size_t)blockIdx.x * q.cols;
+        for (uint32_t c = threadIdx.x; c < q.cols; c += 512u) {
+            const float k = acc[c];
+            const bool none = k != k;                                      // NaN: the column owns no bin
+            oc[c] = (st || none) ? __builtin_nanf("") : fminf(fmaxf(k + gain, -100.0f), 0.0f);
+        }
+    } else if (st) {
+        float *o = q.out + (size_t)blockIdx.x * q.f.n_bins;
+        for (uint32_t idx = threadIdx.x; idx < q.f.n_bins; idx += 512u) o[idx] = __builtin_nanf("");   // (this thread's own bins)
+    }
+}
+
+hipError_t launch_meter_bank_spectrum(const BankSpectrumParams &p, bool columns, hipStream_t s)
+{
+    if (!p.n_streams || !p.rows || !p.f.n_bins) return hipSuccess;
+    const dim3 grid(p.n_streams * p.rows), block(512);
+    if (columns) hipLaunchKernelGGL(k_meter_bank_spectrum<true>, grid, block, 0, s, p);
+    else hipLaunchKernelGGL(k_meter_bank_spectrum<false>, grid, block, 0, s, p);
+    return hipGetLastError();
+}
+
+// the newest min(frames, 16384) frames of every stream's input into its history ring
+__global__ __launch_bounds__(256) void k_bank_history_append(float *hist, const float *pcm, uint64_t stride, uint64_t first_frame,
+                                                             uint32_t take, uint32_t slot0, uint32_t n_streams, uint32_t channels)
+{
+    const uint32_t per = take * channels;
+    for (uint32_t s = blockIdx.y; s < n_streams; s += gridDim.y) {
+        const float *src = pcm + (size_t)s * stride + first_frame * channels;
+        float *dst = hist + (size_t)s * kBankSpecN * channels;
+        for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < per; e += gridDim.x * 256u) {
+            const uint32_t f = e / channels, c = e - f * channels;
+            dst[(size_t)((slot0 + f) & kBankSpecMask) * channels + c] = src[e];
+        }
+    }
+}
+
+hipError_t launch_bank_history_append(float *hist, const float *pcm, uint64_t stride, uint64_t frames, uint64_t fed,
+                                      uint32_t n_streams, uint32_t channels, hipStream_t s)
+{
+    if (!frames || !n_streams) return hipSuccess;
+    const uint32_t take = frames < kBankSpecN ? (uint32_t)frames : kBankSpecN;
+    const uint64_t first = frames - take;
+    const uint32_t slot0 = (uint32_t)((fed + first) & kBankSpecMask);
+    const uint32_t per = take * channels;
+    const uint32_t gx = (per + 255u) / 256u;
+    const dim3 grid(gx < 64u ? gx : 64u, n_streams < 65535u ? n_streams : 65535u);
+    hipLaunchKernelGGL(k_bank_history_append, grid, dim3(256), 0, s, hist, pcm, stride, first, take, slot0, n_streams, channels);
+    return hipGetLastError();
+}
+
 }  // namespace ssk
 
 #ifdef SS_FFT_PROF

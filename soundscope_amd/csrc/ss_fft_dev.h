@@ -168,7 +168,17 @@ constexpr int kPlane = 16 * kRow;   // 288 complex per outer index; 16 planes = 
 //  TWO of these workgroups on an otherwise idle chip, and one exposed memory round trip per bin was most of its 17 us.
 // ============================================================================
 constexpr int kFft16kLdsBytes = (2 * 16 * kPlane + 256) * 8;                // 75776
-__device__ __forceinline__ void fft16k_window(const FftBatchParams &p, int midside, uint32_t fft_ch, uint32_t bid, void *lds)
+// The body, with what varies between its users in a window source `src` (the arithmetic is one text, so every user's dB values
+// are the same bits for the same windowed samples):
+//   src.begin():   which window this workgroup transforms; false: none (the transform returns at once)
+//   src.load(i):   the windowed real samples 2i, 2i + 1 of the window as one complex value
+//   src.loaded():  called once a thread's 32 values are loaded, ahead of the transform's first barrier (a meter bank folds its
+//                  non-finite flags there without a barrier of its own)
+//   src.row():     called once the transform is published; returns store(idx, r, pk), which takes the dB value r (pink not
+//                  added) of retained bin first_bin + idx and pk = p.pink[idx] (0 without p.pink)
+//   src.done():    called behind the last store
+template <class Src>
+__device__ __forceinline__ void fft16k_transform(const FftBatchParams &p, Src &src, void *lds)
 {
     v2f (*const xbuf2)[16 * kPlane] = reinterpret_cast<v2f (*)[16 * kPlane]>(lds);      // [2][16 * kPlane]: 2 x 36864 B
     v2f *const tw2s = reinterpret_cast<v2f *>(lds) + 2 * 16 * kPlane;                    // [256]
@@ -177,39 +187,16 @@ __device__ __forceinline__ void fft16k_window(const FftBatchParams &p, int midsi
     const int q = threadIdx.x >> 8;                 // which half-problem
     const int t = threadIdx.x & 255;
     v2f *xbuf = xbuf2[q];
-    const uint32_t ch = bid % fft_ch; bid /= fft_ch;
-    const uint32_t w = bid % p.n_windows;
-    const uint32_t stream = bid / p.n_windows;
-    if (p.windows_of && w >= p.windows_of[stream]) return;                          // ragged batches
-    const size_t start = p.first_start + (size_t)w * p.hop;
-    const float *base = p.pcm + ((size_t)stream * p.frames_per_stream + start) * p.channels;
+    if (!src.begin()) return;
     const v2f *tw16k = reinterpret_cast<const v2f *>(p.tw_n);       // W_16384^k, k < 8192
     const v2f *tw4k = reinterpret_cast<const v2f *>(p.tw_core);     // W_4096^k
     if (threadIdx.x < 256) tw2s[t] = reinterpret_cast<const v2f *>(p.tw_256)[t];
 
-    // windowed real samples 2i, 2i+1 as one complex value
-    auto zload = [&](uint32_t i) -> v2f {
-        float x0, x1;
-        if (midside) {
-            const float2 va = reinterpret_cast<const float2 *>(base)[2 * (size_t)i];       // frames 2i, 2i+1: (l,r)
-            const float2 vb = reinterpret_cast<const float2 *>(base)[2 * (size_t)i + 1];
-            x0 = ch == 0 ? (va.x + va.y) * 0.5f : (va.x - va.y) * 0.5f;
-            x1 = ch == 0 ? (vb.x + vb.y) * 0.5f : (vb.x - vb.y) * 0.5f;
-        } else if (p.channels == 1) {
-            const float2 v = reinterpret_cast<const float2 *>(base)[i];                     // mono buffer: samples 2i, 2i+1 in one load
-            x0 = v.x; x1 = v.y;
-        } else {
-            x0 = base[(size_t)(2 * i) * p.channels + ch];
-            x1 = base[(size_t)(2 * i + 1) * p.channels + ch];
-        }
-        const float2 hw = *reinterpret_cast<const float2 *>(p.window + 2 * (size_t)i);
-        return v2f{x0 * hw.x, x1 * hw.y};
-    };
     v2f z[16];
 #pragma unroll
     for (int j = 0; j < 16; j++) {
         const uint32_t i = (uint32_t)t + 256u * j;
-        const v2f a = zload(i), b = zload(i + 4096u);
+        const v2f a = src.load(i), b = src.load(i + 4096u);
         z[j] = q ? pk_cmul(a - b, tw16k[2 * i]) : a + b;             // W_8192^i = W_16384^(2i)
     }
     const int tb = t & 15, hi = t >> 4;
@@ -228,6 +215,7 @@ __device__ __forceinline__ void fft16k_window(const FftBatchParams &p, int midsi
         if (ka & 12) v = pk_cmul(v, twg[ka & 12]);
         xbuf[X1W(ka, tb, hi)] = v;
     }
+    src.loaded();
     __syncthreads();
 #pragma unroll
     for (int ta = 0; ta < 16; ta++) z[ta] = xbuf[X1W(hi, tb, ta)];
@@ -246,7 +234,7 @@ __device__ __forceinline__ void fft16k_window(const FftBatchParams &p, int midsi
     for (int kc = 0; kc < 16; kc++) xbuf[kc * 256 + t] = z[R16(kc)];
     __syncthreads();
     // ---- real-FFT recombination + dB for the retained bins; consecutive threads own consecutive bins
-    float *o = p.out + (((size_t)stream * p.n_windows + w) * fft_ch + ch) * p.bin_stride;
+    const auto store = src.row();
     constexpr int kAhead = 8;
     for (uint32_t idx0 = threadIdx.x; idx0 < p.n_bins; idx0 += 512u * kAhead) {
         v2f wv[kAhead];
@@ -283,18 +271,73 @@ __device__ __forceinline__ void fft16k_window(const FftBatchParams &p, int midsi
             const float qv = fmaf(xr, xr, xi * xi);
             float r = fmaf(__log2f(qv), 3.01029995663981195f, p.db_offset);
             r = (qv == 0.0f) ? -150.0f : r;
-            o[idx] = r + pk[m];
+            store(idx, r, pk[m]);
         }
     }
-    if (p.done_flag) {
-        // every wave completes its own stores system-wide (a workgroup barrier alone does not wait for vector stores), then one
-        // lane tells the host: whoever sees the flag sees the row
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(p.done_flag + ch, p.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    src.done();
 #undef X1W
 #undef X2W
+}
+
+// k_fft16k and k_tick: window w of channel ch of stream `stream` in a contiguous buffer; midside 0: mono buffer or channel `ch` of
+// an interleaved one, 1: stereo -> mid/side
+struct Fft16kFlat {
+    const FftBatchParams &p;
+    int midside;
+    uint32_t fft_ch, bid;
+    uint32_t ch, w, stream;
+    const float *base;
+    __device__ __forceinline__ bool begin()
+    {
+        ch = bid % fft_ch; bid /= fft_ch;
+        w = bid % p.n_windows;
+        stream = bid / p.n_windows;
+        if (p.windows_of && w >= p.windows_of[stream]) return false;                  // ragged batches
+        const size_t start = p.first_start + (size_t)w * p.hop;
+        base = p.pcm + ((size_t)stream * p.frames_per_stream + start) * p.channels;
+        return true;
+    }
+    // windowed real samples 2i, 2i+1 as one complex value
+    __device__ __forceinline__ v2f load(uint32_t i) const
+    {
+        float x0, x1;
+        if (midside) {
+            const float2 va = reinterpret_cast<const float2 *>(base)[2 * (size_t)i];       // frames 2i, 2i+1: (l,r)
+            const float2 vb = reinterpret_cast<const float2 *>(base)[2 * (size_t)i + 1];
+            x0 = ch == 0 ? (va.x + va.y) * 0.5f : (va.x - va.y) * 0.5f;
+            x1 = ch == 0 ? (vb.x + vb.y) * 0.5f : (vb.x - vb.y) * 0.5f;
+        } else if (p.channels == 1) {
+            const float2 v = reinterpret_cast<const float2 *>(base)[i];                     // mono buffer: samples 2i, 2i+1 in one load
+            x0 = v.x; x1 = v.y;
+        } else {
+            x0 = base[(size_t)(2 * i) * p.channels + ch];
+            x1 = base[(size_t)(2 * i + 1) * p.channels + ch];
+        }
+        const float2 hw = *reinterpret_cast<const float2 *>(p.window + 2 * (size_t)i);
+        return v2f{x0 * hw.x, x1 * hw.y};
+    }
+    __device__ __forceinline__ void loaded() const {}
+    __device__ __forceinline__ auto row() const
+    {
+        float *o = p.out + (((size_t)stream * p.n_windows + w) * fft_ch + ch) * p.bin_stride;
+        return [o](uint32_t idx, float r, float pk) { o[idx] = r + pk; };
+    }
+    __device__ __forceinline__ void done() const
+    {
+        if (p.done_flag) {
+            // every wave completes its own stores system-wide (a workgroup barrier alone does not wait for vector stores), then
+            // one lane tells the host: whoever sees the flag sees the row
+            __threadfence_system();
+            __syncthreads();
+            if (threadIdx.x == 0) __hip_atomic_store(p.done_flag + ch, p.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+};
+
+__device__ __forceinline__ void fft16k_window(const FftBatchParams &p, int midside, uint32_t fft_ch, uint32_t bid, void *lds)
+{
+    Fft16kFlat src{p, midside, fft_ch, bid, 0u, 0u, 0u, nullptr};
+    fft16k_transform(p, src, lds);
 }
 
 }  // namespace ssk

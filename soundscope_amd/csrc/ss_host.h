@@ -142,6 +142,13 @@ SS_HIDDEN int get_bin_tables(uint32_t rate, size_t n, BinTables **out);
 SS_HIDDEN int get_td_tables(uint32_t rate, int factor, uint32_t channels, TdTables **out);
 SS_HIDDEN int get_hist_tables(const double **energies, const double **bounds);
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
+// chart column of a bin: floor(chart_x / 100 * cols), the last column closed on the right (include/soundscope_hip.h)
+inline uint32_t spectrum_column_of(double chart_x, uint32_t cols)
+{
+    double f = std::floor(chart_x / 100.0 * (double)cols);
+    if (f < 0) f = 0;
+    return f >= (double)cols ? cols - 1 : (uint32_t)f;
+}
 
 // run-in of a time segment that starts from a zero filter state, in 100 ms sub-blocks.  What the missing history would
 // have contributed to the OUTPUT is the tail of the K-weighting impulse response: the slowest pole pair (38 Hz high-pass,

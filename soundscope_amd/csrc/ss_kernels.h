@@ -268,6 +268,29 @@ hipError_t launch_meter_bank_readings(const MeterBankParams &p, MeterReading *ou
 // clears the listed streams' meters (streams == nullptr: streams 0 .. count - 1)
 hipError_t launch_meter_bank_reset(const MeterBankParams &p, const uint32_t *streams, uint32_t count, hipStream_t s);
 
+// meter-bank spectra (ss_fft.hip): every stream's newest 16384 frames, kept in a ring, transformed in one launch
+constexpr uint32_t kBankSpecN = 16384;
+struct BankSpectrumParams {
+    FftBatchParams f;                // the transform's tables, first_bin / n_bins / db_offset (pink = nullptr, out unused)
+    const float *hist;               // [stream][kBankSpecN][channels] f32 ring, frame j at slot j & (kBankSpecN - 1)
+    uint32_t start;                  // slot of the window's first frame (fed - kBankSpecN, masked)
+    uint32_t n_streams, channels, rows;   // rows per stream: 2 (mid, side) for stereo, otherwise channels
+    int32_t *status;                 // [stream][row]
+    float *out;                      // rows: [stream][row][n_bins]; columns: [stream][row][cols]
+    // columns (k_meter_bank_spectrum<true>)
+    const double *pink;              // n_bins f64 pink compensation
+    const uint16_t *bin_col;         // n_bins: chart column of every retained bin
+    const float *col_init;           // cols: -inf where the column owns a bin, NaN where it owns none
+    const double *integrated;        // SS_GAIN_REFERENCE: stream s's integrated loudness at integrated[s * integrated_stride]
+    uint32_t integrated_stride;      // (doubles)
+    uint32_t cols;                   // 1 .. 512
+    float gain_db;
+};
+// frames [frames - take, frames) of every stream's input (stream s at pcm + s * stride) into the ring at slots (fed + f) & mask
+hipError_t launch_bank_history_append(float *hist, const float *pcm, uint64_t stride, uint64_t frames, uint64_t fed,
+                                      uint32_t n_streams, uint32_t channels, hipStream_t s);
+hipError_t launch_meter_bank_spectrum(const BankSpectrumParams &p, bool columns, hipStream_t s);
+
 // ---- waveform ---------------------------------------------------------------
 struct WaveParams {
     const float *pcm; uint64_t stream_stride; uint64_t n_samples; // interleaved samples per stream

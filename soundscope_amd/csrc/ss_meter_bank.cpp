@@ -32,6 +32,20 @@ struct ss_meter_bank {
     hipEvent_t pin_ev = nullptr;
     bool pin_busy = false;
     ssk::MeterReading *pin_read = nullptr;
+    // spectra (ss_meter_bank_spectrum_enable): the newest 16384 input frames of every stream, bank-wide frame counter
+    bool spec_on = false;
+    uint64_t spec_fed = 0;
+    BinTables *bt = nullptr;
+    FftTables *ft = nullptr;
+    ssh::DevBuf<float> spec_hist;          // [n][16384][C]
+    ssh::DevBuf<float> spec_out;           // rows or columns of the last spectrum call
+    ssh::DevBuf<int32_t> spec_status;      // [n][rows]
+    ssh::DevBuf<double> spec_pink;         // n_bins f64
+    ssh::DevBuf<uint16_t> spec_bin_col;    // n_bins: chart column of each bin for spec_cols
+    ssh::DevBuf<float> spec_col_init;      // spec_cols
+    uint32_t spec_cols = 0;
+    void *spec_pin = nullptr;              // page-locked results: floats, then the statuses
+    size_t spec_pin_bytes = 0;
     static constexpr uint32_t kSubCap = ss_analyzer::kSubCap;
 };
 
@@ -85,6 +99,10 @@ int advance(ss_meter_bank *m, const float *pcm, uint64_t frames, uint64_t stride
     int rc = get_hist_tables(&he, &hb);
     if (rc) return rc;
     const uint32_t C = m->channels;
+    if (m->spec_on) {
+        HIPCHK(ssk::launch_bank_history_append(m->spec_hist.p, pcm, stride, frames, m->spec_fed, m->n, C, m->stream));
+        m->spec_fed += frames;
+    }
     const uint64_t S = m->s100, piece_frames = 32 * S;
     const ssk::MeterBankParams q = bank_params(m, he, hb);
     for (uint64_t done = 0; done < frames;) {
@@ -127,6 +145,69 @@ int bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
 }
 
 int null_bank() { return require_device() ? SS_ERR_DEVICE : SS_ERR_INVALID_ARG; }
+
+static_assert(SS_BANK_SPECTRUM_N == ssk::kBankSpecN, "one window length");
+
+uint32_t spec_rows(const ss_meter_bank *m) { return m->channels == 2 ? 2u : m->channels; }
+
+// the spectrum launch of every (stream, row) and one copy of its results (`per_row` floats each) and statuses into page-locked memory
+int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, float gain_db, uint32_t per_row,
+                 float **vals, int32_t **status)
+{
+    const uint32_t R = spec_rows(m);
+    const size_t rows = (size_t)m->n * R, fbytes = rows * per_row * sizeof(float), sbytes = rows * sizeof(int32_t);
+    HIPCHK(m->spec_out.ensure(rows * per_row));
+    if (fbytes + sbytes > m->spec_pin_bytes) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        if (m->spec_pin) { (void)hipHostFree(m->spec_pin); m->spec_pin = nullptr; m->spec_pin_bytes = 0; }
+        HIPCHK(hipHostMalloc(&m->spec_pin, fbytes + sbytes, hipHostMallocDefault));
+        m->spec_pin_bytes = fbytes + sbytes;
+    }
+    ssk::BankSpectrumParams q{};
+    ssk::FftBatchParams &p = q.f;
+    p.window = m->ft->window.p; p.tw_n = m->ft->tw_n.p; p.tw_core = m->ft->core_tw4096; p.tw_256 = m->ft->core_tw256;
+    p.pink = nullptr; p.n = SS_BANK_SPECTRUM_N;
+    p.first_bin = (uint32_t)m->bt->first; p.n_bins = (uint32_t)m->bt->count; p.bin_stride = p.n_bins;
+    p.db_offset = (float)(20.0 * std::log10(4.0 / (double)SS_BANK_SPECTRUM_N));      // ss_get_fft's, bit for bit
+    q.hist = m->spec_hist.p;
+    q.start = (uint32_t)((m->spec_fed - SS_BANK_SPECTRUM_N) & (SS_BANK_SPECTRUM_N - 1));
+    q.n_streams = m->n; q.channels = m->channels; q.rows = R;
+    q.status = m->spec_status.p; q.out = m->spec_out.p;
+    if (columns) {
+        if (cols != m->spec_cols) {
+            std::vector<uint16_t> bc(m->bt->count);
+            std::vector<float> cinit(cols, std::numeric_limits<float>::quiet_NaN());
+            for (size_t i = 0; i < bc.size(); i++) {
+                bc[i] = (uint16_t)spectrum_column_of(m->bt->chart_x[i], cols);
+                cinit[bc[i]] = -std::numeric_limits<float>::infinity();
+            }
+            HIPCHK(m->spec_bin_col.upload(bc));
+            HIPCHK(m->spec_col_init.upload(cinit));
+            m->spec_cols = cols;
+        }
+        q.pink = m->spec_pink.p; q.bin_col = m->spec_bin_col.p; q.col_init = m->spec_col_init.p;
+        q.cols = cols; q.gain_db = gain_db;
+        if (gain_mode == SS_GAIN_REFERENCE) {
+            // every stream's integrated loudness after the last add: the readings read() returns, on the device
+            const double *he, *hb;
+            int rc = get_hist_tables(&he, &hb);
+            if (rc) return rc;
+            HIPCHK(ssk::launch_meter_bank_readings(bank_params(m, he, hb), m->readings.p, m->stream));
+            static_assert(sizeof(ssk::MeterReading) % sizeof(double) == 0, "readings as doubles");
+            q.integrated = &m->readings.p[0].integrated;
+            q.integrated_stride = sizeof(ssk::MeterReading) / sizeof(double);
+        }
+    }
+    HIPCHK(ssk::launch_meter_bank_spectrum(q, columns, m->stream));
+    char *pin = static_cast<char *>(m->spec_pin);
+    HIPCHK(hipMemcpyAsync(pin, m->spec_out.p, fbytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(pin + fbytes, m->spec_status.p, sbytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->pin_busy = false;
+    *vals = reinterpret_cast<float *>(pin);
+    *status = reinterpret_cast<int32_t *>(pin + fbytes);
+    return SS_OK;
+}
 
 }  // namespace
 
@@ -181,6 +262,7 @@ void ss_meter_bank_destroy(ss_meter_bank *m)
     if (m->pin_ev) (void)hipEventDestroy(m->pin_ev);
     if (m->pin) (void)hipHostFree(m->pin);
     if (m->pin_read) (void)hipHostFree(m->pin_read);
+    if (m->spec_pin) (void)hipHostFree(m->spec_pin);
     delete m;
 }
 
@@ -278,6 +360,83 @@ int ss_meter_bank_histograms(ss_meter_bank *m, uint32_t stream, uint64_t *out200
                           hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     m->pin_busy = false;
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_enable(ss_meter_bank *m, int enable)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!enable) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        m->spec_on = false;
+        m->spec_hist.release(); m->spec_out.release(); m->spec_status.release();
+        return SS_OK;
+    }
+    if (20000.0f > (float)m->rate / 2.0f) return SS_ERR_FREQ_LIMIT;         // get_fft's FrequencyLimit check, before any allocation
+    int rc = get_fft_tables(SS_BANK_SPECTRUM_N, &m->ft);
+    if (rc) return rc;
+    rc = get_bin_tables(m->rate, SS_BANK_SPECTRUM_N, &m->bt);
+    if (rc) return rc;
+    if (!m->spec_pink.p) HIPCHK(m->spec_pink.upload(m->bt->pink));
+    const size_t floats = (size_t)m->n * SS_BANK_SPECTRUM_N * m->channels;
+    HIPCHK(m->spec_hist.ensure(floats));
+    HIPCHK(hipMemsetAsync(m->spec_hist.p, 0, floats * sizeof(float), m->stream));  // (re-enabling starts again from zeros)
+    HIPCHK(m->spec_status.ensure((size_t)m->n * spec_rows(m)));
+    m->spec_fed = 0;
+    m->spec_on = true;
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_layout(const ss_meter_bank *m, uint32_t *rows_per_stream, uint32_t *n_bins, double *chart_x, double *pink,
+                                  uint32_t cap_bins)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->spec_on) return SS_ERR_INVALID_MODE;
+    const uint32_t nb = (uint32_t)m->bt->count;
+    if ((chart_x || pink) && cap_bins < nb) return SS_ERR_CAPACITY;
+    if (rows_per_stream) *rows_per_stream = spec_rows(m);
+    if (n_bins) *n_bins = nb;
+    for (uint32_t i = 0; i < nb; i++) {
+        if (chart_x) chart_x[i] = m->bt->chart_x[i];
+        if (pink) pink[i] = m->bt->pink[i];
+    }
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum(ss_meter_bank *m, float *rows, size_t cap_floats, int32_t *status, uint32_t cap_rows)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!rows || !status) return SS_ERR_INVALID_ARG;
+    if (!m->spec_on) return SS_ERR_INVALID_MODE;
+    const uint32_t nb = (uint32_t)m->bt->count;
+    const size_t R = (size_t)m->n * spec_rows(m);
+    if (cap_floats < R * nb || cap_rows < R) return SS_ERR_CAPACITY;
+    float *v; int32_t *st;
+    int rc = spectrum_run(m, false, 0, SS_GAIN_FIXED, 0.0f, nb, &v, &st);
+    if (rc) return rc;
+    std::memcpy(rows, v, R * nb * sizeof(float));
+    std::memcpy(status, st, R * sizeof(int32_t));
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_columns(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db, float *out, size_t cap_floats,
+                                   int32_t *status, uint32_t cap_rows)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!out || !status || cols == 0 || cols > 512 || (gain_mode != SS_GAIN_FIXED && gain_mode != SS_GAIN_REFERENCE))
+        return SS_ERR_INVALID_ARG;
+    if (!m->spec_on) return SS_ERR_INVALID_MODE;
+    const size_t R = (size_t)m->n * spec_rows(m);
+    if (cap_floats < R * cols || cap_rows < R) return SS_ERR_CAPACITY;
+    float *v; int32_t *st;
+    int rc = spectrum_run(m, true, cols, gain_mode, gain_db, cols, &v, &st);
+    if (rc) return rc;
+    std::memcpy(out, v, R * cols * sizeof(float));
+    std::memcpy(status, st, R * sizeof(int32_t));
     return SS_OK;
 }
 

@@ -2,6 +2,8 @@
 
 Stream s of a bank behaves exactly like an `Analyzer` loudness meter fed the same blocks; a call advances every stream with a
 time-domain launch and a gating launch, and `read()` returns every stream's readings behind one launch and one copy.
+With `enable_spectrum()` the bank also keeps every stream's newest 16384 input frames, and `spectrum()` /
+`spectrum_columns()` transform all of them (mid and side for stereo banks) in one launch.
 """
 import ctypes as C
 
@@ -77,3 +79,48 @@ class MeterBank:
         out = np.empty(2000, np.uint64)
         _check(L.lib().ss_meter_bank_histograms(self._h, stream, out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out[:1000].copy(), out[1000:].copy()
+
+    # ---- spectra (ss_meter_bank_spectrum_*) ------------------------------------------------------------------------------------
+    def enable_spectrum(self, on=True):
+        """Keep (on) or drop every stream's history of the newest 16384 frames; enabling starts from a zero window."""
+        _check(L.lib().ss_meter_bank_spectrum_enable(self._h, 1 if on else 0))
+
+    def spectrum_layout(self):
+        """(rows per stream, n_bins, chart_x [n_bins] f64): chart_x is the first element of get_fft's pairs."""
+        r, nb = C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_meter_bank_spectrum_layout(self._h, C.byref(r), C.byref(nb), None, None, 0))
+        x = np.empty(nb.value, np.float64)
+        _check(L.lib().ss_meter_bank_spectrum_layout(self._h, None, None, x.ctypes.data_as(C.POINTER(C.c_double)), None, nb.value))
+        return r.value, nb.value, x
+
+    def spectrum_pink(self):
+        """The f64 pink compensation [n_bins] that get_fft adds to a row's dB values."""
+        _, nb, _ = self.spectrum_layout()
+        p = np.empty(nb, np.float64)
+        _check(L.lib().ss_meter_bank_spectrum_layout(self._h, None, None, None, p.ctypes.data_as(C.POINTER(C.c_double)), nb))
+        return p
+
+    def spectrum(self):
+        """(rows [n_streams, rows, n_bins] f32 dBFS before pink compensation, status [n_streams, rows] i32 ss_status)."""
+        r, nb, _ = self.spectrum_layout()
+        rows = np.empty((self.n_streams, r, nb), np.float32)
+        st = np.empty((self.n_streams, r), np.int32)
+        _check(L.lib().ss_meter_bank_spectrum(self._h, rows.ctypes.data_as(C.POINTER(C.c_float)), rows.size,
+                                              st.ctypes.data_as(C.POINTER(C.c_int32)), st.size))
+        return rows, st
+
+    def spectrum_columns(self, cols, gain=None):
+        """(columns [n_streams, rows, cols] f32, status [n_streams, rows] i32).  gain: None (0 dB), a float in dB, or "reference"
+        (-13 - integrated loudness of each stream, tui.rs:1234)."""
+        r, _, _ = self.spectrum_layout()
+        if isinstance(gain, str):
+            if gain != "reference":
+                raise ValueError(f"gain {gain!r}: None, a number or 'reference'")
+            mode, g = L.SS_GAIN_REFERENCE, 0.0
+        else:
+            mode, g = L.SS_GAIN_FIXED, 0.0 if gain is None else float(gain)
+        out = np.empty((self.n_streams, r, int(cols)), np.float32)
+        st = np.empty((self.n_streams, r), np.int32)
+        _check(L.lib().ss_meter_bank_spectrum_columns(self._h, int(cols), mode, g, out.ctypes.data_as(C.POINTER(C.c_float)), out.size,
+                                                      st.ctypes.data_as(C.POINTER(C.c_int32)), st.size))
+        return out, st
