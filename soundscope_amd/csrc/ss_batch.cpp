@@ -133,9 +133,6 @@ extern "C" {
 //    length that maximises   useful fraction  seg / (seg + warm)  x  fill of the last round  waves / (ceil(waves / W0) W0)
 //    (ranks the measured config-5 sweep seg = 2..13 in the right order; measured within noise for config 3).
 // mode (ss_batch_set_time_domain_mode): 0 the better score of the two, 1 segments, 2 whole-stream workgroups where the shape allows.
-#ifndef SS_TD_SPLIT_LONG_RUN_IN
-#define SS_TD_SPLIT_LONG_RUN_IN 1      // 0: split segments hand over through the second launch like every other segmented batch (A/B builds)
-#endif
 static void choose_td_geometry(ss_batch *b)
 {
     if (!b->td) return;
@@ -203,7 +200,7 @@ static void choose_td_geometry(ss_batch *b)
     // launch would have started from (a zero-state run over 0.2 s: 1.6e-21 of the true state's response left), the run-in tiles
     // cost the filter passes only, no second launch.
     if (plan.nseg > 1) {
-        if (split == ssk::kTdSplitSegments && SS_TD_SPLIT_LONG_RUN_IN) plan.warm_sub = kTdFixSub;
+        if (split == ssk::kTdSplitSegments) plan.warm_sub = kTdFixSub;
         else if (b->td_mode == 1) plan.warm_sub = kTdWarmSub;
         else { plan.fixup = true; plan.fix_sub = plan.seg_sub < kTdFixSub ? plan.seg_sub : kTdFixSub; }
     }
@@ -292,11 +289,8 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
 #endif
         // Rows start 16-byte aligned (16-byte stores).  Padding them to whole 128-byte lines lifts a pure streaming-store
         // kernel with this row pattern from 3.7 to 4.4 TB/s (tools/ubench_fftio.hip) but does nothing for the real kernel
-        // (A/B in one process: 3.14 vs 3.12 ms), so the rows stay compact.  -DSS_FFT_ROW_ALIGN=32u rebuilds the padded form.
-#ifndef SS_FFT_ROW_ALIGN
-#define SS_FFT_ROW_ALIGN 4u
-#endif
-        L.fft_bin_stride = (L.n_bins + (SS_FFT_ROW_ALIGN - 1u)) & ~(SS_FFT_ROW_ALIGN - 1u);
+        // (A/B in one process: 3.14 vs 3.12 ms), so the rows stay compact.
+        L.fft_bin_stride = (L.n_bins + 3u) & ~3u;
         if (columns_only) {
             // the fused reduction lives in the epilogue of k_fft4096_ms1
             if (!(b->fft_fast && hop == 1024)) return SS_ERR_UNSUPPORTED;

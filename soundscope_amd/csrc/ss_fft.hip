@@ -8,17 +8,10 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef SS_COLS_FOLD
-#define SS_COLS_FOLD 1    // columns-only epilogue: 1 folds a lane's four bins in registers first (one or two atomics per row and group); 0 one atomic per bin
-#endif
-#ifndef SS_FFT_PAIRW_WAVES
-#define SS_FFT_PAIRW_WAVES 3   // min waves per SIMD k_fft4096_pairw is register-allocated for (4: 128 VGPRs with 13 spilled, measured 10 % slower)
-#endif
-#ifndef SS_FFT_WAVES
-#define SS_FFT_WAVES 2   // min waves per SIMD the N=4096 pair kernel is register-allocated for
-#endif
-
 namespace ssk {
+
+constexpr int kFftPairwWaves = 3;   // min waves per SIMD k_fft4096_pairw is register-allocated for (4: 128 VGPRs with 13 spilled, measured 10 % slower)
+constexpr int kFftWaves = 2;        // min waves per SIMD the N=4096 pair kernel is register-allocated for
 
 // ============================================================================
 //  Spectrum, N = 4096, stereo -> mid/side packed as one complex FFT.
@@ -85,7 +78,7 @@ constexpr int kPlaneB = 16 * kRowB;
 //     consecutive bins lie in ONE column or straddle one boundary.  coltab[g] = (o0 | o3 << 16, n): the offsets
 //     of the first and the last bin's column and the number n of bins in the first (0: a general group, below).  The two run maxima are taken in registers
 //     (five selects, three maxima per row) and one atomic per row goes out — two where the group straddles.  One atomic per BIN
-//     and no arithmetic at all (SS_COLS_FOLD 0) was measured: 3.86 ms — the sixteen-odd lanes that share a wide column queue on
+//     and no arithmetic at all was measured: 3.86 ms — the sixteen-odd lanes that share a wide column queue on
 //     one LDS address (SQ_LDS_BANK_CONFLICT 40 % of the LDS cycles), profiles/r05_ab_columns.txt.
 //   * Groups the two-run form cannot express (three or four columns inside the group: the lowest bins; the row padding in the
 //     last group, whose offsets point at a spare slot) carry n = 0 and fold bin by bin from colbins — a wave-uniform branch.
@@ -134,7 +127,6 @@ __device__ __forceinline__ void fft4096_epilogue(const v2f *xb, int t, uint32_t 
     lds_char *const cb = (lds_char *)colbuf;
     auto fold_group = [&](const int i, const uint32_t g) {
                 const uint2 ct = coltab[g];
-#if SS_COLS_FOLD
                 const uint32_t o0 = ct.x & 0xFFFFu, o3 = ct.x >> 16, nf = ct.y;     // (a whole dword: compares against inline constants)
                 const bool general = nf == 0u;
                 if (__builtin_expect(__ballot(general) != 0ull, 0)) {          // (wave-uniform: the wave that owns the lowest bins / the padding)
@@ -166,15 +158,6 @@ __device__ __forceinline__ void fft4096_epilogue(const v2f *xb, int t, uint32_t 
                         if (!p3) lds_fmax((lds_f32 *)(cb + o3) + row * kColStride, l);
                     }
                 }
-#else
-                const uint32_t o[4] = {ct.x & 0xFFFFu, ct.x >> 16, ct.y & 0xFFFFu, ct.y >> 16};
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    lds_f32 *a = (lds_f32 *)(cb + o[e]);
-                    lds_fmax(a, rm[i][e]);
-                    lds_fmax(a + kColStride, rs[i][e]);
-                }
-#endif
     };
 #pragma unroll
     for (int i = 0; i < 2; i++) {
@@ -406,7 +389,7 @@ __device__ __forceinline__ void read_levels2(const uint32_t (*lv)[2], uint32_t &
 // phase carries two independent radix-16 problems (half the barriers per window, twice the
 // instruction-level parallelism to cover LDS latency).
 template <int HS>
-__global__ __launch_bounds__(256, SS_FFT_WAVES) void k_fft4096_ms(FftBatchParams p)
+__global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms(FftBatchParams p)
 {
     constexpr int NS = 16 + HS;                                              // sample slots held
     __shared__ __attribute__((aligned(16))) v2f xbuf[2][16 * kPlane];     // 2 x 36864 B
@@ -590,30 +573,16 @@ __global__ __launch_bounds__(256, SS_FFT_WAVES) void k_fft4096_ms(FftBatchParams
 #undef X1W
 #undef X2W
 
-// Single-window variant (one window per iteration): built for occupancy — three (TW6: four) workgroups
-// per CU instead of two.  With TW6 the 15 pass-1 twiddles W^(t ka) are rebuilt from six resident ones,
-// W^(t ka) = W^(t (ka & 3)) * W^(t (ka & 12)), at the price of 9 extra complex multiplies per window.
-#ifndef SS_FFT1_WAVES
-#define SS_FFT1_WAVES 3
-#endif
-#ifndef SS_MS1_TW
-#define SS_MS1_TW 12     // resident pass-1 twiddles of k_fft4096_ms1 (6, 9, 12; 0 = all fifteen): 168 VGPRs at 12, the three-waves limit
-#endif
-#ifndef SS_COLS_TW
-#define SS_COLS_TW SS_MS1_TW      // the columns-only instantiation: the SAME count, or its rows would round differently from the stored ones
-#endif
+// Single-window variant (one window per iteration): built for occupancy — three workgroups per CU instead of two.
+// Of the 15 pass-1 twiddles W^(t ka), TWN stay resident; the others are rebuilt as W^(t ka) = W^(t (ka & 3)) * W^(t (ka & 12)),
+// one extra complex multiply each per window.
+// Resident pass-1 twiddles of k_fft4096_ms1 (6, 9, 12 or all fifteen were built): 168 VGPRs at 12, the three-waves limit.  Both
+// instantiations take this one count: the columns-only rows would otherwise round differently from the stored ones.
+constexpr int kMs1Tw = 12;
 // Wave priority by phase: a wave that is exchanging through LDS (writes, barrier, reads) runs at raised priority so
 // its few LDS instructions issue ahead of the other workgroups' butterflies; measured 3.15 -> 3.05 ms (A/B in one process)
-#ifndef SS_FFT_PRIO
-#define SS_FFT_PRIO 3
-#endif
-#if SS_FFT_PRIO > 0
-#define SS_PRIO_HI() __builtin_amdgcn_s_setprio(SS_FFT_PRIO)
+#define SS_PRIO_HI() __builtin_amdgcn_s_setprio(3)
 #define SS_PRIO_LO() __builtin_amdgcn_s_setprio(0)
-#else
-#define SS_PRIO_HI()
-#define SS_PRIO_LO()
-#endif
 // Development build (-DSS_FFT_PROF): per-phase shader-clock totals of k_fft4096_ms1 over all waves (tools/probe_fft_phases.py)
 #ifdef SS_FFT_PROF
 __device__ unsigned long long g_fft_prof[16];
@@ -626,7 +595,7 @@ __device__ unsigned long long g_fft_prof[16];
 #define SS_FPROF_END
 #endif
 template <int HS, int TWN, bool COLS>
-__global__ __launch_bounds__(256, SS_FFT1_WAVES) void k_fft4096_ms1(FftBatchParams p)
+__global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
 {
     constexpr int NH = 16 / HS;                                           // hops per window
     __shared__ __attribute__((aligned(16))) v2f xbuf[16 * kPlaneB];       // 34816 B (the published spectrum uses 32768)
@@ -638,11 +607,7 @@ __global__ __launch_bounds__(256, SS_FFT1_WAVES) void k_fft4096_ms1(FftBatchPara
     __shared__ __attribute__((aligned(16))) uint32_t xlev[4][2];
     // 8192 B: db_offset + pink per retained bin (n_bins <= 2047 at N = 4096).  Columns-only mode (COLS) uses the room for the
     // bins' chart columns (u16 each) and the two rows' column accumulators instead, and reads the table from global memory.
-#ifdef SS_MS1_NO_LDS_TABLE      // experiment (review item 6): no table in LDS, so that FOUR workgroups fit a CU (with -DSS_FFT1_WAVES=4)
-    __shared__ __attribute__((aligned(16))) float offp[4];
-#else
     __shared__ __attribute__((aligned(16))) float offp[2048];
-#endif
     // COLS: + 4096 B offset table (one uint2 per group of four bins) + 4128 B column accumulators [mid, side][kColStride]
     // (three workgroups per CU leave 53 KB each: 53.4 KB with these)
     __shared__ __attribute__((aligned(16))) uint2 coltab[COLS ? 512 : 1];
@@ -666,26 +631,19 @@ __global__ __launch_bounds__(256, SS_FFT1_WAVES) void k_fft4096_ms1(FftBatchPara
 #pragma unroll
     for (int j = 0; j < 8; j++) hwp[j] = v2f{p.half_window[t + 256 * (2 * j)], p.half_window[t + 256 * (2 * j + 1)]};
     v2f tw1[16];
-    constexpr bool TW6 = TWN != 0;                                        // some of the fifteen are rebuilt
+    static_assert(TWN == 6 || TWN == 9 || TWN == 12, "resident pass-1 twiddles: 6, 9 or 12");
     // TWN resident pass-1 twiddles: 6 = {1, 2, 3, 4, 8, 12}; 9 adds {5, 6, 7}; 12 adds {9, 10, 11} (one multiply instead of two each)
     auto tw_resident = [](int ka) -> bool { return (ka & 3) == 0 || (ka & 12) == 0 || (TWN >= 9 && (ka >> 2) == 1) || (TWN >= 12 && (ka >> 2) == 2); };
-    if (TW6) {
 #pragma unroll
-        for (int ka = 1; ka < 16; ka++) if (tw_resident(ka)) tw1[ka] = twn[ka * t];
-    } else {
-#pragma unroll
-        for (int ka = 1; ka < 16; ka++) tw1[ka] = twn[t * ka];
-    }
+    for (int ka = 1; ka < 16; ka++) if (tw_resident(ka)) tw1[ka] = twn[ka * t];
     tw2s[t] = reinterpret_cast<const v2f *>(p.tw_256)[(t & 15) * (t >> 4)];      // [kb][tb]: W_256^(tb kb) at kb * 16 + tb
     if (COLS) {
-        for (uint32_t g = (uint32_t)t; 4u * g < p.bin_stride; g += 256u) coltab[g] = SS_COLS_FOLD ? p.col_groups[g] : p.col_bins[g];
+        for (uint32_t g = (uint32_t)t; 4u * g < p.bin_stride; g += 256u) coltab[g] = p.col_groups[g];
         for (uint32_t c = (uint32_t)t; c < p.cols; c += 256u) { const float v = p.col_init[c]; colbuf[c] = v; colbuf[kColStride + c] = v; }
         if (t < 4) { colbuf[512 + t] = 0.0f; colbuf[kColStride + 512 + t] = 0.0f; }      // the spare slots the row padding folds into
     }
-#ifndef SS_MS1_NO_LDS_TABLE
     for (uint32_t g = (uint32_t)t; 4u * g < p.bin_stride; g += 256u)
         reinterpret_cast<float4 *>(offp)[g] = reinterpret_cast<const float4 *>(p.offpink)[g];
-#endif
     // columns-only mode: gain of this stream, and where a finished window's columns go (flushed one window late, behind the
     // loop-end barrier that closes its epilogue's atomics, by the threads that idle least: all of them, one column pair each)
     const float cgain = COLS ? (p.integrated ? -13.0f - (float)p.integrated[stream] : p.gain_db) : 0.0f;
@@ -807,7 +765,7 @@ __global__ __launch_bounds__(256, SS_FFT1_WAVES) void k_fft4096_ms1(FftBatchPara
 #pragma unroll
         for (int ka = 1; ka < 16; ka++) {
             v2f v = z[R16(ka)];
-            if (TW6 && !tw_resident(ka)) {
+            if (!tw_resident(ka)) {
                 // (the product tw1[ka & 3] tw1[ka & 12] formed per window off the data's dependent chain, then ONE multiply of the data:
                 // measured in round 6, six interleaved repetitions: 2.996 vs 2.995 ms — nothing)
                 v = pk_cmul(v, tw1[ka & 3]);
@@ -890,11 +848,7 @@ __global__ __launch_bounds__(256, SS_FFT1_WAVES) void k_fft4096_ms1(FftBatchPara
             presettle();
         }
         float *o_mid = outp + (size_t)(w - w_begin) * out_win_stride;
-#ifdef SS_MS1_NO_LDS_TABLE
-        fft4096_epilogue<false, COLS>(xbuf, t, p.first_bin, p.n_bins, p.db_offset, p.offpink, o_mid, o_mid + p.bin_stride, true, soff, colbuf, coltab, p.col_bins);
-#else
         fft4096_epilogue<true, COLS>(xbuf, t, p.first_bin, p.n_bins, p.db_offset, offp, o_mid, o_mid + p.bin_stride, true, soff, colbuf, coltab, p.col_bins);
-#endif
         if (__builtin_expect(zrow_m || zrow_d, 0)) {
             if (!COLS) fft4096_floor_rows(t, p.n_bins, p.db_offset, p.offpink, o_mid, o_mid + p.bin_stride, zrow_m, zrow_d);
             else fft4096_floor_columns(t, p.n_bins, p.db_offset, p.offpink, colbuf, p.bin_col, p.col_init, p.cols, zrow_m, zrow_d);
@@ -915,7 +869,7 @@ __global__ __launch_bounds__(256, SS_FFT1_WAVES) void k_fft4096_ms1(FftBatchPara
 // walks window PAIRS; the sliding registers hold 20 slots and advance by 8 (2048 frames) per iteration.  E is the second
 // window's block exponent ("Two rows, one transform": a fade-in, or a programme behind a quiet passage, puts the two
 // windows at different levels); it lives in the second row's window weights hw2 = 2^E hann.
-__global__ __launch_bounds__(256, SS_FFT_PAIRW_WAVES) void k_fft4096_pairw(FftBatchParams p, uint32_t fft_ch)
+__global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchParams p, uint32_t fft_ch)
 {
     __shared__ __attribute__((aligned(16))) v2f xbuf[16 * kPlaneB];       // 34816 B
     __shared__ __attribute__((aligned(16))) v2f tw2s[256];                //  2048 B
@@ -1133,7 +1087,7 @@ hipError_t launch_fft4096_pairw(const FftBatchParams &p, int mode, hipStream_t s
 }
 
 // generic hop (not a multiple of 256 or >= N/2 slots): one window per iteration, full reload
-__global__ __launch_bounds__(256, SS_FFT_WAVES) void k_fft4096_ms_anyhop(FftBatchParams p)
+__global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms_anyhop(FftBatchParams p)
 {
     __shared__ __attribute__((aligned(16))) v2f xbuf[16 * kX1Stride];
     __shared__ __attribute__((aligned(16))) v2f tw2s[256];
@@ -1252,11 +1206,8 @@ __global__ __launch_bounds__(512, 2) void k_fft16k(FftBatchParams p, int midside
 //  two workgroups are FOUR waves per SIMD: config 5 7.11 -> 6.89 ms, native stereo 4.66 -> 4.53 ms in one call
 //  (profiles/r04_ab_fft16k_eight_waves.txt).  q is wave-uniform (a wave belongs to one half), so nothing diverges.
 // ============================================================================
-#ifndef SS_RUN8_WAVES
-#define SS_RUN8_WAVES 4
-#endif
 template <bool MIDSIDE, int NE_LAST>
-__global__ __launch_bounds__(512, SS_RUN8_WAVES) void k_fft16k_run(FftBatchParams p, uint32_t fft_ch)
+__global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_t fft_ch)
 {
     __shared__ __attribute__((aligned(16))) v2f xbuf2[2][16 * kPlaneB];      // 2 x 34816 B
     __shared__ __attribute__((aligned(16))) v2f tw2s[256];                    //  2048 B
@@ -1573,8 +1524,8 @@ hipError_t launch_fft4096_ms(const FftBatchParams &p, hipStream_t s)
     dim3 grid(groups * p.n_streams), block(256);
     // hop 1024 (the reference's cadence): the single-window kernel at 3 workgroups per CU measured 2.5 %
     // faster than the window-pair kernel k_fft4096_ms<4> at 2 (A/B in one process, 3.48 vs 3.57 ms)
-    if (p.hop == 1024 && p.out_cols) hipLaunchKernelGGL((k_fft4096_ms1<4, SS_COLS_TW, true>), grid, block, 0, s, p);
-    else if (p.hop == 1024) hipLaunchKernelGGL((k_fft4096_ms1<4, SS_MS1_TW, false>), grid, block, 0, s, p);
+    if (p.hop == 1024 && p.out_cols) hipLaunchKernelGGL((k_fft4096_ms1<4, kMs1Tw, true>), grid, block, 0, s, p);
+    else if (p.hop == 1024) hipLaunchKernelGGL((k_fft4096_ms1<4, kMs1Tw, false>), grid, block, 0, s, p);
     else if (p.hop == 512) hipLaunchKernelGGL(k_fft4096_ms<2>, grid, block, 0, s, p);
     else if (p.hop == 2048) hipLaunchKernelGGL(k_fft4096_ms<8>, grid, block, 0, s, p);
     else hipLaunchKernelGGL(k_fft4096_ms_anyhop, grid, block, 0, s, p);

@@ -158,10 +158,7 @@ inline uint32_t spectrum_column_of(double chart_x, uint32_t cols)
 // arithmetic noise of the recurrence on such material (tools: tests/test_gpu_bench_shapes.py
 // ::test_segmented_run_in_on_dc_offset_material pins the histograms).  One sub-block it is: the run-in is redundant work
 // (config 5: 4 instead of 5 sub-blocks per 3-sub-block segment).
-#ifndef SS_TD_WARM_SUB
-#define SS_TD_WARM_SUB 1
-#endif
-constexpr uint32_t kTdWarmSub = SS_TD_WARM_SUB;
+constexpr uint32_t kTdWarmSub = 1;
 // sub-blocks at the head of a time segment > 0 that the fix-up launch re-runs from the exact incoming state.  Behind them the main
 // launch's trajectory (zero state at the segment's start) differs from the true one by A^n s: e^-48 (1 + 48) ~ 7e-20 of the state
 // after 0.2 s — on the DC-offset torture material (state 4e4 x the offset) 1e-13 of the filtered signal, under the 2e-11 at which any

@@ -358,9 +358,7 @@ __global__ __launch_bounds__(64) void k_finalize_stream(FinalizeParams p)
     }
 }
 
-#ifndef SS_FINALIZE_SMALL_MAX
-#define SS_FINALIZE_SMALL_MAX 64u      // streams up to which a launch counts as latency-bound (the form with the tables in LDS)
-#endif
+constexpr uint32_t kFinalizeSmallMax = 64u;      // streams up to which a launch counts as latency-bound (the form with the tables in LDS)
 hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s)
 {
     if (p.n_streams == 0) return hipSuccess;
@@ -372,7 +370,7 @@ hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s)
         const uint64_t nsub = p.sub_end - p.sub_begin;
         const uint32_t threads = nsub > 2048 ? 1024u : 256u;
         // a handful of short streams: the launch is a chain of memory round trips, not work -> the form that shortens the chain
-        if (p.n_streams <= SS_FINALIZE_SMALL_MAX && threads == 256u) hipLaunchKernelGGL(k_finalize<true>, dim3(p.n_streams), dim3(threads), 0, s, p);
+        if (p.n_streams <= kFinalizeSmallMax && threads == 256u) hipLaunchKernelGGL(k_finalize<true>, dim3(p.n_streams), dim3(threads), 0, s, p);
         else hipLaunchKernelGGL(k_finalize<false>, dim3(p.n_streams), dim3(threads), 0, s, p);
     }
     return hipGetLastError();
@@ -471,7 +469,7 @@ hipError_t launch_loudness_series(const FinalizeParams &p, double *series, uint6
     if (p.sub_begin != 0 || p.sub_end > p.sub_cap || p.sub_end > series_stride || p.sub_end > 0xFFFFFFFFull) return hipErrorInvalidValue;
     // a thread per sub-block, whole waves (a 10 s stream: two waves, not four mostly idle ones); the SMALL form where k_finalize takes it
     const uint64_t nsub = p.sub_end;
-    const bool small = p.n_streams <= SS_FINALIZE_SMALL_MAX && nsub <= 2048;
+    const bool small = p.n_streams <= kFinalizeSmallMax && nsub <= 2048;
     const uint64_t most = small ? 256u : 1024u;
     uint64_t threads = (nsub + 63u) & ~63ull;
     threads = threads < 64u ? 64u : (threads > most ? most : threads);

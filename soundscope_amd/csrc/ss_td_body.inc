@@ -1343,10 +1343,8 @@
                         auto absmax4 = [](float m, const floatx4 &a) {
                             return fmaxf(fmaxf(fmaxf(m, fabsf(a[0])), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3])));
                         };
-#ifndef SS_TD_MFMA_GROUPS4
-#define SS_TD_MFMA_GROUPS4 2      // groups per iteration of this loop in the four-waves-per-SIMD build (the three-waves build: 4)
-#endif
-                        constexpr int NG = (WPS >= 4) ? SS_TD_MFMA_GROUPS4 : 4;              // independent accumulator chains (2 or 4)
+                        // groups per iteration of this loop: 2 in the four-waves-per-SIMD build, 4 in the three-waves build
+                        constexpr int NG = (WPS >= 4) ? 2 : 4;              // independent accumulator chains (2 or 4)
                         constexpr int NGS = NG == 4 ? 2 : 1;
                         const uint32_t nquad = nplanar >> NGS;
                         if (nquad) {

@@ -13,10 +13,6 @@
 #include <cstdlib>
 #include <cstdio>
 
-#ifndef SS_TD_WAVES
-#define SS_TD_WAVES 4    // min waves per SIMD the time-domain kernel is register-allocated for
-#endif
-
 
 namespace ssk {
 // ============================================================================
@@ -82,10 +78,7 @@ typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
 // (the builtin wants a literal: two priority bits per phase, packed)
 // (round 6, the true peak now a VALU phase — packed FMAs instead of MFMAs: its level re-measured, three interleaved repetitions at
 // the bench shape: 0 -> 2.14 ms, 1 -> 2.02 (kept), 2 -> 2.05, 3 -> 2.04)
-#ifndef SS_TD_PRIO_MASK
-#define SS_TD_PRIO_MASK 0x05ECu     // {0, 3, 2, 3, 1, 1, 0, 0}
-#endif
-#define SS_TD_PHASE_PRIORITY(mark) __builtin_amdgcn_s_setprio((SS_TD_PRIO_MASK >> (2 * (mark))) & 3u)
+#define SS_TD_PHASE_PRIORITY(mark) __builtin_amdgcn_s_setprio((0x05ECu >> (2 * (mark))) & 3u)     // {0, 3, 2, 3, 1, 1, 0, 0}
 
 // Development build (-DSS_TD_PROF): per-phase shader-clock totals of k_time_domain, summed over all waves
 // (s_memtime at the phase boundaries of the tile loop; read back with ss_debug_td_prof).  Not in release builds.
@@ -475,18 +468,13 @@ constexpr int kTdTailFrames = 16;     // zeroed slack past the tile end: K-weigh
 // floats per wave would cost a quarter of the resident waves
 __host__ __device__ constexpr uint32_t td_slack_floats(uint32_t C) { return (12u * C + 64u) > (16u * C) ? (12u * C + 64u) : (16u * C); }
 constexpr int kTdWavesPerBlock = 4;
+constexpr int kTdWaves = 4;             // min waves per SIMD of the large-grid register build (td_three_waves: the other one)
 constexpr int kTdSplitWaves = 8;        // SPLIT: waves that share one streaming call (four when eight slices do not fit the LDS)
-#ifndef SS_TD_PREFETCH
-#define SS_TD_PREFETCH 8
-#endif
-constexpr int kTdPrefetch = SS_TD_PREFETCH;        // float4 per lane held in flight for the next tile
+constexpr int kTdPrefetch = 8;        // float4 per lane held in flight for the next tile
 // (round 6, with the true peak on the VALU: 3 / 5 / 6 / 10 reads per batch -> 2.16 / 2.03 / 2.05 / 2.08 ms at the bench shape on one box,
 // 15 -> +1 % on another; five is also 1-4 % better at 44.1 kHz, 5.1 and mono, 1.7 % worse at one odd length,
 // profiles/r06_ab_td_read_batch.txt)
-#ifndef SS_TD_BATCH
-#define SS_TD_BATCH 5
-#endif
-constexpr int kTdBatch = SS_TD_BATCH;          // LDS reads issued together in the sequential passes
+constexpr int kTdBatch = 5;          // LDS reads issued together in the sequential passes
 
 // one K-weighting state step (DF-II, zero-based state v1..v4); the critical path is one FMA
 #define SS_KW_STATE(xd)                         \
@@ -811,12 +799,12 @@ static inline uint32_t td_device_cus()
 }
 
 // register build of a grid of `blocks` four-wave workgroups: the spill-free three-waves-per-SIMD build where three workgroups per CU
-// hold the whole grid, the SS_TD_WAVES build otherwise
+// hold the whole grid, the kTdWaves build otherwise
 static inline bool td_three_waves(uint64_t blocks)
 {
-    bool three = SS_TD_WAVES == 4 && blocks <= 3ull * td_device_cus();
+    bool three = blocks <= 3ull * td_device_cus();
 #ifdef SS_TUNING        // development builds only: SS_TD_WPS=3|4 forces a register build
-    if (const char *e = std::getenv("SS_TD_WPS")) three = SS_TD_WAVES == 4 && std::atoi(e) == 3;
+    if (const char *e = std::getenv("SS_TD_WPS")) three = std::atoi(e) == 3;
 #endif
     return three;
 }
@@ -829,7 +817,7 @@ static hipError_t td_launch_split_batch(const TdParams &p, hipStream_t s)
     // of a segment's tiles is what the launch takes
     if (p.split_batch == kTdSplitSegments) return td_launch_w<FACTOR, false, CT, WAVE, 2, true, true>(p, s);      // (two waves per SIMD: nothing spilled; the grid is small by definition)
     if (td_three_waves(td_launch_units(p))) return td_launch_w<FACTOR, false, CT, WAVE, 3, true>(p, s);
-    return td_launch_w<FACTOR, false, CT, WAVE, SS_TD_WAVES, true>(p, s);
+    return td_launch_w<FACTOR, false, CT, WAVE, kTdWaves, true>(p, s);
 }
 
 template <int FACTOR, bool RING, int CT, int WAVE>
@@ -839,7 +827,7 @@ static hipError_t td_launch(const TdParams &p, hipStream_t s)
     if constexpr (RING) return td_launch_w<FACTOR, RING, CT, WAVE, 3>(p, s);      // a streaming call is one stream: one workgroup
     else {                                             // (else: the four-waves build of a streaming form is never instantiated)
         if (td_three_waves((td_launch_units(p) + kTdWavesPerBlock - 1) / kTdWavesPerBlock)) return td_launch_w<FACTOR, RING, CT, WAVE, 3>(p, s);
-        return td_launch_w<FACTOR, RING, CT, WAVE, SS_TD_WAVES>(p, s);
+        return td_launch_w<FACTOR, RING, CT, WAVE, kTdWaves>(p, s);
     }
 }
 

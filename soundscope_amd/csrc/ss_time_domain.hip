@@ -23,11 +23,11 @@ namespace ssk {
 // 48 kHz stereo 4800 = 5 x 32 x 30 — k_time_domain 2.14 -> 1.98 ms against L = 33 (5 tiles of 29 chunks + 3 frames)
 // although the walk of an even L is 2-way bank conflicted; 96 kHz stereo 2.91 -> 2.17 ms (was L = 65); BASELINE
 // config 5 (96 kHz, 8 channels) 3.02 -> 2.08 ms (was L = 65: 19 tiles of 7 chunks + 51 frames; now 40 tiles of 8 x 30).
-// four-wave workgroups of `lds` bytes one CU holds at once (the launch bound allows SS_TD_WAVES waves per SIMD)
+// four-wave workgroups of `lds` bytes one CU holds at once (the launch bound allows kTdWaves waves per SIMD)
 static uint32_t td_lds_blocks(size_t lds)
 {
     const uint32_t blocks = (uint32_t)(kTdLdsBytes / lds);
-    const uint32_t max_blocks = (4u * SS_TD_WAVES) / kTdWavesPerBlock;
+    const uint32_t max_blocks = (4u * kTdWaves) / kTdWavesPerBlock;
     return blocks > max_blocks ? max_blocks : blocks;
 }
 

@@ -175,7 +175,7 @@ def test_a_rank_that_cannot_set_up_takes_every_rank_down_within_seconds(tmp_path
     """RCCL transport, two ranks, no usable GPU on this box: what goes wrong on a rank BEFORE the ranks meet (no device, a device
     ordinal that does not exist, no librccl) is exchanged right behind the join, so every rank fails within seconds and names the
     reason — the healthy ones do not wait out SS_COMM_TIMEOUT_S for a peer that has already left (a rank whose LOCAL_RANK named
-    no device cost its peer 2 x 180 s: tools/launch_path_two_ranks.sh).  Here both ranks lack a device."""
+    no device cost its peer 2 x 180 s with the driver's two-rank command line on a one-GPU box).  Here both ranks lack a device."""
     import time
     from soundscope_amd import _lib as L
     # the library's own device count, not torch's: importing torch here would load its bundled HIP runtime and librccl

@@ -25,7 +25,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # 5).  All of them are register builds for FOUR waves per SIMD (128 VGPRs) of forms whose three-waves build (168 VGPRs) is spill-free;
 # the launcher takes the four-waves build only for grids of more than 768 workgroups, where it still beats the spill-free build by
 # 10-37 % (profiles/r05_td_kernel_resources.txt).
-#   SPLIT (whole-stream workgroups, SS_TD_WHOLE_STREAMS: opt-in, 11-16 % slower than time segments at such grids anyway)
+#   SPLIT (whole-stream workgroups, time-domain mode 2 of ss_batch_set_time_domain_mode: opt-in, 11-16 % slower than time segments at such grids anyway)
 ALLOW = {
     r"k_time_domain<[420], false, [28], [0123], 4, true, false>": 48,      # (ten of them, 8-44 B; round 5: 64)
 }

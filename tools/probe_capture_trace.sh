@@ -1,5 +1,9 @@
-root=${GRAFT_REPO_ROOT:-$(pwd)}
-out=$root/gpurun_out/r5h; mkdir -p $out
+#!/bin/bash
+# kernel and copy durations inside the capture tick (rocprofv3 kernel + memory-copy trace over 100 capture ticks)
+set -Ee
+trap 'echo "probe_capture_trace.sh: stopped, status $? at line $LINENO: $BASH_COMMAND" >&2' ERR
+root=$(cd "$(dirname "$0")/.." && pwd)
+out=$root/tools/out/r5h; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 cat > /tmp/cap.py <<PY
 import sys, time
@@ -13,8 +17,8 @@ cap = ssa.CaptureSession(2, rate)
 ring = np.concatenate([x, x, x])[:30 * rate]
 for tick in range(100): cap.analyze_microphone_input(ring)
 PY
-rocprofv3 --kernel-trace --memory-copy-trace --stats -d $out/kt -o kt -- python /tmp/cap.py > $out/cap.log 2>&1
-db=$(find $out/kt -name '*.db' | head -1)
+timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --stats -d $out/kt -o kt -- python /tmp/cap.py > $out/cap.log 2>&1
+db=$(find $out/kt -name '*.db' -print -quit)
 python $root/tools/rocpd_summary.py "$db" | head -12 | cut -c1-60,150-230
 python - <<PY
 import sqlite3

@@ -1,6 +1,9 @@
 #!/bin/bash
-root=${GRAFT_REPO_ROOT:-$(pwd)}
-out=$root/gpurun_out/r5open2; mkdir -p $out
+# where a session open's wall time goes: kernel trace and host timeline of five opens of a 12 s file, the calls of the last one
+set -Ee
+trap 'echo "probe_open_timeline.sh: stopped, status $? at line $LINENO: $BASH_COMMAND" >&2' ERR
+root=$(cd "$(dirname "$0")/.." && pwd)
+out=$root/tools/out/r5open2; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 cat > /tmp/open6.py <<PY
 import sys, time
@@ -16,9 +19,9 @@ time.sleep(0.05)
 t0 = time.perf_counter(); s = ssa.FileSession(x, 2, 48000); t1 = time.perf_counter()
 print(f"LAST open {1e3 * (t1 - t0):.2f} ms", flush=True)
 PY
-rocprofv3 --hip-trace --kernel-trace -f csv -d $out/ht -o ht -- python /tmp/open6.py > $out/open.log 2>&1
+timeout -k 10 600 rocprofv3 --hip-trace --kernel-trace -f csv -d $out/ht -o ht -- python /tmp/open6.py > $out/open.log 2>&1
 grep -v rocprofv3 $out/open.log | grep open
-f=$(find $out/ht -name '*hip_api_trace.csv' | head -1)
+f=$(find $out/ht -name '*hip_api_trace.csv' -print -quit)
 python3 - "$f" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))

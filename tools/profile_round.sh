@@ -2,28 +2,28 @@
 # Refresh the judged measurement set on the GPU box (one call): the bench line, the rocprofv3 kernel-trace summary of
 # the SAME bench command, and PMC passes (each counter group in its own rocprofv3 run, no tracing beside --pmc) over
 # the config 3 probe (tools/perf_probe.py) and the config 5 probe (tools/probe_cfg5.py).
-# usage: tools/profile_round.sh <tag>     (outputs under gpurun_out/<tag>/; copy what is judged into profiles/)
-set -u
+# usage: tools/profile_round.sh <tag>     (outputs under tools/out/<tag>/; copy what is judged into profiles/)
+# The first run that fails or times out ends the set.
+set -Eeu
+trap 'echo "profile_round.sh: stopped, status $? at line $LINENO: $BASH_COMMAND" >&2' ERR
 tag=${1:-prof}
-root=${GRAFT_REPO_ROOT:-$(pwd)}
-out=$root/gpurun_out/$tag
+root=$(cd "$(dirname "$0")/.." && pwd)
+out=$root/tools/out/$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 if [ "${SKIP_BENCH:-0}" != 1 ]; then        # (SKIP_BENCH=1: the PMC passes only)
-python $root/bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
-rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- python $root/bench.py --steps 20 --warmup 5 > $out/kt_bench.json 2> $out/kt.err
-db=$(find $out/kt -name '*.db' | head -1)
-[ -n "$db" ] && python $root/tools/rocpd_summary.py "$db" $out/kernel_stats.txt
+timeout -k 10 600 python $root/bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- python $root/bench.py --steps 20 --warmup 5 > $out/kt_bench.json 2> $out/kt.err
+db=$(find $out/kt -name '*.db' -print -quit)
+python $root/tools/rocpd_summary.py "$db" $out/kernel_stats.txt
 rm -rf $out/kt
 fi
 pmc() {   # pmc <name> <probe script> <probe args> <counters...>
   name=$1; probe=$2; pargs=$3; shift 3
-  timeout 600 rocprofv3 --pmc "$@" -d $out/pmc_$name -o p -- python $root/$probe $pargs > $out/pmc_$name.log 2>&1
-  db=$(find $out/pmc_$name -name '*.db' | head -1)
-  if [ -n "$db" ]; then
-    echo "## rocprofv3 --pmc $* -- python $probe $pargs" >> $out/pmc_summary.txt
-    python $root/tools/rocpd_summary.py "$db" | grep -E "ssk::k_(fft|time_domain|finalize)" | grep -v "^ *[0-9]+ +[0-9.]+ +[0-9.]+ +[0-9.]+ +[0-9.]+" >> $out/pmc_summary.txt
-  fi
+  timeout -k 10 600 rocprofv3 --pmc "$@" -d $out/pmc_$name -o p -- python $root/$probe $pargs > $out/pmc_$name.log 2>&1
+  db=$(find $out/pmc_$name -name '*.db' -print -quit)
+  echo "## rocprofv3 --pmc $* -- python $probe $pargs" >> $out/pmc_summary.txt
+  python $root/tools/rocpd_summary.py "$db" | grep -E "ssk::k_(fft|time_domain|finalize)" | grep -v "^ *[0-9]+ +[0-9.]+ +[0-9.]+ +[0-9.]+ +[0-9.]+" >> $out/pmc_summary.txt
   rm -rf $out/pmc_$name
 }
 [ "${SKIP_PMC:-0}" = 1 ] && { cat $out/bench.json | head -c 600; echo; cat $out/kernel_stats.txt | head -24; exit 0; }     # bench line + kernel trace only

@@ -1,5 +1,5 @@
 // Instruction-rate microbenchmarks for gfx950 (calibrates DESIGN.md's cost model):
-// hipcc --offload-arch=gfx950 -O3 tools/ubench.hip -o gpurun_out/ubench && gpurun_out/ubench
+// hipcc --offload-arch=gfx950 -O3 tools/ubench.hip -o tools/bin/ubench && tools/bin/ubench
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
