@@ -12,34 +12,16 @@ namespace ssh {
 // has succeeded — on failure the handle keeps its previous meter (only sample_rate has changed by then).
 SS_HIDDEN int handle_make_meter(ss_analyzer *h, uint32_t channels, uint32_t rate)
 {
-    int rc = meter_args_ok(channels, rate);
+    MeterStore meter;
+    int rc = meter.build(1, channels, rate, h->tp_cfg);
     if (rc) return rc;
-    const int tp_factor = h->tp_cfg ? h->tp_cfg : sst::true_peak_factor_for_rate(rate);
-    TdTables *td = nullptr;
-    rc = get_td_tables(rate, tp_factor, channels, &td);
-    if (rc) return rc;
-    const uint64_t s100 = (rate + 5) / 10;
-    uint64_t ring_frames = (uint64_t)rate * 3000 / 1000;
-    if (ring_frames % s100) ring_frames += s100 - ring_frames % s100;
-    DevBuf<ssk::TdState> state;
-    DevBuf<uint64_t> hist;
-    DevBuf<double> sub, ring, weights, out2, ring_scratch;
-    DevBuf<uint32_t> counts;
-    HIPCHK(state.alloc(1));
-    HIPCHK(hist.alloc(2 * sst::kHistBins));
-    HIPCHK(sub.alloc((size_t)ss_analyzer::kSubCap * channels));
-    HIPCHK(ring.alloc(ring_frames * channels));
-    HIPCHK(counts.alloc(2));
+    DevBuf<double> out2, ring_scratch;
     HIPCHK(out2.alloc(2));
     HIPCHK(ring_scratch.alloc(ssk::kRingScratchDoubles));
     HIPCHK(hipMemset(ring_scratch.p, 0, ssk::kRingScratchDoubles * sizeof(double)));      // (k_ring_energy's completion counter starts at zero)
-    std::vector<double> w(channels);
-    sst::channel_weights(channels, w.data());
-    HIPCHK(weights.upload(w));
     // commit
-    h->channels = channels; h->meter_rate = rate; h->tp_factor = tp_factor; h->tp_cfg_applied = h->tp_cfg; h->td = td; h->ring_frames = ring_frames;
-    h->state.swap(state); h->hist.swap(hist); h->sub.swap(sub); h->ring.swap(ring); h->counts.swap(counts);
-    h->out2.swap(out2); h->ring_scratch.swap(ring_scratch); h->weights.swap(weights);
+    h->meter = std::move(meter); h->out2.swap(out2); h->ring_scratch.swap(ring_scratch);
+    h->tp_cfg_applied = h->tp_cfg;
     h->meter_ok = true;
     h->change_count++;
     return SS_OK;
@@ -50,14 +32,15 @@ int handle_reset(ss_analyzer *h)
     if (!h->meter_ok) return SS_OK;
     if (h->tp_cfg != h->tp_cfg_applied) {        // ss_analyzer_set_true_peak_factor since the meter was built
         HIPCHK(hipStreamSynchronize(h->stream));
-        int rc = handle_make_meter(h, h->channels, h->meter_rate);
+        int rc = handle_make_meter(h, h->meter.channels, h->meter.rate);
         if (rc) return rc;
     }
-    HIPCHK(hipMemsetAsync(h->state.p, 0, sizeof(ssk::TdState), h->stream));
-    HIPCHK(hipMemsetAsync(h->hist.p, 0, h->hist.n * sizeof(uint64_t), h->stream));
-    HIPCHK(hipMemsetAsync(h->sub.p, 0, h->sub.n * sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(h->ring.p, 0, h->ring.n * sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(h->counts.p, 0, 2 * sizeof(uint32_t), h->stream));
+    const MeterStore &m = h->meter;
+    HIPCHK(hipMemsetAsync(m.state.p, 0, sizeof(ssk::TdState), h->stream));
+    HIPCHK(hipMemsetAsync(m.hist.p, 0, m.hist.n * sizeof(uint64_t), h->stream));
+    HIPCHK(hipMemsetAsync(m.sub.p, 0, m.sub.n * sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(m.ring.p, 0, m.ring.n * sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(m.counts.p, 0, 2 * sizeof(uint32_t), h->stream));
     h->frames_fed = 0;
     h->change_count++;
     return SS_OK;
@@ -119,7 +102,7 @@ int attach_readings(ss_analyzer *h, ssk::FinalizeParams *gating)
     if (rc) return rc;
     h->readings_seq = h->readings_seq + 1u ? h->readings_seq + 1u : 1u;
     gating->readings_out = h->pin_eval_dev;
-    gating->readings_peaks_src = &h->state.p->sample_peak[0]; gating->readings_peaks_dst = h->pin_peaks_dev;
+    gating->readings_peaks_src = &h->meter.state.p->sample_peak[0]; gating->readings_peaks_dst = h->pin_peaks_dev;
     gating->readings_flag = h->pin_flag_dev; gating->readings_seq = h->readings_seq;
     h->prefetch_stamp = h->change_count;
     return SS_OK;
@@ -132,10 +115,7 @@ int prefetch_readings(ss_analyzer *h, bool on_demand)
     { static const bool off = std::getenv("SS_NO_PREFETCH") != nullptr; if (off && !on_demand) return SS_OK; }
 #endif
     (void)on_demand;
-    const double *he, *hb;
-    int rc = get_hist_tables(&he, &hb);
-    if (rc) return rc;
-    rc = pin_ready(h);
+    int rc = pin_ready(h);
     if (rc) return rc;
     static_assert(offsetof(ssk::TdState, true_peak) == offsetof(ssk::TdState, sample_peak) + sizeof(float) * ssk::kMaxChannels,
                   "sample_peak and true_peak are read as one block");
@@ -143,8 +123,8 @@ int prefetch_readings(ss_analyzer *h, bool on_demand)
     // pinned memory behind everything — what the getter waits for (no event, no copy command: the launch has to fit the few
     // microseconds a tick has left between its charts and the end of the loudness call)
     h->readings_seq = h->readings_seq + 1u ? h->readings_seq + 1u : 1u;
-    const ssk::ReadingsExtra x{&h->state.p->sample_peak[0], h->pin_peaks_dev, h->pin_flag_dev, h->readings_seq};
-    HIPCHK(ssk::launch_hist_eval(h->hist.p, he, hb, h->pin_eval_dev, h->stream, &x));
+    const ssk::ReadingsExtra x{&h->meter.state.p->sample_peak[0], h->pin_peaks_dev, h->pin_flag_dev, h->readings_seq};
+    HIPCHK(ssk::launch_hist_eval(h->meter.hist.p, h->meter.hist_energies, h->meter.hist_bounds, h->pin_eval_dev, h->stream, &x));
     h->prefetch_stamp = h->change_count;
     return SS_OK;
 }
@@ -286,16 +266,9 @@ int ss_get_fft(const ss_analyzer *hc, const float *samples, size_t n,
     // (the transform reads its window many times in small pieces: from page-locked host memory in place that costs the kernel
     // 20 us more than it takes from HBM — one DMA of the page-locked copy first)
     HIPCHK(hipMemcpyAsync(h->in.p, h->pin_in[pin], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    ssk::FftBatchParams p{};
-    p.pcm = h->in.p; p.out = h->pin_out_dev;
-    p.window = ft->window.p; p.half_window = ft->half_window.p;
-    p.tw_n = ft->tw_n.p; p.tw_256 = ft->tw_256.p; p.pink = nullptr;
-    p.frames_per_stream = n; p.first_start = 0; p.n_streams = 1; p.channels = 1;
-    p.n_windows = 1; p.hop = 0; p.n = (uint32_t)n;
-    p.first_bin = (uint32_t)bt->first; p.n_bins = (uint32_t)bt->count; p.bin_stride = p.n_bins; p.windows_per_block = 1;
-    p.db_offset = (float)(20.0 * std::log10(4.0 / (double)n));
+    ssk::FftBatchParams p = one_window_fft(*ft, *bt);
+    p.pcm = h->in.p; p.out = h->pin_out_dev; p.channels = 1;
     if (n == 16384) {
-        p.tw_core = ft->core_tw4096; p.tw_256 = ft->core_tw256;
         HIPCHK(ssk::launch_fft16k(p, 0, h->stream));
     } else if (n == 4096) {
         // the radix-16 machine of the batch path on one window: k_fft4096_pairw with its second window absent
@@ -425,12 +398,10 @@ int ssh::add_samples_impl(ss_analyzer *h, const float *samples, size_t n, bool o
     if (!h->meter_ok) return SS_ERR_INVALID_MODE;
     if (n == 0) return SS_OK;
     if (!samples) return SS_ERR_INVALID_ARG;
-    const uint32_t C = h->channels;
+    const MeterStore &m = h->meter;
+    const uint32_t C = m.channels;
     if (n % C) return SS_ERR_NOMEM;             // add_frames_f32: partial frame
-    const uint64_t S = h->td->host.s100;
-    const double *he, *hb;
-    int rc = get_hist_tables(&he, &hb);
-    if (rc) return rc;
+    const uint64_t S = m.s100;
     // pieces of at most 32 sub-blocks so the sub-block ring (96) always holds the
     // 30-block history a short-term block needs
     const uint64_t piece_frames = 32 * S;
@@ -440,7 +411,7 @@ int ssh::add_samples_impl(ss_analyzer *h, const float *samples, size_t n, bool o
     // launches (the event tells the next user of that buffer when the kernel is through with it)
     int pin = -1;
     if (!on_device && n <= ss_analyzer::kPinFloats && frames <= piece_frames) {
-        rc = pin_acquire(h, &pin);
+        int rc = pin_acquire(h, &pin);
         if (rc) return rc;
         std::memcpy(h->pin_in[pin], samples, n * sizeof(float));
         // ... and on to HBM by one DMA (reading the page-locked copy in place over PCIe cost the kernel 33 instead of 22 us)
@@ -455,22 +426,16 @@ int ssh::add_samples_impl(ss_analyzer *h, const float *samples, size_t n, bool o
             HIPCHK(h->in.ensure(take * C));
             HIPCHK(hipMemcpyAsync(h->in.p, samples + done * C, take * C * sizeof(float), hipMemcpyHostToDevice, h->stream));
         }
-        ssk::TdParams p{};
-        p.pcm = on_device ? samples + done * C : h->in.p; p.stream_stride = 0; p.n_frames = take; p.n_streams = 1; p.channels = C;
-        p.k = h->td->dev.p; p.state = h->state.p;
-        p.subblocks = h->sub.p; p.sub_stride = 0; p.sub_cap = ss_analyzer::kSubCap;
-        p.ring = h->ring.p; p.ring_frames = h->ring_frames; p.tp_factor = h->tp_factor;
-        p.s100 = (uint32_t)S; p.nseg = 1; p.seg_sub = 0; p.warm_sub = 0;
+        ssk::TdParams p = m.td_params(on_device ? samples + done * C : h->in.p, 0, take);
         p.tp_f32 = h->tp_arith == SS_TP_ARITH_F32 ? 1u : 0u;           // default: ebur128's f32 interpolator width (the handle IS the reference's Analyzer)
         const bool with_tick = tick && tick->fft && on_device && take == frames;
         const uint64_t st_frames = S * 30;                              // the short-term window (3 s)
-        if (with_tick && tick->shortterm_out && take <= st_frames && st_frames <= h->ring_frames &&
-            h->ring_frames * C < (1ull << 31)) {
+        if (with_tick && tick->shortterm_out && take <= st_frames && m.st_on) {
             // the window ends with this call: frames [fed + take - st_frames, fed + take); the part in front of the call is the
             // ring workgroups' (frames before 0 are the zeroed ring)
             const uint64_t end_new = h->frames_fed + take;
-            const uint64_t begin = (end_new % h->ring_frames + h->ring_frames - st_frames) % h->ring_frames;
-            p.st_out = tick->shortterm_out; p.st_scratch = h->ring_scratch.p + ssk::kRingTickScratch; p.st_weights = h->weights.p;
+            const uint64_t begin = (end_new % m.ring_frames + m.ring_frames - st_frames) % m.ring_frames;
+            p.st_out = tick->shortterm_out; p.st_scratch = h->ring_scratch.p + ssk::kRingTickScratch; p.st_weights = m.weights.p;
             p.st_frames = (double)st_frames;
             p.st_begin_elem = (uint32_t)(begin * C); p.st_old_total = (uint32_t)((st_frames - take) * C);
             p.st_blocks = ssk::kRingTickBlocks;
@@ -479,17 +444,11 @@ int ssh::add_samples_impl(ss_analyzer *h, const float *samples, size_t n, bool o
         if (with_tick) tick->st_fused = tick->fused && p.st_out != nullptr;
         const uint64_t sb0 = h->frames_fed / S, sb1 = (h->frames_fed + take) / S;
         if (sb1 > sb0) {
-            ssk::FinalizeParams f{};
-            f.k = h->td->dev.p; f.subblocks = h->sub.p; f.sub_stride = 0; f.sub_cap = ss_analyzer::kSubCap;
-            f.hist_energies = he; f.hist_bounds = hb; f.weights = h->weights.p;
-            f.hist = h->hist.p; f.corpus_hist = nullptr; f.n_streams = 1; f.channels = C;
-            f.sub_begin = sb0; f.sub_end = sb1;
-            f.out_integrated = nullptr; f.out_lra = nullptr; f.out_counts = h->counts.p;
-            f.state = h->state.p;
+            const ssk::FinalizeParams f = m.stream_gating(sb0, sb1);
             // a caller that has something shorter to put in front (a tick's short-term reading) launches the gating of a
             // single-piece call itself, on the same stream
             if (deferred && on_device && take == frames) *deferred = f;
-            else HIPCHK(ssk::launch_finalize(f, h->stream));
+            else HIPCHK(ssk::launch_finalize_stream(f, h->stream));
         }
         // the staging buffer is reused by the next piece
         if (!on_device) HIPCHK(hipStreamSynchronize(h->stream));
@@ -521,8 +480,9 @@ void ss_reset(ss_analyzer *h)
 int ssh::ring_loudness_enqueue(ss_analyzer *h, uint64_t frames, double *out2_dev)
 {
     SS_ON_DEVICE(h);
-    HIPCHK(ssk::launch_ring_energy(h->ring.p, h->ring_frames, h->channels, h->frames_fed, frames,
-                                   h->weights.p, out2_dev ? out2_dev : h->out2.p, h->ring_scratch.p, h->stream));
+    const MeterStore &m = h->meter;
+    HIPCHK(ssk::launch_ring_energy(m.ring.p, m.ring_frames, m.channels, h->frames_fed, frames,
+                                   m.weights.p, out2_dev ? out2_dev : h->out2.p, h->ring_scratch.p, h->stream));
     return SS_OK;
 }
 extern "C" {
@@ -532,7 +492,7 @@ static int ring_loudness(ss_analyzer *h, uint64_t frames, double *out)
     SS_ON_DEVICE(h);
     if (!h || !out) return SS_ERR_INVALID_ARG;
     if (!h->meter_ok) return SS_ERR_INVALID_MODE;
-    if (frames > h->ring_frames) return SS_ERR_INVALID_MODE;
+    if (frames > h->meter.ring_frames) return SS_ERR_INVALID_MODE;
     int rc = pin_ready(h);
     if (rc) return rc;
     rc = ring_loudness_enqueue(h, frames, h->pin_d_dev);        // (energy, loudness) straight into page-locked memory
@@ -550,14 +510,14 @@ int ss_get_shortterm_lufs(ss_analyzer *h, double *out)
 {
     SS_ON_DEVICE(h);
     if (!h || !h->meter_ok) return h ? SS_ERR_INVALID_MODE : SS_ERR_INVALID_ARG;
-    return ring_loudness(h, (uint64_t)h->td->host.s100 * 30, out);
+    return ring_loudness(h, h->meter.s100 * 30, out);
 }
 
 int ss_get_momentary_lufs(ss_analyzer *h, double *out)
 {
     SS_ON_DEVICE(h);
     if (!h || !h->meter_ok) return h ? SS_ERR_INVALID_MODE : SS_ERR_INVALID_ARG;
-    return ring_loudness(h, (uint64_t)h->td->host.s100 * 4, out);
+    return ring_loudness(h, h->meter.s100 * 4, out);
 }
 
 // integrated loudness + loudness range (one histogram evaluation) and every channel's peaks (one copy), behind ONE wait: the
@@ -623,7 +583,7 @@ static int read_peaks(ss_analyzer *h, uint32_t ch, double *sample_pk, double *tr
     SS_ON_DEVICE(h);
     if (!h) return SS_ERR_INVALID_ARG;
     if (!h->meter_ok) return SS_ERR_INVALID_MODE;
-    if (ch >= h->channels) return SS_ERR_INVALID_CHANNEL;
+    if (ch >= h->meter.channels) return SS_ERR_INVALID_CHANNEL;
     int rc = refresh_readings(h);
     if (rc) return rc;
     const float sp = h->peaks_cache[ch], tp = h->peaks_cache[ssk::kMaxChannels + ch];
@@ -664,14 +624,14 @@ int ss_inspect_filter_state(ss_analyzer *h, uint32_t channel, double v4[4])
     SS_ON_DEVICE(h);
     if (!h || !v4) return SS_ERR_INVALID_ARG;
     if (!h->meter_ok) return SS_ERR_INVALID_MODE;
-    if (channel >= h->channels) return SS_ERR_INVALID_CHANNEL;
+    if (channel >= h->meter.channels) return SS_ERR_INVALID_CHANNEL;
     {   // a channel the crate maps to Channel::Unused is not filtered there at all: its state stays what reset left.  (The device
         // runs the recurrence on every channel — the lanes are there anyway — and no reading ever looks at such a channel.)
-        std::vector<double> w(h->channels);
-        sst::channel_weights(h->channels, w.data());
+        std::vector<double> w(h->meter.channels);
+        sst::channel_weights(h->meter.channels, w.data());
         if (w[channel] == 0.0) { v4[0] = v4[1] = v4[2] = v4[3] = 0.0; return SS_OK; }
     }
-    HIPCHK(hipMemcpyAsync(v4, &h->state.p->v[channel][0], 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(v4, &h->meter.state.p->v[channel][0], 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SS_OK;
 }

@@ -211,11 +211,7 @@ int get_td_tables(uint32_t rate, int factor, uint32_t channels, TdTables **out)
         if (factor == 4) sst::true_peak_fold4(k.tp_fold);
     }
     k.s100 = (rate + 5) / 10;
-    {
-        uint64_t ring = (uint64_t)rate * 3000 / 1000;                    // the meter's ring (ss_analyzer.cpp: the same rule)
-        if (ring % k.s100) ring += k.s100 - ring % k.s100;
-        k.st_off = (uint64_t)k.s100 * 30 > ring ? 1u : 0u;
-    }
+    k.st_off = (uint64_t)k.s100 * 30 > MeterStore::ring_frames_for(rate) ? 1u : 0u;
     std::vector<ssk::TdConst> v(1, k);
     HIPCHK(t->dev.upload(v));
     *out = t.get();
@@ -244,6 +240,78 @@ int meter_args_ok(uint32_t channels, uint32_t rate)
     if (channels == 0 || channels > 64) return SS_ERR_NOMEM;
     if (rate < 16 || rate > 2822400) return SS_ERR_NOMEM;
     return SS_OK;
+}
+
+uint64_t MeterStore::ring_frames_for(uint32_t rate)
+{
+    const uint64_t s = (rate + 5) / 10, frames = (uint64_t)rate * 3000 / 1000;
+    return frames % s ? frames + s - frames % s : frames;
+}
+
+int MeterStore::build(uint32_t n_streams, uint32_t channels_, uint32_t rate_, int tp_cfg)
+{
+    int rc = meter_args_ok(channels_, rate_);
+    if (rc) return rc;
+    const int factor = tp_cfg ? tp_cfg : sst::true_peak_factor_for_rate(rate_);
+    rc = get_td_tables(rate_, factor, channels_, &td);
+    if (rc) return rc;
+    rc = get_hist_tables(&hist_energies, &hist_bounds);
+    if (rc) return rc;
+    n = n_streams; channels = channels_; rate = rate_; tp_factor = factor;
+    s100 = td->host.s100; ring_frames = ring_frames_for(rate); st_on = !td->host.st_off;
+    if (ring_frames * channels >= (1ull << 31)) return SS_ERR_UNSUPPORTED;        // (32-bit ring positions in the kernels)
+    const size_t N = n;
+    HIPCHK(state.alloc(N));
+    HIPCHK(hist.alloc(N * 2 * sst::kHistBins));
+    HIPCHK(sub.alloc(N * kSubCap * channels));
+    HIPCHK(ring.alloc(N * ring_frames * channels));
+    HIPCHK(counts.alloc(N * 2));
+    std::vector<double> w(channels);
+    sst::channel_weights(channels, w.data());
+    HIPCHK(weights.upload(w));
+    return SS_OK;
+}
+
+ssk::TdParams MeterStore::td_params(const float *pcm, uint64_t stream_stride, uint64_t frames) const
+{
+    ssk::TdParams p{};
+    p.pcm = pcm; p.stream_stride = stream_stride; p.n_frames = frames; p.n_streams = n; p.channels = channels;
+    p.k = td->dev.p; p.state = state.p; p.subblocks = sub.p; p.sub_stride = (uint64_t)kSubCap * channels; p.sub_cap = kSubCap;
+    p.ring = ring.p; p.ring_frames = ring_frames; p.ring_stride = ring_frames * channels;
+    p.tp_factor = tp_factor; p.s100 = (uint32_t)s100; p.nseg = 1;
+    return p;
+}
+
+ssk::MeterBankParams MeterStore::bank_params() const
+{
+    ssk::MeterBankParams q{};
+    q.k = td->dev.p; q.state = state.p;
+    q.subblocks = sub.p; q.sub_stride = (uint64_t)kSubCap * channels; q.sub_cap = kSubCap;
+    q.ring = ring.p; q.ring_stride = ring_frames * channels; q.ring_frames = ring_frames;
+    q.weights = weights.p; q.hist = hist.p; q.counts = counts.p;
+    q.hist_energies = hist_energies; q.hist_bounds = hist_bounds;
+    q.n_streams = n; q.channels = channels; q.st_on = st_on ? 1u : 0u;
+    return q;
+}
+
+ssk::FinalizeParams MeterStore::stream_gating(uint64_t sub_begin, uint64_t sub_end) const
+{
+    ssk::FinalizeParams f{};
+    f.k = td->dev.p; f.subblocks = sub.p; f.sub_stride = (uint64_t)kSubCap * channels; f.sub_cap = kSubCap;
+    f.hist_energies = hist_energies; f.hist_bounds = hist_bounds; f.weights = weights.p; f.hist = hist.p;
+    f.n_streams = 1; f.channels = channels; f.sub_begin = sub_begin; f.sub_end = sub_end; f.out_counts = counts.p; f.state = state.p;
+    return f;
+}
+
+ssk::FftBatchParams one_window_fft(const FftTables &ft, const BinTables &bt)
+{
+    ssk::FftBatchParams p{};
+    p.window = ft.window.p; p.half_window = ft.half_window.p; p.tw_n = ft.tw_n.p; p.tw_256 = ft.tw_256.p;
+    if (ft.n == 16384) { p.tw_core = ft.core_tw4096; p.tw_256 = ft.core_tw256; }
+    p.n_streams = 1; p.n_windows = 1; p.n = (uint32_t)ft.n; p.windows_per_block = 1;
+    p.first_bin = (uint32_t)bt.first; p.n_bins = (uint32_t)bt.count; p.bin_stride = p.n_bins;
+    p.db_offset = (float)(20.0 * std::log10(4.0 / (double)ft.n));
+    return p;
 }
 
 }  // namespace ssh

@@ -1,10 +1,13 @@
 // ss_host.h — what the host-side translation units of the library share (never installed): the HIP error channel,
-// RAII device buffers, the per-device caches of constant tables, per-thread scratch, and the handle type.
-//   ss_host.cpp      caches, device selection, status strings, table inspection
-//   ss_analyzer.cpp  the Analyzer mirror (one entry point per Rust method, analyzer.rs:29-183)
-//   ss_ingest.cpp    RIFF/WAVE header walk and PCM conversion
-//   ss_batch.cpp     the batch extension (BASELINE configs 3-5) and the render-side reductions (N3)
-//   ss_session.cpp   the tick drivers (N1)
+// RAII device buffers, the per-device caches of constant tables, per-thread scratch, the live meter and the handle type.
+//   ss_host.cpp         caches, device selection, status strings, table inspection, the live meter (MeterStore)
+//   ss_analyzer.cpp     the Analyzer mirror (one entry point per Rust method, analyzer.rs:29-183)
+//   ss_ingest.cpp       RIFF/WAVE header walk and PCM conversion
+//   ss_batch.cpp        the batch extension (BASELINE configs 3-5) and the render-side reductions (N3)
+//   ss_session.cpp      the tick drivers (N1)
+//   ss_meter_bank.cpp   meter banks: many live meters advanced together
+//   ss_comm.cpp         the all-reduce of the corpus histograms (RCCL opened at run time; does not include this header)
+//   ss_tables.cpp       the host-side design of the constant tables (includes ss_tables.h only)
 #pragma once
 #include "../../include/soundscope_hip.h"
 
@@ -43,6 +46,8 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }     // (o frees what this held)
     ~DevBuf() { release(); }
     void release()
     {
@@ -167,6 +172,40 @@ constexpr uint32_t kTdFixSub = 2;
 
 SS_HIDDEN int meter_args_ok(uint32_t channels, uint32_t rate);
 
+// The live loudness meter of n streams, laid out per stream as [stream][...]: a handle holds one (n = 1), a meter bank one of n.
+struct SS_HIDDEN MeterStore {
+    // sub-block ring slots per stream: calls are cut into pieces of at most 32 sub-blocks, so the ring always holds the thirty
+    // sub-blocks a short-term block reads
+    static constexpr uint32_t kSubCap = 96;
+    TdTables *td = nullptr;
+    const double *hist_energies = nullptr, *hist_bounds = nullptr;      // the gate's histogram tables (get_hist_tables)
+    int tp_factor = 0;                   // effective
+    uint32_t n = 0, channels = 0, rate = 0;
+    uint64_t s100 = 0;                   // frames per 100 ms sub-block
+    uint64_t ring_frames = 0;            // the filtered-sample ring: 3 s rounded up to a whole sub-block
+    bool st_on = false;                  // thirty sub-blocks fit the ring (otherwise the crate has no short-term blocks at this rate)
+    DevBuf<ssk::TdState> state;          // [n]
+    DevBuf<uint64_t> hist;               // [n][2][1000]
+    DevBuf<double> sub, ring, weights;   // [n][kSubCap][C], [n][ring_frames][C], [C]
+    DevBuf<uint32_t> counts;             // [n][2]
+
+    static uint64_t ring_frames_for(uint32_t rate);
+    // EbuR128::new for n streams into a FRESH store: argument checks, tables, geometry, buffers, weights (tp_cfg: the true-peak
+    // factor, 0 = the crate's rule for the rate).  Nothing else is touched, so a caller that must keep its meter on failure builds
+    // into a local store and moves it in on success.
+    int build(uint32_t n_streams, uint32_t channels, uint32_t rate, int tp_cfg);
+    // a streaming call of `frames` frames of every stream (stream s at pcm + s * stream_stride) on the meter: one time segment, the
+    // sub-block and filtered-sample rings.  The caller sets tp_f32 (and a tick's short-term fields).
+    ssk::TdParams td_params(const float *pcm, uint64_t stream_stride, uint64_t frames) const;
+    ssk::MeterBankParams bank_params() const;
+    // the gating of stream 0's sub-blocks [sub_begin, sub_end) (ssk::launch_finalize_stream: the handle)
+    ssk::FinalizeParams stream_gating(uint64_t sub_begin, uint64_t sub_end) const;
+};
+
+// one window of ft.n points of one stream (ss_get_fft, the ticks, the meter banks: their rows agree bit for bit): the tables, the bins
+// of bt in unpadded rows, raw dBFS (db_offset = 20 log10(4 / n)).  The caller sets pcm, out, channels and the window's start.
+SS_HIDDEN ssk::FftBatchParams one_window_fft(const FftTables &ft, const BinTables &bt);
+
 }  // namespace ssh
 
 // ============================================================================
@@ -174,29 +213,19 @@ SS_HIDDEN int meter_args_ok(uint32_t channels, uint32_t rate);
 // ============================================================================
 struct ss_analyzer {
     int device = 0;            // the HIP device this handle's buffers live on
-    uint32_t channels = 0, rate = 0;
-    uint32_t meter_rate = 0;   // the rate the current meter was built for (rate sticks on a failed configure, the meter does not change)
+    uint32_t rate = 0;         // sticks on a failed configure (meter.rate: the rate the current meter was built for)
     int tp_cfg = 0;            // 0 = crate rule
-    int tp_factor = 0;         // effective
     int tp_arith = SS_TP_ARITH_F32;   // ss_analyzer_set_true_peak_arith
     int tp_cfg_applied = 0;    // the tp_cfg the current meter was built with
     bool meter_ok = false;
     hipStream_t stream = nullptr;
-    ssh::TdTables *td = nullptr;
-    ssh::DevBuf<ssk::TdState> state;
-    ssh::DevBuf<uint64_t> hist;          // 2 x 1000
-    ssh::DevBuf<double> sub;             // kSubCap x C
-    ssh::DevBuf<double> ring;            // ring_frames x C
-    ssh::DevBuf<double> weights;
-    ssh::DevBuf<uint32_t> counts;
+    ssh::MeterStore meter;               // one stream
     ssh::DevBuf<double> out2, ring_scratch;
     ssh::DevBuf<float> in;
     // get_fft(&self): the handle is const at the boundary; the payload of the last error (ss_get_fft_error_values) and the
     // page-locked mailboxes below are the call's own scratch
     mutable float fft_err_a = 0.0f, fft_err_b = 0.0f;
-    uint64_t ring_frames = 0;
     uint64_t frames_fed = 0;
-    static constexpr uint32_t kSubCap = 96;
     // The reference's render loop asks for the integrated loudness, the loudness range and the true peak on EVERY frame (tui.rs:917,
     // :950, :969; a frame every 8 ms, a tick every 21): a reading is taken from the device once per state of the meter —
     // `change_count` moves with every feed, reset and re-configuration — and handed out from here until the state moves again.
@@ -241,7 +270,7 @@ SS_HIDDEN int prefetch_readings(ss_analyzer *h, bool on_demand = false);      //
 SS_HIDDEN int attach_readings(ss_analyzer *h, ssk::FinalizeParams *gating);
 // add_frames_f32 on the handle's meter; on_device: `samples` already lives in HBM (nothing is copied or waited for)
 // `deferred`: a single-piece device-resident call hands the gating launch (k_finalize_stream) of its new sub-blocks back to the
-// caller instead of enqueueing it (n_streams != 0: launch it with ssk::launch_finalize on h->stream before anything else reads the
+// caller instead of enqueueing it (n_streams != 0: launch it with ssk::launch_finalize_stream on h->stream before anything else reads the
 // histograms) — the tick drivers put the short-term reading in front of it
 // `tick`: what a tick wants to ride the launch of a single-piece device-resident call (ssk::launch_time_domain / k_tick): its
 // spectrum, and the short-term reading of the window that ends with the call; `fused` tells whether both did — if not, neither

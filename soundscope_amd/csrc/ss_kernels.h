@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -210,12 +210,17 @@ struct FinalizeParams {
     uint32_t *out_counts;            // [stream][2] gating / short-term blocks evaluated (nullable)
     const uint32_t *sub_end_of;   // ragged batches: sub-blocks of each stream (nullable = sub_end for all)
     const TdState *state;         // [stream]: bad_key (first sub-block with a non-finite sample per channel); nullable
-    // streaming form only (one handle): behind the histogram updates the same wave takes the handle's readings — (integrated,
+    // launch_finalize_stream only (one handle): behind the histogram updates the same wave takes the handle's readings — (integrated,
     // range) into readings_out, the peaks and the flag as in ReadingsExtra below (readings_out == nullptr: off)
     double *readings_out;
     const float *readings_peaks_src; float *readings_peaks_dst; uint32_t *readings_flag; uint32_t readings_seq;
 };
+// batches: the gating of every stream's sub-blocks [sub_begin, sub_end) into its own and the corpus histograms, the per-stream outputs
 hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s);
+// a handle (one stream, a few new sub-blocks per call): k_finalize_stream — the histograms updated in place and, when readings_out
+// is set, the handle's readings taken behind them
+// (hidden: not among the library's exported symbols)
+__attribute__((visibility("hidden"))) hipError_t launch_finalize_stream(const FinalizeParams &p, hipStream_t s);
 // Momentary / short-term loudness series of every stream of a batch and their maxima (SS_BATCH_LOUDNESS_SERIES), behind
 // launch_finalize on the same stream: p as given there (batches: slot == sub-block index); series[stream][series_stride][2]
 // (momentary, short-term) LUFS, extremes[stream] laid out as ss_loudness_extremes.

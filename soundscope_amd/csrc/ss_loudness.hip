@@ -362,17 +362,20 @@ constexpr uint32_t kFinalizeSmallMax = 64u;      // streams up to which a launch
 hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s)
 {
     if (p.n_streams == 0) return hipSuccess;
-    const bool streaming = p.n_streams == 1 && !p.corpus_hist && !p.out_integrated && !p.out_lra && p.sub_stride == 0;
-    if (streaming) hipLaunchKernelGGL(k_finalize_stream, dim3(1), dim3(64), 0, s, p);
-    else {
-        // four waves per stream (even a 100-sub-block stream moves two 8 KB histograms in and out of LDS: 64 / 128 / 256 / 512
-        // threads at the bench shape: 0.043 / 0.036 / 0.033 / 0.045 ms), sixteen for a long stream
-        const uint64_t nsub = p.sub_end - p.sub_begin;
-        const uint32_t threads = nsub > 2048 ? 1024u : 256u;
-        // a handful of short streams: the launch is a chain of memory round trips, not work -> the form that shortens the chain
-        if (p.n_streams <= kFinalizeSmallMax && threads == 256u) hipLaunchKernelGGL(k_finalize<true>, dim3(p.n_streams), dim3(threads), 0, s, p);
-        else hipLaunchKernelGGL(k_finalize<false>, dim3(p.n_streams), dim3(threads), 0, s, p);
-    }
+    // four waves per stream (even a 100-sub-block stream moves two 8 KB histograms in and out of LDS: 64 / 128 / 256 / 512
+    // threads at the bench shape: 0.043 / 0.036 / 0.033 / 0.045 ms), sixteen for a long stream
+    const uint64_t nsub = p.sub_end - p.sub_begin;
+    const uint32_t threads = nsub > 2048 ? 1024u : 256u;
+    // a handful of short streams: the launch is a chain of memory round trips, not work -> the form that shortens the chain
+    if (p.n_streams <= kFinalizeSmallMax && threads == 256u) hipLaunchKernelGGL(k_finalize<true>, dim3(p.n_streams), dim3(threads), 0, s, p);
+    else hipLaunchKernelGGL(k_finalize<false>, dim3(p.n_streams), dim3(threads), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_finalize_stream(const FinalizeParams &p, hipStream_t s)
+{
+    if (p.n_streams == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_finalize_stream, dim3(1), dim3(64), 0, s, p);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // ss_meter_bank.cpp — meter banks (include/soundscope_hip.h, "Meter banks"): N live meters of one shape advanced together.  Host
-// logic only: argument checks in the handle's order, the per-stream device state (laid out as ss_analyzer holds its meter), the
+// logic only: argument checks in the handle's order, the per-stream meters (one MeterStore, as a handle holds one of one stream), the
 // staging of the input and the launches — k_time_domain's streaming forms over all streams, k_meter_bank_gate,
 // k_meter_bank_readings, k_meter_bank_reset (ss_loudness.hip).  No CPU compute path.
 #include "ss_host.h"
@@ -8,18 +8,8 @@ using namespace ssh;
 
 struct ss_meter_bank {
     int device = 0;
-    uint32_t n = 0, channels = 0, rate = 0;
-    int tp_factor = 0;
     hipStream_t stream = nullptr;
-    TdTables *td = nullptr;
-    uint64_t s100 = 0, ring_frames = 0;
-    bool st_on = false;
-    ssh::DevBuf<ssk::TdState> state;
-    ssh::DevBuf<uint64_t> hist;            // [n][2][1000]
-    ssh::DevBuf<double> sub;               // [n][kSubCap][C]
-    ssh::DevBuf<double> ring;              // [n][ring_frames][C]
-    ssh::DevBuf<double> weights;
-    ssh::DevBuf<uint32_t> counts;          // [n][2]
+    ssh::MeterStore meter;                 // n streams
     ssh::DevBuf<uint32_t> list;            // ss_meter_bank_reset's stream indices
     ssh::DevBuf<float> in;                 // the f32 input of a host call
     ssh::DevBuf<unsigned char> raw;        // ss_meter_bank_add_pcm's bytes
@@ -46,7 +36,6 @@ struct ss_meter_bank {
     uint32_t spec_cols = 0;
     void *spec_pin = nullptr;              // page-locked results: floats, then the statuses
     size_t spec_pin_bytes = 0;
-    static constexpr uint32_t kSubCap = ss_analyzer::kSubCap;
 };
 
 static_assert(sizeof(ss_meter_reading) == 72 && sizeof(ssk::MeterReading) == sizeof(ss_meter_reading), "ss_meter_reading layout");
@@ -54,18 +43,6 @@ static_assert(offsetof(ss_meter_reading, true_peak) == offsetof(ssk::MeterReadin
               offsetof(ss_meter_reading, frames) == offsetof(ssk::MeterReading, frames), "ss_meter_reading layout");
 
 namespace {
-
-ssk::MeterBankParams bank_params(const ss_meter_bank *m, const double *he, const double *hb)
-{
-    ssk::MeterBankParams q{};
-    q.k = m->td->dev.p; q.state = m->state.p;
-    q.subblocks = m->sub.p; q.sub_stride = (uint64_t)ss_meter_bank::kSubCap * m->channels; q.sub_cap = ss_meter_bank::kSubCap;
-    q.ring = m->ring.p; q.ring_stride = m->ring_frames * m->channels; q.ring_frames = m->ring_frames;
-    q.weights = m->weights.p; q.hist = m->hist.p; q.counts = m->counts.p;
-    q.hist_energies = he; q.hist_bounds = hb;
-    q.n_streams = m->n; q.channels = m->channels; q.st_on = m->st_on ? 1u : 0u;
-    return q;
-}
 
 // a page-locked buffer of at least `bytes` no copy is still reading
 int pin_take(ss_meter_bank *m, size_t bytes)
@@ -95,29 +72,22 @@ int upload(ss_meter_bank *m, void *dst, const void *src, size_t bytes)
 // sub-blocks, so that the 96-slot sub-block ring always holds the thirty sub-blocks a short-term block reads (ss_add_samples' rule)
 int advance(ss_meter_bank *m, const float *pcm, uint64_t frames, uint64_t stride)
 {
-    const double *he, *hb;
-    int rc = get_hist_tables(&he, &hb);
-    if (rc) return rc;
-    const uint32_t C = m->channels;
+    const MeterStore &ms = m->meter;
+    const uint32_t C = ms.channels;
     if (m->spec_on) {
-        HIPCHK(ssk::launch_bank_history_append(m->spec_hist.p, pcm, stride, frames, m->spec_fed, m->n, C, m->stream));
+        HIPCHK(ssk::launch_bank_history_append(m->spec_hist.p, pcm, stride, frames, m->spec_fed, ms.n, C, m->stream));
         m->spec_fed += frames;
     }
-    const uint64_t S = m->s100, piece_frames = 32 * S;
-    const ssk::MeterBankParams q = bank_params(m, he, hb);
+    const uint64_t S = ms.s100, piece_frames = 32 * S;
+    const ssk::MeterBankParams q = ms.bank_params();
     for (uint64_t done = 0; done < frames;) {
         const uint64_t take = frames - done < piece_frames ? frames - done : piece_frames;
-        ssk::TdParams p{};
-        p.pcm = pcm + done * C; p.stream_stride = stride; p.n_frames = take; p.n_streams = m->n; p.channels = C;
-        p.k = m->td->dev.p; p.state = m->state.p;
-        p.subblocks = q.subblocks; p.sub_stride = q.sub_stride; p.sub_cap = q.sub_cap;
-        p.ring = q.ring; p.ring_frames = q.ring_frames; p.ring_stride = q.ring_stride;
-        p.tp_factor = m->tp_factor; p.s100 = (uint32_t)S; p.nseg = 1; p.seg_sub = 0; p.warm_sub = 0;
+        ssk::TdParams p = ms.td_params(pcm + done * C, stride, take);
         p.tp_f32 = 1u;                                                   // SS_TP_ARITH_F32, the handle's default
         HIPCHK(ssk::launch_time_domain(p, m->stream));
         // the gating launch only when some stream completes a sub-block (each stream's range is derived on the device)
         bool any = false;
-        for (uint32_t s = 0; s < m->n; s++) {
+        for (uint32_t s = 0; s < ms.n; s++) {
             any = any || (m->fed[s] + take) / S > m->fed[s] / S;
             m->fed[s] += take;
         }
@@ -129,17 +99,14 @@ int advance(ss_meter_bank *m, const float *pcm, uint64_t frames, uint64_t stride
 
 int bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
 {
-    const double *he, *hb;
-    int rc = get_hist_tables(&he, &hb);
-    if (rc) return rc;
     const uint32_t *dev = nullptr;
     if (streams) {
         HIPCHK(m->list.ensure(count));
-        rc = upload(m, m->list.p, streams, count * sizeof(uint32_t));
+        int rc = upload(m, m->list.p, streams, count * sizeof(uint32_t));
         if (rc) return rc;
         dev = m->list.p;
     }
-    HIPCHK(ssk::launch_meter_bank_reset(bank_params(m, he, hb), dev, count, m->stream));
+    HIPCHK(ssk::launch_meter_bank_reset(m->meter.bank_params(), dev, count, m->stream));
     for (uint32_t i = 0; i < count; i++) m->fed[streams ? streams[i] : i] = 0;
     return SS_OK;
 }
@@ -148,14 +115,14 @@ int null_bank() { return require_device() ? SS_ERR_DEVICE : SS_ERR_INVALID_ARG; 
 
 static_assert(SS_BANK_SPECTRUM_N == ssk::kBankSpecN, "one window length");
 
-uint32_t spec_rows(const ss_meter_bank *m) { return m->channels == 2 ? 2u : m->channels; }
+uint32_t spec_rows(const ss_meter_bank *m) { return m->meter.channels == 2 ? 2u : m->meter.channels; }
 
 // the spectrum launch of every (stream, row) and one copy of its results (`per_row` floats each) and statuses into page-locked memory
 int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, float gain_db, uint32_t per_row,
                  float **vals, int32_t **status)
 {
     const uint32_t R = spec_rows(m);
-    const size_t rows = (size_t)m->n * R, fbytes = rows * per_row * sizeof(float), sbytes = rows * sizeof(int32_t);
+    const size_t rows = (size_t)m->meter.n * R, fbytes = rows * per_row * sizeof(float), sbytes = rows * sizeof(int32_t);
     HIPCHK(m->spec_out.ensure(rows * per_row));
     if (fbytes + sbytes > m->spec_pin_bytes) {
         HIPCHK(hipStreamSynchronize(m->stream));
@@ -164,14 +131,10 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
         m->spec_pin_bytes = fbytes + sbytes;
     }
     ssk::BankSpectrumParams q{};
-    ssk::FftBatchParams &p = q.f;
-    p.window = m->ft->window.p; p.tw_n = m->ft->tw_n.p; p.tw_core = m->ft->core_tw4096; p.tw_256 = m->ft->core_tw256;
-    p.pink = nullptr; p.n = SS_BANK_SPECTRUM_N;
-    p.first_bin = (uint32_t)m->bt->first; p.n_bins = (uint32_t)m->bt->count; p.bin_stride = p.n_bins;
-    p.db_offset = (float)(20.0 * std::log10(4.0 / (double)SS_BANK_SPECTRUM_N));      // ss_get_fft's, bit for bit
+    q.f = one_window_fft(*m->ft, *m->bt);
     q.hist = m->spec_hist.p;
     q.start = (uint32_t)((m->spec_fed - SS_BANK_SPECTRUM_N) & (SS_BANK_SPECTRUM_N - 1));
-    q.n_streams = m->n; q.channels = m->channels; q.rows = R;
+    q.n_streams = m->meter.n; q.channels = m->meter.channels; q.rows = R;
     q.status = m->spec_status.p; q.out = m->spec_out.p;
     if (columns) {
         if (cols != m->spec_cols) {
@@ -189,10 +152,7 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
         q.cols = cols; q.gain_db = gain_db;
         if (gain_mode == SS_GAIN_REFERENCE) {
             // every stream's integrated loudness after the last add: the readings read() returns, on the device
-            const double *he, *hb;
-            int rc = get_hist_tables(&he, &hb);
-            if (rc) return rc;
-            HIPCHK(ssk::launch_meter_bank_readings(bank_params(m, he, hb), m->readings.p, m->stream));
+            HIPCHK(ssk::launch_meter_bank_readings(m->meter.bank_params(), m->readings.p, m->stream));
             static_assert(sizeof(ssk::MeterReading) % sizeof(double) == 0, "readings as doubles");
             q.integrated = &m->readings.p[0].integrated;
             q.integrated_stride = sizeof(ssk::MeterReading) / sizeof(double);
@@ -223,29 +183,13 @@ int ss_meter_bank_create(uint32_t n_streams, uint32_t channels, uint32_t rate, i
     if (n_streams == 0 || (true_peak_factor != 0 && true_peak_factor != 2 && true_peak_factor != 4)) return SS_ERR_INVALID_ARG;
     std::unique_ptr<ss_meter_bank, decltype(&ss_meter_bank_destroy)> m(new ss_meter_bank(), &ss_meter_bank_destroy);
     m->device = current_device();
-    m->n = n_streams; m->channels = channels; m->rate = rate;
-    m->tp_factor = true_peak_factor ? true_peak_factor : sst::true_peak_factor_for_rate(rate);
-    rc = get_td_tables(rate, m->tp_factor, channels, &m->td);
+    rc = m->meter.build(n_streams, channels, rate, true_peak_factor);
     if (rc) return rc;
-    // the handle's geometry (handle_make_meter): 3 s of filtered samples rounded up to a whole sub-block
-    m->s100 = (rate + 5) / 10;
-    m->ring_frames = (uint64_t)rate * 3000 / 1000;
-    if (m->ring_frames % m->s100) m->ring_frames += m->s100 - m->ring_frames % m->s100;
-    if (m->ring_frames * channels >= (1ull << 31)) return SS_ERR_UNSUPPORTED;       // (32-bit ring positions in the kernels)
-    m->st_on = 30 * m->s100 <= m->ring_frames;                  // ss_get_shortterm_lufs' own condition
     HIPCHK(stream_acquire(&m->stream));
     HIPCHK(hipEventCreateWithFlags(&m->pin_ev, hipEventDisableTiming));
     const size_t N = n_streams;
-    HIPCHK(m->state.alloc(N));
-    HIPCHK(m->hist.alloc(N * 2 * sst::kHistBins));
-    HIPCHK(m->sub.alloc(N * ss_meter_bank::kSubCap * channels));
-    HIPCHK(m->ring.alloc(N * m->ring_frames * channels));
-    HIPCHK(m->counts.alloc(N * 2));
     HIPCHK(m->readings.alloc(N));
     HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&m->pin_read), N * sizeof(ssk::MeterReading), hipHostMallocDefault));
-    std::vector<double> w(channels);
-    sst::channel_weights(channels, w.data());
-    HIPCHK(m->weights.upload(w));
     m->fed.assign(N, 0);
     rc = bank_reset(m.get(), nullptr, n_streams);
     if (rc) return rc;
@@ -272,7 +216,7 @@ int ss_meter_bank_add(ss_meter_bank *m, const float *pcm, uint64_t frames)
     if (!m) return null_bank();
     if (frames == 0) return SS_OK;
     if (!pcm) return SS_ERR_INVALID_ARG;
-    const uint64_t per = frames * m->channels, total = per * m->n;
+    const uint64_t per = frames * m->meter.channels, total = per * m->meter.n;
     HIPCHK(m->in.ensure(total));
     int rc = upload(m, m->in.p, pcm, total * sizeof(float));
     if (rc) return rc;
@@ -284,7 +228,7 @@ int ss_meter_bank_add_device(ss_meter_bank *m, const float *pcm_device, uint64_t
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
     if (frames == 0) return SS_OK;
-    if (!pcm_device || stream_stride_floats < frames * m->channels) return SS_ERR_INVALID_ARG;
+    if (!pcm_device || stream_stride_floats < frames * m->meter.channels) return SS_ERR_INVALID_ARG;
     return advance(m, pcm_device, frames, stream_stride_floats);
 }
 
@@ -296,7 +240,7 @@ int ss_meter_bank_add_pcm(ss_meter_bank *m, const void *pcm, uint64_t frames, in
     if (!sb) return SS_ERR_INVALID_ARG;
     if (frames == 0) return SS_OK;
     if (!pcm) return SS_ERR_INVALID_ARG;
-    const uint64_t per = frames * m->channels, total = per * m->n;
+    const uint64_t per = frames * m->meter.channels, total = per * m->meter.n;
     HIPCHK(m->raw.ensure(total * sb + 8));                       // (+8: the converter's wide reads of 24-bit samples)
     HIPCHK(m->in.ensure(total));
     int rc = upload(m, m->raw.p, pcm, total * sb);
@@ -309,8 +253,8 @@ int ss_meter_bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t coun
 {
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
-    if (!streams) return bank_reset(m, nullptr, m->n);
-    for (uint32_t i = 0; i < count; i++) if (streams[i] >= m->n) return SS_ERR_INVALID_ARG;
+    if (!streams) return bank_reset(m, nullptr, m->meter.n);
+    for (uint32_t i = 0; i < count; i++) if (streams[i] >= m->meter.n) return SS_ERR_INVALID_ARG;
     return bank_reset(m, streams, count);
 }
 
@@ -319,15 +263,12 @@ int ss_meter_bank_read(ss_meter_bank *m, ss_meter_reading *out, uint32_t cap_str
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
     if (!out) return SS_ERR_INVALID_ARG;
-    if (cap_streams < m->n) return SS_ERR_CAPACITY;
-    const double *he, *hb;
-    int rc = get_hist_tables(&he, &hb);
-    if (rc) return rc;
-    HIPCHK(ssk::launch_meter_bank_readings(bank_params(m, he, hb), m->readings.p, m->stream));
-    HIPCHK(hipMemcpyAsync(m->pin_read, m->readings.p, m->n * sizeof(ssk::MeterReading), hipMemcpyDeviceToHost, m->stream));
+    if (cap_streams < m->meter.n) return SS_ERR_CAPACITY;
+    HIPCHK(ssk::launch_meter_bank_readings(m->meter.bank_params(), m->readings.p, m->stream));
+    HIPCHK(hipMemcpyAsync(m->pin_read, m->readings.p, m->meter.n * sizeof(ssk::MeterReading), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     m->pin_busy = false;
-    std::memcpy(out, m->pin_read, m->n * sizeof(ss_meter_reading));
+    std::memcpy(out, m->pin_read, m->meter.n * sizeof(ss_meter_reading));
     return SS_OK;
 }
 
@@ -335,15 +276,15 @@ int ss_meter_bank_peaks(ss_meter_bank *m, uint32_t stream, double *true_pk, doub
 {
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
-    if (stream >= m->n) return SS_ERR_INVALID_ARG;
-    if ((true_pk || sample_pk) && cap_channels < m->channels) return SS_ERR_CAPACITY;
+    if (stream >= m->meter.n) return SS_ERR_INVALID_ARG;
+    if ((true_pk || sample_pk) && cap_channels < m->meter.channels) return SS_ERR_CAPACITY;
     static_assert(offsetof(ssk::TdState, true_peak) == offsetof(ssk::TdState, sample_peak) + sizeof(float) * ssk::kMaxChannels,
                   "sample_peak and true_peak are read as one block");
     float pk[2 * ssk::kMaxChannels];
-    HIPCHK(hipMemcpyAsync(pk, &m->state.p[stream].sample_peak[0], sizeof pk, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(pk, &m->meter.state.p[stream].sample_peak[0], sizeof pk, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     m->pin_busy = false;
-    for (uint32_t c = 0; c < m->channels; c++) {
+    for (uint32_t c = 0; c < m->meter.channels; c++) {
         const float sp = pk[c], tp = pk[ssk::kMaxChannels + c];
         if (sample_pk) sample_pk[c] = (double)sp;
         if (true_pk) true_pk[c] = (double)(tp > sp ? tp : sp);       // true_peak(): max(true, sample)
@@ -355,8 +296,8 @@ int ss_meter_bank_histograms(ss_meter_bank *m, uint32_t stream, uint64_t *out200
 {
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
-    if (stream >= m->n || !out2000) return SS_ERR_INVALID_ARG;
-    HIPCHK(hipMemcpyAsync(out2000, m->hist.p + (size_t)stream * 2 * sst::kHistBins, 2 * sst::kHistBins * sizeof(uint64_t),
+    if (stream >= m->meter.n || !out2000) return SS_ERR_INVALID_ARG;
+    HIPCHK(hipMemcpyAsync(out2000, m->meter.hist.p + (size_t)stream * 2 * sst::kHistBins, 2 * sst::kHistBins * sizeof(uint64_t),
                           hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     m->pin_busy = false;
@@ -373,16 +314,16 @@ int ss_meter_bank_spectrum_enable(ss_meter_bank *m, int enable)
         m->spec_hist.release(); m->spec_out.release(); m->spec_status.release();
         return SS_OK;
     }
-    if (20000.0f > (float)m->rate / 2.0f) return SS_ERR_FREQ_LIMIT;         // get_fft's FrequencyLimit check, before any allocation
+    if (20000.0f > (float)m->meter.rate / 2.0f) return SS_ERR_FREQ_LIMIT;         // get_fft's FrequencyLimit check, before any allocation
     int rc = get_fft_tables(SS_BANK_SPECTRUM_N, &m->ft);
     if (rc) return rc;
-    rc = get_bin_tables(m->rate, SS_BANK_SPECTRUM_N, &m->bt);
+    rc = get_bin_tables(m->meter.rate, SS_BANK_SPECTRUM_N, &m->bt);
     if (rc) return rc;
     if (!m->spec_pink.p) HIPCHK(m->spec_pink.upload(m->bt->pink));
-    const size_t floats = (size_t)m->n * SS_BANK_SPECTRUM_N * m->channels;
+    const size_t floats = (size_t)m->meter.n * SS_BANK_SPECTRUM_N * m->meter.channels;
     HIPCHK(m->spec_hist.ensure(floats));
     HIPCHK(hipMemsetAsync(m->spec_hist.p, 0, floats * sizeof(float), m->stream));  // (re-enabling starts again from zeros)
-    HIPCHK(m->spec_status.ensure((size_t)m->n * spec_rows(m)));
+    HIPCHK(m->spec_status.ensure((size_t)m->meter.n * spec_rows(m)));
     m->spec_fed = 0;
     m->spec_on = true;
     return SS_OK;
@@ -412,7 +353,7 @@ int ss_meter_bank_spectrum(ss_meter_bank *m, float *rows, size_t cap_floats, int
     if (!rows || !status) return SS_ERR_INVALID_ARG;
     if (!m->spec_on) return SS_ERR_INVALID_MODE;
     const uint32_t nb = (uint32_t)m->bt->count;
-    const size_t R = (size_t)m->n * spec_rows(m);
+    const size_t R = (size_t)m->meter.n * spec_rows(m);
     if (cap_floats < R * nb || cap_rows < R) return SS_ERR_CAPACITY;
     float *v; int32_t *st;
     int rc = spectrum_run(m, false, 0, SS_GAIN_FIXED, 0.0f, nb, &v, &st);
@@ -430,7 +371,7 @@ int ss_meter_bank_spectrum_columns(ss_meter_bank *m, uint32_t cols, int gain_mod
     if (!out || !status || cols == 0 || cols > 512 || (gain_mode != SS_GAIN_FIXED && gain_mode != SS_GAIN_REFERENCE))
         return SS_ERR_INVALID_ARG;
     if (!m->spec_on) return SS_ERR_INVALID_MODE;
-    const size_t R = (size_t)m->n * spec_rows(m);
+    const size_t R = (size_t)m->meter.n * spec_rows(m);
     if (cap_floats < R * cols || cap_rows < R) return SS_ERR_CAPACITY;
     float *v; int32_t *st;
     int rc = spectrum_run(m, true, cols, gain_mode, gain_db, cols, &v, &st);

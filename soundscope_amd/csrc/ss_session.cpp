@@ -114,17 +114,70 @@ int session_stage(ss_session *s, size_t floats)
 // (the session's device rows, or the pinned stage as the device sees it)
 ssk::FftBatchParams session_fft_params(const ss_session *s, const float *pairs, size_t lb, float *out)
 {
-    ssk::FftBatchParams p{};
-    p.pcm = pairs; p.out = out;
-    p.window = s->ft->window.p; p.half_window = s->ft->half_window.p;
-    p.tw_n = s->ft->tw_n.p; p.tw_core = s->ft->core_tw4096; p.tw_256 = s->ft->core_tw256; p.pink = nullptr;
-    p.frames_per_stream = 0; p.first_start = lb; p.n_streams = 1; p.channels = 2;
-    p.n_windows = 1; p.hop = 0; p.n = SS_TICK_WINDOW;
-    p.first_bin = (uint32_t)s->bt->first; p.n_bins = (uint32_t)s->bt->count; p.bin_stride = s->bin_stride;
-    p.windows_per_block = 1;
-    p.db_offset = (float)(20.0 * std::log10(4.0 / (double)SS_TICK_WINDOW));
+    ssk::FftBatchParams p = one_window_fft(*s->ft, *s->bt);
+    p.pcm = pairs; p.out = out; p.first_start = lb; p.channels = 2;
+    p.bin_stride = s->bin_stride;                   // (the side row stands behind the mid row, 16-B aligned)
     return p;
 }
+
+// What both tick drivers enqueue on the analyzer's stream, in this order: the loudness call on SS_TICK_WINDOW samples with the
+// spectrum and the short-term reading riding its launch (k_tick), whichever of the two did not ride it, then the event the tick
+// waits for, then the gating of the new sub-blocks with the readings the render loop asks for on its next frame riding it
+// (tui.rs:917, :950, :969: integrated loudness, range, peaks).  A driver's own launches go between run() and close().
+struct TickCore {
+    ss_session *s;
+    ss_analyzer *h;
+    ssk::FinalizeParams gating{};
+    bool fft_launched = false, st_launched = false, any_launch = false;
+    TickCore(ss_session *s_) : s(s_), h(s_->an) {}
+    // The gating of this tick's new sub-blocks is handed back by add_samples_impl AFTER frames_fed has advanced: if the tick is
+    // left early (a failed launch, an event error) it is still launched — otherwise those sub-blocks would be missing from the
+    // histograms for the rest of the session.
+    ~TickCore() { if (gating.n_streams) (void)ssk::launch_finalize_stream(gating, h->stream); }
+
+    // samples == nullptr: no loudness call this tick (then no short-term reading either); fft == nullptr: no spectrum
+    int run(const float *samples, const ssk::FftBatchParams *fft, ss_tick_result *res)
+    {
+        if (samples) {
+            TickExtras extras;
+            extras.fft = fft;
+            extras.shortterm_out = s->stage_d_dev;
+            res->add_status = add_samples_impl(h, samples, SS_TICK_WINDOW, true, &gating, &extras);
+            if (res->add_status == SS_ERR_DEVICE) return SS_ERR_DEVICE;
+            any_launch = res->add_status == SS_OK;
+            fft_launched = extras.fused;
+            st_launched = extras.st_fused;
+        }
+        if (fft && !fft_launched) {                     // (no loudness call this tick, or one that could not take the spectrum along)
+            HIPCHK(ssk::launch_fft16k(*fft, 1, h->stream));
+            fft_launched = any_launch = true;
+        }
+        if (samples && !st_launched) {                  // (the reading did not ride the tick launch)
+            if (!h->meter_ok) {
+                res->shortterm_status = SS_ERR_INVALID_MODE;
+            } else {
+                // (energy, loudness) written by the kernel into the pinned pair itself
+                int rc = ring_loudness_enqueue(h, h->meter.s100 * 30, s->stage_d_dev);
+                if (rc) return rc;
+                st_launched = any_launch = true;
+            }
+        }
+        return SS_OK;
+    }
+
+    int close(bool record_event)
+    {
+        if (record_event) HIPCHK(hipEventRecord(s->ev_tick, h->stream));
+        if (gating.n_streams) {
+            int rc = attach_readings(h, &gating);
+            if (rc) return rc;
+            const ssk::FinalizeParams g = gating;
+            gating.n_streams = 0;                       // (launched here, whatever the outcome: the destructor is done with it)
+            HIPCHK(ssk::launch_finalize_stream(g, h->stream));
+        }
+        return SS_OK;
+    }
+};
 
 // wait (bounded: about 200 us) until a spectrum workgroup has stored `seq` behind its row
 bool wait_row_flag(const uint32_t *flag, uint32_t seq)
@@ -375,7 +428,6 @@ int ss_session_tick_file(ss_session *s, size_t pos, double *mid_xy, double *side
     std::memset(res, 0, sizeof *res);
     const size_t pos_f = pos / s->file_channels;
     res->playhead = pos_f;
-    bool fft_launched = false, st_launched = false;
     int mid_st = SS_OK, side_st = SS_OK;
 
     // ---- what the tick will run (host-side checks only)
@@ -405,62 +457,29 @@ int ss_session_tick_file(ss_session *s, size_t pos, double *mid_xy, double *side
     // until round 4 — when their hardware queues happened to sit on one pipe of the command processor the spectrum did not
     // start before the time-domain kernel had finished: 98 instead of 65 us for the whole life of such a session,
     // tools/probe_tick_queues.sh.)  Results land in pinned memory straight from the kernels.
-    bool any_launch = false;
     ssk::FftBatchParams fft_p = fft_wanted ? session_fft_params(s, s->pcm.p, fft_lb, s->stage_dev) : ssk::FftBatchParams{};
     const uint32_t seq = ++s->tick_seq ? s->tick_seq : ++s->tick_seq;          // (never 0: the flags' initial value)
     fft_p.done_flag = s->row_flag_dev; fft_p.done_value = seq;
     // loudness: the last 16384 interleaved samples, every tick (8x overlap at hop 1024 frames)
     const size_t pos_i = pos_f * s->file_channels;
     const size_t lufs_lb = pos_i > SS_TICK_WINDOW ? pos_i - SS_TICK_WINDOW : 0;
-    ssk::FinalizeParams gating{};
-    // The gating of this tick's new sub-blocks is handed back by add_samples_impl AFTER frames_fed has advanced: if the tick is
-    // left early (a failed launch, an event error) it is still launched — otherwise those sub-blocks would be missing from the
-    // histograms for the rest of the session.
-    struct DeferredGating {
-        ss_analyzer *h; ssk::FinalizeParams *g; bool launched = false;
-        ~DeferredGating() { if (!launched && g->n_streams) (void)ssk::launch_finalize(*g, h->stream); }
-    } gating_guard{h, &gating};
+    const float *lufs_in = nullptr;
     if (lufs_lb != 0) {
         res->lufs_ran = 1;
         std::memmove(&s->lufs[0], &s->lufs[1], (SS_LUFS_HISTORY - 1) * sizeof(double));
         if (pos_i <= s->n_samples && lufs_lb < s->n_samples) {
             res->fed = 1;
-            TickExtras extras;
-            extras.fft = fft_wanted ? &fft_p : nullptr;
-            extras.shortterm_out = s->stage_d_dev;
-            res->add_status = add_samples_impl(h, s->pcm.p + lufs_lb, SS_TICK_WINDOW, true, &gating, &extras);
-            if (res->add_status == SS_ERR_DEVICE) return SS_ERR_DEVICE;
-            if (res->add_status == SS_OK) any_launch = true;
-            if (extras.fused) fft_launched = true;
-            if (extras.st_fused) st_launched = true;
+            lufs_in = s->pcm.p + lufs_lb;
         }
     }
+    TickCore tick(s);
+    int rc = tick.run(lufs_in, fft_wanted ? &fft_p : nullptr, res);
+    if (rc) return rc;
     SS_TICK_T(1);
-    if (fft_wanted && !fft_launched) {                  // (no loudness call this tick, or one that could not take the spectrum along)
-        HIPCHK(ssk::launch_fft16k(fft_p, 1, h->stream));
-        fft_launched = true; any_launch = true;
-    }
-    SS_TICK_T(2);
-    if (res->fed && !st_launched) {                     // (the reading did not ride the tick launch)
-        if (!h->meter_ok) {
-            res->shortterm_status = SS_ERR_INVALID_MODE;
-        } else {
-            // (energy, loudness) written by the kernel into the pinned pair itself
-            int rc = ring_loudness_enqueue(h, (uint64_t)h->td->host.s100 * 30, s->stage_d_dev);
-            if (rc) return rc;
-            st_launched = true; any_launch = true;
-        }
-    }
-    if (any_launch) HIPCHK(hipEventRecord(s->ev_tick, h->stream));
-    // behind the event: the gating — and riding it, what the render loop asks the file analyzer for on its next frame
-    // (tui.rs:917, :950, :969: integrated loudness, range, peaks)
-    if (gating.n_streams) {
-        int rc = attach_readings(h, &gating);
-        if (rc) return rc;
-        gating_guard.launched = true;
-        HIPCHK(ssk::launch_finalize(gating, h->stream));
-    }
+    rc = tick.close(tick.any_launch);
+    if (rc) return rc;
     SS_TICK_T(3);
+    const bool fft_launched = tick.fft_launched;
     // while the device works: the x halves of the two charts (they do not depend on it)
     if (res->fft_ran) {
         session_emit_x(s, fft_launched ? mid_st : (mid_st ? mid_st : SS_OK), mid_xy);
@@ -484,8 +503,8 @@ int ss_session_tick_file(ss_session *s, size_t pos, double *mid_xy, double *side
     }
     SS_TICK_T(5);
     // (a tick that completed no sub-block has no gating launch to ride: the readings get their own)
-    if (res->fed && res->add_status == SS_OK && h->prefetch_stamp != h->change_count) { int rc = prefetch_readings(h); if (rc) return rc; }
-    if (any_launch) HIPCHK(hipEventSynchronize(s->ev_tick));
+    if (res->fed && res->add_status == SS_OK && h->prefetch_stamp != h->change_count) { rc = prefetch_readings(h); if (rc) return rc; }
+    if (tick.any_launch) HIPCHK(hipEventSynchronize(s->ev_tick));
     SS_TICK_T(6);
     if (res->fft_ran) {
         if (!mid_done)
@@ -494,7 +513,7 @@ int ss_session_tick_file(ss_session *s, size_t pos, double *mid_xy, double *side
         if (!side_done)
             session_emit_spectrum(s, s->stage + s->bin_stride, side_st, side_xy, &res->side_status, &res->n_side, true);
     }
-    if (res->fed) s->lufs[SS_LUFS_HISTORY - 1] = st_launched ? s->stage_d[1] : 0.0;
+    if (res->fed) s->lufs[SS_LUFS_HISTORY - 1] = tick.st_launched ? s->stage_d[1] : 0.0;
     res->shortterm = s->lufs[SS_LUFS_HISTORY - 1];
     return SS_OK;
 }
@@ -515,36 +534,10 @@ static int capture_tick_body(ss_session *s, const float *newest, double *mid_xy,
     // while the device works.
     const bool fft_wanted = !lim && s->bt->count;
     ssk::FftBatchParams fft_p = fft_wanted ? session_fft_params(s, s->pcm.p, lb, s->stage_dev) : ssk::FftBatchParams{};
-    bool fft_launched = false, st_launched = false;
     std::memmove(&s->lufs[0], &s->lufs[1], (SS_LUFS_HISTORY - 1) * sizeof(double));
-    ssk::FinalizeParams gating{};
-    // The gating of this tick's new sub-blocks is handed back by add_samples_impl AFTER frames_fed has advanced: if the tick is
-    // left early (a failed launch, an event error) it is still launched — otherwise those sub-blocks would be missing from the
-    // histograms for the rest of the session.
-    struct DeferredGating {
-        ss_analyzer *h; ssk::FinalizeParams *g; bool launched = false;
-        ~DeferredGating() { if (!launched && g->n_streams) (void)ssk::launch_finalize(*g, h->stream); }
-    } gating_guard{h, &gating};
-    TickExtras extras;
-    extras.fft = fft_wanted ? &fft_p : nullptr;
-    extras.shortterm_out = s->stage_d_dev;
-    res->add_status = add_samples_impl(h, s->pcm.p + (n - SS_TICK_WINDOW), SS_TICK_WINDOW, true, &gating, &extras);
-    if (res->add_status == SS_ERR_DEVICE) return SS_ERR_DEVICE;
-    if (extras.fused) fft_launched = true;
-    if (extras.st_fused) st_launched = true;
-    if (fft_wanted && !fft_launched) {
-        HIPCHK(ssk::launch_fft16k(fft_p, 1, h->stream));
-        fft_launched = true;
-    }
-    if (!st_launched) {
-        if (!h->meter_ok) {
-            res->shortterm_status = SS_ERR_INVALID_MODE;
-        } else {
-            int rc = ring_loudness_enqueue(h, (uint64_t)h->td->host.s100 * 30, s->stage_d_dev);
-            if (rc) return rc;
-            st_launched = true;
-        }
-    }
+    TickCore tick(s);
+    int rc = tick.run(s->pcm.p + (n - SS_TICK_WINDOW), fft_wanted ? &fft_p : nullptr, res);
+    if (rc) return rc;
     // microphone_input_chart = get_waveform(&mid_samples, 15.)
     if (wave_xy && bins) {
         ssk::WaveParams p{};
@@ -552,14 +545,9 @@ static int capture_tick_body(ss_session *s, const float *newest, double *mid_xy,
         p.window = (uint32_t)window; p.out = s->stage_dev + (size_t)2 * s->bin_stride; p.out_stride = 2 * bins;
         HIPCHK(ssk::launch_waveform(p, h->stream));
     }
-    HIPCHK(hipEventRecord(s->ev_tick, h->stream));
-    if (gating.n_streams) {
-        int rc = attach_readings(h, &gating);
-        if (rc) return rc;
-        gating_guard.launched = true;
-        HIPCHK(ssk::launch_finalize(gating, h->stream));
-    }
-    if (res->add_status == SS_OK && h->prefetch_stamp != h->change_count) { int rc = prefetch_readings(h); if (rc) return rc; }
+    rc = tick.close(true);
+    if (rc) return rc;
+    if (res->add_status == SS_OK && h->prefetch_stamp != h->change_count) { rc = prefetch_readings(h); if (rc) return rc; }
     // get_fft's value checks on the two 16384-sample slices (the device is working)
     std::vector<std::pair<size_t, uint8_t>> bad;
     for (size_t i = 0; i < (size_t)SS_TICK_WINDOW; i++) {
@@ -582,11 +570,10 @@ static int capture_tick_body(ss_session *s, const float *newest, double *mid_xy,
         for (size_t i = 0; i < bins; i++) { wave_xy[4 * i + 1] = (double)mm[2 * i]; wave_xy[4 * i + 3] = (double)mm[2 * i + 1]; }
         if (wave_n) *wave_n = 2 * bins;
     }
-    s->lufs[SS_LUFS_HISTORY - 1] = st_launched ? s->stage_d[1] : 0.0;
+    s->lufs[SS_LUFS_HISTORY - 1] = tick.st_launched ? s->stage_d[1] : 0.0;
     res->shortterm = s->lufs[SS_LUFS_HISTORY - 1];
     return SS_OK;
 }
-
 
 static int capture_args(ss_session *s, double *mid_xy, double *side_xy, size_t cap_pairs, double *wave_xy, size_t wave_cap_pairs,
                         size_t *wave_n, ss_tick_result *res, size_t *window, size_t *bins)

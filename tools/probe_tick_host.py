@@ -31,7 +31,7 @@ for p in pos[20:]:
 wall = wall / len(pos[20:]) * 1e6
 f(out, 1)
 n = len(pos[20:])
-names = ["host-side checks", "tick launch", "separate spectrum launch", "short-term enqueue + event + gating", "x halves (host)",
+names = ["host-side checks", "tick launch (+ separate spectrum, short-term)", "(unused)", "event + gating", "x halves (host)",
          "row flags + y halves", "wait: event"]
 print(f"tick wall (python loop) {wall:.1f} us")
 for i, nm in enumerate(names):
