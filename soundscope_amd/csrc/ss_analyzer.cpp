@@ -266,22 +266,11 @@ int ss_get_fft(const ss_analyzer *hc, const float *samples, size_t n,
     // (the transform reads its window many times in small pieces: from page-locked host memory in place that costs the kernel
     // 20 us more than it takes from HBM — one DMA of the page-locked copy first)
     HIPCHK(hipMemcpyAsync(h->in.p, h->pin_in[pin], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    ssk::FftBatchParams p = one_window_fft(*ft, *bt);
+    // (a batch of one window: N = 4096 and 16384 run the batch path's radix-16 machines, the first with its window pair half empty)
+    const ssk::SpecPlan plan = ssk::plan_spectrum((uint32_t)n, 1, kOneWindowHop, 1, 1);
+    ssk::FftBatchParams p = one_window_fft(plan, *ft, *bt);
     p.pcm = h->in.p; p.out = h->pin_out_dev; p.channels = 1;
-    if (n == 16384) {
-        HIPCHK(ssk::launch_fft16k(p, 0, h->stream));
-    } else if (n == 4096) {
-        // the radix-16 machine of the batch path on one window: k_fft4096_pairw with its second window absent
-        // (through round 3 this size took k_fft_generic's radix-2 passes)
-        p.hop = 1024; p.windows_per_block = 2;
-        p.bin_stride = (uint32_t)((bt->count + 3) & ~(size_t)3);
-        p.db_offset = (float)(10.0 * std::log10(4.0 / (4096.0 * 4096.0)));
-        p.offpink = bt->off4096_dev.p;
-        p.publish_mask = ssk::fft4096_publish_mask(p.first_bin, p.n_bins);
-        HIPCHK(ssk::launch_fft4096_pairw(p, 0, h->stream));
-    } else {
-        HIPCHK(ssk::launch_fft_generic(p, 0, h->stream));
-    }
+    HIPCHK(ssk::launch_spectrum(plan, p, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     pin_all_free(h);
     const float *db = h->pin_out;

@@ -15,12 +15,9 @@ struct ss_batch {
     ss_batch_layout lay{};
     hipStream_t stream = nullptr;
     int tp_factor = 0;
-    int fft_mode = 1;           // generic-kernel mode (1 mid/side, 2 per channel)
-    bool fft_fast = false;      // N=4096 stereo kernel
-    bool fft_pairw = false;     // N=4096, hop 1024, mono / per-channel: two windows per transform
+    ssk::SpecPlan spec;         // the spectrum kernel, its rows and its grid (ssk::plan_spectrum)
     uint64_t first_start = 0;
     uint32_t wave_window = 0;
-    uint32_t windows_per_block = 16;
     struct {                        // how the time-domain launch cuts the streams (choose_td_geometry): TdParams' fields of these names
         uint32_t nseg = 1, seg_sub = 0, warm_sub = 0, fix_sub = 0;
         uint32_t split_batch = ssk::kTdSplitNone;       // (ragged lengths: one wave per stream / segment)
@@ -47,7 +44,7 @@ struct ss_batch {
     // ragged batches (ss_batch_set_lengths): per-stream frames / windows / sub-blocks / decimation bins
     bool ragged = false;
     std::vector<uint64_t> frames_h, wave_samples_h;
-    std::vector<uint32_t> windows_h, sub_h, wave_window_h, wave_bins_h;
+    std::vector<uint32_t> windows_h, sub_h, wave_window_h;
     DevBuf<uint64_t> frames_d, wave_samples_d;
     DevBuf<uint32_t> windows_d, sub_d, wave_window_d;
     // render-side reductions (N3)
@@ -109,13 +106,40 @@ int batch_collect_timing(ss_batch *b)
     return SS_OK;
 }
 
-// N = 16384 with hop 1024 and at least eight windows: k_fft16k_run (runs of windows per workgroup), otherwise k_fft16k
-static bool fft16k_runs(const ss_batch *b)
+// What a stream of F frames holds under a batch's config (ss_batch_create, ss_batch_set_lengths, ss_batch_stream_shape):
+//  * spectrum windows at the cadence of analyze_audio_file_samples (tui.rs:1482-1526): window [p-N, p) at p = k*hop, skipped
+//    when p - N == 0 (saturating_sub) => k from N/hop + 1 to F/hop;
+//  * 100 ms sub-blocks of s100 frames (s100 = 0: no time-domain pass);
+//  * get_waveform's decimation window and bins over the F x C samples (waveform_shape).
+struct StreamShape {
+    uint32_t windows = 0, subblocks = 0;
+    size_t wave_window = 0, wave_bins = 0;
+};
+StreamShape stream_shape(const ss_batch_config &c, uint64_t s100, uint64_t F)
 {
-#ifdef SS_TUNING
-    if (std::getenv("SS_FFT16K_SINGLE")) return false;
-#endif
-    return b->cfg.fft_n == 16384 && !b->fft_fast && !b->fft_pairw && b->cfg.hop_frames == 1024 && b->lay.n_windows >= 8;
+    StreamShape sh;
+    if ((c.flags & SS_BATCH_FFT) && c.hop_frames) {
+        const uint64_t hop = c.hop_frames, k_min = c.fft_n / hop + 1, k_max = F / hop;
+        sh.windows = k_max >= k_min ? (uint32_t)(k_max - k_min + 1) : 0;
+    }
+    if (s100) sh.subblocks = (uint32_t)(F / s100);
+    if (c.flags & SS_BATCH_WAVEFORM) {
+        const double win = c.waveform_window > 0.0 ? c.waveform_window : (double)F / (double)c.sample_rate;
+        waveform_shape((size_t)(F * c.channels), win, &sh.wave_window, &sh.wave_bins);
+    }
+    return sh;
+}
+
+// the spectrum launch of a batch (ss_batch_run, ss_batch_traffic_floor): the plan's and the tables' fields, rows with the pink
+// compensation, the batch's input and rows
+ssk::FftBatchParams batch_fft_params(const ss_batch *b)
+{
+    const ss_batch_config &c = b->cfg;
+    ssk::FftBatchParams p = spectrum_params(b->spec, *b->ft, *b->bt, true);
+    p.pcm = b->pcm.p; p.out = b->fft.p;
+    p.frames_per_stream = c.frames_per_stream; p.first_start = b->first_start;
+    p.n_streams = c.n_streams; p.channels = c.channels; p.n_windows = b->lay.n_windows; p.hop = c.hop_frames;
+    return p;
 }
 
 }  // namespace
@@ -239,6 +263,14 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
     ss_batch_layout &L = b->lay;
     L.input_bytes = (uint64_t)cfg->n_streams * F * C * sizeof(float);
     HIPCHK(b->pcm.alloc((size_t)cfg->n_streams * F * C));
+    if (cfg->flags & (SS_BATCH_LUFS | SS_BATCH_TRUE_PEAK)) {
+        b->tp_factor = (cfg->flags & SS_BATCH_TRUE_PEAK)
+                           ? (cfg->true_peak_factor ? cfg->true_peak_factor : sst::true_peak_factor_for_rate(cfg->sample_rate))
+                           : 0;
+        int rc = get_td_tables(cfg->sample_rate, b->tp_factor, C, &b->td);
+        if (rc) return rc;
+    }
+    const StreamShape sh = stream_shape(*cfg, b->td ? b->td->host.s100 : 0, F);
 
     if (cfg->flags & SS_BATCH_FFT) {
         const size_t n = cfg->fft_n;
@@ -251,49 +283,20 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
         if (rc) return rc;
         rc = get_bin_tables(cfg->sample_rate, n, &b->bt);
         if (rc) return rc;
-        // cadence of analyze_audio_file_samples (tui.rs:1482-1526): window [p-N, p) at
-        // p = k*hop, skipped when p - N == 0 (saturating_sub) => k from N/hop + 1
         const uint64_t hop = cfg->hop_frames;
-        const uint64_t k_min = n / hop + 1, k_max = F / hop;
-        L.n_windows = k_max >= k_min ? (uint32_t)(k_max - k_min + 1) : 0;
-        b->first_start = k_min * hop - n;
-        L.fft_channels = (C == 2) ? 2 : C;
-        b->fft_mode = (C == 2) ? 1 : (C == 1 ? 0 : 2);
+        L.n_windows = sh.windows;
+        b->first_start = (n / hop + 1) * hop - n;         // window 0 ends at (N/hop + 1) * hop (stream_shape)
+        b->spec = ssk::plan_spectrum((uint32_t)n, C, (uint32_t)hop, cfg->n_streams, L.n_windows);
+        L.fft_channels = b->spec.fft_ch;
         L.n_bins = (uint32_t)b->bt->count;
         L.first_bin = (uint32_t)b->bt->first;
-        b->fft_fast = (C == 2 && n == 4096 && hop % 256 == 0);
-        b->fft_pairw = (C != 2 && n == 4096 && hop == 1024);
-#ifdef SS_TUNING        // development builds only: the shipped library takes no kernel selection from the environment
-        if (std::getenv("SS_FFT_NO_PAIRW")) b->fft_pairw = false;
-#endif
-        {
-            // windows per workgroup: long runs amortise the per-workgroup constants and the 3-hop halo,
-            // but keep >= ~4096 workgroups (8 rounds of the 512 resident ones) for load balance
-            uint32_t tgt = (4096u + cfg->n_streams - 1) / cfg->n_streams;
-            if (tgt > L.n_windows / 16) tgt = L.n_windows / 16;
-            if (tgt < 1) tgt = 1;
-            uint32_t wpb = (L.n_windows + tgt - 1) / tgt;
-            // ... unless runs of sixteen leave most of the chip idle (one file, a handful of streams): then the pass is bound by
-            // the length of a run, not by its constants — as many workgroups as the chip holds at once (three per CU), runs of two
-            // windows at least (config 2, one 10 s stream: 29 workgroups x 16 windows 50 us -> 232 x 2)
-            const uint64_t total = (uint64_t)cfg->n_streams * L.n_windows;
-            if ((uint64_t)cfg->n_streams * ((L.n_windows + wpb - 1) / (wpb ? wpb : 1)) < 512u) {
-                const uint64_t w = (total + 767u) / 768u;
-                wpb = (uint32_t)(w < 2 ? 2 : w);
-            }
-            wpb = (wpb + 1) & ~1u;
-            b->windows_per_block = wpb < 2 ? 2 : wpb;
-        }
-#ifdef SS_TUNING
-        if (const char *e = std::getenv("SS_FFT_WPB")) { int v = std::atoi(e); if (v >= 2 && v <= 4096) b->windows_per_block = (uint32_t)(v & ~1); }
-#endif
         // Rows start 16-byte aligned (16-byte stores).  Padding them to whole 128-byte lines lifts a pure streaming-store
         // kernel with this row pattern from 3.7 to 4.4 TB/s (tools/ubench_fftio.hip) but does nothing for the real kernel
         // (A/B in one process: 3.14 vs 3.12 ms), so the rows stay compact.
         L.fft_bin_stride = (L.n_bins + 3u) & ~3u;
         if (columns_only) {
             // the fused reduction lives in the epilogue of k_fft4096_ms1
-            if (!(b->fft_fast && hop == 1024)) return SS_ERR_UNSUPPORTED;
+            if (b->spec.kernel != ssk::SpecKernel::ms1) return SS_ERR_UNSUPPORTED;
             const uint32_t cols = cfg->spectrum_columns;
             std::vector<uint16_t> bc(L.fft_bin_stride, (uint16_t)0xFFFF);
             for (uint32_t i = 0; i < L.n_bins; i++) bc[i] = (uint16_t)spectrum_column_of(b->bt->chart_x[i], cols);
@@ -329,14 +332,8 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
             HIPCHK(b->fft.alloc((size_t)(L.fft_bytes / sizeof(float))));
         }
     }
-    if (cfg->flags & (SS_BATCH_LUFS | SS_BATCH_TRUE_PEAK)) {
-        b->tp_factor = (cfg->flags & SS_BATCH_TRUE_PEAK)
-                           ? (cfg->true_peak_factor ? cfg->true_peak_factor : sst::true_peak_factor_for_rate(cfg->sample_rate))
-                           : 0;
-        int rc = get_td_tables(cfg->sample_rate, b->tp_factor, C, &b->td);
-        if (rc) return rc;
-        const uint64_t S = b->td->host.s100;
-        L.n_subblocks = (uint32_t)(F / S);
+    if (b->td) {
+        L.n_subblocks = sh.subblocks;
         HIPCHK(b->state.alloc(cfg->n_streams));
         HIPCHK(b->sub.alloc((size_t)cfg->n_streams * (L.n_subblocks ? L.n_subblocks : 1) * C));
         HIPCHK(b->hist.alloc((size_t)cfg->n_streams * 2 * sst::kHistBins));
@@ -354,21 +351,11 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
         }
     }
     if (cfg->flags & SS_BATCH_WAVEFORM) {
-        const double win = cfg->waveform_window > 0.0 ? cfg->waveform_window : (double)F / (double)cfg->sample_rate;
-        const double wd = win * 1000.0;
-        const uint64_t W = (wd != wd || wd <= 0.0) ? 0 : (uint64_t)wd;
-        if (W > 0xFFFFFFFFull) return SS_ERR_UNSUPPORTED;
-        b->wave_window = (uint32_t)W;
-        // points: bins whose start floor(i*spp) < len
-        const uint64_t len = F * C;
+        if (sh.wave_window > 0xFFFFFFFFull) return SS_ERR_UNSUPPORTED;
+        const uint64_t W = sh.wave_window, len = F * C;
         const double spp = (double)len / (double)W;
-        uint64_t bins = W;
-        if (W > len) {
-            uint64_t lo = 0, hi = W;
-            while (lo < hi) { uint64_t mid = lo + (hi - lo) / 2; if ((uint64_t)((double)mid * spp) >= len) hi = mid; else lo = mid + 1; }
-            bins = lo;
-        }
-        L.n_wave_points = (uint32_t)(2 * bins);
+        b->wave_window = (uint32_t)W;
+        L.n_wave_points = (uint32_t)(2 * sh.wave_bins);
         HIPCHK(b->wave.alloc((size_t)cfg->n_streams * (W ? 2 * W : 2)));
         // fuse into the time-domain pass when that pass runs and a bin (plus its shared edge sample)
         // fits the per-wave halo; otherwise the standalone kernel handles it
@@ -449,20 +436,13 @@ int ss_batch_set_lengths(ss_batch *b, const uint64_t *frames, uint32_t count)
     for (uint32_t i = 0; i < count; i++) if (frames[i] > c.frames_per_stream) return SS_ERR_INVALID_ARG;
     b->frames_h.assign(frames, frames + count);
     b->windows_h.assign(count, 0); b->sub_h.assign(count, 0);
-    b->wave_window_h.assign(count, 0); b->wave_bins_h.assign(count, 0); b->wave_samples_h.assign(count, 0);
+    b->wave_window_h.assign(count, 0); b->wave_samples_h.assign(count, 0);
     for (uint32_t i = 0; i < count; i++) {
-        const uint64_t F = frames[i];
-        if (c.flags & SS_BATCH_FFT) {
-            const uint64_t hop = c.hop_frames, k_min = c.fft_n / hop + 1, k_max = F / hop;
-            b->windows_h[i] = k_max >= k_min ? (uint32_t)(k_max - k_min + 1) : 0;
-        }
-        if (b->td) b->sub_h[i] = (uint32_t)(F / b->td->host.s100);
+        const StreamShape sh = stream_shape(c, b->td ? b->td->host.s100 : 0, frames[i]);
+        if (sh.wave_window > b->wave_window) return SS_ERR_INVALID_ARG;      // cannot happen for F <= frames_per_stream
+        b->windows_h[i] = sh.windows; b->sub_h[i] = sh.subblocks;
         if (c.flags & SS_BATCH_WAVEFORM) {
-            const double win = c.waveform_window > 0.0 ? c.waveform_window : (double)F / (double)c.sample_rate;
-            size_t window, bins;
-            waveform_shape((size_t)(F * C), win, &window, &bins);
-            if (window > b->wave_window) return SS_ERR_INVALID_ARG;      // cannot happen for F <= frames_per_stream
-            b->wave_window_h[i] = (uint32_t)window; b->wave_bins_h[i] = (uint32_t)bins; b->wave_samples_h[i] = F * C;
+            b->wave_window_h[i] = (uint32_t)sh.wave_window; b->wave_samples_h[i] = frames[i] * C;
         }
     }
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -485,13 +465,10 @@ int ss_batch_stream_shape(const ss_batch *b, uint32_t stream, ss_stream_shape *o
 {
     SS_ON_DEVICE(b);
     if (!b || !out || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    if (b->ragged) {
-        out->frames = b->frames_h[stream]; out->n_windows = b->windows_h[stream];
-        out->n_subblocks = b->sub_h[stream]; out->n_wave_points = 2 * b->wave_bins_h[stream];
-    } else {
-        out->frames = b->cfg.frames_per_stream; out->n_windows = b->lay.n_windows;
-        out->n_subblocks = b->lay.n_subblocks; out->n_wave_points = b->lay.n_wave_points;
-    }
+    const uint64_t F = b->ragged ? b->frames_h[stream] : b->cfg.frames_per_stream;
+    const StreamShape sh = stream_shape(b->cfg, b->td ? b->td->host.s100 : 0, F);
+    out->frames = F; out->n_windows = sh.windows;
+    out->n_subblocks = sh.subblocks; out->n_wave_points = (uint32_t)(2 * sh.wave_bins);
     out->reserved = 0;
     return SS_OK;
 }
@@ -626,38 +603,14 @@ int ss_batch_run(ss_batch *b)
     auto launch_spectrum = [&]() -> int {
     HIPCHK(rec(2 * SS_KERNEL_FFT));
     if ((c.flags & SS_BATCH_FFT) && L.n_windows) {
-        ssk::FftBatchParams p{};
-        p.pcm = b->pcm.p; p.out = b->fft.p;
-        p.window = b->ft->window.p; p.half_window = b->ft->half_window.p;
-        p.tw_n = b->ft->tw_n.p; p.tw_256 = b->ft->tw_256.p; p.pink = b->bt->pink_dev.p;
-        p.frames_per_stream = c.frames_per_stream; p.first_start = b->first_start;
-        p.n_streams = c.n_streams; p.channels = C; p.n_windows = L.n_windows; p.hop = c.hop_frames;
-        p.n = c.fft_n; p.first_bin = L.first_bin; p.n_bins = L.n_bins; p.bin_stride = L.fft_bin_stride;
-        p.windows_per_block = b->windows_per_block;
+        ssk::FftBatchParams p = batch_fft_params(b);
         p.windows_of = b->ragged ? b->windows_d.p : nullptr;
         if (b->columns_only) {
             p.out_cols = b->render_spec.p; p.bin_col = b->bin_col.p; p.col_groups = b->col_groups.p; p.col_init = b->col_init.p; p.col_bins = b->col_bins.p; p.cols = b->render_cols;
             p.integrated = b->columns_gain_mode == SS_GAIN_REFERENCE ? b->integrated.p : nullptr;
             p.gain_db = b->columns_gain_db;
         }
-        if (b->fft_fast || b->fft_pairw) {
-            p.db_offset = (float)(10.0 * std::log10(4.0 / ((double)c.fft_n * (double)c.fft_n)));
-            p.offpink = b->bt->offpink4096_dev.p;
-            p.publish_mask = ssk::fft4096_publish_mask(L.first_bin, L.n_bins);
-            if (b->fft_fast) HIPCHK(ssk::launch_fft4096_ms(p, fft_stream));
-            else HIPCHK(ssk::launch_fft4096_pairw(p, b->fft_mode, fft_stream));
-        } else {
-            p.db_offset = (float)(20.0 * std::log10(4.0 / (double)c.fft_n));
-            if (c.fft_n == 16384) {
-                p.tw_core = b->ft->core_tw4096; p.tw_256 = b->ft->core_tw256;
-                if (fft16k_runs(b))
-                    HIPCHK(ssk::launch_fft16k_run(p, b->fft_mode, fft_stream));
-                else
-                    HIPCHK(ssk::launch_fft16k(p, b->fft_mode, fft_stream));
-            } else {
-                HIPCHK(ssk::launch_fft_generic(p, b->fft_mode, fft_stream));
-            }
-        }
+        HIPCHK(ssk::launch_spectrum(b->spec, p, fft_stream));
     }
     HIPCHK(rec(2 * SS_KERNEL_FFT + 1));
     return SS_OK;
@@ -751,16 +704,9 @@ int ss_batch_traffic_floor(ss_batch *b, uint32_t reps, double *ms_per_launch)
 {
     SS_ON_DEVICE(b);
     if (!b || !ms_per_launch || reps == 0) return SS_ERR_INVALID_ARG;
-    const ss_batch_config &c = b->cfg;
-    const ss_batch_layout &L = b->lay;
-    if (!(c.flags & SS_BATCH_FFT) || !b->fft_fast || c.hop_frames != 1024 || !L.n_windows || b->ragged) return SS_ERR_UNSUPPORTED;
+    if (!(b->cfg.flags & SS_BATCH_FFT) || b->spec.kernel != ssk::SpecKernel::ms1 || !b->lay.n_windows || b->ragged) return SS_ERR_UNSUPPORTED;
     if (!b->fft.p) return SS_ERR_INVALID_MODE;          // columns-only batches have no spectrum rows to store into
-    ssk::FftBatchParams p{};
-    p.pcm = b->pcm.p; p.out = b->fft.p;
-    p.frames_per_stream = c.frames_per_stream; p.first_start = b->first_start;
-    p.n_streams = c.n_streams; p.channels = c.channels; p.n_windows = L.n_windows; p.hop = c.hop_frames;
-    p.n = c.fft_n; p.first_bin = L.first_bin; p.n_bins = L.n_bins; p.bin_stride = L.fft_bin_stride;
-    p.windows_per_block = b->windows_per_block;
+    const ssk::FftBatchParams p = batch_fft_params(b);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(hipEventCreate(&e0));
     hipError_t err = hipEventCreate(&e1);
@@ -842,21 +788,8 @@ int ss_batch_geometry_get(const ss_batch *b, ss_batch_geometry *out)
     std::memset(out, 0, sizeof *out);
     const ss_batch_layout &L = b->lay;
     if ((b->cfg.flags & SS_BATCH_FFT) && L.n_windows) {
-        out->fft_windows_per_block = b->windows_per_block;
-        if (b->fft_fast) {
-            out->fft_blocks = b->cfg.n_streams * ((L.n_windows + b->windows_per_block - 1) / b->windows_per_block);
-        } else if (b->fft_pairw) {
-            const uint32_t ppb = b->windows_per_block >> 1, np = (L.n_windows + 1) >> 1;
-            out->fft_blocks = b->cfg.n_streams * L.fft_channels * ((np + ppb - 1) / ppb);
-        } else if (fft16k_runs(b)) {
-            uint32_t wpb = 0, groups = 0;
-            ssk::fft16k_run_geometry(b->cfg.n_streams, L.fft_channels, L.n_windows, &wpb, &groups);
-            out->fft_windows_per_block = wpb;
-            out->fft_blocks = b->cfg.n_streams * L.fft_channels * groups;
-        } else {
-            out->fft_windows_per_block = 1;
-            out->fft_blocks = b->cfg.n_streams * L.n_windows * L.fft_channels;
-        }
+        out->fft_windows_per_block = b->spec.windows_per_block;
+        out->fft_blocks = b->spec.blocks;
     }
     if (b->td) {
         out->td_segments = b->td_plan.nseg;
@@ -1198,14 +1131,7 @@ int ss_batch_timing_read(ss_batch *b, int kernel, double *total_ms, uint64_t *la
 const char *ss_batch_kernel_name(const ss_batch *b, int kernel)
 {
     if (!b || kernel != SS_KERNEL_FFT) return ss_kernel_name(kernel);
-    if (b->fft_pairw) return "k_fft4096_pairw";
-    if (b->fft_fast) {
-        const uint32_t hop = b->cfg.hop_frames;
-        return hop == 1024 ? "k_fft4096_ms1" : ((hop == 512 || hop == 2048) ? "k_fft4096_ms" : "k_fft4096_ms_anyhop");
-    }
-    if (b->cfg.fft_n == 16384)
-        return fft16k_runs(b) ? "k_fft16k_run" : "k_fft16k";
-    return "k_fft_generic";
+    return ssk::spectrum_kernel_name(b->spec.kernel);
 }
 
 const char *ss_kernel_name(int kernel)

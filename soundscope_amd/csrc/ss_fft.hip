@@ -1074,18 +1074,6 @@ __global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchP
 #undef X2W
 }
 
-hipError_t launch_fft4096_pairw(const FftBatchParams &p, int mode, hipStream_t s)
-{
-    if (p.n_windows == 0 || p.n_streams == 0) return hipSuccess;
-    const uint32_t fft_ch = (mode == 0) ? 1u : p.channels;
-    const uint32_t pairs_per_block = p.windows_per_block >> 1;
-    const uint32_t n_pairs = (p.n_windows + 1) >> 1;
-    const uint32_t groups = (n_pairs + pairs_per_block - 1) / pairs_per_block;
-    const uint64_t total = (uint64_t)p.n_streams * groups * fft_ch;
-    hipLaunchKernelGGL(k_fft4096_pairw, dim3((uint32_t)((total + 7) & ~(uint64_t)7)), dim3(256), 0, s, p, fft_ch);
-    return hipGetLastError();
-}
-
 // generic hop (not a multiple of 256 or >= N/2 slots): one window per iteration, full reload
 __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms_anyhop(FftBatchParams p)
 {
@@ -1474,64 +1462,6 @@ __global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_
 #undef X2W
 }
 
-// run geometry of k_fft16k_run: enough workgroups to fill 256 CUs x 2, runs of at least 16 windows (the run's first
-// window costs a full load)
-void fft16k_run_geometry(uint32_t n_streams, uint32_t fft_ch, uint32_t n_windows, uint32_t *windows_per_block, uint32_t *groups_out)
-{
-    const uint64_t pairs = (uint64_t)n_streams * fft_ch;
-    uint32_t groups = (uint32_t)((4096 + pairs - 1) / pairs);
-    const uint32_t max_groups = n_windows / 16u ? n_windows / 16u : 1u;
-    if (groups > max_groups) groups = max_groups;
-    if (groups < 1) groups = 1;
-#ifdef SS_TUNING        // development builds only (tools/ab_cfg5.sh with SS_FFT16K_GROUPS)
-    if (const char *e = std::getenv("SS_FFT16K_GROUPS")) { const int v = std::atoi(e); if (v >= 1 && (uint32_t)v <= n_windows) groups = (uint32_t)v; }
-#endif
-    const uint32_t wpb = (n_windows + groups - 1) / groups;
-    *windows_per_block = wpb;
-    *groups_out = (n_windows + wpb - 1) / wpb;
-}
-
-// runs of windows at hop 1024 (batches); `mode` as launch_fft16k
-hipError_t launch_fft16k_run(FftBatchParams p, int mode, hipStream_t s)
-{
-    if (p.n_windows == 0 || p.n_streams == 0 || p.n_bins == 0) return hipSuccess;
-    const uint32_t fft_ch = (mode == 0) ? 1u : (mode == 1 ? 2u : p.channels);
-    const uint64_t pairs = (uint64_t)p.n_streams * fft_ch;
-    uint32_t groups = 1;
-    fft16k_run_geometry(p.n_streams, fft_ch, p.n_windows, &p.windows_per_block, &groups);
-    const dim3 grid((uint32_t)((pairs * groups + 7) & ~(uint64_t)7)), block(512);      // multiple of 8: see the XCD mapping in the kernel
-    const uint32_t ngroups = (p.n_bins + 3) >> 2, n_iter = (4u * ngroups + 2047u) >> 11;
-    const uint32_t ne_last = (4u * ngroups - 2048u * (n_iter - 1u) + 511u) >> 9;       // slices of the epilogue's last iteration, 1 .. 4
-#define SS_RUN16K(MS, NE) hipLaunchKernelGGL((k_fft16k_run<MS, NE>), grid, block, 0, s, p, fft_ch)
-    if (mode == 1) { if (ne_last == 1) SS_RUN16K(true, 1); else if (ne_last == 2) SS_RUN16K(true, 2); else if (ne_last == 3) SS_RUN16K(true, 3); else SS_RUN16K(true, 4); }
-    else { if (ne_last == 1) SS_RUN16K(false, 1); else if (ne_last == 2) SS_RUN16K(false, 2); else if (ne_last == 3) SS_RUN16K(false, 3); else SS_RUN16K(false, 4); }
-#undef SS_RUN16K
-    return hipGetLastError();
-}
-
-hipError_t launch_fft16k(const FftBatchParams &p, int mode, hipStream_t s)
-{
-    if (p.n_windows == 0 || p.n_streams == 0 || p.n_bins == 0) return hipSuccess;
-    const uint32_t fft_ch = (mode == 0) ? 1u : (mode == 1 ? 2u : p.channels);
-    hipLaunchKernelGGL(k_fft16k, dim3(p.n_streams * p.n_windows * fft_ch), dim3(512), 0, s, p, mode == 1 ? 1 : 0, fft_ch);
-    return hipGetLastError();
-}
-
-hipError_t launch_fft4096_ms(const FftBatchParams &p, hipStream_t s)
-{
-    if (p.n_windows == 0 || p.n_streams == 0) return hipSuccess;
-    const uint32_t groups = (p.n_windows + p.windows_per_block - 1) / p.windows_per_block;
-    dim3 grid(groups * p.n_streams), block(256);
-    // hop 1024 (the reference's cadence): the single-window kernel at 3 workgroups per CU measured 2.5 %
-    // faster than the window-pair kernel k_fft4096_ms<4> at 2 (A/B in one process, 3.48 vs 3.57 ms)
-    if (p.hop == 1024 && p.out_cols) hipLaunchKernelGGL((k_fft4096_ms1<4, kMs1Tw, true>), grid, block, 0, s, p);
-    else if (p.hop == 1024) hipLaunchKernelGGL((k_fft4096_ms1<4, kMs1Tw, false>), grid, block, 0, s, p);
-    else if (p.hop == 512) hipLaunchKernelGGL(k_fft4096_ms<2>, grid, block, 0, s, p);
-    else if (p.hop == 2048) hipLaunchKernelGGL(k_fft4096_ms<8>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(k_fft4096_ms_anyhop, grid, block, 0, s, p);
-    return hipGetLastError();
-}
-
 // ============================================================================
 //  Spectrum, generic power-of-two N (2..32768), one real channel per workgroup:
 //  real FFT through an N/2-point complex FFT held in LDS (in-place radix-2
@@ -1607,22 +1537,133 @@ __global__ __launch_bounds__(256) void k_fft_generic(FftBatchParams p, int mode,
     }
 }
 
-hipError_t launch_fft_generic(const FftBatchParams &p, int mode, hipStream_t s)
+// ============================================================================
+//  The spectrum plan (ss_kernels.h): kernel, rows, windows per workgroup and grid of a shape, and its launch
+// ============================================================================
+SpecPlan plan_spectrum(uint32_t n, uint32_t channels, uint32_t hop, uint32_t n_streams, uint32_t n_windows)
 {
-    if (p.n_windows == 0 || p.n_streams == 0 || p.n_bins == 0) return hipSuccess;
-    const uint32_t fft_ch = (mode == 0) ? 1u : (mode == 1 ? 2u : p.channels);
-    const uint32_t m = p.n >> 1;
-    int log2m = 0;
-    while ((1u << log2m) < m) log2m++;
-    const size_t lds = (size_t)(m ? m : 1) * sizeof(float2);
-    static DevicePrep prepared;
-    const hipError_t pe = prepare_on_device(prepared, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_generic), hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    });
-    if (pe != hipSuccess) return pe;
-    dim3 grid(p.n_streams * p.n_windows * fft_ch), block(256);
-    hipLaunchKernelGGL(k_fft_generic, grid, block, lds, s, p, mode, log2m);
+    SpecPlan pl;
+    pl.rows = channels == 2 ? SpecRows::mid_side : (channels == 1 ? SpecRows::mono : SpecRows::per_channel);
+    pl.fft_ch = channels;               // mono: 1, mid and side: 2, otherwise one row per channel
+    const bool ms = channels == 2 && n == 4096 && hop % 256 == 0;
+    bool pairw = channels != 2 && n == 4096 && hop == 1024;
+    bool run16k = n == 16384 && hop == 1024 && n_windows >= 8;
+#ifdef SS_TUNING        // development builds only: the shipped library takes no kernel selection from the environment
+    if (std::getenv("SS_FFT_NO_PAIRW")) pairw = false;
+    if (std::getenv("SS_FFT16K_SINGLE")) run16k = false;
+#endif
+    if (ms || pairw) {
+        // windows per workgroup: long runs amortise the per-workgroup constants and the 3-hop halo,
+        // but keep >= ~4096 workgroups (8 rounds of the 512 resident ones) for load balance
+        uint32_t tgt = (4096u + n_streams - 1) / n_streams;
+        if (tgt > n_windows / 16) tgt = n_windows / 16;
+        if (tgt < 1) tgt = 1;
+        uint32_t wpb = (n_windows + tgt - 1) / tgt;
+        // ... unless runs of sixteen leave most of the chip idle (one file, a handful of streams): then the pass is bound by
+        // the length of a run, not by its constants — as many workgroups as the chip holds at once (three per CU), runs of two
+        // windows at least (config 2, one 10 s stream: 29 workgroups x 16 windows 50 us -> 232 x 2)
+        const uint64_t total = (uint64_t)n_streams * n_windows;
+        if ((uint64_t)n_streams * ((n_windows + wpb - 1) / (wpb ? wpb : 1)) < 512u) {
+            const uint64_t w = (total + 767u) / 768u;
+            wpb = (uint32_t)(w < 2 ? 2 : w);
+        }
+        wpb = (wpb + 1) & ~1u;
+        wpb = wpb < 2 ? 2 : wpb;
+#ifdef SS_TUNING
+        if (const char *e = std::getenv("SS_FFT_WPB")) { int v = std::atoi(e); if (v >= 2 && v <= 4096) wpb = (uint32_t)(v & ~1); }
+#endif
+        pl.windows_per_block = wpb;
+        if (ms) {
+            pl.kernel = hop == 1024 ? SpecKernel::ms1 : ((hop == 512 || hop == 2048) ? SpecKernel::ms : SpecKernel::ms_anyhop);
+            pl.blocks = n_streams * ((n_windows + wpb - 1) / wpb);
+        } else {
+            const uint32_t pairs_per_block = wpb >> 1, n_pairs = (n_windows + 1) >> 1;
+            pl.kernel = SpecKernel::pairw;
+            pl.blocks = n_streams * channels * ((n_pairs + pairs_per_block - 1) / pairs_per_block);
+        }
+    } else if (run16k) {
+        // runs of windows: enough workgroups to fill 256 CUs x 2, runs of at least 16 windows (the run's first window costs a
+        // full load)
+        const uint64_t rows = (uint64_t)n_streams * channels;
+        uint32_t groups = (uint32_t)((4096 + rows - 1) / rows);
+        const uint32_t max_groups = n_windows / 16u ? n_windows / 16u : 1u;
+        if (groups > max_groups) groups = max_groups;
+        if (groups < 1) groups = 1;
+#ifdef SS_TUNING        // (tools/ab_cfg5.sh)
+        if (const char *e = std::getenv("SS_FFT16K_GROUPS")) { const int v = std::atoi(e); if (v >= 1 && (uint32_t)v <= n_windows) groups = (uint32_t)v; }
+#endif
+        const uint32_t wpb = (n_windows + groups - 1) / groups;
+        pl.kernel = SpecKernel::fft16k_run;
+        pl.windows_per_block = wpb;
+        pl.blocks = n_streams * channels * ((n_windows + wpb - 1) / wpb);
+    } else {
+        pl.kernel = n == 16384 ? SpecKernel::fft16k : SpecKernel::generic;
+        pl.blocks = n_streams * n_windows * channels;
+    }
+    return pl;
+}
+
+hipError_t launch_spectrum(const SpecPlan &pl, const FftBatchParams &p, hipStream_t s)
+{
+    if (p.n_windows == 0 || p.n_streams == 0) return hipSuccess;
+    const dim3 grid(pl.blocks), grid8((pl.blocks + 7u) & ~7u);      // grid8: a multiple of 8, see the XCD mapping in the kernels
+    const bool midside = pl.rows == SpecRows::mid_side;
+    switch (pl.kernel) {
+    case SpecKernel::fft16k_run: {
+        if (p.n_bins == 0) return hipSuccess;
+        const uint32_t ngroups = (p.n_bins + 3) >> 2, n_iter = (4u * ngroups + 2047u) >> 11;
+        const uint32_t ne_last = (4u * ngroups - 2048u * (n_iter - 1u) + 511u) >> 9;   // slices of the epilogue's last iteration, 1 .. 4
+#define SS_RUN16K(MS, NE) hipLaunchKernelGGL((k_fft16k_run<MS, NE>), grid8, dim3(512), 0, s, p, pl.fft_ch)
+        if (midside) { if (ne_last == 1) SS_RUN16K(true, 1); else if (ne_last == 2) SS_RUN16K(true, 2); else if (ne_last == 3) SS_RUN16K(true, 3); else SS_RUN16K(true, 4); }
+        else { if (ne_last == 1) SS_RUN16K(false, 1); else if (ne_last == 2) SS_RUN16K(false, 2); else if (ne_last == 3) SS_RUN16K(false, 3); else SS_RUN16K(false, 4); }
+#undef SS_RUN16K
+        break;
+    }
+    // hop 1024 (the reference's cadence): the single-window kernel at 3 workgroups per CU measured 2.5 %
+    // faster than the window-pair kernel k_fft4096_ms<4> at 2 (A/B in one process, 3.48 vs 3.57 ms)
+    case SpecKernel::ms1:
+        if (p.out_cols) hipLaunchKernelGGL((k_fft4096_ms1<4, kMs1Tw, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((k_fft4096_ms1<4, kMs1Tw, false>), grid, dim3(256), 0, s, p);
+        break;
+    case SpecKernel::ms:
+        if (p.hop == 512) hipLaunchKernelGGL(k_fft4096_ms<2>, grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(k_fft4096_ms<8>, grid, dim3(256), 0, s, p);
+        break;
+    case SpecKernel::ms_anyhop: hipLaunchKernelGGL(k_fft4096_ms_anyhop, grid, dim3(256), 0, s, p); break;
+    case SpecKernel::pairw: hipLaunchKernelGGL(k_fft4096_pairw, grid8, dim3(256), 0, s, p, pl.fft_ch); break;
+    case SpecKernel::fft16k:
+        if (p.n_bins == 0) return hipSuccess;
+        hipLaunchKernelGGL(k_fft16k, grid, dim3(512), 0, s, p, midside ? 1 : 0, pl.fft_ch);
+        break;
+    case SpecKernel::generic: {
+        if (p.n_bins == 0) return hipSuccess;
+        const uint32_t m = p.n >> 1;
+        int log2m = 0;
+        while ((1u << log2m) < m) log2m++;
+        const size_t lds = (size_t)(m ? m : 1) * sizeof(float2);
+        static DevicePrep prepared;
+        const hipError_t pe = prepare_on_device(prepared, [] {
+            return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_generic), hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+        });
+        if (pe != hipSuccess) return pe;
+        hipLaunchKernelGGL(k_fft_generic, grid, dim3(256), lds, s, p, (int)pl.rows, log2m);
+        break;
+    }
+    }
     return hipGetLastError();
+}
+
+const char *spectrum_kernel_name(SpecKernel k)
+{
+    switch (k) {
+        case SpecKernel::ms1: return "k_fft4096_ms1";
+        case SpecKernel::ms: return "k_fft4096_ms";
+        case SpecKernel::ms_anyhop: return "k_fft4096_ms_anyhop";
+        case SpecKernel::pairw: return "k_fft4096_pairw";
+        case SpecKernel::fft16k_run: return "k_fft16k_run";
+        case SpecKernel::fft16k: return "k_fft16k";
+        default: return "k_fft_generic";
+    }
 }
 
 // ============================================================================

@@ -303,14 +303,30 @@ ssk::FinalizeParams MeterStore::stream_gating(uint64_t sub_begin, uint64_t sub_e
     return f;
 }
 
-ssk::FftBatchParams one_window_fft(const FftTables &ft, const BinTables &bt)
+ssk::FftBatchParams spectrum_params(const ssk::SpecPlan &plan, const FftTables &ft, const BinTables &bt, bool pink)
 {
+    using ssk::SpecKernel;
     ssk::FftBatchParams p{};
     p.window = ft.window.p; p.half_window = ft.half_window.p; p.tw_n = ft.tw_n.p; p.tw_256 = ft.tw_256.p;
     if (ft.n == 16384) { p.tw_core = ft.core_tw4096; p.tw_256 = ft.core_tw256; }
-    p.n_streams = 1; p.n_windows = 1; p.n = (uint32_t)ft.n; p.windows_per_block = 1;
-    p.first_bin = (uint32_t)bt.first; p.n_bins = (uint32_t)bt.count; p.bin_stride = p.n_bins;
-    p.db_offset = (float)(20.0 * std::log10(4.0 / (double)ft.n));
+    p.n = (uint32_t)ft.n; p.windows_per_block = plan.windows_per_block;
+    p.first_bin = (uint32_t)bt.first; p.n_bins = (uint32_t)bt.count; p.bin_stride = (p.n_bins + 3u) & ~3u;
+    p.pink = pink ? bt.pink_dev.p : nullptr;
+    if (plan.kernel == SpecKernel::ms1 || plan.kernel == SpecKernel::ms || plan.kernel == SpecKernel::ms_anyhop ||
+        plan.kernel == SpecKernel::pairw) {
+        p.db_offset = (float)(10.0 * std::log10(4.0 / ((double)ft.n * (double)ft.n)));
+        p.offpink = pink ? bt.offpink4096_dev.p : bt.off4096_dev.p;
+        p.publish_mask = ssk::fft4096_publish_mask(p.first_bin, p.n_bins);
+    } else {
+        p.db_offset = (float)(20.0 * std::log10(4.0 / (double)ft.n));
+    }
+    return p;
+}
+
+ssk::FftBatchParams one_window_fft(const ssk::SpecPlan &plan, const FftTables &ft, const BinTables &bt)
+{
+    ssk::FftBatchParams p = spectrum_params(plan, ft, bt, false);
+    p.n_streams = 1; p.n_windows = 1; p.hop = kOneWindowHop;
     return p;
 }
 

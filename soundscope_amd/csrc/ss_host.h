@@ -202,9 +202,15 @@ struct SS_HIDDEN MeterStore {
     ssk::FinalizeParams stream_gating(uint64_t sub_begin, uint64_t sub_end) const;
 };
 
-// one window of ft.n points of one stream (ss_get_fft, the ticks, the meter banks: their rows agree bit for bit): the tables, the bins
-// of bt in unpadded rows, raw dBFS (db_offset = 20 log10(4 / n)).  The caller sets pcm, out, channels and the window's start.
-SS_HIDDEN ssk::FftBatchParams one_window_fft(const FftTables &ft, const BinTables &bt);
+// The FftBatchParams fields that follow from a spectrum plan and the tables: the tables (the N = 16384 core twiddles included),
+// n and windows_per_block, the bins of bt in rows padded to four (16-B aligned), the dB offset and, for the N = 4096 forms, offpink
+// and publish_mask.  pink: the rows carry the pink compensation (batches); otherwise raw dBFS (a handle adds it in f64 on the host).
+SS_HIDDEN ssk::FftBatchParams spectrum_params(const ssk::SpecPlan &plan, const FftTables &ft, const BinTables &bt, bool pink);
+// One window of ft.n points of one stream (ss_get_fft, the ticks, the meter banks: their rows agree bit for bit) is a batch of one
+// stream and one window at this hop: plan it with ssk::plan_spectrum(n, channels, kOneWindowHop, 1, 1).
+constexpr uint32_t kOneWindowHop = 1024;
+// spectrum_params in raw dBFS for that one window; the caller sets pcm, out, channels and the window's start
+SS_HIDDEN ssk::FftBatchParams one_window_fft(const ssk::SpecPlan &plan, const FftTables &ft, const BinTables &bt);
 
 }  // namespace ssh
 

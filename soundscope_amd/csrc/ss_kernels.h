@@ -90,17 +90,28 @@ inline uint32_t fft4096_publish_mask(uint32_t first_bin, uint32_t n_bins)
     }
     return mask;
 }
-// mid/side packed N=4096 kernel (stereo only).  hop must be a multiple of 256.
-hipError_t launch_fft4096_ms(const FftBatchParams &p, hipStream_t s);
-// any power-of-two N in [2, 32768]; mode 0: mono buffers (channels == 1),
-// 1: stereo -> mid/side, 2: per channel
-hipError_t launch_fft_generic(const FftBatchParams &p, int mode, hipStream_t s);
-// N = 16384 real FFT per channel (two radix-16 4096-point halves); same modes as the generic kernel
-hipError_t launch_fft16k(const FftBatchParams &p, int mode, hipStream_t s);
-// N = 4096, hop 1024, one real channel per workgroup run, two windows per transform (mode 0 mono, 2 per channel)
-hipError_t launch_fft4096_pairw(const FftBatchParams &p, int mode, hipStream_t s);
-hipError_t launch_fft16k_run(FftBatchParams p, int mode, hipStream_t s);   // hop 1024, runs of windows
-void fft16k_run_geometry(uint32_t n_streams, uint32_t fft_ch, uint32_t n_windows, uint32_t *windows_per_block, uint32_t *groups);
+// The spectrum kernels (ss_fft.hip), one per launch form:
+//   ms1, ms, ms_anyhop  N = 4096 stereo -> mid/side packed as one complex FFT, hop a multiple of 256 (1024 / 512 or 2048 / other)
+//   pairw               N = 4096, hop 1024, mono / per channel: one real channel per workgroup run, two windows per transform
+//   fft16k_run          N = 16384, hop 1024, eight windows or more: runs of windows per workgroup
+//   fft16k              N = 16384, one window per workgroup
+//   generic             any other power-of-two N in [2, 32768]
+enum class SpecKernel : uint32_t { ms1, ms, ms_anyhop, pairw, fft16k_run, fft16k, generic };
+// what a window's rows are (the values are the kernels' `mode`)
+enum class SpecRows : uint32_t { mono = 0, mid_side = 1, per_channel = 2 };
+struct SpecPlan {
+    SpecKernel kernel = SpecKernel::generic;
+    SpecRows rows = SpecRows::mono;
+    uint32_t fft_ch = 1;             // rows per window
+    uint32_t windows_per_block = 1;  // consecutive windows a workgroup walks (FftBatchParams::windows_per_block)
+    uint32_t blocks = 0;             // workgroups (pairw / fft16k_run launch this rounded up to a multiple of 8)
+};
+// which kernel runs n_streams x n_windows windows of N = n points of `channels`-channel input at `hop`, on what grid.  The one
+// decision for batches and one-window callers alike (a handle's get_fft, a tick: one stream, one window at hop 1024).
+SpecPlan plan_spectrum(uint32_t n, uint32_t channels, uint32_t hop, uint32_t n_streams, uint32_t n_windows);
+// p: n_streams / n_windows as planned, windows_per_block = plan.windows_per_block
+hipError_t launch_spectrum(const SpecPlan &plan, const FftBatchParams &p, hipStream_t s);
+const char *spectrum_kernel_name(SpecKernel k);         // as rocprofv3 prints it, without template arguments
 
 // ---- time domain ------------------------------------------------------------
 struct TdConst {                 // one per (rate, true-peak factor), device resident

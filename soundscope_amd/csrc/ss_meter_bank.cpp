@@ -131,7 +131,7 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
         m->spec_pin_bytes = fbytes + sbytes;
     }
     ssk::BankSpectrumParams q{};
-    q.f = one_window_fft(*m->ft, *m->bt);
+    q.f = one_window_fft(ssk::plan_spectrum(SS_BANK_SPECTRUM_N, m->meter.channels, kOneWindowHop, 1, 1), *m->ft, *m->bt);
     q.hist = m->spec_hist.p;
     q.start = (uint32_t)((m->spec_fed - SS_BANK_SPECTRUM_N) & (SS_BANK_SPECTRUM_N - 1));
     q.n_streams = m->meter.n; q.channels = m->meter.channels; q.rows = R;

@@ -32,6 +32,7 @@ struct ss_session {
     size_t stage_floats = 0;
     FftTables *ft = nullptr;
     BinTables *bt = nullptr;
+    ssk::SpecPlan fft_plan;             // a tick's mid/side spectrum: one stereo window of SS_TICK_WINDOW frames
     uint32_t bin_stride = 0;
     // pairs whose mid or side value is NaN / infinite (normally none): index -> class bits
     // (1 mid NaN, 2 mid inf, 4 side NaN, 8 side inf)
@@ -88,6 +89,7 @@ int session_common_init(ss_session *s, uint32_t meter_channels, uint32_t rate)
     if (rc) return rc;
     rc = get_bin_tables(rate, SS_TICK_WINDOW, &s->bt);
     if (rc) return rc;
+    s->fft_plan = ssk::plan_spectrum(SS_TICK_WINDOW, 2, kOneWindowHop, 1, 1);
     s->bin_stride = (uint32_t)((s->bt->count + 3) & ~(size_t)3);
     if (s->bin_stride == 0) s->bin_stride = 4;
     HIPCHK(hipEventCreateWithFlags(&s->ev_tick, hipEventDisableTiming));
@@ -114,7 +116,7 @@ int session_stage(ss_session *s, size_t floats)
 // (the session's device rows, or the pinned stage as the device sees it)
 ssk::FftBatchParams session_fft_params(const ss_session *s, const float *pairs, size_t lb, float *out)
 {
-    ssk::FftBatchParams p = one_window_fft(*s->ft, *s->bt);
+    ssk::FftBatchParams p = one_window_fft(s->fft_plan, *s->ft, *s->bt);
     p.pcm = pairs; p.out = out; p.first_start = lb; p.channels = 2;
     p.bin_stride = s->bin_stride;                   // (the side row stands behind the mid row, 16-B aligned)
     return p;
@@ -149,7 +151,7 @@ struct TickCore {
             st_launched = extras.st_fused;
         }
         if (fft && !fft_launched) {                     // (no loudness call this tick, or one that could not take the spectrum along)
-            HIPCHK(ssk::launch_fft16k(*fft, 1, h->stream));
+            HIPCHK(ssk::launch_spectrum(s->fft_plan, *fft, h->stream));
             fft_launched = any_launch = true;
         }
         if (samples && !st_launched) {                  // (the reading did not ride the tick launch)

@@ -697,6 +697,34 @@ def test_launch_geometry_across_batch_sizes(oracle, n_streams):
         assert np.array_equal(b.waveform(i).reshape(-1), ref["wave"][:, 1].astype(np.float32)), i
 
 
+# (channels, streams, frames, N, hop) -> (kernel, fft_windows_per_block, fft_blocks), as the parent of the spectrum plan reported them
+_SPECTRUM_FORMS = [
+    ((2, 64, 480000, 4096, 1024), ("k_fft4096_ms1", 16, 1856)),
+    ((2, 16, 480000, 4096, 512), ("k_fft4096_ms", 18, 832)),
+    ((2, 2, 192000, 4096, 2048), ("k_fft4096_ms", 2, 92)),
+    ((2, 2, 96000, 4096, 768), ("k_fft4096_ms_anyhop", 2, 120)),
+    ((1, 5, 96000, 4096, 1024), ("k_fft4096_pairw", 2, 225)),
+    ((6, 40, 480000, 4096, 1024), ("k_fft4096_pairw", 16, 6960)),
+    ((2, 3, 240000, 16384, 1024), ("k_fft16k_run", 17, 78)),
+    ((2, 2, 144000, 16384, 2048), ("k_fft16k", 1, 248)),
+    ((2, 2, 96000, 2048, 1024), ("k_fft_generic", 1, 364)),
+]
+
+
+@pytest.mark.parametrize("shape,expect", _SPECTRUM_FORMS, ids=[f"{e[0]}-C{s[0]}-hop{s[4]}" for s, e in _SPECTRUM_FORMS])
+def test_spectrum_form_geometry(shape, expect):
+    """Every spectrum launch form, one batch shape each: the kernel the batch names and the geometry it reports (windows per
+    workgroup, workgroups before any round-up of the grid), then one pass through that launch."""
+    channels, n_streams, frames, n, hop = shape
+    b = ssa.Batch(48000, channels, n_streams, frames, n, hop, flags=L.SS_BATCH_FFT)
+    assert b.layout.n_windows == frames // hop - n // hop
+    g = b.geometry
+    assert (L.lib().ss_batch_kernel_name(b._h, L.SS_KERNEL_FFT).decode(), g.fft_windows_per_block, g.fft_blocks) == expect
+    b.synthesize(0x5EED0000, 0)
+    b.run(); b.sync()
+    assert np.isfinite(b.fft(n_streams - 1)).all()
+
+
 @pytest.mark.parametrize("frames", [1, 100, 4095, 4096, 4097, 5120, 5121, 19199, 19200, 19201, 19679, 19680, 24000, 143999, 144000, 144001, 148800, 148801])
 def test_stream_length_edges(oracle, frames):
     """Lengths at every threshold of the path at 48 kHz: no window / the first window (the reference skips the window whose
