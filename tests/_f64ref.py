@@ -6,7 +6,9 @@ module, not a test file): none of it calls the product or the oracle.
   * the crate's true-peak interpolator: 49 Hann-windowed sinc taps rounded to f32, a zero-stuffed polyphase convolution in f64;
   * ebur128's channel weights, and the momentary / short-term series as `loudness_momentary()` / `loudness_shortterm()` return
     them after every 100 ms sub-block (zeros before the start);
-  * get_waveform's min-max decimation (analyzer.rs:107-137).
+  * get_waveform's min-max decimation (analyzer.rs:107-137);
+  * the spectrum rows (analyzer.rs:11-27, :55-105): the retained-bin rule, mid / side formed in f32, one row of any mono window
+    with the transform in f64, and `row_error`, the metric the spectrum forms are held to.
 """
 import numpy as np
 from scipy import signal
@@ -144,3 +146,76 @@ def waveform_numpy(x, window_s):
         out += [np.nanmin(seg) if seg.size and not np.all(np.isnan(seg)) else (np.nan if seg.size else 0.0),
                 np.nanmax(seg) if seg.size and not np.all(np.isnan(seg)) else (np.nan if seg.size else 0.0)]
     return np.array(out, np.float32)
+
+
+def retained_bins(rate, n):
+    """(first bin, count) of the bins a row keeps: f32 frequencies k * (rate / n), both in f32, within [20, 20000]"""
+    f = np.arange(n // 2 + 1, dtype=np.float32) * (np.float32(rate) / np.float32(n))
+    keep = np.nonzero((f >= np.float32(20.0)) & (f <= np.float32(20000.0)))[0]
+    return (int(keep[0]), int(keep.size)) if keep.size else (0, 0)
+
+
+def pink_db(rate, n):
+    """the pink compensation the retained bins carry: 10 log10(f / 1000), f the f32 bin frequency, in f64"""
+    first, count = retained_bins(rate, n)
+    f = (np.arange(first, first + count, dtype=np.float32) * (np.float32(rate) / np.float32(n))).astype(np.float64)
+    return 10.0 * np.log10(f / 1000.0)
+
+
+def mid_side_f32(lr):
+    """mid and side of [frames][2] stereo as the crate forms them: (l + r) / 2 and (l - r) / 2 in f32"""
+    lr = np.asarray(lr, np.float32)
+    two = np.float32(2.0)
+    return ((lr[:, 0] + lr[:, 1]) / two).astype(np.float32), ((lr[:, 0] - lr[:, 1]) / two).astype(np.float32)
+
+
+def hann_f32(n):
+    """the crate's periodic Hann window, its weights rounded to f32"""
+    i = np.arange(n, dtype=np.float64)
+    return (0.5 * (1.0 - np.cos(2.0 * np.pi * i / n))).astype(np.float32).astype(np.float64)
+
+
+def spectrum_row_f64(x, rate, n=None, pink=True):
+    """One row of get_fft for the mono window x (n samples, taken as they are: pass f32 data as f32): f32 Hann weights, the
+    product and the rfft in f64, 20 log10(|X| 4 / N) on the retained bins, -150 for an exact zero, + 10 log10(f / 1000)."""
+    x = np.asarray(x)
+    n = x.size if n is None else n
+    mag = np.abs(np.fft.rfft(x.astype(np.float64) * hann_f32(n)))
+    first, count = retained_bins(rate, n)
+    m = mag[first:first + count]
+    with np.errstate(divide="ignore"):
+        db = np.where(m == 0.0, -150.0, 20.0 * np.log10(np.where(m == 0.0, 1.0, m) * 4.0 / n))
+    return db + pink_db(rate, n) if pink else db
+
+
+def spectrum_f64(x, rate, n):
+    """One window of the reference's get_fft restated with numpy in f64 (window values rounded to f32 as the crate's)."""
+    return spectrum_row_f64(x, rate, n)
+
+
+def row_error(got_db, ref_db, pink):
+    """max_k |a_got - a_ref| / max_k a_ref: a row's error as a fraction of its own peak amplitude, pink taken out of both rows
+    (a = 10^(dB / 20)).  Each bin is first allowed the rounding of its stored f32 dB value (two ulps of it), so that a quiet
+    row is bounded by its transform and not by how its output is stored."""
+    got = np.asarray(got_db, np.float64)
+    ref = np.asarray(ref_db, np.float64)
+    assert got.shape == ref.shape and got.ndim == 1, (got.shape, ref.shape)
+    a_got = 10.0 ** ((got - pink) / 20.0)
+    a_ref = 10.0 ** ((ref - pink) / 20.0)
+    ulp2 = 2.0 * np.abs(np.spacing(got.astype(np.float32))).astype(np.float64)
+    allow = a_got * (10.0 ** (ulp2 / 20.0) - 1.0)
+    return float(np.maximum(np.abs(a_got - a_ref) - allow, 0.0).max() / a_ref.max())
+
+
+def floor_error(got_db, ref_db, pink, below_db=40.0):
+    """row_error over the bins at least `below_db` under the row's peak only: the transform's rounding noise, apart from what the
+    dB conversion rounds in proportion to each bin (that sets row_error at the peak; this sees the twiddles and the butterflies)"""
+    got = np.asarray(got_db, np.float64)
+    ref = np.asarray(ref_db, np.float64)
+    a_got = 10.0 ** ((got - pink) / 20.0)
+    a_ref = 10.0 ** ((ref - pink) / 20.0)
+    quiet = a_ref <= a_ref.max() * 10.0 ** (-below_db / 20.0)
+    if not quiet.any():
+        return 0.0
+    allow = a_got * (10.0 ** (2.0 * np.abs(np.spacing(got.astype(np.float32))).astype(np.float64) / 20.0) - 1.0)
+    return float(np.maximum(np.abs(a_got - a_ref) - allow, 0.0)[quiet].max() / a_ref.max())

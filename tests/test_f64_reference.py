@@ -70,3 +70,87 @@ def test_channel_weights():
     assert list(R.channel_weights(4)) == [1.0, 1.0, 1.41, 1.41]
     assert list(R.channel_weights(5)) == [1.0, 1.0, 1.0, 1.41, 1.41]
     assert list(R.channel_weights(8)) == [1.0, 1.0, 1.0, 0.0, 1.41, 1.41, 0.0, 0.0]
+
+
+# ---- the spectrum yardstick of tests/test_gpu_spectrum_forms.py
+
+@pytest.mark.parametrize("rate", [40000, 40960, 44100, 48000, 50000, 96000, 192000, 384000])
+def test_retained_bins_equal_the_product(rate):
+    """The bin rule for N = 2 ... 32768: 40 kHz keeps its Nyquist bin, 40960 Hz puts 20 Hz and 20 kHz exactly on bins 2 and 2000
+    (a rate with no bins at some N included)."""
+    import ctypes as C
+    from soundscope_amd import _lib as L
+    n = 2
+    while n <= 32768:
+        fb, nb = C.c_uint32(), C.c_uint32()
+        assert L.lib().ss_inspect_bins(rate, n, C.byref(fb), C.byref(nb)) == 0
+        assert R.retained_bins(rate, n) == (fb.value, nb.value), (rate, n)
+        assert R.pink_db(rate, n).size == nb.value
+        n *= 2
+    if rate == 40000:
+        first, count = R.retained_bins(rate, 4096)
+        assert first + count - 1 == 2048                    # the Nyquist bin
+    if rate == 40960:
+        assert R.retained_bins(rate, 4096) == (2, 1999)
+
+
+@pytest.mark.parametrize("rate,n", [(48000, 4096), (48000, 16384), (40000, 4096), (40000, 4), (44100, 1024), (192000, 32768)])
+def test_spectrum_row_closed_forms(rate, n):
+    """A bin-centred sine of amplitude A reads 20 log10 A + pink in its bin (a cosine on the Nyquist bin, its own mirror, reads
+    20 log10 2A), an all-zero window -150 + pink in every bin.  The Hann weights are rounded to f32 like the crate's: that moves
+    the bin by up to 1.5e-8 dB (measured), so the bar is 5e-8 dB; in f64 weights the rest of the arithmetic is exact to 1e-12."""
+    first, count = R.retained_bins(rate, n)
+    pink = R.pink_db(rate, n)
+    t = np.arange(n)
+    for k in sorted({first, first + count - 1, first + count // 3}):
+        for A in (1.0, 0.25, 1e-3):
+            nyq = 2 * k == n
+            x = A * np.cos(np.pi * t) if nyq else A * np.sin(2 * np.pi * k * t / n + 0.7)
+            row = R.spectrum_row_f64(x, rate, n)
+            want = 20 * np.log10(2 * A if nyq else A) + pink[k - first]
+            assert abs(row[k - first] - want) <= 5e-8, (k, A, row[k - first] - want)
+    assert np.array_equal(R.spectrum_row_f64(np.zeros(n, np.float32), rate, n), -150.0 + pink)
+
+
+def test_mid_side_f32():
+    lr = np.array([[1.0, 3.0], [np.float32(0.1), np.float32(0.2)], [1e-30, -1e-30]], np.float32)
+    m, s = R.mid_side_f32(lr)
+    assert m.dtype == np.float32 and s.dtype == np.float32
+    assert np.array_equal(m, (lr[:, 0] + lr[:, 1]) / np.float32(2)) and np.array_equal(s, (lr[:, 0] - lr[:, 1]) / np.float32(2))
+
+
+def test_row_error_metric():
+    """row_error: relative to the row's own peak amplitude, pink out, the stored value's two ulps allowed."""
+    rate, n = 48000, 4096
+    pink = R.pink_db(rate, n)
+    ref = np.full(pink.size, -100.0) + pink
+    ref[10] = -20.0 + pink[10]
+    got = ref.astype(np.float32).astype(np.float64)
+    assert R.row_error(got, ref, pink) == 0.0                   # storing the row in f32 is not an error
+    got = ref.copy()
+    got[500] = 20 * np.log10(10 ** (-100 / 20) + 1e-6 * 10 ** (-20 / 20)) + pink[500]
+    assert abs(R.row_error(got, ref, pink) - 1e-6) < 1e-9        # one bin off by 1e-6 of the peak
+    got = ref + 20 * np.log10(1 + 1e-5)                          # every bin 1e-5 high: the peak's bin sets it, less its allowance
+    assert 1e-5 - 5e-7 <= R.row_error(got, ref, pink) <= 1e-5
+    assert R.floor_error(got, ref, pink) < 1e-9                  # ... and nothing in the bins 40 dB under it
+    got = ref.copy()
+    got[500] = 20 * np.log10(10 ** (-100 / 20) + 1e-6 * 10 ** (-20 / 20)) + pink[500]
+    assert abs(R.floor_error(got, ref, pink) - 1e-6) < 1e-9
+
+
+def test_oracle_get_fft_against_the_f64_row(oracle):
+    """The oracle's f32 radix-2 get_fft on random windows (noise 0 ... 80 dB under a tone) against the f64 row: within db_close,
+    and its worst row_error is 1.8e-7 of the row's peak (measured; bar 1e-6) — the size of an f32 transform's rounding."""
+    from conftest import db_close
+    rng = np.random.default_rng(7)
+    worst = 0.0
+    for rate in (40000, 44100, 48000, 96000):
+        for n in (1024, 4096, 16384, 32768):
+            for _ in range(3):
+                x = (rng.standard_normal(n) * 10 ** rng.uniform(-4, 0)).astype(np.float32)
+                x += (0.5 * np.sin(2 * np.pi * rng.uniform(20, 19000) * np.arange(n) / rate)).astype(np.float32)
+                got = oracle.get_fft(rate, x)[:, 1]
+                ref = R.spectrum_row_f64(x, rate, n)
+                assert db_close(got, ref, 0.01), (rate, n)
+                worst = max(worst, R.row_error(got, ref, R.pink_db(rate, n)))
+    assert worst <= 1e-6, worst

@@ -13,21 +13,9 @@ from scipy import signal
 import soundscope_amd as ssa
 from soundscope_amd import _lib as L
 from conftest import db_close, db_report, make_stereo
-from _f64ref import interpolator_taps, waveform_numpy
+from _f64ref import interpolator_taps, spectrum_f64, waveform_numpy
 
 pytestmark = pytest.mark.gpu
-
-
-def spectrum_f64(x, rate, n):
-    """One window of the reference's get_fft restated with numpy in f64 (window values rounded to f32 as the crate's)."""
-    i = np.arange(n, dtype=np.float64)
-    w = (0.5 * (1.0 - np.cos(2.0 * np.pi * i / n))).astype(np.float32).astype(np.float64)
-    mag = np.abs(np.fft.rfft(x.astype(np.float64) * w))
-    freq32 = np.arange(n // 2 + 1, dtype=np.float32) * (np.float32(rate) / np.float32(n))
-    keep = (freq32 >= 20.0) & (freq32 <= 20000.0)
-    with np.errstate(divide="ignore"):
-        db = np.where(mag[keep] == 0.0, -150.0, 20.0 * np.log10(mag[keep] * 4.0 / n))
-    return db + 10.0 * np.log10(freq32[keep].astype(np.float64) / 1000.0)
 
 
 @pytest.mark.parametrize("rate,n,hop", [(48000, 4096, 1024), (44100, 4096, 1024), (48000, 16384, 1024), (96000, 16384, 1024)])

@@ -13,7 +13,7 @@ from soundscope_amd import _lib as L
 from oracle import pyoracle as po
 from conftest import db_close, db_report, make_multich, window_peak_db
 
-RATES = [8000, 22050, 32000, 44100, 48000, 48000, 48000, 88200, 96000, 96000, 192000]
+RATES = [8000, 22050, 32000, 40000, 44100, 48000, 48000, 48000, 50000, 88200, 96000, 96000, 192000]   # 40 kHz: the Nyquist bin; 50 kHz: NE_LAST 1
 CHANNELS = [1, 2, 2, 2, 2, 3, 6, 8, 8]
 STREAMS = [1, 1, 2, 3, 7, 20, 64, 65, 130]
 
