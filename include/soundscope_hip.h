@@ -433,6 +433,7 @@ double ss_corpus_loudness_range(const uint64_t *st_hist1000);
  *  of a bank behaves exactly like an ss_analyzer fed the same blocks (true peak in SS_TP_ARITH_F32, the handle's default); a
  *  call costs a time-domain launch and a gating launch for ALL streams (calls longer than 32 sub-blocks are cut into pieces,
  *  as ss_add_samples cuts them), a read one launch and one copy.  A non-finite sample poisons its own stream only.
+ *  The streams need not move together: the _ragged calls give every stream its own frame count per call, none included.
  *  Device memory per stream, laid out as a handle holds its meter: the filter state (9.3 KB), a 96-slot sub-block ring, the
  *  filtered-sample ring of 3 s (rounded up to a whole 100 ms sub-block) x channels f64, two 1000-bin u64 histograms:
  *  about 2.33 MB at 48 kHz stereo — 2.4 GB for 1024 streams.
@@ -459,6 +460,23 @@ int ss_meter_bank_add(ss_meter_bank *m, const float *pcm, uint64_t frames);
 int ss_meter_bank_add_device(ss_meter_bank *m, const float *pcm_device, uint64_t frames, uint64_t stream_stride_floats);
 /* raw little-endian interleaved PCM of an ss_pcm_format, [stream][frame][channel], converted on the device */
 int ss_meter_bank_add_pcm(ss_meter_bank *m, const void *pcm, uint64_t frames, int format);
+/* Ragged adds: stream s gets frames[s] frames — inputs that arrive in packets of different sizes, pause, start, stop or drift
+ * against each other.  `frames` is a host array of n_streams entries, copied before the call returns.  Afterwards stream s is in
+ * the state an ss_analyzer of the bank's shape is in after one ss_add_samples of those frames[s] frames (the bank's contract, per
+ * stream); a stream with frames[s] == 0 is not touched at all — its readings, histograms, peaks and spectrum history stay byte
+ * for byte — and an all-zero call is a no-op.  A call launches the time domain at most twice per piece of 32 sub-blocks (the
+ * streams that take up to one tile of the kernel, and the longer ones: each runs the form a handle runs for that length) and the
+ * gating once where some stream completes a sub-block.
+ * Checked before anything is advanced or copied: frames == NULL, pcm[s] == NULL where frames[s] > 0, an unknown format, a stride
+ * below max(frames) * channels SS_ERR_INVALID_ARG; more than 2^40 samples in one stream or in all SS_ERR_NOMEM (ss_batch_create's rule).
+ * stream s's frames are pcm[s], interleaved f32 (pcm[s] may be NULL where frames[s] == 0); the inputs are staged tightly packed
+ * and copied, with the lengths, in one transfer before the call returns */
+int ss_meter_bank_add_ragged(ss_meter_bank *m, const float *const *pcm, const uint64_t *frames);
+/* the same for raw little-endian PCM of an ss_pcm_format, converted on the device */
+int ss_meter_bank_add_ragged_pcm(ss_meter_bank *m, const void *const *pcm, const uint64_t *frames, int format);
+/* producers on the GPU: stream s's frames[s] frames start at pcm_device + s * stream_stride_floats (stride >= max(frames) *
+ * channels); only queued, as ss_meter_bank_add_device */
+int ss_meter_bank_add_ragged_device(ss_meter_bank *m, const float *pcm_device, const uint64_t *frames, uint64_t stream_stride_floats);
 /* resets the listed streams (streams == NULL: all of them), as EbuR128::reset; the others are untouched */
 int ss_meter_bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count);
 /* one record per stream for the state after the last add; waits; one device-to-host copy */
@@ -472,8 +490,9 @@ int ss_meter_bank_histograms(ss_meter_bank *m, uint32_t stream, uint64_t *out200
  * (the reference's microphone tick, tui.rs:1427-1445), one row per channel otherwise (as ss_batch does; the reference's mono
  * device is a stereo bank fed a zero right channel, audio_capture.rs).  One launch transforms every row of every stream.
  *  - The history is the raw input, not the meter: ss_meter_bank_reset leaves it alone (so does the reference's
- *    analyzer.reset()), and a non-finite sample refuses a row only while it lies inside that row's window.  Every stream gets
- *    the same frames per call, so one bank-wide frame counter places the window; a call longer than the window keeps its newest
+ *    analyzer.reset()), and a non-finite sample refuses a row only while it lies inside that row's window.  Every stream has
+ *    its own frame counter, which places its window: [fed_s - 16384, fed_s) for what stream s itself was given, by uniform and
+ *    ragged adds alike (a stream given nothing keeps its window); a call longer than the window keeps its newest
  *    SS_BANK_SPECTRUM_N frames.  The window starts full of zeros, as the reference's capture ring does (tui.rs:1783-1784).
  *  - Refusals follow the crate's order on the windowed signal (for stereo the f32 mid / side values): a windowed NaN (an
  *    infinite sample under a zero window weight included; +inf in L with -inf in R is a NaN mid) SS_ERR_NAN, else a windowed

@@ -45,6 +45,7 @@ SYMBOLS = [
     "ss_inspect_kweight", "ss_inspect_true_peak", "ss_inspect_true_peak_fold", "ss_inspect_hann", "ss_inspect_bins", "ss_inspect_histogram",
     "ss_batch_download_loudness_series", "ss_batch_loudness_extremes",
     "ss_meter_bank_create", "ss_meter_bank_destroy", "ss_meter_bank_add", "ss_meter_bank_add_device", "ss_meter_bank_add_pcm",
+    "ss_meter_bank_add_ragged", "ss_meter_bank_add_ragged_pcm", "ss_meter_bank_add_ragged_device",
     "ss_meter_bank_reset", "ss_meter_bank_read", "ss_meter_bank_peaks", "ss_meter_bank_histograms",
     "ss_meter_bank_spectrum_enable", "ss_meter_bank_spectrum_layout", "ss_meter_bank_spectrum", "ss_meter_bank_spectrum_columns",
 ]
@@ -250,6 +251,9 @@ def _bind(lib):
         "ss_meter_bank_add": (C.c_int, [vp, f32p, C.c_uint64]),
         "ss_meter_bank_add_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64]),
         "ss_meter_bank_add_pcm": (C.c_int, [vp, vp, C.c_uint64, C.c_int]),
+        "ss_meter_bank_add_ragged": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+        "ss_meter_bank_add_ragged_pcm": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_int]),
+        "ss_meter_bank_add_ragged_device": (C.c_int, [vp, vp, C.POINTER(C.c_uint64), C.c_uint64]),
         "ss_meter_bank_reset": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_meter_bank_read": (C.c_int, [vp, vp, C.c_uint32]),
         "ss_meter_bank_peaks": (C.c_int, [vp, C.c_uint32, f64p, f64p, C.c_uint32]),

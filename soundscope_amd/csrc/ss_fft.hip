@@ -1688,16 +1688,18 @@ struct BankWindow {
     uint32_t *wave_flags;            // [8]: each wave's non-finite flags
     uint32_t stream, sig;                 // sig: the row's signal (mid / side, or a channel)
     const float *ring = nullptr;
+    uint32_t start = 0;              // slot of the stream's own window start
     uint32_t nf = 0;                 // bit 0: a windowed NaN, bit 1: a windowed infinity
     uint32_t bad = 0;                // a non-finite dB value
     __device__ __forceinline__ bool begin()
     {
         ring = q.hist + (size_t)stream * kBankSpecN * q.channels;
+        start = q.start + (q.ahead ? (uint32_t)q.ahead[stream] : 0u);      // (masked where it is used; the low bits are all that counts)
         return true;
     }
     __device__ __forceinline__ v2f load(uint32_t i)
     {
-        const uint32_t f0 = (q.start + 2u * i) & kBankSpecMask, f1 = (q.start + 2u * i + 1u) & kBankSpecMask;
+        const uint32_t f0 = (start + 2u * i) & kBankSpecMask, f1 = (start + 2u * i + 1u) & kBankSpecMask;
         float x0, x1;
         if (q.channels == 2) {                                             // mid / side (audio_player.rs:400-419)
             const float2 va = reinterpret_cast<const float2 *>(ring)[f0], vb = reinterpret_cast<const float2 *>(ring)[f1];
@@ -1778,21 +1780,23 @@ hipError_t launch_meter_bank_spectrum(const BankSpectrumParams &p, bool columns,
 
 // the newest min(frames, 16384) frames of every stream's input into its history ring
 __global__ __launch_bounds__(256) void k_bank_history_append(float *hist, const float *pcm, uint64_t stride, uint64_t first_frame,
-                                                             uint32_t take, uint32_t slot0, uint32_t n_streams, uint32_t channels)
+                                                             uint32_t take, uint32_t slot0, const uint64_t *ahead, uint32_t n_streams,
+                                                             uint32_t channels)
 {
     const uint32_t per = take * channels;
     for (uint32_t s = blockIdx.y; s < n_streams; s += gridDim.y) {
         const float *src = pcm + (size_t)s * stride + first_frame * channels;
         float *dst = hist + (size_t)s * kBankSpecN * channels;
+        const uint32_t slot = slot0 + (ahead ? (uint32_t)ahead[s] : 0u);
         for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < per; e += gridDim.x * 256u) {
             const uint32_t f = e / channels, c = e - f * channels;
-            dst[(size_t)((slot0 + f) & kBankSpecMask) * channels + c] = src[e];
+            dst[(size_t)((slot + f) & kBankSpecMask) * channels + c] = src[e];
         }
     }
 }
 
 hipError_t launch_bank_history_append(float *hist, const float *pcm, uint64_t stride, uint64_t frames, uint64_t fed,
-                                      uint32_t n_streams, uint32_t channels, hipStream_t s)
+                                      const uint64_t *ahead, uint32_t n_streams, uint32_t channels, hipStream_t s)
 {
     if (!frames || !n_streams) return hipSuccess;
     const uint32_t take = frames < kBankSpecN ? (uint32_t)frames : kBankSpecN;
@@ -1801,7 +1805,43 @@ hipError_t launch_bank_history_append(float *hist, const float *pcm, uint64_t st
     const uint32_t per = take * channels;
     const uint32_t gx = (per + 255u) / 256u;
     const dim3 grid(gx < 64u ? gx : 64u, n_streams < 65535u ? n_streams : 65535u);
-    hipLaunchKernelGGL(k_bank_history_append, grid, dim3(256), 0, s, hist, pcm, stride, first, take, slot0, n_streams, channels);
+    hipLaunchKernelGGL(k_bank_history_append, grid, dim3(256), 0, s, hist, pcm, stride, first, take, slot0, ahead, n_streams, channels);
+    return hipGetLastError();
+}
+
+// The same for a ragged add: every stream its own length, input base and counter.  ONE workgroup per stream, because the counter
+// moves here: all threads read ahead[s] in front of the barrier, thread 0 writes ahead[s] + frames behind it.  A stream without
+// frames leaves before it touches its ring or its counter.
+__global__ __launch_bounds__(256) void k_bank_history_append_ragged(float *hist, const float *pcm, uint64_t stride, const uint64_t *offset_of,
+                                                                    const uint64_t *frames_of, uint64_t fed, uint64_t *ahead,
+                                                                    uint32_t n_streams, uint32_t channels)
+{
+    for (uint32_t s = blockIdx.x; s < n_streams; s += gridDim.x) {
+        const uint64_t frames = frames_of[s];
+        if (frames == 0) continue;                                         // (uniform over the workgroup)
+        const uint64_t before = ahead[s];
+        __syncthreads();
+        if (threadIdx.x == 0) ahead[s] = before + frames;
+        const uint32_t take = frames < kBankSpecN ? (uint32_t)frames : kBankSpecN;
+        const uint64_t first = frames - take;
+        const float *src = pcm + (offset_of ? offset_of[s] : (uint64_t)s * stride) + first * channels;
+        float *dst = hist + (size_t)s * kBankSpecN * channels;
+        const uint32_t slot = (uint32_t)(fed + before + first);
+        const uint32_t per = take * channels;
+        for (uint32_t e = threadIdx.x; e < per; e += 256u) {
+            const uint32_t f = e / channels, c = e - f * channels;
+            dst[(size_t)((slot + f) & kBankSpecMask) * channels + c] = src[e];
+        }
+    }
+}
+
+hipError_t launch_bank_history_append_ragged(float *hist, const float *pcm, uint64_t stride, const uint64_t *offset_of,
+                                             const uint64_t *frames_of, uint64_t fed, uint64_t *ahead, uint32_t n_streams,
+                                             uint32_t channels, hipStream_t s)
+{
+    if (!n_streams) return hipSuccess;
+    hipLaunchKernelGGL(k_bank_history_append_ragged, dim3(n_streams < 65535u ? n_streams : 65535u), dim3(256), 0, s, hist, pcm, stride,
+                       offset_of, frames_of, fed, ahead, n_streams, channels);
     return hipGetLastError();
 }
 

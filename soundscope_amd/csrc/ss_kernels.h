@@ -169,11 +169,19 @@ struct TdParams {
     uint32_t seg_sub;            // sub-blocks per segment (nseg > 1)
     uint32_t warm_sub;           // run-in sub-blocks of segments > 0
     // fused min-max decimation (batch only; nullptr = off): out[stream][bin] = (min, max)
-    float *wave_out;
+    union {                      // (one slot: decimation is a batch feature, per-stream bases one of the streaming launches — never both)
+        float *wave_out;
+        // streaming launches on the ring (meter banks' ragged adds): stream s's input starts at pcm + offset_of[s] floats instead of
+        // pcm + s * stream_stride (nullable: the stride).  Read by the RING instantiations only.
+        const uint64_t *offset_of;
+    };
     uint64_t wave_stride;        // floats between streams
     uint32_t wave_window;        // number of decimation bins W
     uint32_t halo_frames;        // frames kept in front of each tile: >= longest bin, multiple of 4
-    const uint64_t *frames_of;    // ragged batches: frames of each stream (nullable = n_frames for all)
+    const uint64_t *frames_of;    // ragged batches: frames of each stream (nullable = n_frames for all).  Streaming launches on the
+                                  // ring (meter banks' ragged adds) take it too: a stream of 0 frames is not touched at all, and
+                                  // every other entry lies on n_frames' side of td_ring_tile_frames — the launch form is chosen from
+                                  // n_frames, so the caller launches the short and the long streams of a call as two groups
     uint32_t tp_f32;              // 1: the factor-4 true peak as the f32 MFMA product everywhere (no f16 split)
     // Exact segment hand-over (batches, nseg > 1, warm_sub == 0): every segment's wave leaves the filter state behind its last frame in
     // seg_state[stream][segment][channel][4]; a second, light launch (fixup = 1: no true peak, no decimation) then re-runs the first
@@ -205,6 +213,9 @@ uint32_t td_chunk_frames(uint32_t channels, uint32_t s100);
 // the same for a streaming call whose tiles are shared by the waves of one workgroup (SPLIT): see ss_time_domain.hip
 uint32_t td_split_chunk_frames(uint32_t channels, uint32_t s100);
 uint32_t td_resident_waves_per_cu(uint32_t channels, uint32_t s100, uint32_t halo_frames);
+// the longest streaming call (frames) that one wave walks; a longer one is shared by the eight waves of a workgroup (SPLIT), with
+// another chunk length and hence other rounding — the one rule for handles, ticks and every stream of a meter bank
+uint32_t td_ring_tile_frames(uint32_t channels, uint32_t s100);
 
 struct FinalizeParams {
     const TdConst *k;
@@ -276,9 +287,10 @@ struct MeterReading {
     double true_peak[2], sample_peak[2];
     uint64_t frames;
 };
-// gating behind a time-domain launch of `frames` frames per stream: stream s's new sub-blocks are
-// [(fed - frames) / S, fed / S), fed = state[s].frames_fed (the streams' phases differ after a selective reset)
-hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, hipStream_t s);
+// gating behind a time-domain launch of `frames` frames per stream (frames_of, device memory, nullable: frames_of[s] for stream s
+// instead): stream s's new sub-blocks are [(fed - frames) / S, fed / S), fed = state[s].frames_fed (the streams' phases differ
+// after a selective reset or a ragged add)
+hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, const uint64_t *frames_of, hipStream_t s);
 // every stream's readings into out[stream] (device or mapped host memory)
 hipError_t launch_meter_bank_readings(const MeterBankParams &p, MeterReading *out, hipStream_t s);
 // clears the listed streams' meters (streams == nullptr: streams 0 .. count - 1)
@@ -289,7 +301,9 @@ constexpr uint32_t kBankSpecN = 16384;
 struct BankSpectrumParams {
     FftBatchParams f;                // the transform's tables, first_bin / n_bins / db_offset (pink = nullptr, out unused)
     const float *hist;               // [stream][kBankSpecN][channels] f32 ring, frame j at slot j & (kBankSpecN - 1)
-    uint32_t start;                  // slot of the window's first frame (fed - kBankSpecN, masked)
+    uint32_t start;                  // slot of the window's first frame (fed - kBankSpecN, masked), fed the bank-wide frame counter
+    const uint64_t *ahead;           // [stream], nullable: frames stream s has had beyond the bank-wide counter (ragged adds) — its
+                                     // window starts at slot (start + ahead[s]) masked
     uint32_t n_streams, channels, rows;   // rows per stream: 2 (mid, side) for stereo, otherwise channels
     int32_t *status;                 // [stream][row]
     float *out;                      // rows: [stream][row][n_bins]; columns: [stream][row][cols]
@@ -302,9 +316,15 @@ struct BankSpectrumParams {
     uint32_t cols;                   // 1 .. 512
     float gain_db;
 };
-// frames [frames - take, frames) of every stream's input (stream s at pcm + s * stride) into the ring at slots (fed + f) & mask
+// frames [frames - take, frames) of every stream's input (stream s at pcm + s * stride) into the ring at slots (fed + f) & mask;
+// ahead (nullable): stream s's own counter is fed + ahead[s]
 hipError_t launch_bank_history_append(float *hist, const float *pcm, uint64_t stride, uint64_t frames, uint64_t fed,
-                                      uint32_t n_streams, uint32_t channels, hipStream_t s);
+                                      const uint64_t *ahead, uint32_t n_streams, uint32_t channels, hipStream_t s);
+// ragged adds: stream s's newest min(frames_of[s], 16384) frames (its input at pcm + offset_of[s], or pcm + s * stride where
+// offset_of is null) behind its own counter fed + ahead[s], and ahead[s] += frames_of[s]; a stream of 0 frames is left alone
+hipError_t launch_bank_history_append_ragged(float *hist, const float *pcm, uint64_t stride, const uint64_t *offset_of,
+                                             const uint64_t *frames_of, uint64_t fed, uint64_t *ahead, uint32_t n_streams,
+                                             uint32_t channels, hipStream_t s);
 hipError_t launch_meter_bank_spectrum(const BankSpectrumParams &p, bool columns, hipStream_t s);
 
 // ---- waveform ---------------------------------------------------------------

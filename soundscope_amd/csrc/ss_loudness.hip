@@ -603,9 +603,12 @@ hipError_t launch_ring_energy(const double *ring, uint64_t ring_frames, uint32_t
 // Gating of every stream's new sub-blocks behind a bank's time-domain launch: one wave per stream, k_finalize_stream's gating
 // (the same window form, hence a handle's histograms bit for bit) over the stream's own range, derived from its frame count.
 // Streams that completed no sub-block leave at once.  The tables are read where they are (L2): a wave has a few blocks to gate.
-__global__ __launch_bounds__(64) void k_meter_bank_gate(MeterBankParams p, uint64_t frames)
+// frames_of (ragged adds): what the launch gave each stream; a stream that got nothing leaves before it reads its state.
+__global__ __launch_bounds__(64) void k_meter_bank_gate(MeterBankParams p, uint64_t frames_all, const uint64_t *frames_of)
 {
     const uint32_t stream = blockIdx.x, lane = threadIdx.x;
+    const uint64_t frames = frames_of ? frames_of[stream] : frames_all;
+    if (frames == 0) return;
     const TdState *st = p.state + stream;
     const uint64_t S = p.k->s100;
     const uint64_t fed = st->frames_fed;
@@ -617,10 +620,10 @@ __global__ __launch_bounds__(64) void k_meter_bank_gate(MeterBankParams p, uint6
                       p.hist_bounds[0], sb0, sb1, bad_from, gh, p.counts + 2 * (size_t)stream, lane);
 }
 
-hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, hipStream_t s)
+hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, const uint64_t *frames_of, hipStream_t s)
 {
-    if (p.n_streams == 0 || frames == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_meter_bank_gate, dim3(p.n_streams), dim3(64), 0, s, p, frames);
+    if (p.n_streams == 0 || (frames == 0 && !frames_of)) return hipSuccess;
+    hipLaunchKernelGGL(k_meter_bank_gate, dim3(p.n_streams), dim3(64), 0, s, p, frames, frames_of);
     return hipGetLastError();
 }
 

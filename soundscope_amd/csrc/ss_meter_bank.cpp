@@ -22,9 +22,13 @@ struct ss_meter_bank {
     hipEvent_t pin_ev = nullptr;
     bool pin_busy = false;
     ssk::MeterReading *pin_read = nullptr;
-    // spectra (ss_meter_bank_spectrum_enable): the newest 16384 input frames of every stream, bank-wide frame counter
+    ssh::DevBuf<unsigned char> rag;        // a ragged add's staging: the per-stream arrays, then (host forms) the packed input
+    // spectra (ss_meter_bank_spectrum_enable): the newest 16384 input frames of every stream.  Stream s's frame counter is
+    // spec_fed + spec_ahead[s]: what the uniform adds gave everyone, kept here, plus what ragged adds gave that stream, kept on the
+    // device (allocated by the first ragged add) — a spectrum call uploads nothing and a uniform add stays as it was
     bool spec_on = false;
     uint64_t spec_fed = 0;
+    ssh::DevBuf<uint64_t> spec_ahead;      // [n]
     BinTables *bt = nullptr;
     FftTables *ft = nullptr;
     ssh::DevBuf<float> spec_hist;          // [n][16384][C]
@@ -75,7 +79,7 @@ int advance(ss_meter_bank *m, const float *pcm, uint64_t frames, uint64_t stride
     const MeterStore &ms = m->meter;
     const uint32_t C = ms.channels;
     if (m->spec_on) {
-        HIPCHK(ssk::launch_bank_history_append(m->spec_hist.p, pcm, stride, frames, m->spec_fed, ms.n, C, m->stream));
+        HIPCHK(ssk::launch_bank_history_append(m->spec_hist.p, pcm, stride, frames, m->spec_fed, m->spec_ahead.p, ms.n, C, m->stream));
         m->spec_fed += frames;
     }
     const uint64_t S = ms.s100, piece_frames = 32 * S;
@@ -91,10 +95,138 @@ int advance(ss_meter_bank *m, const float *pcm, uint64_t frames, uint64_t stride
             any = any || (m->fed[s] + take) / S > m->fed[s] / S;
             m->fed[s] += take;
         }
-        if (any) HIPCHK(ssk::launch_meter_bank_gate(q, take, m->stream));
+        if (any) HIPCHK(ssk::launch_meter_bank_gate(q, take, nullptr, m->stream));
         done += take;
     }
     return SS_OK;
+}
+
+// ---- ragged adds: every stream its own frame count --------------------------------------------------------------------------------
+// What a ragged call stages, in ONE page-locked copy: arrays of n u64 each, then (host forms) the streams' input, tightly packed.
+//   [0] frames of the whole call (the history ring), [1] where each stream's input starts (floats; samples for raw PCM),
+//   then per piece of 32 sub-blocks: what each stream takes in it (the gating launch), and — only where the piece has streams on
+//   both sides of the form switch — that array once more with the long streams zeroed and once with the short ones zeroed.
+struct RaggedPlan {
+    struct Piece { size_t take, lo, hi; uint64_t max_short, max_long; bool gate; };   // array indices (lo == hi == take: one group)
+    std::vector<uint64_t> arrays;          // n entries each
+    std::vector<Piece> pieces;
+    uint64_t total = 0;                    // samples of packed input, every stream's start a multiple of four
+};
+
+// the checks every ragged form shares, then the plan; SS_OK with an empty plan: nothing to do
+int ragged_plan(const ss_meter_bank *m, const uint64_t *frames, bool pack, RaggedPlan *pl, uint64_t *max_frames)
+{
+    const MeterStore &ms = m->meter;
+    const uint32_t n = ms.n, C = ms.channels;
+    uint64_t total = 0, longest = 0;
+    for (uint32_t s = 0; s < n; s++) {                                   // ss_batch_create's rule: more than 2^40 samples is no buffer
+        if (frames[s] > (1ull << 40) || frames[s] * C > (1ull << 40) || (total += (frames[s] * C + 3u) & ~3ull) > (1ull << 40)) return SS_ERR_NOMEM;
+        if (frames[s] > longest) longest = frames[s];
+    }
+    *max_frames = longest;
+    if (!longest) return SS_OK;
+    const uint64_t S = ms.s100, piece_frames = 32 * S, tile = ssk::td_ring_tile_frames(C, (uint32_t)S);
+    const size_t n_pieces = (size_t)((longest + piece_frames - 1) / piece_frames);
+    pl->arrays.assign((2 + n_pieces) * (size_t)n, 0);
+    pl->total = pack ? total : 0;
+    uint64_t at = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        pl->arrays[s] = frames[s];
+        pl->arrays[n + s] = at;
+        if (pack) at += (frames[s] * C + 3u) & ~3ull;
+    }
+    for (size_t k = 0; k < n_pieces; k++) {
+        RaggedPlan::Piece pc{(2 + k) * (size_t)n, 0, 0, 0, 0, false};
+        for (uint32_t s = 0; s < n; s++) {
+            const uint64_t done = k * piece_frames < frames[s] ? k * piece_frames : frames[s], left = frames[s] - done;
+            const uint64_t take = left < piece_frames ? left : piece_frames;
+            pl->arrays[pc.take + s] = take;
+            if (take > tile) { if (take > pc.max_long) pc.max_long = take; }
+            else if (take > pc.max_short) pc.max_short = take;
+            const uint64_t fed = m->fed[s] + done;
+            pc.gate = pc.gate || (fed + take) / S > fed / S;
+        }
+        pc.lo = pc.hi = pc.take;
+        if (pc.max_short && pc.max_long) {                               // both forms in one piece: two launches, each with its own lengths
+            pc.lo = pl->arrays.size(); pc.hi = pc.lo + n;
+            pl->arrays.resize(pl->arrays.size() + 2 * (size_t)n, 0);
+            for (uint32_t s = 0; s < n; s++) {
+                const uint64_t take = pl->arrays[pc.take + s];
+                pl->arrays[(take > tile ? pc.hi : pc.lo) + s] = take;
+            }
+        }
+        pl->pieces.push_back(pc);
+    }
+    return SS_OK;
+}
+
+// the launches of a ragged call behind its staging: `arr` the plan's arrays on the device, stream s's input at pcm + offset_of[s]
+// (offset_of null: pcm + s * stride)
+int advance_ragged(ss_meter_bank *m, const RaggedPlan &pl, const uint64_t *frames, const uint64_t *arr, const float *pcm,
+                   const uint64_t *offset_of, uint64_t stride)
+{
+    const MeterStore &ms = m->meter;
+    const uint32_t n = ms.n, C = ms.channels;
+    if (m->spec_on) {
+        if (!m->spec_ahead.p) {
+            HIPCHK(m->spec_ahead.alloc(n));
+            HIPCHK(hipMemsetAsync(m->spec_ahead.p, 0, n * sizeof(uint64_t), m->stream));
+        }
+        HIPCHK(ssk::launch_bank_history_append_ragged(m->spec_hist.p, pcm, stride, offset_of, arr, m->spec_fed, m->spec_ahead.p, n, C, m->stream));
+    }
+    const uint64_t piece_frames = 32 * ms.s100;
+    const ssk::MeterBankParams q = ms.bank_params();
+    for (size_t k = 0; k < pl.pieces.size(); k++) {
+        const RaggedPlan::Piece &pc = pl.pieces[k];
+        // a stream runs the form a handle runs for a call of its length: one wave up to a tile, the eight-wave workgroup beyond
+        for (int g = 0; g < 2; g++) {
+            const uint64_t longest = g ? pc.max_long : pc.max_short;
+            if (!longest) continue;
+            ssk::TdParams p = ms.td_params(pcm + k * piece_frames * C, stride, longest);
+            p.frames_of = arr + (g ? pc.hi : pc.lo);
+            p.offset_of = offset_of;
+            p.tp_f32 = 1u;                                               // SS_TP_ARITH_F32, the handle's default
+            HIPCHK(ssk::launch_time_domain(p, m->stream));
+        }
+        if (pc.gate) HIPCHK(ssk::launch_meter_bank_gate(q, 0, arr + pc.take, m->stream));
+    }
+    for (uint32_t s = 0; s < n; s++) m->fed[s] += frames[s];
+    return SS_OK;
+}
+
+// host forms: arrays and packed input (sb bytes per sample; 4: f32, used where it lands) through one page-locked copy
+int add_ragged_host(ss_meter_bank *m, const void *const *pcm, const uint64_t *frames, int format, size_t sb)
+{
+    if (!frames) return SS_ERR_INVALID_ARG;
+    const uint32_t n = m->meter.n, C = m->meter.channels;
+    for (uint32_t s = 0; s < n; s++) if (frames[s] && (!pcm || !pcm[s])) return SS_ERR_INVALID_ARG;
+    RaggedPlan pl;
+    uint64_t longest = 0;
+    int rc = ragged_plan(m, frames, true, &pl, &longest);
+    if (rc || !longest) return rc;
+    const size_t head = (pl.arrays.size() * sizeof(uint64_t) + 15u) & ~(size_t)15u, body = (size_t)pl.total * sb;
+    HIPCHK(m->rag.ensure(head + body + 8));                          // (+8: the converter's wide reads of 24-bit samples)
+    if (format) HIPCHK(m->in.ensure(pl.total));
+    rc = pin_take(m, head + body);
+    if (rc) return rc;
+    char *pin = static_cast<char *>(m->pin);
+    std::memcpy(pin, pl.arrays.data(), pl.arrays.size() * sizeof(uint64_t));
+    for (uint32_t s = 0; s < n; s++) {
+        const size_t bytes = (size_t)frames[s] * C * sb, padded = (size_t)((frames[s] * C + 3u) & ~3ull) * sb;
+        char *dst = pin + head + (size_t)pl.arrays[n + s] * sb;
+        if (bytes) std::memcpy(dst, pcm[s], bytes);
+        std::memset(dst + bytes, 0, padded - bytes);
+    }
+    HIPCHK(hipMemcpyAsync(m->rag.p, pin, head + body, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipEventRecord(m->pin_ev, m->stream));
+    m->pin_busy = true;
+    const uint64_t *arr = reinterpret_cast<const uint64_t *>(m->rag.p);
+    const float *in = reinterpret_cast<const float *>(m->rag.p + head);
+    if (format) {
+        HIPCHK(ssk::launch_pcm_to_f32(m->rag.p + head, pl.total, format, m->in.p, m->stream));
+        in = m->in.p;
+    }
+    return advance_ragged(m, pl, frames, arr, in, arr + n, 0);
 }
 
 int bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
@@ -134,6 +266,7 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
     q.f = one_window_fft(ssk::plan_spectrum(SS_BANK_SPECTRUM_N, m->meter.channels, kOneWindowHop, 1, 1), *m->ft, *m->bt);
     q.hist = m->spec_hist.p;
     q.start = (uint32_t)((m->spec_fed - SS_BANK_SPECTRUM_N) & (SS_BANK_SPECTRUM_N - 1));
+    q.ahead = m->spec_ahead.p;
     q.n_streams = m->meter.n; q.channels = m->meter.channels; q.rows = R;
     q.status = m->spec_status.p; q.out = m->spec_out.p;
     if (columns) {
@@ -249,6 +382,39 @@ int ss_meter_bank_add_pcm(ss_meter_bank *m, const void *pcm, uint64_t frames, in
     return advance(m, m->in.p, frames, per);
 }
 
+int ss_meter_bank_add_ragged(ss_meter_bank *m, const float *const *pcm, const uint64_t *frames)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    return add_ragged_host(m, reinterpret_cast<const void *const *>(pcm), frames, 0, sizeof(float));
+}
+
+int ss_meter_bank_add_ragged_pcm(ss_meter_bank *m, const void *const *pcm, const uint64_t *frames, int format)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    const size_t sb = ss_pcm_sample_bytes(format);
+    if (!sb) return SS_ERR_INVALID_ARG;
+    return add_ragged_host(m, pcm, frames, format, sb);
+}
+
+int ss_meter_bank_add_ragged_device(ss_meter_bank *m, const float *pcm_device, const uint64_t *frames, uint64_t stream_stride_floats)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!frames) return SS_ERR_INVALID_ARG;
+    RaggedPlan pl;
+    uint64_t longest = 0;
+    int rc = ragged_plan(m, frames, false, &pl, &longest);
+    if (rc || !longest) return rc;
+    if (!pcm_device || stream_stride_floats < longest * m->meter.channels) return SS_ERR_INVALID_ARG;
+    const size_t bytes = pl.arrays.size() * sizeof(uint64_t);
+    HIPCHK(m->rag.ensure(bytes));
+    rc = upload(m, m->rag.p, pl.arrays.data(), bytes);
+    if (rc) return rc;
+    return advance_ragged(m, pl, frames, reinterpret_cast<const uint64_t *>(m->rag.p), pcm_device, nullptr, stream_stride_floats);
+}
+
 int ss_meter_bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
 {
     SS_ON_DEVICE(m);
@@ -325,6 +491,7 @@ int ss_meter_bank_spectrum_enable(ss_meter_bank *m, int enable)
     HIPCHK(hipMemsetAsync(m->spec_hist.p, 0, floats * sizeof(float), m->stream));  // (re-enabling starts again from zeros)
     HIPCHK(m->spec_status.ensure((size_t)m->meter.n * spec_rows(m)));
     m->spec_fed = 0;
+    if (m->spec_ahead.p) HIPCHK(hipMemsetAsync(m->spec_ahead.p, 0, m->meter.n * sizeof(uint64_t), m->stream));
     m->spec_on = true;
     return SS_OK;
 }

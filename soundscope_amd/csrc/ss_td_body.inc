@@ -51,7 +51,13 @@
     float *tile = tilebuf + halo_frames * C;            // tile[f*C + c]; tile[-q*C + c] = x[-q]
     unsigned *tpk = reinterpret_cast<unsigned *>(tilebuf + wave_lds_floats - kMaxChannels);   // per-channel peak slots
     TdState &st = p.state[stream];
-    const float *src = p.pcm + (size_t)stream * p.stream_stride;
+    // streaming launches over many streams (meter banks' ragged adds): a stream without frames in this launch is not touched — the
+    // wave (SPLIT: the workgroup, the length is the stream's) leaves in front of its first read of the stream's state — and the
+    // tightly packed input has a base per stream.  RING only: the batch instantiations keep their instructions.
+    if constexpr (RING) { if (p.frames_of && p.frames_of[stream] == 0) return; }
+    const float *src_base = p.pcm + (size_t)stream * p.stream_stride;
+    if constexpr (RING) { if (p.offset_of) src_base = p.pcm + p.offset_of[stream]; }
+    const float *const src = src_base;
 
     // ---- this wave's frame range (relative to the call) and its run-in.
     // Segment boundaries sit on the absolute sub-block grid so every sub-block has one owner.

@@ -877,14 +877,15 @@ static hipError_t td_launch_c(const TdParams &p, hipStream_t s, const FftBatchPa
     }
     // streaming calls (the handle's add_samples, the session ticks) longer than one tile: the eight waves of a workgroup share
     // the call's tiles (SPLIT, see TdShare); the spill-free three-waves-per-SIMD build — a handful of workgroups at most
-    bool split = RING && p.nseg == 1 && !p.frames_of;
+    // (per-stream lengths, frames_of: the caller has grouped the streams by this very rule, n_frames standing for its group)
+    bool split = RING && p.nseg == 1;
 #ifdef SS_TUNING        // development builds only: SS_TD_SPLIT=0 keeps streaming calls on one wave (A/B, drift measurements)
     if (const char *e = std::getenv("SS_TD_SPLIT")) split = split && std::atoi(e) != 0;
 #endif
     if constexpr (RING) if (split) {            // (constexpr: the batch side never instantiates these forms)
         // "longer than one tile" is measured with the BATCH's chunk length, not the split launch's own (td_split_chunk_frames)
         const uint32_t C = p.channels, S = p.s100;
-        const uint32_t batch_tile_len = td_tile(C, S, td_chunk_frames(C, S), kTdHaloFrames, kTdWavesPerBlock, false).tile_len;
+        const uint32_t batch_tile_len = td_ring_tile_frames(C, S);
         if (p.n_frames > batch_tile_len) {
             if (RING && tick_fft && p.n_streams == 1) {                 // a tick: the spectrum's workgroups ride the same launch
                 const hipError_t e = p.channels == 2 ? td_launch_tick<FACTOR, 2>(p, *tick_fft, s, fused)

@@ -100,6 +100,11 @@ uint32_t td_resident_waves_per_cu(uint32_t C, uint32_t s100, uint32_t halo_frame
     return (blocks ? blocks : 1u) * kTdWavesPerBlock;
 }
 
+uint32_t td_ring_tile_frames(uint32_t C, uint32_t s100)
+{
+    return td_tile(C, s100, td_chunk_frames(C, s100), kTdHaloFrames, kTdWavesPerBlock, false).tile_len;
+}
+
 hipError_t launch_time_domain(const TdParams &p, hipStream_t s, const FftBatchParams *tick_fft, bool *tick_fused)
 {
     bool fused_local = false;

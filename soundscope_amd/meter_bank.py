@@ -2,6 +2,7 @@
 
 Stream s of a bank behaves exactly like an `Analyzer` loudness meter fed the same blocks; a call advances every stream with a
 time-domain launch and a gating launch, and `read()` returns every stream's readings behind one launch and one copy.
+The streams need not move together: `add_ragged()` gives every stream its own number of frames per call, none included.
 With `enable_spectrum()` the bank also keeps every stream's newest 16384 input frames, and `spectrum()` /
 `spectrum_columns()` transform all of them (mid and side for stereo banks) in one launch.
 """
@@ -52,6 +53,45 @@ class MeterBank:
         sb = int(L.lib().ss_pcm_sample_bytes(int(fmt))) or 1
         frames = self._frames(b.size, sb)
         _check(L.lib().ss_meter_bank_add_pcm(self._h, b.ctypes.data_as(C.c_void_p), frames, int(fmt)))
+
+    def _ragged(self, blocks, to_bytes, per_sample):
+        """(pointer array, frames array, the arrays kept alive) of one block per stream; None or an empty block: no frames"""
+        if len(blocks) != self.n_streams:
+            raise ValueError(f"{len(blocks)} blocks for {self.n_streams} streams")
+        keep, ptrs, frames = [], (C.c_void_p * self.n_streams)(), (C.c_uint64 * self.n_streams)()
+        for s, blk in enumerate(blocks):
+            if blk is None:
+                continue
+            a = to_bytes(blk)
+            per = self.channels * per_sample
+            if a.size % per:
+                raise ValueError(f"stream {s}: {a.size} values are not whole frames of {self.channels} channels")
+            if a.size:
+                keep.append(a)
+                ptrs[s], frames[s] = a.ctypes.data, a.size // per
+        return ptrs, frames, keep
+
+    def add_ragged(self, blocks):
+        """blocks: one per stream, [frames_s * channels] f32 (any shape with that many values) or None for no frames.  Stream s
+        advances by its own frames_s; a stream given nothing is not touched."""
+        ptrs, frames, keep = self._ragged(blocks, lambda b: np.ascontiguousarray(b, dtype=np.float32).reshape(-1), 1)
+        _check(L.lib().ss_meter_bank_add_ragged(self._h, ptrs, frames))
+
+    def add_ragged_pcm(self, blocks, fmt):
+        """The same for raw little-endian interleaved samples of an ss_pcm_format: bytes or a numpy array per stream, or None."""
+        def raw(b):
+            return np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray)) else np.ascontiguousarray(b).view(np.uint8).reshape(-1)
+        sb = int(L.lib().ss_pcm_sample_bytes(int(fmt))) or 1
+        ptrs, frames, keep = self._ragged(blocks, raw, sb)
+        _check(L.lib().ss_meter_bank_add_ragged_pcm(self._h, ptrs, frames, int(fmt)))
+
+    def add_ragged_device(self, ptr, frames, stream_stride_floats):
+        """Device-resident f32 input: stream s's frames[s] frames at `ptr` + s * stream_stride_floats.  Only queued, as add_device."""
+        f = np.ascontiguousarray(frames, dtype=np.uint64).reshape(-1)
+        if f.size != self.n_streams:
+            raise ValueError(f"{f.size} frame counts for {self.n_streams} streams")
+        _check(L.lib().ss_meter_bank_add_ragged_device(self._h, C.c_void_p(int(ptr)), f.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       int(stream_stride_floats)))
 
     def reset(self, streams=None):
         """Reset the listed streams (None: all), as EbuR128::reset; the others are untouched."""
