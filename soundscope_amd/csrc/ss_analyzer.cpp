@@ -46,51 +46,49 @@ int handle_reset(ss_analyzer *h)
     return SS_OK;
 }
 
-int pin_ready(ss_analyzer *h)
+// the handle's page-locked mailboxes, allocated together at first use
+static int pin_ready(ss_analyzer *h)
 {
-    if (h->pin_d) return SS_OK;
-    // Idempotent per resource: a call that failed part-way leaves what it got in the handle, and the next one allocates only what
-    // is still missing (nothing is leaked; ss_analyzer_destroy frees whatever is there).
-    auto host_alloc = [](auto **slot, size_t bytes) -> hipError_t {
-        return *slot ? hipSuccess : hipHostMalloc(reinterpret_cast<void **>(slot), bytes, hipHostMallocDefault);
-    };
-    auto event = [](hipEvent_t *e) -> hipError_t { return *e ? hipSuccess : hipEventCreateWithFlags(e, hipEventDisableTiming); };
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(host_alloc(&h->pin_in[i], ss_analyzer::kPinFloats * sizeof(float)));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&h->pin_in_dev[i]), h->pin_in[i], 0));
-        HIPCHK(event(&h->pin_ev[i]));
+    if (h->pin_ok) return SS_OK;
+    // (ensure keeps what is there: a call that failed part-way leaves what it got in the handle, and the next one allocates only
+    // what is still missing)
+    for (HostStage &st : h->pin_in) HIPCHK(st.take(ss_analyzer::kPinFloats * sizeof(float)));
+    if (!h->ring_ev) HIPCHK(hipEventCreateWithFlags(&h->ring_ev, hipEventDisableTiming));
+    HIPCHK(h->pin_out.ensure(ss_analyzer::kPinFloats / 2 + 4));
+    HIPCHK(h->pin_peaks.ensure(2 * ssk::kMaxChannels));
+    HIPCHK(h->pin_eval.ensure(2));
+    if (!h->pin_flag.p) {
+        HIPCHK(h->pin_flag.alloc(1));
+        *h->pin_flag.p = 0u;
     }
-    HIPCHK(event(&h->pin_ev[2]));                                                // behind a short-term / momentary reading
-    HIPCHK(host_alloc(&h->pin_out, (ss_analyzer::kPinFloats / 2 + 4) * sizeof(float)));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&h->pin_out_dev), h->pin_out, 0));
-    HIPCHK(host_alloc(&h->pin_peaks, 2 * ssk::kMaxChannels * sizeof(float)));
-    HIPCHK(host_alloc(&h->pin_eval, 2 * sizeof(double)));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&h->pin_eval_dev), h->pin_eval, 0));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&h->pin_peaks_dev), h->pin_peaks, 0));
-    if (!h->pin_flag) {
-        HIPCHK(host_alloc(&h->pin_flag, sizeof(uint32_t)));
-        *h->pin_flag = 0u;
-    }
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&h->pin_flag_dev), h->pin_flag, 0));
-    HIPCHK(host_alloc(&h->pin_d_pending, 2 * sizeof(double)));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&h->pin_d_dev), h->pin_d_pending, 0));
-    h->pin_d = h->pin_d_pending;                // (last: "ready" means all of them)
-    h->pin_d_pending = nullptr;
+    HIPCHK(h->pin_d.ensure(2));
+    h->pin_ok = true;
     return SS_OK;
 }
 
-int pin_acquire(ss_analyzer *h, int *idx)
+// n <= kPinFloats host samples on their way to h->in: copied into an input stage no copy is still reading, from where ONE DMA takes
+// them to HBM (the kernels read their input many times in small pieces: in place over PCIe that cost them 10-20 us more)
+static int stage_input(ss_analyzer *h, const float *samples, size_t n, HostStage **stage)
 {
     int rc = pin_ready(h);
     if (rc) return rc;
-    const int i = h->pin_next;
-    if (h->pin_busy[i]) { HIPCHK(hipEventSynchronize(h->pin_ev[i])); h->pin_busy[i] = false; }
-    h->pin_next = i ^ 1;
-    *idx = i;
+    HostStage &st = h->pin_in[h->pin_next];
+    HIPCHK(st.take(n * sizeof(float)));
+    h->pin_next ^= 1;
+    std::memcpy(st.buf.p, samples, n * sizeof(float));
+    HIPCHK(h->in.ensure(n));
+    HIPCHK(hipMemcpyAsync(h->in.p, st.buf.p, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    *stage = &st;
     return SS_OK;
 }
 
-void pin_all_free(ss_analyzer *h) { h->pin_busy[0] = h->pin_busy[1] = false; }
+// hipStreamSynchronize of h->stream: both input stages are idle
+static hipError_t stream_sync(ss_analyzer *h)
+{
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) for (HostStage &st : h->pin_in) st.idle();
+    return e;
+}
 
 int attach_readings(ss_analyzer *h, ssk::FinalizeParams *gating)
 {
@@ -101,9 +99,9 @@ int attach_readings(ss_analyzer *h, ssk::FinalizeParams *gating)
     int rc = pin_ready(h);
     if (rc) return rc;
     h->readings_seq = h->readings_seq + 1u ? h->readings_seq + 1u : 1u;
-    gating->readings_out = h->pin_eval_dev;
-    gating->readings_peaks_src = &h->meter.state.p->sample_peak[0]; gating->readings_peaks_dst = h->pin_peaks_dev;
-    gating->readings_flag = h->pin_flag_dev; gating->readings_seq = h->readings_seq;
+    gating->readings_out = h->pin_eval.dev;
+    gating->readings_peaks_src = &h->meter.state.p->sample_peak[0]; gating->readings_peaks_dst = h->pin_peaks.dev;
+    gating->readings_flag = h->pin_flag.dev; gating->readings_seq = h->readings_seq;
     h->prefetch_stamp = h->change_count;
     return SS_OK;
 }
@@ -117,14 +115,12 @@ int prefetch_readings(ss_analyzer *h, bool on_demand)
     (void)on_demand;
     int rc = pin_ready(h);
     if (rc) return rc;
-    static_assert(offsetof(ssk::TdState, true_peak) == offsetof(ssk::TdState, sample_peak) + sizeof(float) * ssk::kMaxChannels,
-                  "sample_peak and true_peak are read as one block");
     // ONE launch, nothing else: the kernel copies the peaks beside its evaluation and stores the launch's number into a flag in
     // pinned memory behind everything — what the getter waits for (no event, no copy command: the launch has to fit the few
     // microseconds a tick has left between its charts and the end of the loudness call)
     h->readings_seq = h->readings_seq + 1u ? h->readings_seq + 1u : 1u;
-    const ssk::ReadingsExtra x{&h->meter.state.p->sample_peak[0], h->pin_peaks_dev, h->pin_flag_dev, h->readings_seq};
-    HIPCHK(ssk::launch_hist_eval(h->meter.hist.p, h->meter.hist_energies, h->meter.hist_bounds, h->pin_eval_dev, h->stream, &x));
+    const ssk::ReadingsExtra x{&h->meter.state.p->sample_peak[0], h->pin_peaks.dev, h->pin_flag.dev, h->readings_seq};
+    HIPCHK(ssk::launch_hist_eval(h->meter.hist.p, h->meter.hist_energies, h->meter.hist_bounds, h->pin_eval.dev, h->stream, &x));
     h->prefetch_stamp = h->change_count;
     return SS_OK;
 }
@@ -157,14 +153,7 @@ void ss_analyzer_destroy(ss_analyzer *h)
     SS_ON_DEVICE(h);
     if (!h) return;
     if (h->stream) { (void)hipStreamSynchronize(h->stream); stream_release(h->stream); }
-    for (int i = 0; i < 2; i++) if (h->pin_in[i]) (void)hipHostFree(h->pin_in[i]);
-    for (int i = 0; i < 3; i++) if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
-    if (h->pin_peaks) (void)hipHostFree(h->pin_peaks);
-    if (h->pin_eval) (void)hipHostFree(h->pin_eval);
-    if (h->pin_flag) (void)hipHostFree(h->pin_flag);
-    if (h->pin_d) (void)hipHostFree(h->pin_d);
-    if (h->pin_d_pending) (void)hipHostFree(h->pin_d_pending);
+    if (h->ring_ev) (void)hipEventDestroy(h->ring_ev);
     delete h;
 }
 
@@ -258,22 +247,17 @@ int ss_get_fft(const ss_analyzer *hc, const float *samples, size_t n,
     if (bt->count > cap_pairs) return SS_ERR_CAPACITY;
     if (bt->count == 0) return SS_OK;
 
-    // the window goes into page-locked memory the kernel reads in place; the dB row comes back the same way
-    int pin = 0;
-    rc = pin_acquire(h, &pin);
+    // the window goes to HBM through page-locked memory; the dB row comes back into page-locked memory the kernel writes in place
+    HostStage *pin = nullptr;
+    rc = stage_input(h, samples, n, &pin);
     if (rc) return rc;
-    std::memcpy(h->pin_in[pin], samples, n * sizeof(float));
-    // (the transform reads its window many times in small pieces: from page-locked host memory in place that costs the kernel
-    // 20 us more than it takes from HBM — one DMA of the page-locked copy first)
-    HIPCHK(hipMemcpyAsync(h->in.p, h->pin_in[pin], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     // (a batch of one window: N = 4096 and 16384 run the batch path's radix-16 machines, the first with its window pair half empty)
     const ssk::SpecPlan plan = ssk::plan_spectrum((uint32_t)n, 1, kOneWindowHop, 1, 1);
     ssk::FftBatchParams p = one_window_fft(plan, *ft, *bt);
-    p.pcm = h->in.p; p.out = h->pin_out_dev; p.channels = 1;
+    p.pcm = h->in.p; p.out = h->pin_out.dev; p.channels = 1;
     HIPCHK(ssk::launch_spectrum(plan, p, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    pin_all_free(h);
-    const float *db = h->pin_out;
+    HIPCHK(stream_sync(h));
+    const float *db = h->pin_out.p;
     for (size_t i = 0; i < bt->count; i++)
         if (std::isnan(db[i]) || std::isinf(db[i])) {
             // ScalingError(original, scaled) of the first bin the scaling function spoiled.  scale_to_dbfs maps a finite
@@ -396,16 +380,12 @@ int ssh::add_samples_impl(ss_analyzer *h, const float *samples, size_t n, bool o
     const uint64_t piece_frames = 32 * S;
     uint64_t frames = n / C, done = 0;
     h->change_count++;                                  // (whatever happens below: cached readings are of the past)
-    // a tick-sized host buffer: copied into page-locked memory the kernel reads in place, and the call returns behind its
-    // launches (the event tells the next user of that buffer when the kernel is through with it)
-    int pin = -1;
+    // a tick-sized host buffer goes through an input stage, and the call returns behind its launches (the stage's event tells its
+    // next user when the copy has left it)
+    HostStage *pin = nullptr;
     if (!on_device && n <= ss_analyzer::kPinFloats && frames <= piece_frames) {
-        int rc = pin_acquire(h, &pin);
+        int rc = stage_input(h, samples, n, &pin);
         if (rc) return rc;
-        std::memcpy(h->pin_in[pin], samples, n * sizeof(float));
-        // ... and on to HBM by one DMA (reading the page-locked copy in place over PCIe cost the kernel 33 instead of 22 us)
-        HIPCHK(h->in.ensure(n));
-        HIPCHK(hipMemcpyAsync(h->in.p, h->pin_in[pin], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
         samples = h->in.p;
         on_device = true;
     }
@@ -444,10 +424,7 @@ int ssh::add_samples_impl(ss_analyzer *h, const float *samples, size_t n, bool o
         h->frames_fed += take;
         done += take;
     }
-    if (pin >= 0) {
-        HIPCHK(hipEventRecord(h->pin_ev[pin], h->stream));
-        h->pin_busy[pin] = true;
-    }
+    if (pin) HIPCHK(pin->sent(h->stream));
     return SS_OK;
 }
 extern "C" {
@@ -484,14 +461,14 @@ static int ring_loudness(ss_analyzer *h, uint64_t frames, double *out)
     if (frames > h->meter.ring_frames) return SS_ERR_INVALID_MODE;
     int rc = pin_ready(h);
     if (rc) return rc;
-    rc = ring_loudness_enqueue(h, frames, h->pin_d_dev);        // (energy, loudness) straight into page-locked memory
+    rc = ring_loudness_enqueue(h, frames, h->pin_d.dev);        // (energy, loudness) straight into page-locked memory
     if (rc) return rc;
     // the call waits for its own reading only; behind it the readings the reference's render loop asks for on its next frame
     // (integrated loudness, range, peaks: tui.rs:917, :950, :969) are put on their way
-    HIPCHK(hipEventRecord(h->pin_ev[2], h->stream));
+    HIPCHK(hipEventRecord(h->ring_ev, h->stream));
     if (h->prefetch_stamp != h->change_count) { rc = prefetch_readings(h); if (rc) return rc; }
-    HIPCHK(hipEventSynchronize(h->pin_ev[2]));
-    *out = h->pin_d[1];
+    HIPCHK(hipEventSynchronize(h->ring_ev));
+    *out = h->pin_d.p[1];
     return SS_OK;
 }
 
@@ -522,14 +499,14 @@ static int refresh_readings(ss_analyzer *h)
     // then — for errors, and as the fallback — the stream
     bool seen = false;
     for (int spin = 0; spin < 4096 && !seen; spin++) {
-        seen = __atomic_load_n(h->pin_flag, __ATOMIC_ACQUIRE) == h->readings_seq;
+        seen = __atomic_load_n(h->pin_flag.p, __ATOMIC_ACQUIRE) == h->readings_seq;
 #if defined(__x86_64__) || defined(__i386__)
         if (!seen) __builtin_ia32_pause();
 #endif
     }
-    if (!seen) { HIPCHK(hipStreamSynchronize(h->stream)); pin_all_free(h); }
-    h->eval_cache[0] = h->pin_eval[0]; h->eval_cache[1] = h->pin_eval[1];
-    std::memcpy(h->peaks_cache, h->pin_peaks, sizeof h->peaks_cache);
+    if (!seen) HIPCHK(stream_sync(h));
+    h->eval_cache[0] = h->pin_eval.p[0]; h->eval_cache[1] = h->pin_eval.p[1];
+    std::memcpy(h->peaks_cache, h->pin_peaks.p, sizeof h->peaks_cache);
     h->eval_stamp = h->peaks_stamp = h->change_count;
     return SS_OK;
 }
@@ -575,9 +552,7 @@ static int read_peaks(ss_analyzer *h, uint32_t ch, double *sample_pk, double *tr
     if (ch >= h->meter.channels) return SS_ERR_INVALID_CHANNEL;
     int rc = refresh_readings(h);
     if (rc) return rc;
-    const float sp = h->peaks_cache[ch], tp = h->peaks_cache[ssk::kMaxChannels + ch];
-    if (sample_pk) *sample_pk = (double)sp;
-    if (true_pk) *true_pk = (double)(tp > sp ? tp : sp);    // true_peak(): max(true, sample)
+    peaks_of(h->peaks_cache, ch, sample_pk, true_pk);
     return SS_OK;
 }
 

@@ -416,7 +416,7 @@ int ss_batch_upload_pcm(ss_batch *b, uint32_t first, uint32_t count, const void 
     const size_t per = (size_t)b->cfg.frames_per_stream * b->cfg.channels;
     const size_t n = per * count;
     DevBuf<unsigned char> raw;
-    HIPCHK(raw.alloc(n * sb + 8));
+    HIPCHK(raw.alloc(n * sb + kPcmReadSlack));
     HIPCHK(hipMemcpyAsync(raw.p, pcm, n * sb, hipMemcpyHostToDevice, b->stream));
     HIPCHK(ssk::launch_pcm_to_f32(raw.p, n, format, b->pcm.p + (size_t)first * per, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -491,6 +491,16 @@ int ss_host_unregister(void *ptr)
     return SS_OK;
 }
 
+// one raw staging area per batch, sized for the whole batch at sb bytes per sample (ranges of different streams do not overlap);
+// growing it waits for whatever still reads the old one
+static hipError_t raw_area(ss_batch *b, size_t sb)
+{
+    const size_t bytes = (size_t)b->cfg.frames_per_stream * b->cfg.channels * b->cfg.n_streams * sb + kPcmReadSlack;
+    if (b->raw.n >= bytes) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(b->stream);
+    return e == hipSuccess ? b->raw.alloc(bytes) : e;
+}
+
 // like ss_batch_upload_pcm, but returns as soon as the copy and the conversion are queued on the batch's stream:
 // `pcm` must stay valid (and should be page-locked) until the next ss_batch_sync / ss_batch_results on this batch
 int ss_batch_upload_pcm_async(ss_batch *b, uint32_t first, uint32_t count, const void *pcm, int format)
@@ -505,12 +515,7 @@ int ss_batch_upload_pcm_async(ss_batch *b, uint32_t first, uint32_t count, const
         HIPCHK(hipMemcpyAsync(b->pcm.p + (size_t)first * per, pcm, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
         return SS_OK;
     }
-    // one raw staging area per batch, sized for the whole batch; ranges of different `first` do not overlap
-    const size_t total = per * b->cfg.n_streams;
-    if (b->raw.n < total * sb + 8) {
-        HIPCHK(hipStreamSynchronize(b->stream));
-        HIPCHK(b->raw.alloc(total * sb + 8));
-    }
+    HIPCHK(raw_area(b, sb));
     unsigned char *dst = b->raw.p + (size_t)first * per * sb;
     HIPCHK(hipMemcpyAsync(dst, pcm, n * sb, hipMemcpyHostToDevice, b->stream));
     HIPCHK(ssk::launch_pcm_to_f32(dst, n, format, b->pcm.p + (size_t)first * per, b->stream));
@@ -532,11 +537,7 @@ int ss_batch_upload_samples(ss_batch *b, uint32_t stream, const void *pcm, size_
         HIPCHK(hipMemcpyAsync(dst, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice, b->stream));
         return SS_OK;
     }
-    const size_t total = per * b->cfg.n_streams;
-    if (b->raw.n < total * sb + 8) {
-        HIPCHK(hipStreamSynchronize(b->stream));
-        HIPCHK(b->raw.alloc(total * sb + 8));
-    }
+    HIPCHK(raw_area(b, sb));
     unsigned char *raw = b->raw.p + (size_t)stream * per * sb;
     HIPCHK(hipMemcpyAsync(raw, pcm, n_samples * sb, hipMemcpyHostToDevice, b->stream));
     HIPCHK(ssk::launch_pcm_to_f32(raw, n_samples, format, dst, b->stream));
@@ -770,15 +771,12 @@ int ss_batch_peaks(ss_batch *b, uint32_t stream, double *true_pk, double *sample
     if (!b->state.p) return SS_ERR_INVALID_MODE;                 // the batch runs no meter pass
     const uint32_t C = b->cfg.channels;
     if (cap_channels < C) return SS_ERR_CAPACITY;
-    float sp[ssk::kMaxChannels], tp[ssk::kMaxChannels];
+    float pk[2 * ssk::kMaxChannels];
     const ssk::TdState *st = b->state.p + stream;
-    HIPCHK(hipMemcpyAsync(sp, st->sample_peak, C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipMemcpyAsync(tp, st->true_peak, C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(pk, st->sample_peak, C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(pk + ssk::kMaxChannels, st->true_peak, C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
-    for (uint32_t c = 0; c < C; c++) {
-        if (sample_pk) sample_pk[c] = (double)sp[c];
-        if (true_pk) true_pk[c] = (double)(tp[c] > sp[c] ? tp[c] : sp[c]);
-    }
+    for (uint32_t c = 0; c < C; c++) peaks_of(pk, c, sample_pk ? sample_pk + c : nullptr, true_pk ? true_pk + c : nullptr);
     return SS_OK;
 }
 

@@ -1,5 +1,6 @@
-// ss_host.h — what the host-side translation units of the library share (never installed): the HIP error channel,
-// RAII device buffers, the per-device caches of constant tables, per-thread scratch, the live meter and the handle type.
+// ss_host.h — what the host-side translation units of the library share (never installed): the HIP error channel, the RAII
+// owners of memory (DevBuf: device, PinBuf: page-locked host, HostStage: a page-locked buffer a copy may still be reading), the
+// per-device caches of constant tables, per-thread scratch, the live meter and the handle type.
 //   ss_host.cpp         caches, device selection, status strings, table inspection, the live meter (MeterStore)
 //   ss_analyzer.cpp     the Analyzer mirror (one entry point per Rust method, analyzer.rs:29-183)
 //   ss_ingest.cpp       RIFF/WAVE header walk and PCM conversion
@@ -71,6 +72,76 @@ struct DevBuf {
         return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
     }
 };
+
+// Page-locked host memory, owned like DevBuf owns device memory.  dev: the same memory as the device sees it (kernels write
+// results straight into it).  A regrow frees first; the caller has made sure that nothing on the device still uses the buffer.
+template <typename T>
+struct PinBuf {
+    T *p = nullptr, *dev = nullptr;
+    size_t n = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    PinBuf(PinBuf &&o) noexcept { swap(o); }
+    PinBuf &operator=(PinBuf &&o) noexcept { swap(o); return *this; }     // (o frees what this held)
+    ~PinBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr; n = 0;
+    }
+    hipError_t alloc(size_t count)
+    {
+        release();
+        if (!count) return hipSuccess;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), count * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&dev), p, 0);
+        if (e == hipSuccess) n = count; else release();
+        return e;
+    }
+    hipError_t ensure(size_t count) { return count <= n ? hipSuccess : alloc(count); }
+    void swap(PinBuf &o) { std::swap(p, o.p); std::swap(dev, o.dev); std::swap(n, o.n); }
+};
+
+// A page-locked buffer that host input is copied into on its way to the device, and an event that says when that copy has left
+// it: the call returns behind its launches, and the next user of the buffer waits for the event only if nobody has waited for the
+// stream in between.
+struct HostStage {
+    PinBuf<unsigned char> buf;
+    hipEvent_t ev = nullptr;             // created at first use
+    bool busy = false;
+    ~HostStage() { if (ev) (void)hipEventDestroy(ev); }
+    // `bytes` of page-locked memory at buf.p that no copy is still reading (a busy buffer is waited for, a small one regrown)
+    hipError_t take(size_t bytes)
+    {
+        hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess && busy && (e = hipEventSynchronize(ev)) == hipSuccess) busy = false;
+        return e == hipSuccess ? buf.ensure(bytes) : e;
+    }
+    // the copy out of the buffer has just been enqueued on `stream`
+    hipError_t sent(hipStream_t stream)
+    {
+        hipError_t e = hipEventRecord(ev, stream);
+        if (e == hipSuccess) busy = true;
+        return e;
+    }
+    void idle() { busy = false; }        // the owner has synchronised the stream
+};
+
+// what ssk::launch_pcm_to_f32's wide reads of 24-bit samples may touch behind the last sample: every raw PCM buffer on the device is
+// allocated this many bytes longer than its samples
+constexpr size_t kPcmReadSlack = 8;
+
+// EbuR128::sample_peak(c) and EbuR128::true_peak(c) = max(true, sample) of channel c, from a host copy of a state's peaks
+// (`block`: TdState::sample_peak | TdState::true_peak, read as one block of 2 * kMaxChannels floats)
+static_assert(offsetof(ssk::TdState, true_peak) == offsetof(ssk::TdState, sample_peak) + sizeof(float) * ssk::kMaxChannels,
+              "sample_peak and true_peak are read as one block");
+inline void peaks_of(const float *block, uint32_t c, double *sample_pk, double *true_pk)
+{
+    const float sp = block[c], tp = block[ssk::kMaxChannels + c];
+    if (sample_pk) *sample_pk = (double)sp;
+    if (true_pk) *true_pk = (double)(tp > sp ? tp : sp);
+}
 
 // ---- per-process caches of device-resident constant tables ------------------
 struct FftTables {
@@ -243,20 +314,18 @@ struct ss_analyzer {
     // data with pageable copy commands and read-backs (a pageable 64 KB hipMemcpyAsync blocks the caller and costs more than the
     // kernel behind it): the samples are copied by the host into page-locked memory, from where ONE DMA takes them to HBM (the
     // kernels read their input in small pieces: in place over PCIe that cost them 10-14 us), and results are written by the
-    // kernels into page-locked memory.  Two input buffers, so that add_samples returns behind its launches (an event says when
-    // a buffer's copy has left it); every call that waits for the stream frees both.
+    // kernels into page-locked memory (PinBuf::dev).  Two input stages, so that add_samples returns behind its launches; every call
+    // that waits for the stream frees both.  All of them are allocated together at first use (pin_ready, ss_analyzer.cpp).
     static constexpr size_t kPinFloats = 32768;
-    float *pin_in[2] = {nullptr, nullptr}, *pin_in_dev[2] = {nullptr, nullptr};
-    hipEvent_t pin_ev[3] = {nullptr, nullptr, nullptr};      // [0], [1]: an input buffer's kernel has read it; [2]: a ring reading is there
-    bool pin_busy[2] = {false, false};
+    ssh::HostStage pin_in[2];                                // kPinFloats floats each
     int pin_next = 0;
-    float *pin_out = nullptr, *pin_out_dev = nullptr;       // kPinFloats / 2 + 1 dB values
-    double *pin_d = nullptr, *pin_d_dev = nullptr;          // a getter's pair of doubles
-    double *pin_d_pending = nullptr;                        // the same while pin_ready has not finished (pin_d set = all of them ready)
-    float *pin_peaks = nullptr;                              // 2 * kMaxChannels floats: the state's peaks, copied there
-    double *pin_eval = nullptr, *pin_eval_dev = nullptr;    // (integrated, range) of the state the readings were last asked for
-    float *pin_peaks_dev = nullptr;
-    uint32_t *pin_flag = nullptr, *pin_flag_dev = nullptr;  // the readings launch stores its number there, last
+    hipEvent_t ring_ev = nullptr;                            // a ring reading (short-term / momentary) is there
+    bool pin_ok = false;                                     // pin_ready has got all of them
+    ssh::PinBuf<float> pin_out;                              // kPinFloats / 2 + 1 dB values
+    ssh::PinBuf<double> pin_d;                               // a getter's pair of doubles
+    ssh::PinBuf<float> pin_peaks;                            // 2 * kMaxChannels floats: the state's peaks, copied there
+    ssh::PinBuf<double> pin_eval;                            // (integrated, range) of the state the readings were last asked for
+    ssh::PinBuf<uint32_t> pin_flag;                          // the readings launch stores its number there, last
     uint32_t readings_seq = 0;                               // readings launches so far
     uint64_t prefetch_stamp = 0;                             // change_count the launch in flight is of (0: none)
 };
@@ -264,10 +333,6 @@ struct ss_analyzer {
 namespace ssh {
 // ss_analyzer.cpp: pieces of the handle the batch one-shot and the tick drivers reuse
 SS_HIDDEN int handle_reset(ss_analyzer *h);
-// the handle's page-locked mailboxes (allocated at first use); pin_acquire: an input buffer no kernel is still reading
-SS_HIDDEN int pin_ready(ss_analyzer *h);
-SS_HIDDEN int pin_acquire(ss_analyzer *h, int *idx);
-SS_HIDDEN void pin_all_free(ss_analyzer *h);           // behind a hipStreamSynchronize of h->stream
 // enqueue (no wait) the readings the reference's render loop asks for on every frame — integrated loudness and range, every
 // channel's peaks — behind whatever has just changed the meter's state: the getters then find them waiting
 SS_HIDDEN int prefetch_readings(ss_analyzer *h, bool on_demand = false);      // on_demand: a getter asking (never switched off)

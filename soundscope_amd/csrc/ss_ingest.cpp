@@ -77,7 +77,7 @@ int ss_pcm_decode(const void *pcm, size_t n_samples, int format, float *out)
     if (require_device()) return SS_ERR_DEVICE;
     Scratch &c = scratch();
     if (!c.stream) HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    HIPCHK(c.raw.ensure(n_samples * sb + 8));
+    HIPCHK(c.raw.ensure(n_samples * sb + kPcmReadSlack));
     HIPCHK(c.out.ensure(n_samples));
     HIPCHK(hipMemcpyAsync(c.raw.p, pcm, n_samples * sb, hipMemcpyHostToDevice, c.stream));
     HIPCHK(ssk::launch_pcm_to_f32(c.raw.p, n_samples, format, c.out.p, c.stream));

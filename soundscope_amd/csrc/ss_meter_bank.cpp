@@ -15,13 +15,10 @@ struct ss_meter_bank {
     ssh::DevBuf<unsigned char> raw;        // ss_meter_bank_add_pcm's bytes
     ssh::DevBuf<ssk::MeterReading> readings;
     std::vector<uint64_t> fed;             // frames since each stream's reset (the device's TdState::frames_fed, mirrored)
-    // page-locked staging: a host call's input is copied there and returns behind its launches (the event says when the copy
-    // to the device has left the buffer); the readings come back through the same kind of buffer
-    void *pin = nullptr;
-    size_t pin_bytes = 0;
-    hipEvent_t pin_ev = nullptr;
-    bool pin_busy = false;
-    ssk::MeterReading *pin_read = nullptr;
+    // page-locked staging: a host call's input is copied there and returns behind its launches; the readings come back through
+    // page-locked memory as well
+    ssh::HostStage stage;
+    ssh::PinBuf<ssk::MeterReading> pin_read;
     ssh::DevBuf<unsigned char> rag;        // a ragged add's staging: the per-stream arrays, then (host forms) the packed input
     // spectra (ss_meter_bank_spectrum_enable): the newest 16384 input frames of every stream.  Stream s's frame counter is
     // spec_fed + spec_ahead[s]: what the uniform adds gave everyone, kept here, plus what ragged adds gave that stream, kept on the
@@ -38,8 +35,7 @@ struct ss_meter_bank {
     ssh::DevBuf<uint16_t> spec_bin_col;    // n_bins: chart column of each bin for spec_cols
     ssh::DevBuf<float> spec_col_init;      // spec_cols
     uint32_t spec_cols = 0;
-    void *spec_pin = nullptr;              // page-locked results: floats, then the statuses
-    size_t spec_pin_bytes = 0;
+    ssh::PinBuf<unsigned char> spec_pin;   // page-locked results: floats, then the statuses
 };
 
 static_assert(sizeof(ss_meter_reading) == 72 && sizeof(ssk::MeterReading) == sizeof(ss_meter_reading), "ss_meter_reading layout");
@@ -48,99 +44,88 @@ static_assert(offsetof(ss_meter_reading, true_peak) == offsetof(ssk::MeterReadin
 
 namespace {
 
-// a page-locked buffer of at least `bytes` no copy is still reading
-int pin_take(ss_meter_bank *m, size_t bytes)
+// the stream has been waited for: the staging buffer is free
+hipError_t bank_sync(ss_meter_bank *m)
 {
-    if (m->pin_busy) { HIPCHK(hipEventSynchronize(m->pin_ev)); m->pin_busy = false; }
-    if (bytes > m->pin_bytes) {
-        if (m->pin) { (void)hipHostFree(m->pin); m->pin = nullptr; m->pin_bytes = 0; }
-        HIPCHK(hipHostMalloc(&m->pin, bytes, hipHostMallocDefault));
-        m->pin_bytes = bytes;
-    }
+    hipError_t e = hipStreamSynchronize(m->stream);
+    if (e == hipSuccess) m->stage.idle();
+    return e;
+}
+
+// the first `bytes` of the staging buffer on their way to the device: one DMA, the event behind it
+int stage_send(ss_meter_bank *m, void *dst, size_t bytes)
+{
+    HIPCHK(hipMemcpyAsync(dst, m->stage.buf.p, bytes, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m->stage.sent(m->stream));
     return SS_OK;
 }
 
-// stage host bytes on the device: page-locked copy, one DMA, an event behind it
+// stage host bytes on the device through the page-locked copy
 int upload(ss_meter_bank *m, void *dst, const void *src, size_t bytes)
 {
-    int rc = pin_take(m, bytes);
-    if (rc) return rc;
-    std::memcpy(m->pin, src, bytes);
-    HIPCHK(hipMemcpyAsync(dst, m->pin, bytes, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipEventRecord(m->pin_ev, m->stream));
-    m->pin_busy = true;
-    return SS_OK;
+    HIPCHK(m->stage.take(bytes));
+    std::memcpy(m->stage.buf.p, src, bytes);
+    return stage_send(m, dst, bytes);
 }
 
-// every stream advanced by `frames` frames of device-resident f32 input (stream s at pcm + s * stride): pieces of at most 32
-// sub-blocks, so that the 96-slot sub-block ring always holds the thirty sub-blocks a short-term block reads (ss_add_samples' rule)
-int advance(ss_meter_bank *m, const float *pcm, uint64_t frames, uint64_t stride)
+// the f32 input of a call whose `samples` samples stand on the device at `bytes`: raw PCM is converted into m->in (the caller has
+// sized it), f32 (format 0) is used where it landed
+int device_input(ss_meter_bank *m, const unsigned char *bytes, uint64_t samples, int format, const float **in)
 {
-    const MeterStore &ms = m->meter;
-    const uint32_t C = ms.channels;
-    if (m->spec_on) {
-        HIPCHK(ssk::launch_bank_history_append(m->spec_hist.p, pcm, stride, frames, m->spec_fed, m->spec_ahead.p, ms.n, C, m->stream));
-        m->spec_fed += frames;
-    }
-    const uint64_t S = ms.s100, piece_frames = 32 * S;
-    const ssk::MeterBankParams q = ms.bank_params();
-    for (uint64_t done = 0; done < frames;) {
-        const uint64_t take = frames - done < piece_frames ? frames - done : piece_frames;
-        ssk::TdParams p = ms.td_params(pcm + done * C, stride, take);
-        p.tp_f32 = 1u;                                                   // SS_TP_ARITH_F32, the handle's default
-        HIPCHK(ssk::launch_time_domain(p, m->stream));
-        // the gating launch only when some stream completes a sub-block (each stream's range is derived on the device)
-        bool any = false;
-        for (uint32_t s = 0; s < ms.n; s++) {
-            any = any || (m->fed[s] + take) / S > m->fed[s] / S;
-            m->fed[s] += take;
-        }
-        if (any) HIPCHK(ssk::launch_meter_bank_gate(q, take, nullptr, m->stream));
-        done += take;
-    }
+    *in = reinterpret_cast<const float *>(bytes);
+    if (!format) return SS_OK;
+    HIPCHK(ssk::launch_pcm_to_f32(bytes, samples, format, m->in.p, m->stream));
+    *in = m->in.p;
     return SS_OK;
 }
 
-// ---- ragged adds: every stream its own frame count --------------------------------------------------------------------------------
-// What a ragged call stages, in ONE page-locked copy: arrays of n u64 each, then (host forms) the streams' input, tightly packed.
+// ---- the plan of an add ------------------------------------------------------------------------------------------------------------
+// A call is cut into pieces of at most 32 sub-blocks, so that the 96-slot sub-block ring always holds the thirty sub-blocks a
+// short-term block reads (ss_add_samples' rule).  A uniform call has no arrays: nothing but its input is uploaded.  A ragged call
+// stages, in ONE page-locked copy, arrays of n u64 each, then (host forms) the streams' input, tightly packed.
 //   [0] frames of the whole call (the history ring), [1] where each stream's input starts (floats; samples for raw PCM),
-//   then per piece of 32 sub-blocks: what each stream takes in it (the gating launch), and — only where the piece has streams on
-//   both sides of the form switch — that array once more with the long streams zeroed and once with the short ones zeroed.
-struct RaggedPlan {
-    struct Piece { size_t take, lo, hi; uint64_t max_short, max_long; bool gate; };   // array indices (lo == hi == take: one group)
-    std::vector<uint64_t> arrays;          // n entries each
+//   then per piece: what each stream takes in it (the gating launch), and — only where the piece has streams on both sides of the
+//   form switch — that array once more with the long streams zeroed and once with the short ones zeroed.
+struct BankPlan {
+    // take, lo, hi: array indices (lo == hi == take: one group); all: what every stream takes (uniform; ragged: 0, see `take`)
+    struct Piece { size_t take, lo, hi; uint64_t max_short, max_long, all; bool gate; };
+    std::vector<uint64_t> arrays;          // n entries each; empty: a uniform call
     std::vector<Piece> pieces;
+    uint64_t longest = 0;                  // frames of the longest stream (uniform: of every stream; 0: nothing to do)
     uint64_t total = 0;                    // samples of packed input, every stream's start a multiple of four
 };
 
-// the checks every ragged form shares, then the plan; SS_OK with an empty plan: nothing to do
-int ragged_plan(const ss_meter_bank *m, const uint64_t *frames, bool pack, RaggedPlan *pl, uint64_t *max_frames)
+// frames: every stream's count, with the checks every ragged form shares (null: a uniform call of `each` frames)
+int bank_plan(const ss_meter_bank *m, const uint64_t *frames, uint64_t each, bool pack, BankPlan *pl)
 {
     const MeterStore &ms = m->meter;
     const uint32_t n = ms.n, C = ms.channels;
-    uint64_t total = 0, longest = 0;
-    for (uint32_t s = 0; s < n; s++) {                                   // ss_batch_create's rule: more than 2^40 samples is no buffer
+    uint64_t total = 0, longest = each;
+    for (uint32_t s = 0; frames && s < n; s++) {                         // ss_batch_create's rule: more than 2^40 samples is no buffer
         if (frames[s] > (1ull << 40) || frames[s] * C > (1ull << 40) || (total += (frames[s] * C + 3u) & ~3ull) > (1ull << 40)) return SS_ERR_NOMEM;
         if (frames[s] > longest) longest = frames[s];
     }
-    *max_frames = longest;
+    pl->longest = longest;
     if (!longest) return SS_OK;
     const uint64_t S = ms.s100, piece_frames = 32 * S, tile = ssk::td_ring_tile_frames(C, (uint32_t)S);
     const size_t n_pieces = (size_t)((longest + piece_frames - 1) / piece_frames);
-    pl->arrays.assign((2 + n_pieces) * (size_t)n, 0);
-    pl->total = pack ? total : 0;
-    uint64_t at = 0;
-    for (uint32_t s = 0; s < n; s++) {
-        pl->arrays[s] = frames[s];
-        pl->arrays[n + s] = at;
-        if (pack) at += (frames[s] * C + 3u) & ~3ull;
+    if (frames) {
+        pl->arrays.assign((2 + n_pieces) * (size_t)n, 0);
+        pl->total = pack ? total : 0;
+        uint64_t at = 0;
+        for (uint32_t s = 0; s < n; s++) {
+            pl->arrays[s] = frames[s];
+            pl->arrays[n + s] = at;
+            if (pack) at += (frames[s] * C + 3u) & ~3ull;
+        }
     }
     for (size_t k = 0; k < n_pieces; k++) {
-        RaggedPlan::Piece pc{(2 + k) * (size_t)n, 0, 0, 0, 0, false};
+        BankPlan::Piece pc{(2 + k) * (size_t)n, 0, 0, 0, 0, 0, false};
         for (uint32_t s = 0; s < n; s++) {
-            const uint64_t done = k * piece_frames < frames[s] ? k * piece_frames : frames[s], left = frames[s] - done;
+            const uint64_t f = frames ? frames[s] : each;
+            const uint64_t done = k * piece_frames < f ? k * piece_frames : f, left = f - done;
             const uint64_t take = left < piece_frames ? left : piece_frames;
-            pl->arrays[pc.take + s] = take;
+            if (frames) pl->arrays[pc.take + s] = take; else pc.all = take;
             if (take > tile) { if (take > pc.max_long) pc.max_long = take; }
             else if (take > pc.max_short) pc.max_short = take;
             const uint64_t fed = m->fed[s] + done;
@@ -160,14 +145,16 @@ int ragged_plan(const ss_meter_bank *m, const uint64_t *frames, bool pack, Ragge
     return SS_OK;
 }
 
-// the launches of a ragged call behind its staging: `arr` the plan's arrays on the device, stream s's input at pcm + offset_of[s]
-// (offset_of null: pcm + s * stride)
-int advance_ragged(ss_meter_bank *m, const RaggedPlan &pl, const uint64_t *frames, const uint64_t *arr, const float *pcm,
-                   const uint64_t *offset_of, uint64_t stride)
+// the launches of an add behind its staging.  Stream s's input stands at pcm + offset_of[s] (offset_of null: pcm + s * stride); `arr`:
+// a ragged plan's arrays on the device (null: a uniform call)
+int advance(ss_meter_bank *m, const BankPlan &pl, const uint64_t *arr, const float *pcm, const uint64_t *offset_of, uint64_t stride)
 {
     const MeterStore &ms = m->meter;
     const uint32_t n = ms.n, C = ms.channels;
-    if (m->spec_on) {
+    if (m->spec_on && !arr) {
+        HIPCHK(ssk::launch_bank_history_append(m->spec_hist.p, pcm, stride, pl.longest, m->spec_fed, m->spec_ahead.p, n, C, m->stream));
+        m->spec_fed += pl.longest;
+    } else if (m->spec_on) {
         if (!m->spec_ahead.p) {
             HIPCHK(m->spec_ahead.alloc(n));
             HIPCHK(hipMemsetAsync(m->spec_ahead.p, 0, n * sizeof(uint64_t), m->stream));
@@ -177,39 +164,47 @@ int advance_ragged(ss_meter_bank *m, const RaggedPlan &pl, const uint64_t *frame
     const uint64_t piece_frames = 32 * ms.s100;
     const ssk::MeterBankParams q = ms.bank_params();
     for (size_t k = 0; k < pl.pieces.size(); k++) {
-        const RaggedPlan::Piece &pc = pl.pieces[k];
-        // a stream runs the form a handle runs for a call of its length: one wave up to a tile, the eight-wave workgroup beyond
+        const BankPlan::Piece &pc = pl.pieces[k];
+        // a stream runs the form a handle runs for a call of its length: one wave up to a tile, the eight-wave workgroup beyond (a
+        // ragged piece with streams of both kinds: one launch each; a uniform piece: one launch, its form chosen by its length)
         for (int g = 0; g < 2; g++) {
             const uint64_t longest = g ? pc.max_long : pc.max_short;
             if (!longest) continue;
             ssk::TdParams p = ms.td_params(pcm + k * piece_frames * C, stride, longest);
-            p.frames_of = arr + (g ? pc.hi : pc.lo);
+            p.frames_of = arr ? arr + (g ? pc.hi : pc.lo) : nullptr;
             p.offset_of = offset_of;
             p.tp_f32 = 1u;                                               // SS_TP_ARITH_F32, the handle's default
             HIPCHK(ssk::launch_time_domain(p, m->stream));
         }
-        if (pc.gate) HIPCHK(ssk::launch_meter_bank_gate(q, 0, arr + pc.take, m->stream));
+        // the gating launch only when some stream completes a sub-block (each stream's range is derived on the device)
+        if (pc.gate) HIPCHK(ssk::launch_meter_bank_gate(q, pc.all, arr ? arr + pc.take : nullptr, m->stream));
     }
-    for (uint32_t s = 0; s < n; s++) m->fed[s] += frames[s];
+    for (uint32_t s = 0; s < n; s++) m->fed[s] += arr ? pl.arrays[s] : pl.longest;
     return SS_OK;
 }
 
-// host forms: arrays and packed input (sb bytes per sample; 4: f32, used where it lands) through one page-locked copy
+// every stream advanced by `frames` frames of device-resident f32 input (stream s at pcm + s * stride)
+int advance_uniform(ss_meter_bank *m, const float *pcm, uint64_t frames, uint64_t stride)
+{
+    BankPlan pl;
+    int rc = bank_plan(m, nullptr, frames, false, &pl);
+    return rc ? rc : advance(m, pl, nullptr, pcm, nullptr, stride);
+}
+
+// host forms: arrays and packed input (sb bytes per sample; format 0: f32, used where it lands) through one page-locked copy
 int add_ragged_host(ss_meter_bank *m, const void *const *pcm, const uint64_t *frames, int format, size_t sb)
 {
     if (!frames) return SS_ERR_INVALID_ARG;
     const uint32_t n = m->meter.n, C = m->meter.channels;
     for (uint32_t s = 0; s < n; s++) if (frames[s] && (!pcm || !pcm[s])) return SS_ERR_INVALID_ARG;
-    RaggedPlan pl;
-    uint64_t longest = 0;
-    int rc = ragged_plan(m, frames, true, &pl, &longest);
-    if (rc || !longest) return rc;
+    BankPlan pl;
+    int rc = bank_plan(m, frames, 0, true, &pl);
+    if (rc || !pl.longest) return rc;
     const size_t head = (pl.arrays.size() * sizeof(uint64_t) + 15u) & ~(size_t)15u, body = (size_t)pl.total * sb;
-    HIPCHK(m->rag.ensure(head + body + 8));                          // (+8: the converter's wide reads of 24-bit samples)
+    HIPCHK(m->rag.ensure(head + body + kPcmReadSlack));
     if (format) HIPCHK(m->in.ensure(pl.total));
-    rc = pin_take(m, head + body);
-    if (rc) return rc;
-    char *pin = static_cast<char *>(m->pin);
+    HIPCHK(m->stage.take(head + body));
+    char *pin = reinterpret_cast<char *>(m->stage.buf.p);
     std::memcpy(pin, pl.arrays.data(), pl.arrays.size() * sizeof(uint64_t));
     for (uint32_t s = 0; s < n; s++) {
         const size_t bytes = (size_t)frames[s] * C * sb, padded = (size_t)((frames[s] * C + 3u) & ~3ull) * sb;
@@ -217,16 +212,13 @@ int add_ragged_host(ss_meter_bank *m, const void *const *pcm, const uint64_t *fr
         if (bytes) std::memcpy(dst, pcm[s], bytes);
         std::memset(dst + bytes, 0, padded - bytes);
     }
-    HIPCHK(hipMemcpyAsync(m->rag.p, pin, head + body, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipEventRecord(m->pin_ev, m->stream));
-    m->pin_busy = true;
+    rc = stage_send(m, m->rag.p, head + body);
+    if (rc) return rc;
     const uint64_t *arr = reinterpret_cast<const uint64_t *>(m->rag.p);
-    const float *in = reinterpret_cast<const float *>(m->rag.p + head);
-    if (format) {
-        HIPCHK(ssk::launch_pcm_to_f32(m->rag.p + head, pl.total, format, m->in.p, m->stream));
-        in = m->in.p;
-    }
-    return advance_ragged(m, pl, frames, arr, in, arr + n, 0);
+    const float *in = nullptr;
+    rc = device_input(m, m->rag.p + head, pl.total, format, &in);
+    if (rc) return rc;
+    return advance(m, pl, arr, in, arr + n, 0);
 }
 
 int bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
@@ -256,11 +248,9 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
     const uint32_t R = spec_rows(m);
     const size_t rows = (size_t)m->meter.n * R, fbytes = rows * per_row * sizeof(float), sbytes = rows * sizeof(int32_t);
     HIPCHK(m->spec_out.ensure(rows * per_row));
-    if (fbytes + sbytes > m->spec_pin_bytes) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        if (m->spec_pin) { (void)hipHostFree(m->spec_pin); m->spec_pin = nullptr; m->spec_pin_bytes = 0; }
-        HIPCHK(hipHostMalloc(&m->spec_pin, fbytes + sbytes, hipHostMallocDefault));
-        m->spec_pin_bytes = fbytes + sbytes;
+    if (fbytes + sbytes > m->spec_pin.n) {
+        HIPCHK(bank_sync(m));
+        HIPCHK(m->spec_pin.ensure(fbytes + sbytes));
     }
     ssk::BankSpectrumParams q{};
     q.f = one_window_fft(ssk::plan_spectrum(SS_BANK_SPECTRUM_N, m->meter.channels, kOneWindowHop, 1, 1), *m->ft, *m->bt);
@@ -292,11 +282,10 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
         }
     }
     HIPCHK(ssk::launch_meter_bank_spectrum(q, columns, m->stream));
-    char *pin = static_cast<char *>(m->spec_pin);
+    char *pin = reinterpret_cast<char *>(m->spec_pin.p);
     HIPCHK(hipMemcpyAsync(pin, m->spec_out.p, fbytes, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(pin + fbytes, m->spec_status.p, sbytes, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->pin_busy = false;
+    HIPCHK(bank_sync(m));
     *vals = reinterpret_cast<float *>(pin);
     *status = reinterpret_cast<int32_t *>(pin + fbytes);
     return SS_OK;
@@ -319,14 +308,13 @@ int ss_meter_bank_create(uint32_t n_streams, uint32_t channels, uint32_t rate, i
     rc = m->meter.build(n_streams, channels, rate, true_peak_factor);
     if (rc) return rc;
     HIPCHK(stream_acquire(&m->stream));
-    HIPCHK(hipEventCreateWithFlags(&m->pin_ev, hipEventDisableTiming));
     const size_t N = n_streams;
     HIPCHK(m->readings.alloc(N));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&m->pin_read), N * sizeof(ssk::MeterReading), hipHostMallocDefault));
+    HIPCHK(m->pin_read.alloc(N));
     m->fed.assign(N, 0);
     rc = bank_reset(m.get(), nullptr, n_streams);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(bank_sync(m.get()));
     *out = m.release();
     return SS_OK;
 }
@@ -336,10 +324,6 @@ void ss_meter_bank_destroy(ss_meter_bank *m)
     SS_ON_DEVICE(m);
     if (!m) return;
     if (m->stream) { (void)hipStreamSynchronize(m->stream); stream_release(m->stream); }
-    if (m->pin_ev) (void)hipEventDestroy(m->pin_ev);
-    if (m->pin) (void)hipHostFree(m->pin);
-    if (m->pin_read) (void)hipHostFree(m->pin_read);
-    if (m->spec_pin) (void)hipHostFree(m->spec_pin);
     delete m;
 }
 
@@ -353,7 +337,7 @@ int ss_meter_bank_add(ss_meter_bank *m, const float *pcm, uint64_t frames)
     HIPCHK(m->in.ensure(total));
     int rc = upload(m, m->in.p, pcm, total * sizeof(float));
     if (rc) return rc;
-    return advance(m, m->in.p, frames, per);
+    return advance_uniform(m, m->in.p, frames, per);
 }
 
 int ss_meter_bank_add_device(ss_meter_bank *m, const float *pcm_device, uint64_t frames, uint64_t stream_stride_floats)
@@ -362,7 +346,7 @@ int ss_meter_bank_add_device(ss_meter_bank *m, const float *pcm_device, uint64_t
     if (!m) return null_bank();
     if (frames == 0) return SS_OK;
     if (!pcm_device || stream_stride_floats < frames * m->meter.channels) return SS_ERR_INVALID_ARG;
-    return advance(m, pcm_device, frames, stream_stride_floats);
+    return advance_uniform(m, pcm_device, frames, stream_stride_floats);
 }
 
 int ss_meter_bank_add_pcm(ss_meter_bank *m, const void *pcm, uint64_t frames, int format)
@@ -374,12 +358,13 @@ int ss_meter_bank_add_pcm(ss_meter_bank *m, const void *pcm, uint64_t frames, in
     if (frames == 0) return SS_OK;
     if (!pcm) return SS_ERR_INVALID_ARG;
     const uint64_t per = frames * m->meter.channels, total = per * m->meter.n;
-    HIPCHK(m->raw.ensure(total * sb + 8));                       // (+8: the converter's wide reads of 24-bit samples)
+    HIPCHK(m->raw.ensure(total * sb + kPcmReadSlack));
     HIPCHK(m->in.ensure(total));
     int rc = upload(m, m->raw.p, pcm, total * sb);
     if (rc) return rc;
-    HIPCHK(ssk::launch_pcm_to_f32(m->raw.p, total, format, m->in.p, m->stream));
-    return advance(m, m->in.p, frames, per);
+    const float *in = nullptr;
+    rc = device_input(m, m->raw.p, total, format, &in);
+    return rc ? rc : advance_uniform(m, in, frames, per);
 }
 
 int ss_meter_bank_add_ragged(ss_meter_bank *m, const float *const *pcm, const uint64_t *frames)
@@ -403,16 +388,15 @@ int ss_meter_bank_add_ragged_device(ss_meter_bank *m, const float *pcm_device, c
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
     if (!frames) return SS_ERR_INVALID_ARG;
-    RaggedPlan pl;
-    uint64_t longest = 0;
-    int rc = ragged_plan(m, frames, false, &pl, &longest);
-    if (rc || !longest) return rc;
-    if (!pcm_device || stream_stride_floats < longest * m->meter.channels) return SS_ERR_INVALID_ARG;
+    BankPlan pl;
+    int rc = bank_plan(m, frames, 0, false, &pl);
+    if (rc || !pl.longest) return rc;
+    if (!pcm_device || stream_stride_floats < pl.longest * m->meter.channels) return SS_ERR_INVALID_ARG;
     const size_t bytes = pl.arrays.size() * sizeof(uint64_t);
     HIPCHK(m->rag.ensure(bytes));
     rc = upload(m, m->rag.p, pl.arrays.data(), bytes);
     if (rc) return rc;
-    return advance_ragged(m, pl, frames, reinterpret_cast<const uint64_t *>(m->rag.p), pcm_device, nullptr, stream_stride_floats);
+    return advance(m, pl, reinterpret_cast<const uint64_t *>(m->rag.p), pcm_device, nullptr, stream_stride_floats);
 }
 
 int ss_meter_bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
@@ -431,10 +415,9 @@ int ss_meter_bank_read(ss_meter_bank *m, ss_meter_reading *out, uint32_t cap_str
     if (!out) return SS_ERR_INVALID_ARG;
     if (cap_streams < m->meter.n) return SS_ERR_CAPACITY;
     HIPCHK(ssk::launch_meter_bank_readings(m->meter.bank_params(), m->readings.p, m->stream));
-    HIPCHK(hipMemcpyAsync(m->pin_read, m->readings.p, m->meter.n * sizeof(ssk::MeterReading), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->pin_busy = false;
-    std::memcpy(out, m->pin_read, m->meter.n * sizeof(ss_meter_reading));
+    HIPCHK(hipMemcpyAsync(m->pin_read.p, m->readings.p, m->meter.n * sizeof(ssk::MeterReading), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(bank_sync(m));
+    std::memcpy(out, m->pin_read.p, m->meter.n * sizeof(ss_meter_reading));
     return SS_OK;
 }
 
@@ -444,17 +427,11 @@ int ss_meter_bank_peaks(ss_meter_bank *m, uint32_t stream, double *true_pk, doub
     if (!m) return null_bank();
     if (stream >= m->meter.n) return SS_ERR_INVALID_ARG;
     if ((true_pk || sample_pk) && cap_channels < m->meter.channels) return SS_ERR_CAPACITY;
-    static_assert(offsetof(ssk::TdState, true_peak) == offsetof(ssk::TdState, sample_peak) + sizeof(float) * ssk::kMaxChannels,
-                  "sample_peak and true_peak are read as one block");
     float pk[2 * ssk::kMaxChannels];
     HIPCHK(hipMemcpyAsync(pk, &m->meter.state.p[stream].sample_peak[0], sizeof pk, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->pin_busy = false;
-    for (uint32_t c = 0; c < m->meter.channels; c++) {
-        const float sp = pk[c], tp = pk[ssk::kMaxChannels + c];
-        if (sample_pk) sample_pk[c] = (double)sp;
-        if (true_pk) true_pk[c] = (double)(tp > sp ? tp : sp);       // true_peak(): max(true, sample)
-    }
+    HIPCHK(bank_sync(m));
+    for (uint32_t c = 0; c < m->meter.channels; c++)
+        peaks_of(pk, c, sample_pk ? sample_pk + c : nullptr, true_pk ? true_pk + c : nullptr);
     return SS_OK;
 }
 
@@ -465,8 +442,7 @@ int ss_meter_bank_histograms(ss_meter_bank *m, uint32_t stream, uint64_t *out200
     if (stream >= m->meter.n || !out2000) return SS_ERR_INVALID_ARG;
     HIPCHK(hipMemcpyAsync(out2000, m->meter.hist.p + (size_t)stream * 2 * sst::kHistBins, 2 * sst::kHistBins * sizeof(uint64_t),
                           hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->pin_busy = false;
+    HIPCHK(bank_sync(m));
     return SS_OK;
 }
 
@@ -475,7 +451,7 @@ int ss_meter_bank_spectrum_enable(ss_meter_bank *m, int enable)
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
     if (!enable) {
-        HIPCHK(hipStreamSynchronize(m->stream));
+        HIPCHK(bank_sync(m));
         m->spec_on = false;
         m->spec_hist.release(); m->spec_out.release(); m->spec_status.release();
         return SS_OK;

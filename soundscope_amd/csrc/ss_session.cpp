@@ -18,18 +18,16 @@ struct ss_session {
     // since the last tick waits in page-locked memory; a tick shifts the ring by that much on the device (into pcm_alt, then the two
     // swap) and uploads only the new samples
     DevBuf<float> pcm_alt;
-    float *pending = nullptr;           // pinned, n_samples floats: the newest pushed samples, oldest first
+    PinBuf<float> pending;              // n_samples floats: the newest pushed samples, oldest first
     size_t pending_n = 0;
     std::vector<float> tail;            // host copy of the ring's newest 2 * SS_TICK_WINDOW samples (the crate's value checks)
     DevBuf<float> wave;                 // file open: [bins][2] of the whole-file chart (released behind it)
     hipEvent_t ev_tick = nullptr;       // behind a file tick's last result (the gating of the new sub-blocks runs after it)
-    float *stage = nullptr;             // pinned: 2 * bin_stride floats (the two dB rows of a tick) | capture: [bins][2] chart floats
-    double *stage_d = nullptr;          // pinned: short-term loudness (2 doubles)
-    float *stage_dev = nullptr;         // the same two, as the device sees them: the file tick's kernels write their results
-    double *stage_d_dev = nullptr;      // straight into the pinned memory (no copy launch behind them)
-    uint32_t *row_flag = nullptr, *row_flag_dev = nullptr;      // pinned: [mid, side] = the tick whose row stands in `stage`
+    // page-locked results: a tick's kernels write them straight into the memory (PinBuf::dev; no copy launch behind them)
+    PinBuf<float> stage;                // 2 * bin_stride floats (the two dB rows of a tick) | capture: [bins][2] chart floats
+    PinBuf<double> stage_d;             // short-term loudness (2 doubles)
+    PinBuf<uint32_t> row_flag;          // [mid, side] = the tick whose row stands in `stage`
     uint32_t tick_seq = 0;              // file ticks so far (the value the spectrum's workgroups store into row_flag)
-    size_t stage_floats = 0;
     FftTables *ft = nullptr;
     BinTables *bt = nullptr;
     ssk::SpecPlan fft_plan;             // a tick's mid/side spectrum: one stereo window of SS_TICK_WINDOW frames
@@ -93,22 +91,9 @@ int session_common_init(ss_session *s, uint32_t meter_channels, uint32_t rate)
     s->bin_stride = (uint32_t)((s->bt->count + 3) & ~(size_t)3);
     if (s->bin_stride == 0) s->bin_stride = 4;
     HIPCHK(hipEventCreateWithFlags(&s->ev_tick, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->stage_d), 2 * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->stage_d_dev), s->stage_d, 0));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->row_flag), 2 * sizeof(uint32_t), hipHostMallocDefault));
-    s->row_flag[0] = s->row_flag[1] = 0u;
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->row_flag_dev), s->row_flag, 0));
-    return SS_OK;
-}
-
-int session_stage(ss_session *s, size_t floats)
-{
-    if (floats <= s->stage_floats) return SS_OK;
-    if (s->stage) (void)hipHostFree(s->stage);
-    s->stage = nullptr; s->stage_dev = nullptr; s->stage_floats = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->stage), floats * sizeof(float), hipHostMallocDefault));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->stage_dev), s->stage, 0));
-    s->stage_floats = floats;
+    HIPCHK(s->stage_d.alloc(2));
+    HIPCHK(s->row_flag.alloc(2));
+    s->row_flag.p[0] = s->row_flag.p[1] = 0u;
     return SS_OK;
 }
 
@@ -143,7 +128,7 @@ struct TickCore {
         if (samples) {
             TickExtras extras;
             extras.fft = fft;
-            extras.shortterm_out = s->stage_d_dev;
+            extras.shortterm_out = s->stage_d.dev;
             res->add_status = add_samples_impl(h, samples, SS_TICK_WINDOW, true, &gating, &extras);
             if (res->add_status == SS_ERR_DEVICE) return SS_ERR_DEVICE;
             any_launch = res->add_status == SS_OK;
@@ -159,7 +144,7 @@ struct TickCore {
                 res->shortterm_status = SS_ERR_INVALID_MODE;
             } else {
                 // (energy, loudness) written by the kernel into the pinned pair itself
-                int rc = ring_loudness_enqueue(h, h->meter.s100 * 30, s->stage_d_dev);
+                int rc = ring_loudness_enqueue(h, h->meter.s100 * 30, s->stage_d.dev);
                 if (rc) return rc;
                 st_launched = any_launch = true;
             }
@@ -250,10 +235,6 @@ void ss_session_close(ss_session *s)
     if (!s) return;
     if (s->an) ss_analyzer_destroy(s->an);
     if (s->ev_tick) (void)hipEventDestroy(s->ev_tick);
-    if (s->stage) (void)hipHostFree(s->stage);
-    if (s->stage_d) (void)hipHostFree(s->stage_d);
-    if (s->row_flag) (void)hipHostFree(s->row_flag);
-    if (s->pending) (void)hipHostFree(s->pending);
     delete s;
 }
 
@@ -329,8 +310,7 @@ int ss_session_open_file(const float *interleaved, size_t n_samples, uint32_t ch
     double integrated = 0.0;
     rc = integrated_oneshot(sample_rate, 2, s->pcm.p, n_samples, true, &integrated);
     s->gain_db = rc ? 0.0f : (-13.0f - (float)integrated);
-    rc = session_stage(s.get(), (size_t)2 * s->bin_stride);
-    if (rc) return rc;
+    HIPCHK(s->stage.ensure((size_t)2 * s->bin_stride));
     *out = s.release();
     return SS_OK;
 }
@@ -352,11 +332,10 @@ int ss_session_open_capture(uint32_t channels, uint32_t sample_rate, ss_session 
     s->tail.assign((size_t)2 * SS_TICK_WINDOW, 0.0f);
     // what the capture callback pushes between two ticks: page-locked, allocated HERE — ss_session_capture_push stands in for the
     // audio callback's audio_buf.extend (a real-time thread) and must not call into the driver
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->pending), s->n_samples * sizeof(float), hipHostMallocDefault));
+    HIPCHK(s->pending.alloc(s->n_samples));
     size_t window, bins;
     waveform_shape(s->n_samples / 2, 15.0, &window, &bins);
-    rc = session_stage(s.get(), (size_t)2 * s->bin_stride + 2 * bins);
-    if (rc) return rc;
+    HIPCHK(s->stage.ensure((size_t)2 * s->bin_stride + 2 * bins));
     *out = s.release();
     return SS_OK;
 }
@@ -459,9 +438,9 @@ int ss_session_tick_file(ss_session *s, size_t pos, double *mid_xy, double *side
     // until round 4 — when their hardware queues happened to sit on one pipe of the command processor the spectrum did not
     // start before the time-domain kernel had finished: 98 instead of 65 us for the whole life of such a session,
     // tools/probe_tick_queues.sh.)  Results land in pinned memory straight from the kernels.
-    ssk::FftBatchParams fft_p = fft_wanted ? session_fft_params(s, s->pcm.p, fft_lb, s->stage_dev) : ssk::FftBatchParams{};
+    ssk::FftBatchParams fft_p = fft_wanted ? session_fft_params(s, s->pcm.p, fft_lb, s->stage.dev) : ssk::FftBatchParams{};
     const uint32_t seq = ++s->tick_seq ? s->tick_seq : ++s->tick_seq;          // (never 0: the flags' initial value)
-    fft_p.done_flag = s->row_flag_dev; fft_p.done_value = seq;
+    fft_p.done_flag = s->row_flag.dev; fft_p.done_value = seq;
     // loudness: the last 16384 interleaved samples, every tick (8x overlap at hop 1024 frames)
     const size_t pos_i = pos_f * s->file_channels;
     const size_t lufs_lb = pos_i > SS_TICK_WINDOW ? pos_i - SS_TICK_WINDOW : 0;
@@ -494,11 +473,11 @@ int ss_session_tick_file(ss_session *s, size_t pos, double *mid_xy, double *side
     // the rows are taken behind the event as before.)
     bool mid_done = false, side_done = false;
     if (res->fft_ran && fft_launched) {
-        if (wait_row_flag(&s->row_flag[0], seq)) {
-            session_emit_spectrum(s, s->stage, mid_st, mid_xy, &res->mid_status, &res->n_mid, true);
+        if (wait_row_flag(&s->row_flag.p[0], seq)) {
+            session_emit_spectrum(s, s->stage.p, mid_st, mid_xy, &res->mid_status, &res->n_mid, true);
             mid_done = true;
-            if (wait_row_flag(&s->row_flag[1], seq)) {
-                session_emit_spectrum(s, s->stage + s->bin_stride, side_st, side_xy, &res->side_status, &res->n_side, true);
+            if (wait_row_flag(&s->row_flag.p[1], seq)) {
+                session_emit_spectrum(s, s->stage.p + s->bin_stride, side_st, side_xy, &res->side_status, &res->n_side, true);
                 side_done = true;
             }
         }
@@ -510,12 +489,12 @@ int ss_session_tick_file(ss_session *s, size_t pos, double *mid_xy, double *side
     SS_TICK_T(6);
     if (res->fft_ran) {
         if (!mid_done)
-            session_emit_spectrum(s, s->stage, fft_launched ? mid_st : (mid_st ? mid_st : SS_OK), mid_xy,
+            session_emit_spectrum(s, s->stage.p, fft_launched ? mid_st : (mid_st ? mid_st : SS_OK), mid_xy,
                                   &res->mid_status, &res->n_mid, true);
         if (!side_done)
-            session_emit_spectrum(s, s->stage + s->bin_stride, side_st, side_xy, &res->side_status, &res->n_side, true);
+            session_emit_spectrum(s, s->stage.p + s->bin_stride, side_st, side_xy, &res->side_status, &res->n_side, true);
     }
-    if (res->fed) s->lufs[SS_LUFS_HISTORY - 1] = tick.st_launched ? s->stage_d[1] : 0.0;
+    if (res->fed) s->lufs[SS_LUFS_HISTORY - 1] = tick.st_launched ? s->stage_d.p[1] : 0.0;
     res->shortterm = s->lufs[SS_LUFS_HISTORY - 1];
     return SS_OK;
 }
@@ -535,7 +514,7 @@ static int capture_tick_body(ss_session *s, const float *newest, double *mid_xy,
     // everything is written into pinned memory by the kernels.  The crate's value checks on the two slices run on the host
     // while the device works.
     const bool fft_wanted = !lim && s->bt->count;
-    ssk::FftBatchParams fft_p = fft_wanted ? session_fft_params(s, s->pcm.p, lb, s->stage_dev) : ssk::FftBatchParams{};
+    ssk::FftBatchParams fft_p = fft_wanted ? session_fft_params(s, s->pcm.p, lb, s->stage.dev) : ssk::FftBatchParams{};
     std::memmove(&s->lufs[0], &s->lufs[1], (SS_LUFS_HISTORY - 1) * sizeof(double));
     TickCore tick(s);
     int rc = tick.run(s->pcm.p + (n - SS_TICK_WINDOW), fft_wanted ? &fft_p : nullptr, res);
@@ -544,7 +523,7 @@ static int capture_tick_body(ss_session *s, const float *newest, double *mid_xy,
     if (wave_xy && bins) {
         ssk::WaveParams p{};
         p.pcm = s->pcm.p; p.stream_stride = 0; p.n_samples = pairs; p.n_streams = 1; p.mid_of_pairs = 1;
-        p.window = (uint32_t)window; p.out = s->stage_dev + (size_t)2 * s->bin_stride; p.out_stride = 2 * bins;
+        p.window = (uint32_t)window; p.out = s->stage.dev + (size_t)2 * s->bin_stride; p.out_stride = 2 * bins;
         HIPCHK(ssk::launch_waveform(p, h->stream));
     }
     rc = tick.close(true);
@@ -565,14 +544,14 @@ static int capture_tick_body(ss_session *s, const float *newest, double *mid_xy,
     if (wave_xy && bins)
         for (size_t i = 0; i < bins; i++) { wave_xy[4 * i + 0] = (double)i; wave_xy[4 * i + 2] = (double)i; }
     HIPCHK(hipEventSynchronize(s->ev_tick));
-    session_emit_spectrum(s, s->stage, mid_st, mid_xy, &res->mid_status, &res->n_mid, true);
-    session_emit_spectrum(s, s->stage + s->bin_stride, side_st, side_xy, &res->side_status, &res->n_side, true);
+    session_emit_spectrum(s, s->stage.p, mid_st, mid_xy, &res->mid_status, &res->n_mid, true);
+    session_emit_spectrum(s, s->stage.p + s->bin_stride, side_st, side_xy, &res->side_status, &res->n_side, true);
     if (wave_xy && bins) {
-        const float *mm = s->stage + (size_t)2 * s->bin_stride;
+        const float *mm = s->stage.p + (size_t)2 * s->bin_stride;
         for (size_t i = 0; i < bins; i++) { wave_xy[4 * i + 1] = (double)mm[2 * i]; wave_xy[4 * i + 3] = (double)mm[2 * i + 1]; }
         if (wave_n) *wave_n = 2 * bins;
     }
-    s->lufs[SS_LUFS_HISTORY - 1] = tick.st_launched ? s->stage_d[1] : 0.0;
+    s->lufs[SS_LUFS_HISTORY - 1] = tick.st_launched ? s->stage_d.p[1] : 0.0;
     res->shortterm = s->lufs[SS_LUFS_HISTORY - 1];
     return SS_OK;
 }
@@ -615,19 +594,19 @@ int ss_session_tick_capture(ss_session *s, const float *latest, size_t n, double
 int ss_session_capture_push(ss_session *s, const float *samples, size_t n)
 {
     // host work only (two memcpy): no HIP call, nothing that can block or fail on the capture callback's thread
-    if (!s || s->is_file || !s->pending || (!samples && n)) return SS_ERR_INVALID_ARG;
+    if (!s || s->is_file || !s->pending.p || (!samples && n)) return SS_ERR_INVALID_ARG;
     if (n == 0) return SS_OK;
     const size_t N = s->n_samples;
     if (n >= N) {                                                // more than a whole ring at once: its newest N samples are the ring
-        std::memcpy(s->pending, samples + (n - N), N * sizeof(float));
+        std::memcpy(s->pending.p, samples + (n - N), N * sizeof(float));
         s->pending_n = N;
     } else {
         if (s->pending_n + n > N) {                              // (no tick for 15 s: the oldest pushed samples have left the ring)
             const size_t drop = s->pending_n + n - N;
-            std::memmove(s->pending, s->pending + drop, (s->pending_n - drop) * sizeof(float));
+            std::memmove(s->pending.p, s->pending.p + drop, (s->pending_n - drop) * sizeof(float));
             s->pending_n -= drop;
         }
-        std::memcpy(s->pending + s->pending_n, samples, n * sizeof(float));
+        std::memcpy(s->pending.p + s->pending_n, samples, n * sizeof(float));
         s->pending_n += n;
     }
     const size_t T = s->tail.size();
@@ -651,11 +630,11 @@ int ss_session_tick_capture_resident(ss_session *s, double *mid_xy, double *side
     const size_t N = s->n_samples, k = s->pending_n;
     hipStream_t st = s->an->stream;
     if (k >= N) {
-        HIPCHK(hipMemcpyAsync(s->pcm.p, s->pending, N * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->pcm.p, s->pending.p, N * sizeof(float), hipMemcpyHostToDevice, st));
     } else if (k) {
         if (!s->pcm_alt.p) HIPCHK(s->pcm_alt.alloc(N));
         HIPCHK(hipMemcpyAsync(s->pcm_alt.p, s->pcm.p + k, (N - k) * sizeof(float), hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->pcm_alt.p + (N - k), s->pending, k * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->pcm_alt.p + (N - k), s->pending.p, k * sizeof(float), hipMemcpyHostToDevice, st));
         s->pcm.swap(s->pcm_alt);
     }
     s->pending_n = 0;                                            // (the tick below waits for the stream: `pending` is free again)

@@ -236,6 +236,47 @@ def test_input_forms(oracle):
     src.close()
 
 
+def test_staging_regrows_between_calls(oracle):
+    """Six calls with nothing that waits for the stream between them: every call but the last grows or reuses the page-locked
+    staging buffer while the previous call's copy may still be in flight (64 frames, 4 800: grown, 64 of s24: reused, a ragged
+    call of (20 000, 0, 7): grown, a reset's list and 960 frames: reused).  Then one read: every stream equals a handle fed and
+    reset the same way, as test_bank_equals_handles_bit_for_bit holds them."""
+    n, rate, channels = 3, 48000, 2
+    ragged = [20000, 0, 7]
+    s24 = np.random.default_rng(11).integers(-(1 << 23), (1 << 23) - 1, (n, 64 * channels), dtype=np.int32)
+    raw = np.stack([s24 & 0xFF, (s24 >> 8) & 0xFF, (s24 >> 16) & 0xFF], axis=-1).astype(np.uint8)          # [n][samples][3]
+    decoded = [oracle.pcm_to_f32(raw[s].tobytes(), L.SS_PCM_S24) for s in range(n)]
+    xs = [material(1100 + s, 64 + 4800 + ragged[s] + 960, channels, rate, level=0.2 + 0.2 * s) for s in range(n)]
+    cut = [np.cumsum([0, 64, 4800, ragged[s], 960]) * channels for s in range(n)]
+    part = lambda s, i: xs[s][cut[s][i]:cut[s][i + 1]]
+
+    bank = ssa.MeterBank(n, channels, rate)
+    bank.add(np.stack([part(s, 0) for s in range(n)]))
+    bank.add(np.stack([part(s, 1) for s in range(n)]))
+    bank.add_pcm(raw, L.SS_PCM_S24)
+    bank.add_ragged([part(s, 2) if ragged[s] else None for s in range(n)])
+    bank.reset([1])
+    bank.add(np.stack([part(s, 3) for s in range(n)]))
+    rec = bank.read()
+
+    for s in range(n):
+        h = ssa.Analyzer()
+        h.create_loudness_meter(channels, rate)
+        for blk in (part(s, 0), part(s, 1), decoded[s], part(s, 2)):
+            h.add_samples(blk)
+        if s == 1:
+            h.reset()
+        h.add_samples(part(s, 3))
+        r = rec[s]
+        assert r["frames"] == (960 if s == 1 else 64 + 4800 + 64 + ragged[s] + 960), s
+        assert r["integrated"] == h.get_integrated_lufs() and r["loudness_range"] == h.get_loudness_range(), s
+        assert close9(r["momentary"], h.get_momentary_lufs()) and close9(r["shortterm"], h.get_shortterm_lufs()), s
+        tp, sp = bank.peaks(s)
+        for c in range(channels):
+            assert sp[c] == h.get_sample_peak_channel(c) and tp[c] == h.get_true_peak_channel(c), (s, c)
+            assert r["sample_peak"][c] == sp[c] and r["true_peak"][c] == tp[c], (s, c)
+
+
 def test_scale_1024_live_inputs(oracle):
     """1024 stereo 48 kHz streams fed 10 ms blocks for 5 s straight from device memory (a batch's synthesised input): 32
     sampled streams against the oracle, every stream's integrated loudness and range against the batch pass over the same
