@@ -1,7 +1,7 @@
 // ss_batch.cpp — the batch extension of the C ABI (NOT in the reference): many streams resident in HBM analysed in one
 // pass — the data-parallel form of receive_audio_file + analyze_audio_file_samples
-// (/root/reference/src/tui.rs:1207-1241, :1482-1552) over a corpus — plus the render-side reductions (N3) and the
-// one-shot calculate_integrated_lufs (/root/reference/src/analyzer.rs:170-182), which runs the batch path on one stream.
+// (the reference's src/tui.rs:1207-1241, :1482-1552) over a corpus — plus the render-side reductions (N3) and the
+// one-shot calculate_integrated_lufs (src/analyzer.rs:170-182), which runs the batch path on one stream.
 #include "ss_host.h"
 
 using namespace ssh;
@@ -9,6 +9,86 @@ using namespace ssh;
 // ============================================================================
 //  batch
 // ============================================================================
+namespace {
+
+// Per-kernel event timing: a ring of kDepth passes' event sets, so that timed passes queue back to back without a host
+// synchronisation between them (bench.py times its kernels INSIDE the timed region); collected when read, or when the ring is full.
+struct TimingRing {
+    static constexpr uint32_t kDepth = 32;
+    bool on = false;
+    hipEvent_t ev[kDepth * 2 * SS_KERNEL_COUNT] = {};   // [pass][kernel][edge]
+    uint32_t mask[kDepth] = {};                         // which of a pass's events were recorded
+    uint32_t head = 0, count = 0;                       // next slot to record into; passes recorded and not yet collected
+    double ms[SS_KERNEL_COUNT] = {};
+    uint64_t launches[SS_KERNEL_COUNT] = {};
+    ~TimingRing() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t create() { hipError_t r = hipSuccess; for (auto &e : ev) if (r == hipSuccess) r = hipEventCreate(&e); return r; }
+    // edge 0: the kernel's slot of this pass begins on `stream`, 1: it has ended (timing off: nothing)
+    hipError_t mark(int kernel, int edge, hipStream_t stream)
+    {
+        if (!on) return hipSuccess;
+        const int idx = 2 * kernel + edge;
+        mask[head] |= 1u << idx;
+        return hipEventRecord(ev[(size_t)head * 2 * SS_KERNEL_COUNT + idx], stream);
+    }
+    void advance() { if (on) { head = (head + 1u) % kDepth; count++; } }      // the pass is queued
+    int collect(hipStream_t stream)
+    {
+        if (!count) return SS_OK;
+        HIPCHK(hipStreamSynchronize(stream));
+        for (uint32_t i = 0; i < count; i++) {
+            const uint32_t slot = (head + kDepth - count + i) % kDepth;
+            hipEvent_t *e = ev + (size_t)slot * 2 * SS_KERNEL_COUNT;
+            for (int k = 0; k < SS_KERNEL_COUNT; k++) {
+                if ((mask[slot] >> (2 * k) & 3u) != 3u) continue;       // this pass did not run kernel k
+                float t = 0.f;
+                if (hipEventElapsedTime(&t, e[2 * k], e[2 * k + 1]) == hipSuccess) { ms[k] += t; launches[k]++; }
+            }
+            mask[slot] = 0;
+        }
+        count = 0;
+        return SS_OK;
+    }
+    void reset() { for (int k = 0; k < SS_KERNEL_COUNT; k++) { ms[k] = 0; launches[k] = 0; } }
+};
+
+// opt-in (ss_batch_set_overlap): the spectrum kernel on a second stream beside the time-domain chain
+struct Overlap {
+    int mode = 0;                     // 0 sequential, 1 the spectrum kernel beside the time-domain chain, 2 beside its tail only
+    hipStream_t stream2 = nullptr;    // (from the pool: ss_batch_destroy hands it back)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    ~Overlap() { for (hipEvent_t e : {ev_fork, ev_join}) if (e) (void)hipEventDestroy(e); }
+    // what is queued on `then` from here on runs behind everything queued on `first` so far
+    static hipError_t order(hipEvent_t ev, hipStream_t first, hipStream_t then) { hipError_t e = hipEventRecord(ev, first); return e == hipSuccess ? hipStreamWaitEvent(then, ev, 0) : e; }
+    // fork: stream2 goes on behind everything already queued on the main stream (uploads, the previous pass)
+    hipError_t fork(hipStream_t main_stream) { return order(ev_fork, main_stream, stream2); }
+    // join: later work on the main stream (downloads, the next pass) sees what stream2 did
+    hipError_t join(hipStream_t main_stream) { return order(ev_join, stream2, main_stream); }
+};
+
+// columns-only spectrum (SS_BATCH_FFT_COLUMNS): the reduction fused into the spectrum kernel's epilogue
+struct Columns {
+    bool on = false;
+    int gain_mode = SS_GAIN_FIXED;
+    float gain_db = 0.0f;
+    DevBuf<uint16_t> bin_col;       // chart column of every retained bin (0xFFFF for the row padding)
+    DevBuf<uint2> groups;           // the same per group of four bins (FftBatchParams::col_groups)
+    DevBuf<float> init;             // FftBatchParams::col_init
+    DevBuf<uint2> bins;             // FftBatchParams::col_bins
+};
+
+// ragged batches (ss_batch_set_lengths): per-stream frames / windows / sub-blocks / decimation bins
+struct Ragged {
+    bool on = false;
+    std::vector<uint64_t> frames_h;
+    std::vector<uint32_t> sub_h;
+    uint32_t max_sub = 0;           // sub-blocks of the LONGEST stream (the time-domain geometry follows the lengths, not the slot size)
+    DevBuf<uint64_t> frames_d, wave_samples_d;
+    DevBuf<uint32_t> windows_d, sub_d, wave_window_d;
+};
+
+}  // namespace
+
 struct ss_batch {
     int device = 0;             // the HIP device this batch lives on
     ss_batch_config cfg{};
@@ -23,13 +103,13 @@ struct ss_batch {
         uint32_t split_batch = ssk::kTdSplitNone;       // (ragged lengths: one wave per stream / segment)
         bool fixup = false;                             // segments > 0 hand over exactly: the fix-up launch re-runs their first fix_sub
     } td_plan;
-    uint32_t td_nsub_hint = 0;      // ragged batches: sub-blocks of the LONGEST stream (the geometry follows the lengths, not the slot size)
     int td_mode = 0;                // ss_batch_set_time_domain_mode
     bool wave_fused = false;     // decimation runs inside the time-domain kernel
     uint32_t wave_halo = 0;
     FftTables *ft = nullptr;
     BinTables *bt = nullptr;
     TdTables *td = nullptr;
+    const double *hist_energies = nullptr, *hist_bounds = nullptr;      // the gate's histogram tables (get_hist_tables)
     DevBuf<float> pcm, fft, wave;
     DevBuf<ssk::TdState> state;
     DevBuf<double> sub, weights, integrated, lra, out2;
@@ -38,43 +118,23 @@ struct ss_batch {
     DevBuf<uint32_t> counts;
     DevBuf<unsigned char> raw;      // device staging of raw PCM for the asynchronous ingest
     DevBuf<uint64_t> checks;        // ss_batch_checksums: [stream][3]
-    // SS_BATCH_LOUDNESS_SERIES: [stream][n_subblocks][2] (momentary, short-term) LUFS and the per-stream maxima
+    // SS_BATCH_LOUDNESS_SERIES: [stream][sub_cap()][2] (momentary, short-term) LUFS and the per-stream maxima
     DevBuf<double> series;
     DevBuf<ssk::LoudnessExtremes> extremes;
-    // ragged batches (ss_batch_set_lengths): per-stream frames / windows / sub-blocks / decimation bins
-    bool ragged = false;
-    std::vector<uint64_t> frames_h, wave_samples_h;
-    std::vector<uint32_t> windows_h, sub_h, wave_window_h;
-    DevBuf<uint64_t> frames_d, wave_samples_d;
-    DevBuf<uint32_t> windows_d, sub_d, wave_window_d;
-    // render-side reductions (N3)
+    Ragged ragged;
+    // render-side reductions (N3); render_spec holds the columns-only rows as well
     DevBuf<float> render_spec, render_wave;
     DevBuf<uint32_t> col_start;
     uint32_t render_cols = 0, render_wave_cols = 0;
-    // columns-only spectrum (SS_BATCH_FFT_COLUMNS): the reduction fused into the spectrum kernel's epilogue
-    bool columns_only = false;
-    int columns_gain_mode = SS_GAIN_FIXED;
-    float columns_gain_db = 0.0f;
-    DevBuf<uint16_t> bin_col;       // chart column of every retained bin (0xFFFF for the row padding)
-    DevBuf<uint2> col_groups;       // the same per group of four bins (FftBatchParams::col_groups)
-    DevBuf<float> col_init;         // FftBatchParams::col_init
-    DevBuf<uint2> col_bins;         // FftBatchParams::col_bins
-    // opt-in (SS_BATCH_OVERLAP=1): the spectrum kernel on a second stream beside the time-domain chain
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Columns cols;
+    Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
     int tp_arith = SS_TP_ARITH_F32;   // SS_TP_ARITH_*: the reference's width unless the caller opts into the f16 split
-    int overlap = 0;                  // 0 sequential, 1 the spectrum kernel beside the time-domain chain, 2 beside its tail only
-    bool timing = false;
-    // per-kernel event timing: a ring of kTimingDepth passes' event sets, so that timed passes queue back to back without a host
-    // synchronisation between them (bench.py times its kernels INSIDE the timed region); collected when read, or when the ring is full
-    static constexpr int kTimingDepth = 32;
-    hipEvent_t ev[kTimingDepth * 2 * SS_KERNEL_COUNT] = {};
-    uint32_t ev_mask[kTimingDepth] = {};       // which of a pass's events were recorded
-    uint32_t ev_head = 0, ev_count = 0;        // next slot to record into; passes recorded and not yet collected
-    bool ev_ready = false;
-    double t_ms[SS_KERNEL_COUNT] = {0, 0, 0, 0};
-    uint64_t t_n[SS_KERNEL_COUNT] = {0, 0, 0, 0};
+    TimingRing timing;
+
+    // sub-block slots per stream in sub and series (a stream shorter than one sub-block still has a slot)
+    uint32_t sub_cap() const { return lay.n_subblocks ? lay.n_subblocks : 1; }
+    size_t samples_per_stream() const { return (size_t)cfg.frames_per_stream * cfg.channels; }
 };
 
 namespace ssi {
@@ -85,26 +145,6 @@ bool &batch_corpus_reduced(ss_batch *b) { return b->corpus_reduced; }
 }  // namespace ssi
 
 namespace {
-
-
-int batch_collect_timing(ss_batch *b)
-{
-    if (!b->ev_count) return SS_OK;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    constexpr uint32_t D = ss_batch::kTimingDepth;
-    for (uint32_t i = 0; i < b->ev_count; i++) {
-        const uint32_t slot = (b->ev_head + D - b->ev_count + i) % D;
-        hipEvent_t *ev = b->ev + (size_t)slot * 2 * SS_KERNEL_COUNT;
-        for (int k = 0; k < SS_KERNEL_COUNT; k++) {
-            if ((b->ev_mask[slot] >> (2 * k) & 3u) != 3u) continue;       // this pass did not run kernel k
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) == hipSuccess) { b->t_ms[k] += ms; b->t_n[k]++; }
-        }
-        b->ev_mask[slot] = 0;
-    }
-    b->ev_count = 0;
-    return SS_OK;
-}
 
 // What a stream of F frames holds under a batch's config (ss_batch_create, ss_batch_set_lengths, ss_batch_stream_shape):
 //  * spectrum windows at the cadence of analyze_audio_file_samples (tui.rs:1482-1526): window [p-N, p) at p = k*hop, skipped
@@ -129,9 +169,12 @@ StreamShape stream_shape(const ss_batch_config &c, uint64_t s100, uint64_t F)
     }
     return sh;
 }
+StreamShape stream_shape(const ss_batch *b, uint64_t F) { return stream_shape(b->cfg, b->td ? b->td->host.s100 : 0, F); }
+
+// ---- the parameter blocks of a pass's launches --------------------------------------------------------------------
 
 // the spectrum launch of a batch (ss_batch_run, ss_batch_traffic_floor): the plan's and the tables' fields, rows with the pink
-// compensation, the batch's input and rows
+// compensation, the batch's input and rows, the ragged window counts, the columns-only reduction
 ssk::FftBatchParams batch_fft_params(const ss_batch *b)
 {
     const ss_batch_config &c = b->cfg;
@@ -139,12 +182,85 @@ ssk::FftBatchParams batch_fft_params(const ss_batch *b)
     p.pcm = b->pcm.p; p.out = b->fft.p;
     p.frames_per_stream = c.frames_per_stream; p.first_start = b->first_start;
     p.n_streams = c.n_streams; p.channels = c.channels; p.n_windows = b->lay.n_windows; p.hop = c.hop_frames;
+    p.windows_of = b->ragged.on ? b->ragged.windows_d.p : nullptr;
+    if (b->cols.on) {
+        p.out_cols = b->render_spec.p; p.bin_col = b->cols.bin_col.p; p.col_groups = b->cols.groups.p; p.col_init = b->cols.init.p; p.col_bins = b->cols.bins.p; p.cols = b->render_cols;
+        p.integrated = b->cols.gain_mode == SS_GAIN_REFERENCE ? b->integrated.p : nullptr;
+        p.gain_db = b->cols.gain_db;
+    }
     return p;
 }
 
-}  // namespace
+// the time-domain launch and its fix-up (a batch with a meter pass: b->td)
+ssk::TdParams batch_td_params(const ss_batch *b)
+{
+    const ss_batch_config &c = b->cfg;
+    const uint32_t C = c.channels;
+    ssk::TdParams p{};
+    p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * C; p.n_frames = c.frames_per_stream;
+    p.n_streams = c.n_streams; p.channels = C; p.k = b->td->dev.p; p.state = b->state.p;
+    p.subblocks = b->sub.p; p.sub_cap = b->sub_cap();
+    p.sub_stride = (uint64_t)p.sub_cap * C; p.tp_factor = b->tp_factor;
+    const auto &plan = b->td_plan;
+    p.s100 = b->td->host.s100; p.nseg = plan.nseg; p.seg_sub = plan.seg_sub;
+    p.warm_sub = plan.warm_sub; p.fix_sub = plan.fix_sub; p.split_batch = plan.split_batch;
+    if (plan.fixup) p.seg_state = b->seg_state.p;       // (sized with the plan: choose_td_geometry)
+    p.frames_of = b->ragged.on ? b->ragged.frames_d.p : nullptr;
+    p.tp_f32 = b->tp_arith == SS_TP_ARITH_F32 ? 1u : 0u;
+    if (b->wave_fused && !b->ragged.on) { p.wave_out = b->wave.p; p.wave_stride = (uint64_t)2 * b->wave_window; p.wave_window = b->wave_window; p.halo_frames = b->wave_halo; }
+    return p;
+}
 
-extern "C" {
+// the gating of every stream's sub-blocks and the loudness series behind it
+ssk::FinalizeParams batch_gating_params(const ss_batch *b)
+{
+    const uint32_t C = b->cfg.channels;
+    ssk::FinalizeParams f{};
+    f.k = b->td->dev.p; f.subblocks = b->sub.p; f.sub_cap = b->sub_cap();
+    f.sub_stride = (uint64_t)f.sub_cap * C;
+    f.hist_energies = b->hist_energies; f.hist_bounds = b->hist_bounds; f.weights = b->weights.p; f.hist = b->hist.p;
+    f.corpus_hist = b->corpus.p; f.n_streams = b->cfg.n_streams; f.channels = C;
+    f.sub_begin = 0; f.sub_end = b->lay.n_subblocks;
+    f.sub_end_of = b->ragged.on ? b->ragged.sub_d.p : nullptr;
+    f.out_integrated = b->integrated.p; f.out_lra = b->lra.p; f.out_counts = b->counts.p;
+    f.state = b->state.p;
+    return f;
+}
+
+// the standalone decimation (where the time-domain kernel does not carry it)
+ssk::WaveParams batch_wave_params(const ss_batch *b)
+{
+    const ss_batch_config &c = b->cfg;
+    ssk::WaveParams p{};
+    p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * c.channels; p.n_samples = c.frames_per_stream * c.channels;
+    p.n_streams = c.n_streams; p.window = b->wave_window; p.out = b->wave.p; p.out_stride = (uint64_t)2 * b->wave_window;
+    if (b->ragged.on) { p.samples_of = b->ragged.wave_samples_d.p; p.window_of = b->ragged.wave_window_d.p; }
+    return p;
+}
+
+// ---- the steps of a pass ------------------------------------------------------------------------------------------
+
+// meter state, histograms, corpus histograms and block counts start from zero: one launch (they were four fills)
+hipError_t zero_meter(ss_batch *b)
+{
+    void *const ptrs[4] = {b->state.p, b->hist.p, b->corpus.p, b->counts.p};
+    const size_t bytes[4] = {b->state.n * sizeof(ssk::TdState), b->hist.n * sizeof(uint64_t), b->corpus.n * sizeof(uint64_t),
+                             b->counts.n * sizeof(uint32_t)};
+    return ssk::launch_zero4(ptrs, bytes, b->stream);
+}
+
+// the spectrum step, wherever the pass puts it; forked: on stream2, behind what the main stream holds so far
+int spectrum_step(ss_batch *b, bool forked)
+{
+    if (forked) HIPCHK(b->ov.fork(b->stream));
+    HIPCHK(b->timing.mark(SS_KERNEL_FFT, 0, b->stream));
+    if ((b->cfg.flags & SS_BATCH_FFT) && b->lay.n_windows)
+        HIPCHK(ssk::launch_spectrum(b->spec, batch_fft_params(b), forked ? b->ov.stream2 : b->stream));
+    HIPCHK(b->timing.mark(SS_KERNEL_FFT, 1, b->stream));
+    return SS_OK;
+}
+
+// ---- plans made when the shape is known ---------------------------------------------------------------------------
 
 // How the time-domain kernel walks a stream.
 //  * whole-stream workgroups (kTdSplitStreams): a stream is ONE segment, its tiles dealt to the four waves of a workgroup, the filter state
@@ -157,13 +273,14 @@ extern "C" {
 //    length that maximises   useful fraction  seg / (seg + warm)  x  fill of the last round  waves / (ceil(waves / W0) W0)
 //    (ranks the measured config-5 sweep seg = 2..13 in the right order; measured within noise for config 3).
 // mode (ss_batch_set_time_domain_mode): 0 the better score of the two, 1 segments, 2 whole-stream workgroups where the shape allows.
-static void choose_td_geometry(ss_batch *b)
+// The plan's hand-over states (seg_state) are sized here, so a pass allocates nothing: nothing may be running on the batch.
+int choose_td_geometry(ss_batch *b)
 {
-    if (!b->td) return;
+    if (!b->td) return SS_OK;
     const ss_batch_config *cfg = &b->cfg;
     const ss_batch_layout &L = b->lay;
     const uint32_t C = cfg->channels;
-    const uint32_t nsub = b->ragged ? b->td_nsub_hint : L.n_subblocks;
+    const uint32_t nsub = b->ragged.on ? b->ragged.max_sub : L.n_subblocks;
     const double W0 = 256.0 * ssk::td_resident_waves_per_cu(C, b->td->host.s100, b->wave_fused ? b->wave_halo : 0);
     // what a segment boundary costs, in sub-blocks of full work: the run-in (mode 1), or the fix-up's re-run of kTdFixSub sub-blocks
     // at about 0.8 of a full tile each (filter and energies are most of a tile) — config 5's sweep seg = 2 ... 10 with the fix-up:
@@ -216,7 +333,7 @@ static void choose_td_geometry(ss_batch *b)
     if (forgets && split_ok && b->td_mode == 0 && split == ssk::kTdSplitNone && nsub > min_seg && 8.0 * cfg->n_streams * nseg_min <= W0) {
         split = ssk::kTdSplitSegments; plan.seg_sub = min_seg; plan.nseg = nseg_min;
     }
-    plan.split_batch = b->ragged ? ssk::kTdSplitNone : split;
+    plan.split_batch = b->ragged.on ? ssk::kTdSplitNone : split;
     // How segments > 0 start.  The exact hand-over: no run-in, their first kTdFixSub sub-blocks re-run from the true state by a
     // second launch (launch_time_domain_fixup).  Mode 1: the 0.1 s run-in from a zero state of rounds 1-4.  Segments of eight
     // waves (the pass is a latency chain, and a second launch is a fifth of it): every segment runs the FILTER over the kTdFixSub
@@ -228,10 +345,103 @@ static void choose_td_geometry(ss_batch *b)
         else if (b->td_mode == 1) plan.warm_sub = kTdWarmSub;
         else { plan.fixup = true; plan.fix_sub = plan.seg_sub < kTdFixSub ? plan.seg_sub : kTdFixSub; }
     }
+    if (plan.fixup) HIPCHK(b->seg_state.ensure((size_t)cfg->n_streams * plan.nseg * C * 4));
+    return SS_OK;
 }
+
+// the columns-only spectrum's tables: the chart column of every retained bin, per bin and packed per group of four
+int upload_column_tables(ss_batch *b)
+{
+    const ss_batch_layout &L = b->lay;
+    const uint32_t cols = b->cfg.spectrum_columns;
+    std::vector<uint16_t> bc(L.fft_bin_stride, (uint16_t)0xFFFF);
+    for (uint32_t i = 0; i < L.n_bins; i++) bc[i] = (uint16_t)spectrum_column_of(b->bt->chart_x[i], cols);
+    HIPCHK(b->cols.bin_col.upload(bc));
+    std::vector<uint2> cg(L.fft_bin_stride / 4), cbins(L.fft_bin_stride / 4);
+    std::vector<float> cinit(cols, std::numeric_limits<float>::quiet_NaN());
+    for (uint32_t i = 0; i < L.n_bins; i++) cinit[bc[i]] = -std::numeric_limits<float>::infinity();
+    for (uint32_t g = 0; g < cg.size(); g++) {
+        uint32_t o[4];
+        bool general = false;
+        for (uint32_t e = 0; e < 4; e++) {
+            const bool pad = bc[4 * g + e] == 0xFFFF;
+            o[e] = pad ? 2048u : 4u * bc[4 * g + e];
+            general = general || pad;
+        }
+        uint32_t n = 1;
+        while (n < 4 && o[n] == o[0]) n++;
+        for (uint32_t e = n; e < 4; e++) general = general || o[e] != o[3];
+        cg[g] = make_uint2(o[0] | (o[3] << 16), general ? 0u : n);
+        cbins[g] = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+    }
+    HIPCHK(b->cols.bins.upload(cbins));
+    HIPCHK(b->cols.init.upload(cinit));
+    HIPCHK(b->cols.groups.upload(cg));
+    return SS_OK;
+}
+
+// the decimation is fused into the time-domain pass when that pass runs and a bin (plus its shared edge sample)
+// fits the per-wave halo; otherwise the standalone kernel handles it
+void choose_wave_fusion(ss_batch *b)
+{
+    const uint32_t C = b->cfg.channels;
+    const uint64_t W = b->wave_window, len = b->cfg.frames_per_stream * C;
+    const double spp = (double)len / (double)W;
+    if (b->td && W > 0 && spp >= 16.0 && spp <= 1000.0 && len < (1ull << 31)) {
+        // (+ 3: the general decimation path reads the aligned 16-byte piece a bin starts in, up to three samples in front of it)
+        const uint32_t need = ((uint32_t)std::ceil(spp) + 5 + C - 1) / C;
+        uint32_t halo = need < 24 ? 24 : need;
+        halo = (halo + 3u) & ~3u;
+        if (halo <= 512) { b->wave_fused = true; b->wave_halo = halo; }
+    }
+}
+
+// ---- moving data ----------------------------------------------------------------------------------------------------
+
+// The one upload: n samples of `format` at `pcm` become the floats at offset `at` of the batch's input, queued on the batch's
+// stream.  f32 is copied straight in; anything else is copied to `raw` (device staging of n samples and kPcmReadSlack bytes
+// that stays untouched until the conversion has run) and converted from there.  wait: return when the input is there.
+int upload_range(ss_batch *b, size_t at, size_t n, const void *pcm, int format, unsigned char *raw, bool wait)
+{
+    float *dst = b->pcm.p + at;
+    if (format == SS_PCM_F32) raw = reinterpret_cast<unsigned char *>(dst);
+    HIPCHK(hipMemcpyAsync(raw, pcm, n * ss_pcm_sample_bytes(format), hipMemcpyHostToDevice, b->stream));
+    if (format != SS_PCM_F32) HIPCHK(ssk::launch_pcm_to_f32(raw, n, format, dst, b->stream));
+    if (wait) HIPCHK(hipStreamSynchronize(b->stream));
+    return SS_OK;
+}
+
+// The uploads that do not wait stage in one raw area per batch, sized for the whole batch at the format's bytes per sample: the
+// sample at float offset `at` stages at the same offset in samples (ranges of different streams do not overlap); growing it
+// waits for whatever still reads the old one.
+int upload_queued(ss_batch *b, size_t at, size_t n, const void *pcm, int format)
+{
+    const size_t sb = ss_pcm_sample_bytes(format);
+    const size_t bytes = b->samples_per_stream() * b->cfg.n_streams * sb + kPcmReadSlack;
+    if (format != SS_PCM_F32 && b->raw.n < bytes) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        HIPCHK(b->raw.alloc(bytes));
+    }
+    return upload_range(b, at, n, pcm, format, format != SS_PCM_F32 ? b->raw.p + at * sb : nullptr, false);
+}
+
+// The one download: count elements from the device to the host (or to `kind`'s side) on the batch's stream, behind everything
+// queued there, and there when this returns.
+template <typename T>
+int fetch(ss_batch *b, T *dst, const T *src, size_t count, hipMemcpyKind kind = hipMemcpyDeviceToHost)
+{
+    HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), kind, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return SS_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
 {
+    // ---- checks
     if (!cfg || !out) return SS_ERR_INVALID_ARG;
     *out = nullptr;
     if (require_device()) return SS_ERR_DEVICE;
@@ -240,14 +450,11 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
     const bool columns_only = (cfg->flags & SS_BATCH_FFT_COLUMNS) != 0;
     if (columns_only && (!(cfg->flags & SS_BATCH_FFT) || cfg->spectrum_columns == 0 || cfg->spectrum_columns > 512)) return SS_ERR_INVALID_ARG;
     if ((cfg->flags & SS_BATCH_LOUDNESS_SERIES) && !(cfg->flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_ARG;      // the series reads the gating pass
-    // destroyed (streams and events included) on every early return
-    std::unique_ptr<ss_batch, decltype(&ss_batch_destroy)> b(new ss_batch(), &ss_batch_destroy);
-    b->device = current_device();
-    b->cfg = *cfg;
     const uint32_t C = cfg->channels;
     const uint64_t F = cfg->frames_per_stream;
+    const bool meter = (cfg->flags & (SS_BATCH_LUFS | SS_BATCH_TRUE_PEAK)) != 0;
     if (C == 0 || C > 64) return SS_ERR_NOMEM;
-    if (cfg->flags & (SS_BATCH_LUFS | SS_BATCH_TRUE_PEAK)) {
+    if (meter) {
         int rc = meter_args_ok(C, cfg->sample_rate);
         if (rc) return rc;
     }
@@ -259,19 +466,24 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
             __builtin_mul_overflow(samples, (unsigned long long)C, &samples) || samples > (1ull << 40))
             return SS_ERR_NOMEM;
     }
+    // ---- the handle, its stream and its input: destroyed (streams and events included) on every early return
+    std::unique_ptr<ss_batch, decltype(&ss_batch_destroy)> b(new ss_batch(), &ss_batch_destroy);
+    b->device = current_device();
+    b->cfg = *cfg;
     HIPCHK(stream_acquire(&b->stream));
     ss_batch_layout &L = b->lay;
     L.input_bytes = (uint64_t)cfg->n_streams * F * C * sizeof(float);
     HIPCHK(b->pcm.alloc((size_t)cfg->n_streams * F * C));
-    if (cfg->flags & (SS_BATCH_LUFS | SS_BATCH_TRUE_PEAK)) {
+
+    // ---- tables (the spectrum's own checks stay in front of its tables: the status of a refused config is what it was)
+    if (meter) {
         b->tp_factor = (cfg->flags & SS_BATCH_TRUE_PEAK)
                            ? (cfg->true_peak_factor ? cfg->true_peak_factor : sst::true_peak_factor_for_rate(cfg->sample_rate))
                            : 0;
         int rc = get_td_tables(cfg->sample_rate, b->tp_factor, C, &b->td);
+        if (!rc) rc = get_hist_tables(&b->hist_energies, &b->hist_bounds);
         if (rc) return rc;
     }
-    const StreamShape sh = stream_shape(*cfg, b->td ? b->td->host.s100 : 0, F);
-
     if (cfg->flags & SS_BATCH_FFT) {
         const size_t n = cfg->fft_n;
         if (n < 2) return SS_ERR_TOO_FEW_SAMPLES;
@@ -283,7 +495,12 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
         if (rc) return rc;
         rc = get_bin_tables(cfg->sample_rate, n, &b->bt);
         if (rc) return rc;
-        const uint64_t hop = cfg->hop_frames;
+    }
+
+    // ---- shape: what a stream of F frames holds, and how the kernels walk it
+    const StreamShape sh = stream_shape(b.get(), F);
+    if (b->ft) {
+        const uint64_t n = cfg->fft_n, hop = cfg->hop_frames;
         L.n_windows = sh.windows;
         b->first_start = (n / hop + 1) * hop - n;         // window 0 ends at (N/hop + 1) * hop (stream_shape)
         b->spec = ssk::plan_spectrum((uint32_t)n, C, (uint32_t)hop, cfg->n_streams, L.n_windows);
@@ -294,48 +511,30 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
         // kernel with this row pattern from 3.7 to 4.4 TB/s (tools/ubench_fftio.hip) but does nothing for the real kernel
         // (A/B in one process: 3.14 vs 3.12 ms), so the rows stay compact.
         L.fft_bin_stride = (L.n_bins + 3u) & ~3u;
+    }
+    if (b->td) L.n_subblocks = sh.subblocks;
+
+    // ---- buffers
+    if (b->ft) {
+        const uint64_t rows = (uint64_t)cfg->n_streams * L.n_windows * L.fft_channels;
         if (columns_only) {
             // the fused reduction lives in the epilogue of k_fft4096_ms1
             if (b->spec.kernel != ssk::SpecKernel::ms1) return SS_ERR_UNSUPPORTED;
-            const uint32_t cols = cfg->spectrum_columns;
-            std::vector<uint16_t> bc(L.fft_bin_stride, (uint16_t)0xFFFF);
-            for (uint32_t i = 0; i < L.n_bins; i++) bc[i] = (uint16_t)spectrum_column_of(b->bt->chart_x[i], cols);
-            HIPCHK(b->bin_col.upload(bc));
-            std::vector<uint2> cg(L.fft_bin_stride / 4), cbins(L.fft_bin_stride / 4);
-            std::vector<float> cinit(cols, std::numeric_limits<float>::quiet_NaN());
-            for (uint32_t i = 0; i < L.n_bins; i++) cinit[bc[i]] = -std::numeric_limits<float>::infinity();
-            for (uint32_t g = 0; g < cg.size(); g++) {
-                uint32_t o[4];
-                bool general = false;
-                for (uint32_t e = 0; e < 4; e++) {
-                    const bool pad = bc[4 * g + e] == 0xFFFF;
-                    o[e] = pad ? 2048u : 4u * bc[4 * g + e];
-                    general = general || pad;
-                }
-                uint32_t n = 1;
-                while (n < 4 && o[n] == o[0]) n++;
-                for (uint32_t e = n; e < 4; e++) general = general || o[e] != o[3];
-                cg[g] = make_uint2(o[0] | (o[3] << 16), general ? 0u : n);
-                cbins[g] = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
-            }
-            HIPCHK(b->col_bins.upload(cbins));
-            HIPCHK(b->col_init.upload(cinit));
-            HIPCHK(b->col_groups.upload(cg));
-            const uint64_t rows = (uint64_t)cfg->n_streams * L.n_windows * L.fft_channels;
-            HIPCHK(b->render_spec.alloc(rows * cols));
-            b->render_cols = cols;
-            b->columns_only = true;
-            b->columns_gain_mode = (cfg->flags & SS_BATCH_LUFS) ? SS_GAIN_REFERENCE : SS_GAIN_FIXED;
-            L.fft_bytes = rows * cols * sizeof(float);
+            int rc = upload_column_tables(b.get());
+            if (rc) return rc;
+            b->render_cols = cfg->spectrum_columns;
+            HIPCHK(b->render_spec.alloc(rows * b->render_cols));
+            b->cols.on = true;
+            b->cols.gain_mode = (cfg->flags & SS_BATCH_LUFS) ? SS_GAIN_REFERENCE : SS_GAIN_FIXED;
+            L.fft_bytes = rows * b->render_cols * sizeof(float);
         } else {
-            L.fft_bytes = (uint64_t)cfg->n_streams * L.n_windows * L.fft_channels * L.fft_bin_stride * sizeof(float);
+            L.fft_bytes = rows * L.fft_bin_stride * sizeof(float);
             HIPCHK(b->fft.alloc((size_t)(L.fft_bytes / sizeof(float))));
         }
     }
     if (b->td) {
-        L.n_subblocks = sh.subblocks;
         HIPCHK(b->state.alloc(cfg->n_streams));
-        HIPCHK(b->sub.alloc((size_t)cfg->n_streams * (L.n_subblocks ? L.n_subblocks : 1) * C));
+        HIPCHK(b->sub.alloc((size_t)cfg->n_streams * b->sub_cap() * C));
         HIPCHK(b->hist.alloc((size_t)cfg->n_streams * 2 * sst::kHistBins));
         HIPCHK(b->corpus.alloc(2 * sst::kHistBins));
         HIPCHK(b->integrated.alloc(cfg->n_streams));
@@ -346,43 +545,33 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
         sst::channel_weights(C, w.data());
         HIPCHK(b->weights.upload(w));
         if (cfg->flags & SS_BATCH_LOUDNESS_SERIES) {
-            HIPCHK(b->series.alloc((size_t)cfg->n_streams * (L.n_subblocks ? L.n_subblocks : 1) * 2));
+            HIPCHK(b->series.alloc((size_t)cfg->n_streams * b->sub_cap() * 2));
             HIPCHK(b->extremes.alloc(cfg->n_streams));
         }
     }
     if (cfg->flags & SS_BATCH_WAVEFORM) {
         if (sh.wave_window > 0xFFFFFFFFull) return SS_ERR_UNSUPPORTED;
-        const uint64_t W = sh.wave_window, len = F * C;
-        const double spp = (double)len / (double)W;
-        b->wave_window = (uint32_t)W;
+        b->wave_window = (uint32_t)sh.wave_window;
         L.n_wave_points = (uint32_t)(2 * sh.wave_bins);
-        HIPCHK(b->wave.alloc((size_t)cfg->n_streams * (W ? 2 * W : 2)));
-        // fuse into the time-domain pass when that pass runs and a bin (plus its shared edge sample)
-        // fits the per-wave halo; otherwise the standalone kernel handles it
-        if (b->td && W > 0 && spp >= 16.0 && spp <= 1000.0 && len < (1ull << 31)) {
-            // (+ 3: the general decimation path reads the aligned 16-byte piece a bin starts in, up to three samples in front of it)
-            const uint32_t need = ((uint32_t)std::ceil(spp) + 5 + C - 1) / C;
-            uint32_t halo = need < 24 ? 24 : need;
-            halo = (halo + 3u) & ~3u;
-            if (halo <= 512) { b->wave_fused = true; b->wave_halo = halo; }
-        }
+        HIPCHK(b->wave.alloc((size_t)cfg->n_streams * (b->wave_window ? 2 * (size_t)b->wave_window : 2)));
     }
-    choose_td_geometry(b.get());
-    for (auto &e : b->ev) HIPCHK(hipEventCreate(&e));
-    b->ev_ready = true;
+
+    // ---- plans
+    if (cfg->flags & SS_BATCH_WAVEFORM) choose_wave_fusion(b.get());
+    int rc = choose_td_geometry(b.get());
+    if (rc) return rc;
+    HIPCHK(b->timing.create());
     *out = b.release();
     return SS_OK;
 }
 
+// synchronise both streams, then release: the members free their events and buffers
 void ss_batch_destroy(ss_batch *b)
 {
     SS_ON_DEVICE(b);
     if (!b) return;
-    if (b->stream) { (void)hipStreamSynchronize(b->stream); }
-    if (b->stream2) { (void)hipStreamSynchronize(b->stream2); stream_release(b->stream2); }
-    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-    if (b->ev_join) (void)hipEventDestroy(b->ev_join);
-    for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->ov.stream2) { (void)hipStreamSynchronize(b->ov.stream2); stream_release(b->ov.stream2); }
     if (b->stream) stream_release(b->stream);
     delete b;
 }
@@ -395,16 +584,15 @@ int ss_batch_layout_get(const ss_batch *b, ss_batch_layout *out)
     return SS_OK;
 }
 
+// ---- uploads: each entry point says where the range is, which staging a conversion uses and whether it waits ----------
+
 int ss_batch_upload(ss_batch *b, uint32_t first, uint32_t count, const float *pcm)
 {
     SS_ON_DEVICE(b);
     if (!b || !pcm) return SS_ERR_INVALID_ARG;
     if ((uint64_t)first + count > b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    const size_t per = (size_t)b->cfg.frames_per_stream * b->cfg.channels;
-    HIPCHK(hipMemcpyAsync(b->pcm.p + (size_t)first * per, pcm, (size_t)count * per * sizeof(float),
-                          hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    const size_t per = b->samples_per_stream();
+    return upload_range(b, (size_t)first * per, (size_t)count * per, pcm, SS_PCM_F32, nullptr, true);
 }
 
 int ss_batch_upload_pcm(ss_batch *b, uint32_t first, uint32_t count, const void *pcm, int format)
@@ -413,60 +601,59 @@ int ss_batch_upload_pcm(ss_batch *b, uint32_t first, uint32_t count, const void 
     const size_t sb = ss_pcm_sample_bytes(format);
     if (!b || !pcm || !sb) return SS_ERR_INVALID_ARG;
     if ((uint64_t)first + count > b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    const size_t per = (size_t)b->cfg.frames_per_stream * b->cfg.channels;
-    const size_t n = per * count;
+    const size_t per = b->samples_per_stream(), n = per * count;
+    // The staging is this call's own, freed behind its wait.  The batch-wide raw area would serve, but every batch that ever
+    // took this path would then hold a second copy of its input for good.
     DevBuf<unsigned char> raw;
-    HIPCHK(raw.alloc(n * sb + kPcmReadSlack));
-    HIPCHK(hipMemcpyAsync(raw.p, pcm, n * sb, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(ssk::launch_pcm_to_f32(raw.p, n, format, b->pcm.p + (size_t)first * per, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    if (format != SS_PCM_F32) HIPCHK(raw.alloc(n * sb + kPcmReadSlack));
+    return upload_range(b, (size_t)first * per, n, pcm, format, raw.p, true);
 }
 
 // ---- ragged batches: streams of different lengths in one batch ------------------------------------------------
 // The batch is created for the longest stream (frames_per_stream = the slot size); every stream then gets its own
 // window count, sub-block count and decimation geometry by the very rules ss_batch_create applies to the whole
 // batch.  Slots are uploaded as before (the tail of a short stream's slot is never read).
+// A refused call leaves the batch as it was: every check comes before the first assignment.
 int ss_batch_set_lengths(ss_batch *b, const uint64_t *frames, uint32_t count)
 {
     SS_ON_DEVICE(b);
     if (!b || !frames || count != b->cfg.n_streams) return SS_ERR_INVALID_ARG;
     const ss_batch_config &c = b->cfg;
-    const uint32_t C = c.channels;
     for (uint32_t i = 0; i < count; i++) if (frames[i] > c.frames_per_stream) return SS_ERR_INVALID_ARG;
-    b->frames_h.assign(frames, frames + count);
-    b->windows_h.assign(count, 0); b->sub_h.assign(count, 0);
-    b->wave_window_h.assign(count, 0); b->wave_samples_h.assign(count, 0);
+    std::vector<uint64_t> frames_h(frames, frames + count), wave_samples(count, 0);
+    std::vector<uint32_t> windows(count, 0), sub_h(count, 0), wave_window(count, 0);
+    uint32_t max_sub = 0;
     for (uint32_t i = 0; i < count; i++) {
-        const StreamShape sh = stream_shape(c, b->td ? b->td->host.s100 : 0, frames[i]);
+        const StreamShape sh = stream_shape(b, frames[i]);
         if (sh.wave_window > b->wave_window) return SS_ERR_INVALID_ARG;      // cannot happen for F <= frames_per_stream
-        b->windows_h[i] = sh.windows; b->sub_h[i] = sh.subblocks;
+        windows[i] = sh.windows; sub_h[i] = sh.subblocks;
+        if (sh.subblocks > max_sub) max_sub = sh.subblocks;
         if (c.flags & SS_BATCH_WAVEFORM) {
-            b->wave_window_h[i] = (uint32_t)sh.wave_window; b->wave_samples_h[i] = frames[i] * C;
+            wave_window[i] = (uint32_t)sh.wave_window; wave_samples[i] = frames[i] * c.channels;
         }
     }
+    Ragged &r = b->ragged;
     HIPCHK(hipStreamSynchronize(b->stream));
-    HIPCHK(b->frames_d.upload(b->frames_h));
-    HIPCHK(b->windows_d.upload(b->windows_h));
-    HIPCHK(b->sub_d.upload(b->sub_h));
-    HIPCHK(b->wave_window_d.upload(b->wave_window_h));
-    HIPCHK(b->wave_samples_d.upload(b->wave_samples_h));
-    b->ragged = true;
+    HIPCHK(r.frames_d.upload(frames_h));
+    HIPCHK(r.windows_d.upload(windows));
+    HIPCHK(r.sub_d.upload(sub_h));
+    HIPCHK(r.wave_window_d.upload(wave_window));
+    HIPCHK(r.wave_samples_d.upload(wave_samples));
+    r.frames_h.swap(frames_h); r.sub_h.swap(sub_h);
+    r.on = true;
     // the time-domain geometry follows the lengths actually set (the longest stream), not the slot size the batch was created with:
     // a batch that is kept and re-used — the one-shot loudness call keeps one — then cuts the same input the same way whatever
     // was analysed before it (the low bits of a reading do not depend on the process' history)
-    b->td_nsub_hint = 0;
-    for (uint32_t i = 0; i < count; i++) if (b->sub_h[i] > b->td_nsub_hint) b->td_nsub_hint = b->sub_h[i];
-    choose_td_geometry(b);
-    return SS_OK;
+    r.max_sub = max_sub;
+    return choose_td_geometry(b);
 }
 
 int ss_batch_stream_shape(const ss_batch *b, uint32_t stream, ss_stream_shape *out)
 {
     SS_ON_DEVICE(b);
     if (!b || !out || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    const uint64_t F = b->ragged ? b->frames_h[stream] : b->cfg.frames_per_stream;
-    const StreamShape sh = stream_shape(b->cfg, b->td ? b->td->host.s100 : 0, F);
+    const uint64_t F = b->ragged.on ? b->ragged.frames_h[stream] : b->cfg.frames_per_stream;
+    const StreamShape sh = stream_shape(b, F);
     out->frames = F; out->n_windows = sh.windows;
     out->n_subblocks = sh.subblocks; out->n_wave_points = (uint32_t)(2 * sh.wave_bins);
     out->reserved = 0;
@@ -491,35 +678,15 @@ int ss_host_unregister(void *ptr)
     return SS_OK;
 }
 
-// one raw staging area per batch, sized for the whole batch at sb bytes per sample (ranges of different streams do not overlap);
-// growing it waits for whatever still reads the old one
-static hipError_t raw_area(ss_batch *b, size_t sb)
-{
-    const size_t bytes = (size_t)b->cfg.frames_per_stream * b->cfg.channels * b->cfg.n_streams * sb + kPcmReadSlack;
-    if (b->raw.n >= bytes) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(b->stream);
-    return e == hipSuccess ? b->raw.alloc(bytes) : e;
-}
-
 // like ss_batch_upload_pcm, but returns as soon as the copy and the conversion are queued on the batch's stream:
 // `pcm` must stay valid (and should be page-locked) until the next ss_batch_sync / ss_batch_results on this batch
 int ss_batch_upload_pcm_async(ss_batch *b, uint32_t first, uint32_t count, const void *pcm, int format)
 {
     SS_ON_DEVICE(b);
-    const size_t sb = ss_pcm_sample_bytes(format);
-    if (!b || !pcm || !sb) return SS_ERR_INVALID_ARG;
+    if (!b || !pcm || !ss_pcm_sample_bytes(format)) return SS_ERR_INVALID_ARG;
     if ((uint64_t)first + count > b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    const size_t per = (size_t)b->cfg.frames_per_stream * b->cfg.channels;
-    const size_t n = per * count;
-    if (format == SS_PCM_F32) {
-        HIPCHK(hipMemcpyAsync(b->pcm.p + (size_t)first * per, pcm, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
-        return SS_OK;
-    }
-    HIPCHK(raw_area(b, sb));
-    unsigned char *dst = b->raw.p + (size_t)first * per * sb;
-    HIPCHK(hipMemcpyAsync(dst, pcm, n * sb, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(ssk::launch_pcm_to_f32(dst, n, format, b->pcm.p + (size_t)first * per, b->stream));
-    return SS_OK;
+    const size_t per = b->samples_per_stream();
+    return upload_queued(b, (size_t)first * per, per * count, pcm, format);
 }
 
 // the first n_samples interleaved samples of one stream's slot, raw PCM of any supported format (ragged batches:
@@ -527,32 +694,19 @@ int ss_batch_upload_pcm_async(ss_batch *b, uint32_t first, uint32_t count, const
 int ss_batch_upload_samples(ss_batch *b, uint32_t stream, const void *pcm, size_t n_samples, int format)
 {
     SS_ON_DEVICE(b);
-    const size_t sb = ss_pcm_sample_bytes(format);
-    if (!b || (!pcm && n_samples) || !sb || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    const size_t per = (size_t)b->cfg.frames_per_stream * b->cfg.channels;
+    if (!b || (!pcm && n_samples) || !ss_pcm_sample_bytes(format) || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+    const size_t per = b->samples_per_stream();
     if (n_samples > per) return SS_ERR_INVALID_ARG;
-    if (!n_samples) return SS_OK;
-    float *dst = b->pcm.p + (size_t)stream * per;
-    if (format == SS_PCM_F32) {
-        HIPCHK(hipMemcpyAsync(dst, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice, b->stream));
-        return SS_OK;
-    }
-    HIPCHK(raw_area(b, sb));
-    unsigned char *raw = b->raw.p + (size_t)stream * per * sb;
-    HIPCHK(hipMemcpyAsync(raw, pcm, n_samples * sb, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(ssk::launch_pcm_to_f32(raw, n_samples, format, dst, b->stream));
-    return SS_OK;
+    return n_samples ? upload_queued(b, (size_t)stream * per, n_samples, pcm, format) : SS_OK;
 }
 
 int ss_batch_download_input(ss_batch *b, uint32_t stream, float *pcm, size_t cap)
 {
     SS_ON_DEVICE(b);
     if (!b || !pcm || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    const size_t per = (size_t)b->cfg.frames_per_stream * b->cfg.channels;
+    const size_t per = b->samples_per_stream();
     if (cap < per) return SS_ERR_CAPACITY;
-    HIPCHK(hipMemcpyAsync(pcm, b->pcm.p + (size_t)stream * per, per * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, pcm, b->pcm.p + (size_t)stream * per, per);
 }
 
 void *ss_batch_input_device_ptr(ss_batch *b) { return b ? b->pcm.p : nullptr; }
@@ -567,136 +721,66 @@ int ss_batch_synthesize(ss_batch *b, uint64_t seed, uint32_t first_stream_id)
     return SS_OK;
 }
 
+// One pass over every stream, queued on the batch's stream(s); nothing is waited for and nothing allocated.
 int ss_batch_run(ss_batch *b)
 {
     SS_ON_DEVICE(b);
     if (!b) return SS_ERR_INVALID_ARG;
-    int rc = (b->ev_count >= (uint32_t)ss_batch::kTimingDepth || !b->timing) ? batch_collect_timing(b) : SS_OK;     // (a full ring: collect first)
+    TimingRing &t = b->timing;
+    int rc = (t.count >= TimingRing::kDepth || !t.on) ? t.collect(b->stream) : SS_OK;     // (a full ring: collect first)
     if (rc) return rc;
     b->corpus_reduced = false;
-    const ss_batch_config &c = b->cfg;
-    const ss_batch_layout &L = b->lay;
-    const uint32_t C = c.channels;
-    const bool tm = b->timing;
-    const uint32_t ev_slot = b->ev_head;
-    auto rec = [&](int idx) -> hipError_t {
-        if (!tm) return hipSuccess;
-        b->ev_mask[ev_slot] |= 1u << idx;
-        return hipEventRecord(b->ev[(size_t)ev_slot * 2 * SS_KERNEL_COUNT + idx], b->stream);
-    };
 
-    // overlap mode: fork — the spectrum kernel goes to stream2 after everything already queued on the main stream
-    // (uploads, the previous pass), the time-domain chain stays on the main stream, join at the end.  Per-kernel
-    // event timing is meaningless while two kernels share the chip, so timing passes stay sequential.
-    // Mode 2 (tail overlap): the time-domain kernel runs first and alone; the spectrum kernel starts behind it on stream2
-    // while the short latency-bound tail of the chain (gating / histograms per stream, a standalone decimation) runs on
-    // the main stream beside it.
-    // columns-only spectrum with the reference's per-file gain: the gain is -13 - integrated of each stream, so the whole
-    // time-domain chain (kernel + gating / histograms) runs first and the spectrum kernel last, on the one stream
-    const bool spectrum_last = b->columns_only && b->columns_gain_mode == SS_GAIN_REFERENCE;
-    const int mode = (tm || spectrum_last) ? 0 : b->overlap;
-    const bool ov = mode != 0;
-    hipStream_t fft_stream = ov ? b->stream2 : b->stream;
-    if (mode == 1) {
-        HIPCHK(hipEventRecord(b->ev_fork, b->stream));
-        HIPCHK(hipStreamWaitEvent(b->stream2, b->ev_fork, 0));
-    }
-    auto launch_spectrum = [&]() -> int {
-    HIPCHK(rec(2 * SS_KERNEL_FFT));
-    if ((c.flags & SS_BATCH_FFT) && L.n_windows) {
-        ssk::FftBatchParams p = batch_fft_params(b);
-        p.windows_of = b->ragged ? b->windows_d.p : nullptr;
-        if (b->columns_only) {
-            p.out_cols = b->render_spec.p; p.bin_col = b->bin_col.p; p.col_groups = b->col_groups.p; p.col_init = b->col_init.p; p.col_bins = b->col_bins.p; p.cols = b->render_cols;
-            p.integrated = b->columns_gain_mode == SS_GAIN_REFERENCE ? b->integrated.p : nullptr;
-            p.gain_db = b->columns_gain_db;
-        }
-        HIPCHK(ssk::launch_spectrum(b->spec, p, fft_stream));
-    }
-    HIPCHK(rec(2 * SS_KERNEL_FFT + 1));
-    return SS_OK;
-    };
-    if (mode != 2 && !spectrum_last) { rc = launch_spectrum(); if (rc) return rc; }
+    // Where the spectrum kernel goes.
+    //  * first, on the main stream: the sequential pass.  Per-kernel event timing is meaningless while two kernels share the
+    //    chip, so timing passes stay sequential.
+    //  * first, forked (overlap mode 1): on stream2 after everything already queued on the main stream (uploads, the previous
+    //    pass); the time-domain chain stays on the main stream, join at the end.
+    //  * behind the time-domain kernel, forked (mode 2, tail overlap): the time-domain kernel runs first and alone; the spectrum
+    //    kernel starts behind it on stream2 while the short latency-bound tail of the chain (gating / histograms per stream, a
+    //    standalone decimation) runs on the main stream beside it.
+    //  * last, on the main stream: a columns-only spectrum with the reference's per-file gain — the gain is -13 - integrated of
+    //    each stream, so the whole time-domain chain (kernel + gating / histograms) runs first.
+    enum class At { first, behind_td, last };
+    const bool gain_from_meter = b->cols.on && b->cols.gain_mode == SS_GAIN_REFERENCE;
+    const int mode = (t.on || gain_from_meter) ? 0 : b->ov.mode;
+    const At at = gain_from_meter ? At::last : mode == 2 ? At::behind_td : At::first;
+    auto spectrum_if = [&](At here) { return here == at ? spectrum_step(b, mode != 0) : SS_OK; };
 
-    const bool td = (c.flags & (SS_BATCH_LUFS | SS_BATCH_TRUE_PEAK)) != 0;
-    HIPCHK(rec(2 * SS_KERNEL_TIME_DOMAIN));
-    if (td) {
-        {   // meter state, histograms, corpus histograms and block counts start from zero: one launch (they were four fills)
-            void *const ptrs[4] = {b->state.p, b->hist.p, b->corpus.p, b->counts.p};
-            const size_t bytes[4] = {b->state.n * sizeof(ssk::TdState), b->hist.n * sizeof(uint64_t), b->corpus.n * sizeof(uint64_t),
-                                     b->counts.n * sizeof(uint32_t)};
-            HIPCHK(ssk::launch_zero4(ptrs, bytes, b->stream));
-        }
-        HIPCHK(rec(2 * SS_KERNEL_TIME_DOMAIN));   // time the kernel, not the memsets
-        ssk::TdParams p{};
-        p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * C; p.n_frames = c.frames_per_stream;
-        p.n_streams = c.n_streams; p.channels = C; p.k = b->td->dev.p; p.state = b->state.p;
-        p.subblocks = b->sub.p; p.sub_cap = L.n_subblocks ? L.n_subblocks : 1;
-        p.sub_stride = (uint64_t)p.sub_cap * C; p.ring = nullptr; p.ring_frames = 0; p.tp_factor = b->tp_factor;
-        const auto &plan = b->td_plan;
-        p.s100 = b->td->host.s100; p.nseg = plan.nseg; p.seg_sub = plan.seg_sub;
-        p.warm_sub = plan.warm_sub; p.fix_sub = plan.fix_sub; p.split_batch = plan.split_batch;
-        if (plan.fixup) {
-            const size_t need = (size_t)c.n_streams * plan.nseg * C * 4;
-            if (b->seg_state.n < need) HIPCHK(b->seg_state.alloc(need));
-            p.seg_state = b->seg_state.p;
-        }
-        p.frames_of = b->ragged ? b->frames_d.p : nullptr;
-        p.tp_f32 = b->tp_arith == SS_TP_ARITH_F32 ? 1u : 0u;
-        if (b->wave_fused && !b->ragged) { p.wave_out = b->wave.p; p.wave_stride = (uint64_t)2 * b->wave_window; p.wave_window = b->wave_window; p.halo_frames = b->wave_halo; }
-        HIPCHK(ssk::launch_time_domain(p, b->stream));
-        if (mode == 2) {
-            // the tail starts HERE: the hand-over's second launch (filter and energies of every segment's first 0.2 s: one wave per
-            // segment, a chain of ten short tiles each — latency, not throughput, and no matrix-core work) runs beside the spectrum
-            // kernel like the gating behind it
-            HIPCHK(hipEventRecord(b->ev_fork, b->stream));
-            HIPCHK(hipStreamWaitEvent(b->stream2, b->ev_fork, 0));
-            rc = launch_spectrum(); if (rc) return rc;
-        }
-        if (plan.fixup) HIPCHK(ssk::launch_time_domain_fixup(p, b->stream));
-    } else if (mode == 2) {                                  // (no time-domain work at all: the spectrum kernel is the pass)
-        HIPCHK(hipEventRecord(b->ev_fork, b->stream));
-        HIPCHK(hipStreamWaitEvent(b->stream2, b->ev_fork, 0));
-        rc = launch_spectrum(); if (rc) return rc;
-    }
-    HIPCHK(rec(2 * SS_KERNEL_TIME_DOMAIN + 1));
+    if ((rc = spectrum_if(At::first))) return rc;
 
-    HIPCHK(rec(2 * SS_KERNEL_FINALIZE));
-    if (td) {
-        const double *he, *hb;
-        rc = get_hist_tables(&he, &hb);
-        if (rc) return rc;
-        ssk::FinalizeParams f{};
-        f.k = b->td->dev.p; f.subblocks = b->sub.p; f.sub_cap = L.n_subblocks ? L.n_subblocks : 1;
-        f.sub_stride = (uint64_t)f.sub_cap * C;
-        f.hist_energies = he; f.hist_bounds = hb; f.weights = b->weights.p; f.hist = b->hist.p;
-        f.corpus_hist = b->corpus.p; f.n_streams = c.n_streams; f.channels = C;
-        f.sub_begin = 0; f.sub_end = L.n_subblocks;
-        f.sub_end_of = b->ragged ? b->sub_d.p : nullptr;
-        f.out_integrated = b->integrated.p; f.out_lra = b->lra.p; f.out_counts = b->counts.p;
-        f.state = b->state.p;
+    HIPCHK(t.mark(SS_KERNEL_TIME_DOMAIN, 0, b->stream));
+    const ssk::TdParams tdp = b->td ? batch_td_params(b) : ssk::TdParams{};
+    if (b->td) {
+        HIPCHK(zero_meter(b));
+        HIPCHK(t.mark(SS_KERNEL_TIME_DOMAIN, 0, b->stream));   // time the kernel, not the memsets
+        HIPCHK(ssk::launch_time_domain(tdp, b->stream));
+    }
+    // the tail starts HERE: the hand-over's second launch (filter and energies of every segment's first 0.2 s: one wave per
+    // segment, a chain of ten short tiles each — latency, not throughput, and no matrix-core work) runs beside the spectrum
+    // kernel like the gating behind it.  (No time-domain work at all: the spectrum kernel is the pass.)
+    if ((rc = spectrum_if(At::behind_td))) return rc;
+    if (b->td && b->td_plan.fixup) HIPCHK(ssk::launch_time_domain_fixup(tdp, b->stream));
+    HIPCHK(t.mark(SS_KERNEL_TIME_DOMAIN, 1, b->stream));
+
+    HIPCHK(t.mark(SS_KERNEL_FINALIZE, 0, b->stream));
+    if (b->td) {
+        const ssk::FinalizeParams f = batch_gating_params(b);
         HIPCHK(ssk::launch_finalize(f, b->stream));
         // the series behind the gating pass, on the same stream: behind the hand-over's fix-up launch like it (exact segment
         // heads), inside the FINALIZE timing slot
-        if (b->series.p) HIPCHK(ssk::launch_loudness_series(f, b->series.p, L.n_subblocks ? L.n_subblocks : 1, b->extremes.p, b->stream));
+        if (b->series.p) HIPCHK(ssk::launch_loudness_series(f, b->series.p, b->sub_cap(), b->extremes.p, b->stream));
     }
-    HIPCHK(rec(2 * SS_KERNEL_FINALIZE + 1));
+    HIPCHK(t.mark(SS_KERNEL_FINALIZE, 1, b->stream));
 
-    HIPCHK(rec(2 * SS_KERNEL_WAVEFORM));
-    if ((c.flags & SS_BATCH_WAVEFORM) && b->wave_window && (!b->wave_fused || b->ragged)) {
-        ssk::WaveParams p{};
-        p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * C; p.n_samples = c.frames_per_stream * C;
-        p.n_streams = c.n_streams; p.window = b->wave_window; p.out = b->wave.p; p.out_stride = (uint64_t)2 * b->wave_window;
-        if (b->ragged) { p.samples_of = b->wave_samples_d.p; p.window_of = b->wave_window_d.p; }
-        HIPCHK(ssk::launch_waveform(p, b->stream));
-    }
-    HIPCHK(rec(2 * SS_KERNEL_WAVEFORM + 1));
-    if (spectrum_last) { rc = launch_spectrum(); if (rc) return rc; }
-    if (ov) {                                  // join: later work on the main stream (downloads, the next pass) sees the spectrum
-        HIPCHK(hipEventRecord(b->ev_join, b->stream2));
-        HIPCHK(hipStreamWaitEvent(b->stream, b->ev_join, 0));
-    }
-    if (tm) { b->ev_head = (b->ev_head + 1u) % (uint32_t)ss_batch::kTimingDepth; b->ev_count++; }
+    HIPCHK(t.mark(SS_KERNEL_WAVEFORM, 0, b->stream));
+    if ((b->cfg.flags & SS_BATCH_WAVEFORM) && b->wave_window && (!b->wave_fused || b->ragged.on))
+        HIPCHK(ssk::launch_waveform(batch_wave_params(b), b->stream));
+    HIPCHK(t.mark(SS_KERNEL_WAVEFORM, 1, b->stream));
+
+    if ((rc = spectrum_if(At::last))) return rc;
+    if (mode) HIPCHK(b->ov.join(b->stream));
+    t.advance();
     return SS_OK;
 }
 
@@ -705,7 +789,7 @@ int ss_batch_traffic_floor(ss_batch *b, uint32_t reps, double *ms_per_launch)
 {
     SS_ON_DEVICE(b);
     if (!b || !ms_per_launch || reps == 0) return SS_ERR_INVALID_ARG;
-    if (!(b->cfg.flags & SS_BATCH_FFT) || b->spec.kernel != ssk::SpecKernel::ms1 || !b->lay.n_windows || b->ragged) return SS_ERR_UNSUPPORTED;
+    if (!(b->cfg.flags & SS_BATCH_FFT) || b->spec.kernel != ssk::SpecKernel::ms1 || !b->lay.n_windows || b->ragged.on) return SS_ERR_UNSUPPORTED;
     if (!b->fft.p) return SS_ERR_INVALID_MODE;          // columns-only batches have no spectrum rows to store into
     const ssk::FftBatchParams p = batch_fft_params(b);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -730,7 +814,7 @@ int ss_batch_sync(ss_batch *b)
     SS_ON_DEVICE(b);
     if (!b) return SS_ERR_INVALID_ARG;
     HIPCHK(hipStreamSynchronize(b->stream));
-    return batch_collect_timing(b);
+    return b->timing.collect(b->stream);
 }
 
 int ss_batch_results(ss_batch *b, ss_stream_result *out, uint32_t cap)
@@ -797,8 +881,8 @@ int ss_batch_geometry_get(const ss_batch *b, ss_batch_geometry *out)
         out->td_fixup_subblocks = b->td_plan.fix_sub;
         out->td_true_peak_factor = (uint32_t)b->tp_factor;
     }
-    out->waveform_fused = (b->wave_fused && !b->ragged) ? 1u : 0u;
-    out->overlap = (uint32_t)b->overlap;
+    out->waveform_fused = (b->wave_fused && !b->ragged.on) ? 1u : 0u;
+    out->overlap = (uint32_t)b->ov.mode;
     return SS_OK;
 }
 
@@ -816,13 +900,14 @@ int ss_batch_set_overlap(ss_batch *b, int enable)
 {
     SS_ON_DEVICE(b);
     if (!b) return SS_ERR_INVALID_ARG;
-    if (enable && !b->stream2) {
-        HIPCHK(stream_acquire(&b->stream2));
-        HIPCHK(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
+    Overlap &ov = b->ov;
+    if (enable && !ov.stream2) {
+        HIPCHK(stream_acquire(&ov.stream2));
+        HIPCHK(hipEventCreateWithFlags(&ov.ev_fork, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ov.ev_join, hipEventDisableTiming));
     }
     HIPCHK(hipStreamSynchronize(b->stream));
-    b->overlap = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
+    ov.mode = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
     return SS_OK;
 }
 
@@ -835,21 +920,12 @@ int ss_batch_checksums(ss_batch *b, uint64_t *out, uint32_t cap_streams)
     HIPCHK(b->checks.ensure((size_t)3 * ns));
     HIPCHK(hipMemsetAsync(b->checks.p, 0, (size_t)3 * ns * sizeof(uint64_t), b->stream));
     const ss_batch_layout &L = b->lay;
-    if (b->fft.p && L.n_windows) {
-        const uint64_t words = (uint64_t)L.n_windows * L.fft_channels * L.fft_bin_stride;
-        HIPCHK(ssk::launch_checksum(b->fft.p, words, words, ns, b->checks.p, 3, b->stream));
-    }
-    if (b->wave.p && b->wave_window) {
-        const uint64_t words = (uint64_t)2 * b->wave_window;
-        HIPCHK(ssk::launch_checksum(b->wave.p, words, words, ns, b->checks.p + 1, 3, b->stream));
-    }
-    if (b->sub.p && L.n_subblocks) {
-        const uint64_t words = (uint64_t)2 * L.n_subblocks * b->cfg.channels;
-        HIPCHK(ssk::launch_checksum(b->sub.p, words, words, ns, b->checks.p + 2, 3, b->stream));
-    }
-    HIPCHK(hipMemcpyAsync(out, b->checks.p, (size_t)3 * ns * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    // 32-bit words per stream of: the spectrum rows, the decimation bins, the sub-block energies
+    const struct { const void *p; uint64_t words; } parts[3] = {{b->fft.p, (uint64_t)L.n_windows * L.fft_channels * L.fft_bin_stride},
+        {b->wave.p, (uint64_t)2 * b->wave_window}, {b->sub.p, (uint64_t)2 * L.n_subblocks * b->cfg.channels}};
+    for (int k = 0; k < 3; k++)
+        if (parts[k].p && parts[k].words) HIPCHK(ssk::launch_checksum(parts[k].p, parts[k].words, parts[k].words, ns, b->checks.p + k, 3, b->stream));
+    return fetch(b, out, b->checks.p, (size_t)3 * ns);
 }
 
 int ss_batch_set_true_peak_arith(ss_batch *b, int arith)
@@ -867,15 +943,14 @@ int ss_batch_set_time_domain_mode(ss_batch *b, int mode)
     if (!b || mode < 0 || mode > 2) return SS_ERR_INVALID_ARG;      // SS_TD_AUTO / SS_TD_RUN_IN / SS_TD_WHOLE_STREAMS
     HIPCHK(hipStreamSynchronize(b->stream));
     b->td_mode = mode;
-    choose_td_geometry(b);
-    return SS_OK;
+    return choose_td_geometry(b);
 }
 
 int ss_batch_download_fft(ss_batch *b, uint32_t stream, float *out, size_t cap)
 {
     SS_ON_DEVICE(b);
     if (!b || !out || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    if (b->columns_only) return SS_ERR_INVALID_MODE;          // the rows were never stored: ss_batch_download_spectrum_columns
+    if (b->cols.on) return SS_ERR_INVALID_MODE;          // the rows were never stored: ss_batch_download_spectrum_columns
     const size_t rows = (size_t)b->lay.n_windows * b->lay.fft_channels;
     const size_t per = rows * b->lay.n_bins;
     if (cap < per) return SS_ERR_CAPACITY;
@@ -907,10 +982,7 @@ int ss_batch_download_waveform(ss_batch *b, uint32_t stream, float *out, size_t 
     const size_t pts = b->lay.n_wave_points;
     if (cap < pts) return SS_ERR_CAPACITY;
     if (!pts) return SS_OK;
-    HIPCHK(hipMemcpyAsync(out, b->wave.p + (size_t)stream * 2 * b->wave_window, pts * sizeof(float),
-                          hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, out, b->wave.p + (size_t)stream * 2 * b->wave_window, pts);
 }
 
 int ss_batch_download_subblocks(ss_batch *b, uint32_t stream, double *out, size_t cap)
@@ -920,9 +992,7 @@ int ss_batch_download_subblocks(ss_batch *b, uint32_t stream, double *out, size_
     const size_t per = (size_t)b->lay.n_subblocks * b->cfg.channels;
     if (cap < per) return SS_ERR_CAPACITY;
     if (!per) return SS_OK;
-    HIPCHK(hipMemcpyAsync(out, b->sub.p + (size_t)stream * per, per * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, out, b->sub.p + (size_t)stream * per, per);
 }
 
 static_assert(sizeof(ss_loudness_extremes) == 24 && sizeof(ssk::LoudnessExtremes) == sizeof(ss_loudness_extremes) &&
@@ -933,13 +1003,12 @@ int ss_batch_download_loudness_series(ss_batch *b, uint32_t stream, double *mome
     SS_ON_DEVICE(b);
     if (!b || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
     if (!b->series.p) return SS_ERR_INVALID_MODE;                // the batch was made without SS_BATCH_LOUDNESS_SERIES
-    const size_t n = b->ragged ? b->sub_h[stream] : b->lay.n_subblocks;
+    const size_t n = b->ragged.on ? b->ragged.sub_h[stream] : b->lay.n_subblocks;
     if (cap < n) return SS_ERR_CAPACITY;
     if (!n || (!momentary && !shortterm)) return SS_OK;
-    const size_t stride = b->lay.n_subblocks ? b->lay.n_subblocks : 1;
     std::vector<double> ms(2 * n);
-    HIPCHK(hipMemcpyAsync(ms.data(), b->series.p + (size_t)stream * stride * 2, 2 * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    int rc = fetch(b, ms.data(), b->series.p + (size_t)stream * b->sub_cap() * 2, 2 * n);
+    if (rc) return rc;
     for (size_t j = 0; j < n; j++) {
         if (momentary) momentary[j] = ms[2 * j];
         if (shortterm) shortterm[j] = ms[2 * j + 1];
@@ -954,27 +1023,21 @@ int ss_batch_loudness_extremes(ss_batch *b, ss_loudness_extremes *out, uint32_t 
     if (!b->extremes.p) return SS_ERR_INVALID_MODE;
     const uint32_t n = b->cfg.n_streams;
     if (cap_streams < n) return SS_ERR_CAPACITY;
-    HIPCHK(hipMemcpyAsync(out, b->extremes.p, n * sizeof(ss_loudness_extremes), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, out, reinterpret_cast<const ss_loudness_extremes *>(b->extremes.p), n);
 }
 
 int ss_batch_histograms(ss_batch *b, uint64_t *out2000)
 {
     SS_ON_DEVICE(b);
     if (!b || !out2000 || !b->corpus.p) return SS_ERR_INVALID_ARG;
-    HIPCHK(hipMemcpyAsync(out2000, b->corpus.p, 2 * sst::kHistBins * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, out2000, b->corpus.p, 2 * sst::kHistBins);
 }
 
 int ss_batch_histograms_device(ss_batch *b, void *dst)
 {
     SS_ON_DEVICE(b);
     if (!b || !dst || !b->corpus.p) return SS_ERR_INVALID_ARG;
-    HIPCHK(hipMemcpyAsync(dst, b->corpus.p, 2 * sst::kHistBins * sizeof(uint64_t), hipMemcpyDeviceToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, static_cast<uint64_t *>(dst), b->corpus.p, 2 * sst::kHistBins, hipMemcpyDeviceToDevice);
 }
 
 // The corpus gate without leaving the device: [sum over the ranks] + loudness_global / loudness_range of the corpus
@@ -989,10 +1052,7 @@ int ss_batch_corpus_gate_enqueue(ss_batch *b, ss_comm *comm)
         int rc = ss_batch_allreduce_histograms(b, comm, nullptr);
         if (rc) return rc;
     }
-    const double *he, *hb;
-    int rc = get_hist_tables(&he, &hb);
-    if (rc) return rc;
-    HIPCHK(ssk::launch_hist_eval(b->corpus.p, he, hb, b->out2.p, b->stream));
+    HIPCHK(ssk::launch_hist_eval(b->corpus.p, b->hist_energies, b->hist_bounds, b->out2.p, b->stream));
     return SS_OK;
 }
 
@@ -1002,8 +1062,8 @@ int ss_batch_corpus_gate_read(ss_batch *b, double *integrated, double *lra)
     if (!b) return SS_ERR_INVALID_ARG;
     if (!b->corpus.p) return SS_ERR_INVALID_MODE;
     double r[2];
-    HIPCHK(hipMemcpyAsync(r, b->out2.p, sizeof r, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    int rc = fetch(b, r, b->out2.p, 2);
+    if (rc) return rc;
     if (integrated) *integrated = r[0];
     if (lra) *lra = r[1];
     return SS_OK;
@@ -1019,7 +1079,7 @@ int ss_batch_render_spectrum(ss_batch *b, uint32_t cols, int gain_mode, float ga
     if (!b || cols == 0 || cols > 65536 || (gain_mode != SS_GAIN_FIXED && gain_mode != SS_GAIN_REFERENCE))
         return SS_ERR_INVALID_ARG;
     const ss_batch_layout &L = b->lay;
-    if (!(b->cfg.flags & SS_BATCH_FFT) || !L.n_windows || !L.n_bins || b->columns_only) return SS_ERR_INVALID_MODE;   // (columns-only: no rows to reduce)
+    if (!(b->cfg.flags & SS_BATCH_FFT) || !L.n_windows || !L.n_bins || b->cols.on) return SS_ERR_INVALID_MODE;   // (columns-only: no rows to reduce)
     if (gain_mode == SS_GAIN_REFERENCE && !(b->cfg.flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_MODE;
     // column of a bin: floor(chart_x / 100 * cols), the last column closed on the right; chart_x ascends
     std::vector<uint32_t> start(cols + 1, L.n_bins);
@@ -1047,10 +1107,10 @@ int ss_batch_render_spectrum(ss_batch *b, uint32_t cols, int gain_mode, float ga
 
 int ss_batch_set_columns_gain(ss_batch *b, int gain_mode, float gain_db)
 {
-    if (!b || !b->columns_only || (gain_mode != SS_GAIN_FIXED && gain_mode != SS_GAIN_REFERENCE)) return SS_ERR_INVALID_ARG;
+    if (!b || !b->cols.on || (gain_mode != SS_GAIN_FIXED && gain_mode != SS_GAIN_REFERENCE)) return SS_ERR_INVALID_ARG;
     if (gain_mode == SS_GAIN_REFERENCE && !(b->cfg.flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_MODE;
-    b->columns_gain_mode = gain_mode;
-    b->columns_gain_db = gain_db;
+    b->cols.gain_mode = gain_mode;
+    b->cols.gain_db = gain_db;
     return SS_OK;
 }
 
@@ -1060,9 +1120,7 @@ int ss_batch_download_spectrum_columns(ss_batch *b, uint32_t stream, float *out,
     if (!b || !out || stream >= b->cfg.n_streams || !b->render_cols) return SS_ERR_INVALID_ARG;
     const size_t per = (size_t)b->lay.n_windows * b->lay.fft_channels * b->render_cols;
     if (cap < per) return SS_ERR_CAPACITY;
-    HIPCHK(hipMemcpyAsync(out, b->render_spec.p + (size_t)stream * per, per * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, out, b->render_spec.p + (size_t)stream * per, per);
 }
 
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max)
@@ -1083,9 +1141,7 @@ int ss_batch_download_waveform_columns(ss_batch *b, uint32_t stream, float *out,
     if (!b || !out || stream >= b->cfg.n_streams || !b->render_wave_cols) return SS_ERR_INVALID_ARG;
     const size_t per = (size_t)2 * b->render_wave_cols;
     if (cap < per) return SS_ERR_CAPACITY;
-    HIPCHK(hipMemcpyAsync(out, b->render_wave.p + (size_t)stream * per, per * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return SS_OK;
+    return fetch(b, out, b->render_wave.p + (size_t)stream * per, per);
 }
 
 // the waveform chart's x bounds in Player mode (tui.rs:664-681), f64 like the reference
@@ -1107,10 +1163,10 @@ int ss_batch_timing_enable(ss_batch *b, int enable)
 {
     SS_ON_DEVICE(b);
     if (!b) return SS_ERR_INVALID_ARG;
-    int rc = batch_collect_timing(b);
+    int rc = b->timing.collect(b->stream);
     if (rc) return rc;
-    b->timing = enable != 0;
-    for (int k = 0; k < SS_KERNEL_COUNT; k++) { b->t_ms[k] = 0; b->t_n[k] = 0; }
+    b->timing.on = enable != 0;
+    b->timing.reset();
     return SS_OK;
 }
 
@@ -1118,10 +1174,10 @@ int ss_batch_timing_read(ss_batch *b, int kernel, double *total_ms, uint64_t *la
 {
     SS_ON_DEVICE(b);
     if (!b || kernel < 0 || kernel >= SS_KERNEL_COUNT) return SS_ERR_INVALID_ARG;
-    int rc = batch_collect_timing(b);
+    int rc = b->timing.collect(b->stream);
     if (rc) return rc;
-    if (total_ms) *total_ms = b->t_ms[kernel];
-    if (launches) *launches = b->t_n[kernel];
+    if (total_ms) *total_ms = b->timing.ms[kernel];
+    if (launches) *launches = b->timing.launches[kernel];
     return SS_OK;
 }
 
@@ -1143,21 +1199,26 @@ const char *ss_kernel_name(int kernel)
     }
 }
 
-// Analyzer::calculate_integrated_lufs (analyzer.rs:170-182): fresh meter at the
-// handle's sample rate, whole buffer fed in 2*sr-sample chunks, loudness_global.
 }  // extern "C"
-namespace oneshot {
+
+// ============================================================================
+//  the one-shot loudness of a whole buffer
+// ============================================================================
+namespace {
 // the one loudness-only batch the process keeps for calculate_integrated_lufs / receive_audio_file (see integrated_oneshot)
-struct Slot { ss_batch *b = nullptr; uint32_t rate = 0, channels = 0; uint64_t cap = 0; int device = -1; };
-static std::mutex mu;
-static Slot slot;
-}  // namespace oneshot
-extern "C" int ss_release_caches(void)
+struct OneshotSlot { ss_batch *b = nullptr; uint32_t rate = 0, channels = 0; uint64_t cap = 0; int device = -1; };
+std::mutex oneshot_mu;
+OneshotSlot oneshot_slot;
+
+// a one-stream, loudness-only batch of `frames` frames
+ss_batch_config oneshot_config(uint32_t rate, uint32_t channels, uint64_t frames)
 {
-    std::lock_guard<std::mutex> lk(oneshot::mu);
-    if (oneshot::slot.b) { ss_batch_destroy(oneshot::slot.b); oneshot::slot = oneshot::Slot{}; }
-    return SS_OK;
+    ss_batch_config cfg{};          // (no spectrum: fft_n and hop_frames stay 0)
+    cfg.sample_rate = rate; cfg.channels = channels; cfg.n_streams = 1; cfg.flags = SS_BATCH_LUFS; cfg.frames_per_stream = frames;
+    return cfg;
 }
+}  // namespace
+
 int ssh::integrated_oneshot(uint32_t rate, uint32_t channels, const float *samples, size_t n,
                             bool on_device, double *out)
 {
@@ -1178,30 +1239,25 @@ int ssh::integrated_oneshot(uint32_t rate, uint32_t channels, const float *sampl
     // batch of their own as before.
     const uint64_t frames = n / channels;
     constexpr size_t kCacheMaxFloats = (size_t)16 << 20;
-    using oneshot::Slot; using oneshot::slot;
-    std::unique_lock<std::mutex> lk(oneshot::mu, std::defer_lock);
+    OneshotSlot &slot = oneshot_slot;
+    std::unique_lock<std::mutex> lk(oneshot_mu, std::defer_lock);
     ss_batch *b = nullptr;
-    bool cached = false;
-    if (n <= kCacheMaxFloats) {
+    const bool cached = n <= kCacheMaxFloats;
+    if (cached) {
         lk.lock();
         const int dev = current_device();
         if (!(slot.b && slot.device == dev && slot.rate == rate && slot.channels == channels && slot.cap >= frames)) {
-            if (slot.b) { ss_batch_destroy(slot.b); slot = Slot{}; }
-            ss_batch_config cfg{};
-            cfg.sample_rate = rate; cfg.channels = channels; cfg.n_streams = 1; cfg.flags = SS_BATCH_LUFS;
-            cfg.frames_per_stream = frames + frames / 4 + rate; cfg.fft_n = 0; cfg.hop_frames = 0;
+            if (slot.b) { ss_batch_destroy(slot.b); slot = OneshotSlot{}; }
+            const ss_batch_config cfg = oneshot_config(rate, channels, frames + frames / 4 + rate);
             rc = ss_batch_create(&cfg, &slot.b);
-            if (rc) { slot = Slot{}; return rc; }
+            if (rc) { slot = OneshotSlot{}; return rc; }
             slot.rate = rate; slot.channels = channels; slot.cap = cfg.frames_per_stream; slot.device = dev;
         }
         b = slot.b;
-        cached = true;
         rc = ss_batch_set_lengths(b, &frames, 1);
         if (rc) return rc;
     } else {
-        ss_batch_config cfg{};
-        cfg.sample_rate = rate; cfg.channels = channels; cfg.n_streams = 1; cfg.flags = SS_BATCH_LUFS;
-        cfg.frames_per_stream = frames; cfg.fft_n = 0; cfg.hop_frames = 0;
+        const ss_batch_config cfg = oneshot_config(rate, channels, frames);
         rc = ss_batch_create(&cfg, &b);
         if (rc) return rc;
     }
@@ -1216,8 +1272,18 @@ int ssh::integrated_oneshot(uint32_t rate, uint32_t channels, const float *sampl
     *out = r.integrated_lufs;
     return SS_OK;
 }
+
 extern "C" {
 
+int ss_release_caches(void)
+{
+    std::lock_guard<std::mutex> lk(oneshot_mu);
+    if (oneshot_slot.b) { ss_batch_destroy(oneshot_slot.b); oneshot_slot = OneshotSlot{}; }
+    return SS_OK;
+}
+
+// Analyzer::calculate_integrated_lufs (analyzer.rs:170-182): fresh meter at the
+// handle's sample rate, whole buffer fed in 2*sr-sample chunks, loudness_global.
 int ss_calculate_integrated_lufs(ss_analyzer *h, uint32_t channels, const float *samples, size_t n, double *out)
 {
     SS_ON_DEVICE(h);
