@@ -116,7 +116,10 @@ const char *spectrum_kernel_name(SpecKernel k);         // as rocprofv3 prints i
 // ---- time domain ------------------------------------------------------------
 struct TdConst {                 // one per (rate, true-peak factor), device resident
     double b[5], a[5];
-    double m_pow[8][16];         // (A^L)^(2^k), A = zero-input transition, L = td_chunk_frames(C)
+    double bu[5];                // input-referred unit-gain output taps of the batch kernels (sst::kweight_unit_gain_taps):
+                                 // bu[k] = (b[k] - b[0] a[k]) / b[0], k = 1 .. 4: y / b[0] = x + bu[1] v1 + ... + bu[4] v4; bu[0] = b[0]^2, the
+                                 // factor an energy summed over y / b[0] takes where it leaves the lanes
+    double m_pow[8][16];        // (A^L)^(2^k), A = zero-input transition, L = td_chunk_frames(C)
     double m_pow_split[8][16];   // the same for L = td_split_chunk_frames(C): streaming calls shared by a workgroup's waves (SPLIT)
     double m_step_split[68][16]; // A^n, n = 0 .. 67 (same coordinates): the partial last chunk of a SPLIT tile (n < L <= 65)
     double m_chunk_split[64][16];// (A^L)^(c + 1) for chunk c of a SPLIT tile: what the state in front of the tile adds to the state

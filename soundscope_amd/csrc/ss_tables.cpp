@@ -95,6 +95,13 @@ void kweight_design(double rate, double b[5], double a[5])
     a[4] = pa[2] * ra[2];
 }
 
+void kweight_unit_gain_taps(const double b[5], const double a[5], double bu[5])
+{
+    bu[0] = b[0] * b[0];
+    // b[k] - b[0] a[k] in one rounding (b[k] and b[0] a[k] agree in their first four or five bits), then the quotient
+    for (int k = 1; k < 5; k++) bu[k] = std::fma(-b[0], a[k], b[k]) / b[0];
+}
+
 // largest pole radius of the K-weighting filter at `rate` (the two biquads of kweight_design, each on its own: the roots of
 // z^2 + a1 z + a2).  Below 1 the filter forgets its state like radius^n; the crate accepts rates (16 Hz .. ~3.4 kHz) at which the
 // 1682 Hz shelf lies beyond Nyquist and the design is not stable at all.

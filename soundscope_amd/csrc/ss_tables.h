@@ -26,6 +26,12 @@ void bin_tables(uint32_t sample_rate, size_t n, std::vector<double> &freq,
 
 // BS.1770 K-weighting as ebur128 0.1.10 designs it (one 4th-order DF-II section)
 void kweight_design(double rate, double b[5], double a[5]);
+// The output taps with the gain b[0] taken out and referred to the input: the DF-II step is v0 = x - a1 v1 - ... - a4 v4 and
+// y = b0 v0 + b1 v1 + ... + b4 v4, so y / b0 = x + bu[1] v1 + ... + bu[4] v4 with bu[k] = (b[k] - b[0] a[k]) / b[0] — small numbers:
+// numerator and denominator nearly cancel around z = 1 — and bu[0] = b[0]^2 (b[0] is a sum of positive terms over a positive a0 at
+// every rate the shelf lies under Nyquist).  A kernel that needs y for its square alone sums (y / b0)^2 — four FMAs per sample
+// instead of a multiply and four — and scales the sum once by bu[0].
+void kweight_unit_gain_taps(const double b[5], const double a[5], double bu[5]);
 // zero-input state transition of the DF-II state (v1..v4) over `steps` samples,
 // row-major 4x4
 double kweight_pole_radius(double rate);      // largest pole radius of the K-weighting filter (>= 1: not stable at this rate)

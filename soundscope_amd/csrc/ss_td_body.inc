@@ -371,7 +371,21 @@
         tp_prev_bits = wave_max_nonneg_bits(h);
     }
     const double a1 = K.a[1], a2 = K.a[2], a3 = K.a[3], a4 = K.a[4];
-    const double b0 = K.b[0], b1 = K.b[1], b2 = K.b[2], b3 = K.b[3], b4 = K.b[4];
+    // output taps: the instantiations that publish y (RING: handles, ticks, banks) keep the gain b0 in them; batches — the fix-up
+    // launch with the main one, so that both halves of a hand-over agree — need y for e += y^2 alone and run them with unit gain,
+    // referred to the input (SS_KW_OUT_UNIT, ss_td_impl.h: y / b0 = x + g1 v1 + ... + g4 v4).  A tile's energy is scaled by b0^2
+    // where it joins e_run, so everything behind that point — the sub-block close, the trailing partial sub-block, TdState::acc,
+    // which a later streaming call continues from — is in y's units
+    // (not the four-waves register build of whole-stream workgroups, opt-in: five samples' tap chains in flight cost that build
+    // 12-24 more bytes of scratch per lane than the partial sums do — it has no hand-over launch to agree with)
+    constexpr bool kUnitGainBuild = !RING && !(kSplitBatch && WPS == 4);
+    // (a tile with a non-finite sample among its frames or in the state in front of it runs the gained taps, whatever the build:
+    // where an infinity turns into a NaN — in the step behind it, Inf - Inf between b0 v0 and b1 v1 — decides which sub-block's
+    // energy is NaN and which +Inf, and the gating reads that as the crate's filter leaves it; x + g1 Inf would stay an infinity
+    // one step longer.  Rare and wave-uniform: see pass 2.)
+    const double bt0 = K.b[0];
+    const double bt1 = kUnitGainBuild ? K.bu[1] : K.b[1], bt2 = kUnitGainBuild ? K.bu[2] : K.b[2];
+    const double bt3 = kUnitGainBuild ? K.bu[3] : K.b[3], bt4 = kUnitGainBuild ? K.bu[4] : K.b[4];
 
     SS_PROF_DECL
 
@@ -842,7 +856,21 @@
                 if (rpos >= rf32) rpos -= rf32;
             }
 #define SS_RING_PUT(v_) do { if (RING) { ring[(size_t)rpos * C + ch] = (v_); rpos = rpos + 1u == rf32 ? 0u : rpos + 1u; } } while (0)
-            if (len == L) {
+            // (wave-uniform) unit gain for this tile: the build's form, unless a non-finite value is in reach of its filter — among
+            // its own frames (tile_nf; a one-wave run's poisoned state shows there too, chunk 0 runs its first pass from it) or in the
+            // state another wave handed over
+            bool unit_tile = false;
+            if (kUnitGainBuild) {
+                bool state_nf = false;
+                if (SPLIT) state_nf = __ballot(lane_ok && !(fabs(cv[0]) < (double)INFINITY && fabs(cv[1]) < (double)INFINITY &&
+                                                            fabs(cv[2]) < (double)INFINITY && fabs(cv[3]) < (double)INFINITY)) != 0ull;
+                unit_tile = !(tile_nf || state_nf);
+            }
+            // the build's output taps (SS_KW_LA_OUT reads kUnitGain); a unit-gain build's non-finite tile skips the look-ahead loops
+            // and takes the plain step-by-step loop below — the form a partial chunk takes anyway — with the gained taps
+            constexpr bool kUnitGain = kUnitGainBuild;
+            const double b0 = bt0, b1 = bt1, b2 = bt2, b3 = bt3, b4 = bt4;
+            if (len == L && (!kUnitGainBuild || unit_tile)) {
                 // sample peak over x[0 .. L+2]: the three look-ahead samples are the next chunk's (or the
                 // zeroed slack behind the tile), so including them cannot change the channel's maximum
                 const float *xp = xs + 3 * C;
@@ -850,6 +878,7 @@
                 sp = fmaxf(fmaxf(fabsf(xa), fabsf(xb1)), fabsf(xc));
                 SS_KW_LA_INIT((double)xa, (double)xb1, (double)xc)
                 SS_KW_LA_OUT_INIT()
+                double xq0 = (double)xa, xq1 = (double)xb1, xq2 = (double)xc;     // the samples the look-ahead has taken in already
                 for (uint32_t bq = 0; bq < nb_full; bq++, xp += kTdBatch * C) {
                     float xb[kTdBatch];
 #pragma unroll
@@ -857,9 +886,10 @@
 #pragma unroll
                     for (int u = 0; u < kTdBatch; u++) {
                         sp = fmaxf(sp, fabsf(xb[u]));
-                        SS_KW_LA_STEP((double)xb[u]) SS_KW_LA_OUT() SS_KW_SHIFT()
+                        SS_KW_LA_STEP((double)xb[u]) SS_KW_LA_OUT(xq0) SS_KW_SHIFT()
                         e = fma(y_, y_, e);
                         SS_RING_PUT(y_);
+                        xq0 = xq1; xq1 = xq2; xq2 = (double)xb[u];
                     }
                 }
                 i = nb_full * kTdBatch;
@@ -873,17 +903,29 @@
                         if ((uint32_t)u < rem) {
                             // (x[i + 3] of the last three steps belongs to the next chunk: harmless in a maximum, see above)
                             sp = fmaxf(sp, fabsf(xb[u]));
-                            SS_KW_LA_STEP((double)xb[u]) SS_KW_LA_OUT() SS_KW_SHIFT()
+                            SS_KW_LA_STEP((double)xb[u]) SS_KW_LA_OUT(xq0) SS_KW_SHIFT()
                             e = fma(y_, y_, e);
                             SS_RING_PUT(y_);
+                            xq0 = xq1; xq1 = xq2; xq2 = (double)xb[u];
                         }
                     i = L;
                 }
             }
+            // (the gained taps of a unit-gain build: scalar loads here, for the non-finite tile alone)
+            double gb0 = bt0, gb1 = bt1, gb2 = bt2, gb3 = bt3, gb4 = bt4;
+            if (kUnitGainBuild && !unit_tile) {
+                const_f64_ptr bp = (const_f64_ptr)(uintptr_t)&K.b[0];
+                asm volatile("" : "+s"(bp));
+                gb0 = bp[0]; gb1 = bp[1]; gb2 = bp[2]; gb3 = bp[3]; gb4 = bp[4];
+            }
             for (; i < len; i++) {
                 const float xf = xs[i * C];
                 sp = fmaxf(sp, fabsf(xf));
-                SS_KW_STATE((double)xf) SS_KW_OUT() SS_KW_SHIFT()
+                SS_KW_STATE((double)xf)
+                double y_;
+                if (kUnitGainBuild && unit_tile) y_ = SS_KW_OUT_UNIT((double)xf);
+                else y_ = fma(gb0, v0_, fma(gb4, v4, fma(gb3, v3, fma(gb2, v2, gb1 * v1))));
+                SS_KW_SHIFT()
                 e = fma(y_, y_, e);
                 SS_RING_PUT(y_);
             }
@@ -893,7 +935,14 @@
                 SS_TRACE(10);
                 e_run = sh->e_lane[lane];
             }
-            if (!warm) { e_run += e; sp_run = fmaxf(sp_run, sp); }
+            if (!warm) {
+                if (unit_tile) {                        // (b0^2 by a scalar load at the point of use: one FMA instead of the add)
+                    const_f64_ptr eg = (const_f64_ptr)(uintptr_t)&K.bu[0];
+                    asm volatile("" : "+s"(eg));
+                    e_run = fma(eg[0], e, e_run);
+                } else e_run += e;
+                sp_run = fmaxf(sp_run, sp);
+            }
             if (SPLIT && RING) e_call += e;
         }
         // carry-out: exact state after the last valid sample, to the lanes of the channel (chunk 0's lane consumes it), and the

@@ -10,6 +10,7 @@
 #include "ss_kernels.h"
 #include "ss_fft_dev.h"
 #include <atomic>
+#include <type_traits>
 #include <cstdlib>
 #include <cstdio>
 
@@ -43,7 +44,8 @@ namespace ssk {
 //      scan  : in-wave Hillis-Steele over chunks with the constant matrices
 //              (A^L)^(2^k); chunks are dealt round-robin to the four DPP rows so that
 //              the long distances are in-row v_mov_dpp shifts, the short ones ds_bpermute
-//      pass 2: rerun each chunk from its true initial state, accumulate y^2.
+//      pass 2: rerun each chunk from its true initial state, accumulate y^2 (batches, which publish no y: (y / b0)^2 by
+//              input-referred unit-gain output taps, four FMAs per sample, and b0^2 once per tile — SS_KW_OUT_UNIT).
 //    L is chosen by td_chunk_frames (below): whole tiles of whole chunks first (48 kHz stereo: L = 30, a
 //    sub-block = 5 tiles x 32 chunks), then occupancy and the bank conflicts of the per-lane walk.
 //  * True peak at the crate's f32 width, the polyphase FIR  y_f[n] = sum_t c_f[t] x[n-t]  (an f32 fma chain per output), in the
@@ -483,12 +485,16 @@ constexpr int kTdBatch = 5;          // LDS reads issued together in the sequent
     t_ = fma(-a4, v4, t_);                      \
     const double v0_ = fma(-a1, v1, t_);
 #define SS_KW_SHIFT() v4 = v3; v3 = v2; v2 = v1; v1 = v0_;
-#define SS_KW_OUT()                              \
-    double u_ = b1 * v1;                         \
-    u_ = fma(b2, v2, u_);                        \
-    u_ = fma(b3, v3, u_);                        \
-    u_ = fma(b4, v4, u_);                        \
-    const double y_ = fma(b0, v0_, u_);
+// (kUnitGain, set by the body's pass 2 per tile: the batch instantiations, which use y for its square alone, run the output taps with the gain b0
+// taken out AND referred to the input: with v0 = x - a1 v1 - ... - a4 v4,  y / b0 = x + g1 v1 + ... + g4 v4,  g_k = (b_k - b0 a_k) / b0
+// (b1 .. b4 hold g_k there, TdConst::bu) — four FMAs on the sample and the states the recurrence keeps anyway, no multiply and
+// no partial sums; the energy takes b0^2 once per tile where it joins the sub-block's.  Numerator and denominator of the
+// K-weighting nearly cancel around z = 1 (g = -0.07, 0.20, -0.18, 0.06 at 48 kHz against b / b0 = -3.75, 5.29, -3.31, 0.78), so the
+// partial sums are a fifteenth of the gained form's: less rounding in y, not more.  `xcur` is the sample of THIS step — the
+// look-ahead loops consume x three samples ahead and carry the three in between as doubles.  The instantiations that publish y
+// itself, RING, keep the gain in the taps — and so does a tile with a non-finite value in reach, through the plain loop of the
+// body's pass 2: where Inf - Inf first turns up between the taps decides which sub-block's energy is NaN.)
+#define SS_KW_OUT_UNIT(xcur) fma(b4, v4, fma(b3, v3, fma(b2, v2, fma(b1, v1, (xcur)))))
 // Look-ahead form of the same recurrence for full chunks: the terms that do not involve the newest
 // state are folded into partial sums one, two and three samples ahead, so every step issues four
 // independent FMAs and the loop-carried dependency is a single FMA (v_i = r1 - a1 v_{i-1}).
@@ -505,17 +511,25 @@ constexpr int kTdBatch = 5;          // LDS reads issued together in the sequent
     r2 = fma(-a3, v1, r3);                       \
     r3 = fma(-a4, v1, (xn));
 // output taps as partial sums too: y_i = b0 v_i + u1, every update depends on v_i only
+// (unit-gain instantiations: no partial sums — SS_KW_OUT_UNIT on the sample and the states, which SS_KW_SHIFT carries along beside the look-ahead)
 #define SS_KW_LA_OUT_INIT()                                          \
-    double u1 = fma(b4, v4, fma(b3, v3, fma(b2, v2, b1 * v1)));      \
-    double u2 = fma(b4, v3, fma(b3, v2, b2 * v1));                   \
-    double u3 = fma(b4, v2, b3 * v1);                                \
-    double u4 = b4 * v1;
-#define SS_KW_LA_OUT()                           \
-    const double y_ = fma(b0, v0_, u1);          \
-    u1 = fma(b1, v0_, u2);                       \
-    u2 = fma(b2, v0_, u3);                       \
-    u3 = fma(b3, v0_, u4);                       \
-    u4 = b4 * v0_;
+    double u1 = 0.0, u2 = 0.0, u3 = 0.0, u4 = 0.0;                   \
+    if (!kUnitGain) {                                                \
+        u1 = fma(b4, v4, fma(b3, v3, fma(b2, v2, b1 * v1)));         \
+        u2 = fma(b4, v3, fma(b3, v2, b2 * v1));                      \
+        u3 = fma(b4, v2, b3 * v1);                                   \
+        u4 = b4 * v1;                                                \
+    }
+#define SS_KW_LA_OUT(xcur)                       \
+    double y_;                                   \
+    if (kUnitGain) y_ = SS_KW_OUT_UNIT(xcur);    \
+    else {                                       \
+        y_ = fma(b0, v0_, u1);                   \
+        u1 = fma(b1, v0_, u2);                   \
+        u2 = fma(b2, v0_, u3);                   \
+        u3 = fma(b3, v0_, u4);                   \
+        u4 = b4 * v0_;                           \
+    }
 
 // one tap of the crate's interpolator loop: the product and the sum rounded separately (Rust does not contract a * b + c)
 __device__ __forceinline__ float tp_mul_then_add(float acc, float x, float c)
