@@ -100,8 +100,7 @@ int attach_readings(ss_analyzer *h, ssk::FinalizeParams *gating)
     if (rc) return rc;
     h->readings_seq = h->readings_seq + 1u ? h->readings_seq + 1u : 1u;
     gating->readings_out = h->pin_eval.dev;
-    gating->readings_peaks_src = &h->meter.state.p->sample_peak[0]; gating->readings_peaks_dst = h->pin_peaks.dev;
-    gating->readings_flag = h->pin_flag.dev; gating->readings_seq = h->readings_seq;
+    gating->readings = ssk::ReadingsExtra{&h->meter.state.p->sample_peak[0], h->pin_peaks.dev, h->pin_flag.dev, h->readings_seq};
     h->prefetch_stamp = h->change_count;
     return SS_OK;
 }

@@ -220,6 +220,10 @@ uint32_t td_resident_waves_per_cu(uint32_t channels, uint32_t s100, uint32_t hal
 // another chunk length and hence other rounding — the one rule for handles, ticks and every stream of a meter bank
 uint32_t td_ring_tile_frames(uint32_t channels, uint32_t s100);
 
+// a handle's readings in one launch: 2 * kMaxChannels floats copied from peaks_src to peaks_dst beside the evaluation of its
+// histograms, then `seq` stored into *flag (host-visible memory: whoever sees the flag sees the evaluation and the peaks)
+struct ReadingsExtra { const float *peaks_src; float *peaks_dst; uint32_t *flag; uint32_t seq; };
+
 struct FinalizeParams {
     const TdConst *k;
     const double *subblocks; uint64_t sub_stride; uint32_t sub_cap;
@@ -236,11 +240,12 @@ struct FinalizeParams {
     const uint32_t *sub_end_of;   // ragged batches: sub-blocks of each stream (nullable = sub_end for all)
     const TdState *state;         // [stream]: bad_key (first sub-block with a non-finite sample per channel); nullable
     // launch_finalize_stream only (one handle): behind the histogram updates the same wave takes the handle's readings — (integrated,
-    // range) into readings_out, the peaks and the flag as in ReadingsExtra below (readings_out == nullptr: off)
+    // range) into readings_out, the peaks and the flag as `readings` says (readings_out == nullptr: off)
     double *readings_out;
-    const float *readings_peaks_src; float *readings_peaks_dst; uint32_t *readings_flag; uint32_t readings_seq;
+    ReadingsExtra readings;
 };
-// batches: the gating of every stream's sub-blocks [sub_begin, sub_end) into its own and the corpus histograms, the per-stream outputs
+// batches: the gating of every stream's sub-blocks [0, sub_end) into its own and the corpus histograms, the per-stream outputs
+// (slot == sub-block index: hipErrorInvalidValue unless sub_begin == 0 and sub_end <= sub_cap, below 2^31)
 hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s);
 // a handle (one stream, a few new sub-blocks per call): k_finalize_stream — the histograms updated in place and, when readings_out
 // is set, the handle's readings taken behind them
@@ -253,9 +258,7 @@ struct LoudnessExtremes { double max_m, max_s; uint32_t at_m, at_s; };
 hipError_t launch_loudness_series(const FinalizeParams &p, double *series, uint64_t series_stride, LoudnessExtremes *extremes,
                                   hipStream_t s);
 // gate + LRA on explicit histograms (corpus gate after the all-reduce; handle getters)
-// `peaks` (optional): a handle's readings in one launch — 2 * kMaxChannels floats copied from peaks_src to peaks_dst beside the
-// evaluation, then `seq` stored into *flag (host-visible memory: whoever sees the flag sees out2 and the peaks)
-struct ReadingsExtra { const float *peaks_src; float *peaks_dst; uint32_t *flag; uint32_t seq; };
+// `peaks` (optional): a handle's readings in one launch (ReadingsExtra above)
 hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, const double *bounds,
                             double *out2, hipStream_t s, const ReadingsExtra *peaks = nullptr);
 // mean-square of the filtered ring over the last `frames` frames (handle getters)

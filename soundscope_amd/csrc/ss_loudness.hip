@@ -4,6 +4,8 @@
 // arithmetic of ebur128 0.1.10 / spectrum-analyzer 1.7.0 / microfft 0.6.0 as restated in DESIGN.md.
 // Nothing here is translated from the reference: the reference has no GPU code.
 #include "ss_kernels.h"
+#include "ss_loudness_dev.h"
+#include <type_traits>
 
 namespace ssk {
 // ============================================================================
@@ -22,13 +24,8 @@ __device__ __forceinline__ uint32_t hist_index(const double *__restrict__ bounds
     return (uint32_t)i;
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v)
 {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -59,7 +56,7 @@ __device__ __forceinline__ void eval_hist(const unsigned long long *hb, const un
     // ---- integrated: relative gate at -10 LU of the mean of all blocks
     double sum = 0.0; unsigned long long cnt = 0;
     for (int i = lane; i < kHistBins; i += 64) { sum += (double)hb[i] * en[i]; cnt += hb[i]; }
-    sum = wave_sum(sum); cnt = wave_sum_u64(cnt);
+    sum = wave_sum(sum); cnt = wave_sum(cnt);
     double integrated;
     if (cnt == 0) integrated = -INFINITY;
     else {
@@ -69,13 +66,13 @@ __device__ __forceinline__ void eval_hist(const unsigned long long *hb, const un
         else { start = hist_index(bd, rel); if (rel > en[start]) start++; }
         double g = 0.0; unsigned long long c2 = 0;
         for (int i = lane; i < kHistBins; i += 64) if ((uint32_t)i >= start) { g += (double)hb[i] * en[i]; c2 += hb[i]; }
-        g = wave_sum(g); c2 = wave_sum_u64(c2);
+        g = wave_sum(g); c2 = wave_sum(c2);
         integrated = c2 ? 10.0 * log10(g / (double)c2) - 0.691 : -INFINITY;
     }
     // ---- LRA (EBU Tech 3342) on the short-term histogram
     double power = 0.0; unsigned long long size = 0;
     for (int i = lane; i < kHistBins; i += 64) { power += (double)hs[i] * en[i]; size += hs[i]; }
-    power = wave_sum(power); size = wave_sum_u64(size);
+    power = wave_sum(power); size = wave_sum(size);
     double lra = 0.0;
     if (size != 0) {
         const double integ = 0.01 * (power / (double)size);
@@ -194,13 +191,94 @@ __device__ __forceinline__ double window_energy_eager(const double *__restrict__
     return sum;
 }
 
+// The weighted energy of the N sub-blocks ending with sub-block j, in the form its launch takes: EAGER for the latency-bound
+// launches (window_energy_eager), DIRECT where slot == sub-block index (batches; otherwise a ring of `cap` slots)
+template <int N, bool EAGER, bool DIRECT>
+__device__ __forceinline__ double block_energy(const double *__restrict__ P, uint64_t j, uint32_t cap, uint32_t C,
+                                               const double *__restrict__ weights)
+{
+    const uint32_t jm = DIRECT ? (uint32_t)j : (uint32_t)(j % cap);
+    return EAGER ? window_energy_eager<N, DIRECT>(P, jm, cap, C, weights) : window_energy<N, DIRECT>(P, jm, cap, C, weights);
+}
+
+// The gating loop, once: the gating and short-term blocks of ONE stream that end with its sub-blocks [sub_begin, sub_end), dealt
+// to threads tid, tid + nthr, ... — a gating block ends with every sub-block j >= 3 (j-3..j), a short-term block with j = 29 + 10 m
+// (j-29..j).  The blocks are independent: every one at or above the absolute gate is an atomic increment of its bin of hb (gating)
+// or hs (short-term) — the LDS pair of a batch's workgroup, or the stream's histograms in memory themselves.  `bd`: the bin
+// boundaries (an LDS copy or the table itself: the same bins either way).  Returns this thread's block counts.
+struct GateCounts { uint32_t nb, ns; };
+template <bool EAGER, bool DIRECT>
+__device__ __forceinline__ GateCounts gate_range(const double *__restrict__ P, uint32_t cap, uint32_t C, const double *__restrict__ weights,
+                                                 const TdConst &K, const double *__restrict__ bd, double bd0, uint64_t sub_begin,
+                                                 uint64_t sub_end, uint64_t bad_from, unsigned long long *hb, unsigned long long *hs,
+                                                 uint32_t tid, uint32_t nthr)
+{
+    // DIRECT: the index is the slot, a 32-bit number (launch_finalize checks).  Counted in 64 bits there, k_finalize<false> spilled
+    // 124 bytes of scratch per lane and k_finalize<true> took 256 VGPRs + 60 AGPRs: one wave per SIMD instead of two
+    using J = std::conditional_t<DIRECT, uint32_t, uint64_t>;
+    const double S = (double)K.s100;
+    GateCounts n{0u, 0u};
+    for (J j = (J)(sub_begin > 3 ? sub_begin : 3) + tid; j < sub_end; j += nthr) {
+        double sum = block_energy<4, EAGER, DIRECT>(P, j, cap, C, weights) / (4.0 * S);
+        if (j > bad_from) sum = __builtin_nan("");
+        n.nb++;
+        if (sum >= bd0) atomicAdd(&hb[hist_index(bd, sum)], 1ull);
+    }
+    // short-term blocks: dealt densely (thread = m), not as every tenth thread of the loop above
+    if (!K.st_off) {
+        const uint64_t m_begin = sub_begin > 29 ? (sub_begin - 29 + 9) / 10 : 0;      // first m with 29 + 10 m >= sub_begin
+        for (J m = (J)m_begin + tid;; m += nthr) {
+            const J j = 29 + 10 * m;
+            if (j >= sub_end) break;
+            double sum = block_energy<30, EAGER, DIRECT>(P, j, cap, C, weights) / (30.0 * S);
+            if (j > bad_from) sum = __builtin_nan("");
+            n.ns++;
+            if (sum >= bd0) atomicAdd(&hs[hist_index(bd, sum)], 1ull);
+        }
+    }
+    return n;
+}
+
+// The two tables the gate reads — bin energies and bin boundaries, 16 KB — into LDS as tab = [energies 1000][bounds 1001]: every
+// dependent table read behind it is an LDS access, not a round trip to L2.  also(i): what else the caller brings in with bin i,
+// requested in the same trip to memory.
+constexpr int kTabDoubles = 2 * kHistBins + 1;
+template <class Also>
+__device__ __forceinline__ void stage_tables(double *tab, const double *en, const double *bd, int tid, int nthr, Also &&also)
+{
+    for (int i = tid; i < kHistBins; i += nthr) { also(i); tab[i] = en[i]; tab[kHistBins + i] = bd[i]; }
+    if (tid == 0) tab[2 * kHistBins] = bd[kHistBins];
+}
+
+// A handle's readings, by one wave whose LDS pair (hb, hs) holds the handle's histograms (the caller's loads, not yet behind a
+// barrier): the 2 * kMaxChannels peak floats copied beside the evaluation, (integrated, range) into out2, then `seq` stored into
+// *flag behind a system fence — host-visible memory: whoever sees the flag sees out2 and the peaks.
+__device__ __forceinline__ void publish_readings(const ReadingsExtra &x, const unsigned long long *hb, const unsigned long long *hs,
+                                                 const double *__restrict__ en, const double *__restrict__ bd, double *out2)
+{
+    static_assert(2 * kMaxChannels == 128, "two floats per lane");
+    const int lane = threadIdx.x;
+    if (x.peaks_dst) {
+        x.peaks_dst[lane] = x.peaks_src[lane];
+        x.peaks_dst[64 + lane] = x.peaks_src[64 + lane];
+    }
+    __syncthreads();
+    eval_hist(hb, hs, en, bd, &out2[0], &out2[1]);
+    if (x.flag) {
+        __threadfence_system();
+        __syncthreads();
+        if (lane == 0) __hip_atomic_store(x.flag, x.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // One workgroup per stream; the gating blocks of a stream are independent (histogram increments are LDS atomics), so a
 // long stream (config 2's 600 s: 6000 sub-blocks) is spread over up to 1024 threads — a thread's iteration is a chain of
 // dependent loads, so the kernel's time is its iteration count; wave 0 then evaluates gate and LRA.
-// SMALL (a handful of streams: config 2, a file open, calculate_integrated_lufs): the two tables the gate reads — bin energies and
-// bin boundaries, 16 KB — come into LDS with the histograms, and the sub-block sums are requested eagerly: the kernel's chain of
+// SMALL (a handful of streams: config 2, a file open, calculate_integrated_lufs): the two tables the gate reads come into LDS with
+// the histograms, and the sub-block sums are requested eagerly: the kernel's chain of
 // dependent trips to L2 / HBM is four long instead of eighteen (config 2: 22.5 -> 20 us, config 5: 31 -> 25 us, profiles/r05_small_batch_finalize.txt).  The big grids keep
 // the lean form: 16 KB more LDS traffic per workgroup buys nothing where a thousand workgroups hide each other's latency.
+// Batches only: slot == sub-block index, from sub-block 0 on (launch_finalize refuses anything else).
 template <bool SMALL>
 __global__ __launch_bounds__(SMALL ? 256 : 1024) void k_finalize(FinalizeParams p)
 {
@@ -208,16 +286,14 @@ __global__ __launch_bounds__(SMALL ? 256 : 1024) void k_finalize(FinalizeParams 
     __shared__ unsigned long long hs[kHistBins];
     __shared__ unsigned int counts[2];
     __shared__ uint32_t bad_from_s;
-    __shared__ double tab[SMALL ? 2 * kHistBins + 1 : 1];          // SMALL: [energies 1000][bounds 1001]
+    __shared__ double tab[SMALL ? kTabDoubles : 1];
     const uint32_t stream = blockIdx.x;
     const int lane = threadIdx.x, nthr = (int)blockDim.x;
     unsigned long long *gh = reinterpret_cast<unsigned long long *>(p.hist) + (size_t)stream * 2 * kHistBins;
     unsigned long long *corpus = reinterpret_cast<unsigned long long *>(p.corpus_hist);
-    for (int i = lane; i < kHistBins; i += nthr) {
-        hb[i] = gh[i]; hs[i] = gh[kHistBins + i];
-        if (SMALL) { tab[i] = p.hist_energies[i]; tab[kHistBins + i] = p.hist_bounds[i]; }
-    }
-    if (SMALL && lane == 0) tab[2 * kHistBins] = p.hist_bounds[kHistBins];
+    auto load_hist = [&](int i) { hb[i] = gh[i]; hs[i] = gh[kHistBins + i]; };
+    if (SMALL) stage_tables(tab, p.hist_energies, p.hist_bounds, lane, nthr, load_hist);
+    else for (int i = lane; i < kHistBins; i += nthr) load_hist(i);
     if (lane < 2) counts[lane] = 0;
     if (lane < 64) {
         const uint32_t bf = first_bad_subblock(p.state ? p.state + stream : nullptr, p.channels, p.weights, (uint32_t)lane);
@@ -226,46 +302,13 @@ __global__ __launch_bounds__(SMALL ? 256 : 1024) void k_finalize(FinalizeParams 
     const double *en = SMALL ? tab : p.hist_energies;
     const double *bd = SMALL ? tab + kHistBins : p.hist_bounds;
     const double bd0 = p.hist_bounds[0];                                                  // (read before the barrier: in flight with the rest)
-    // gating block ending with sub-block j: j-3..j ; short-term block: j-29..j when (j-29) % 10 == 0
     const uint64_t sub_end = p.sub_end_of ? p.sub_end_of[stream] : p.sub_end;          // ragged batches
     __syncthreads();
 
-    const uint32_t C = p.channels;
-    const double S = (double)p.k->s100;
-    const double *P = p.subblocks + (size_t)stream * p.sub_stride;
-    const uint32_t cap = p.sub_cap;
-    const bool direct = p.sub_end <= (uint64_t)cap && p.sub_begin == 0;               // batches: slot == sub-block index
-    const uint64_t bad_from = bad_from_s;
-    uint32_t nb = 0, ns = 0;
-    // gating blocks: one per sub-block j >= 3
-    for (uint64_t j = (p.sub_begin > 3 ? p.sub_begin : 3) + lane; j < sub_end; j += nthr) {
-        const uint32_t jm = direct ? (uint32_t)j : (uint32_t)(j % cap);
-        double sum;
-        if (SMALL) sum = direct ? window_energy_eager<4, true>(P, jm, cap, C, p.weights) : window_energy_eager<4, false>(P, jm, cap, C, p.weights);
-        else sum = direct ? window_energy<4, true>(P, jm, cap, C, p.weights) : window_energy<4, false>(P, jm, cap, C, p.weights);
-        sum /= 4.0 * S;
-        nb++;
-        if (j > bad_from) sum = __builtin_nan("");
-        if (sum >= bd0) atomicAdd(&hb[hist_index(bd, sum)], 1ull);
-    }
-    // short-term blocks: j = 29 + 10 m.  Dealt densely (thread = m), not as every tenth lane of the loop above
-    if (!p.k->st_off) {
-        const uint64_t m_begin = p.sub_begin > 29 ? (p.sub_begin - 29 + 9) / 10 : 0;      // first m with 29 + 10 m >= sub_begin
-        for (uint64_t m = m_begin + lane;; m += nthr) {
-            const uint64_t j = 29 + 10 * m;
-            if (j >= sub_end) break;
-            const uint32_t jm = direct ? (uint32_t)j : (uint32_t)(j % cap);
-            double sum;
-            if (SMALL) sum = direct ? window_energy_eager<30, true>(P, jm, cap, C, p.weights) : window_energy_eager<30, false>(P, jm, cap, C, p.weights);
-            else sum = direct ? window_energy<30, true>(P, jm, cap, C, p.weights) : window_energy<30, false>(P, jm, cap, C, p.weights);
-            sum /= 30.0 * S;
-            ns++;
-            if (j > bad_from) sum = __builtin_nan("");
-            if (sum >= bd0) atomicAdd(&hs[hist_index(bd, sum)], 1ull);
-        }
-    }
-    if (nb) atomicAdd(&counts[0], nb);
-    if (ns) atomicAdd(&counts[1], ns);
+    const GateCounts n = gate_range<SMALL, true>(p.subblocks + (size_t)stream * p.sub_stride, p.sub_cap, p.channels, p.weights, *p.k, bd,
+                                                 bd0, 0, sub_end, bad_from_s, hb, hs, (uint32_t)lane, (uint32_t)nthr);
+    if (n.nb) atomicAdd(&counts[0], n.nb);
+    if (n.ns) atomicAdd(&counts[1], n.ns);
     __syncthreads();
     // corpus contribution = what this call added
     for (int i = lane; i < kHistBins; i += nthr) {
@@ -284,56 +327,26 @@ __global__ __launch_bounds__(SMALL ? 256 : 1024) void k_finalize(FinalizeParams 
                   p.out_lra ? &p.out_lra[stream] : nullptr);
 }
 
-// The gating and short-term blocks of ONE stream that end with its sub-blocks [sub_begin, sub_end), by one wave: histogram
-// increments by global atomics into gh (block ++ short-term), the block counts into out_counts (nullable).  `bd`: the bin
-// boundaries (an LDS copy or the table itself: the same bins either way).  The streaming gating launches (a handle, a meter bank).
-__device__ __forceinline__ void gate_stream_range(const double *__restrict__ P, uint32_t cap, uint32_t C, const double *__restrict__ weights,
-                                                  const TdConst &K, const double *__restrict__ bd, double bd0, uint64_t sub_begin,
-                                                  uint64_t sub_end, uint64_t bad_from, unsigned long long *gh, uint32_t *out_counts,
-                                                  uint32_t lane)
-{
-    const double S = (double)K.s100;
-    uint32_t nb = 0, ns = 0;
-    for (uint64_t j = (sub_begin > 3 ? sub_begin : 3) + lane; j < sub_end; j += 64) {
-        double sum = window_energy_eager<4, false>(P, (uint32_t)(j % cap), cap, C, weights) / (4.0 * S);
-        if (j > bad_from) sum = __builtin_nan("");
-        nb++;
-        if (sum >= bd0) atomicAdd(&gh[hist_index(bd, sum)], 1ull);
-    }
-    if (!K.st_off) {
-        const uint64_t m_begin = sub_begin > 29 ? (sub_begin - 29 + 9) / 10 : 0;
-        for (uint64_t m = m_begin + lane;; m += 64) {
-            const uint64_t j = 29 + 10 * m;
-            if (j >= sub_end) break;
-            double sum = window_energy_eager<30, false>(P, (uint32_t)(j % cap), cap, C, weights) / (30.0 * S);
-            if (j > bad_from) sum = __builtin_nan("");
-            ns++;
-            if (sum >= bd0) atomicAdd(&gh[kHistBins + hist_index(bd, sum)], 1ull);
-        }
-    }
-    if (out_counts) {
-        if (nb) atomicAdd(&out_counts[0], nb);
-        if (ns) atomicAdd(&out_counts[1], ns);
-    }
-}
-
 // Streaming form (one handle, a few new sub-blocks per call, no per-call read-out): the same gating rules
 // with the histogram updated in place by global atomics instead of a 16 KB round trip through LDS.
 __global__ __launch_bounds__(64) void k_finalize_stream(FinalizeParams p)
 {
-    // one wave, and every step waits for the one before it: the tables the gate reads (bin energies, bin boundaries) are staged in
+    // one wave, and every step waits for the one before it: the tables the gate reads are staged in
     // LDS first — ONE round trip to L2 instead of one per dependent table read (two per histogram index, eight in eval_hist)
-    __shared__ double tab[2 * kHistBins + 1];
+    __shared__ double tab[kTabDoubles];
     const int lane = threadIdx.x;
-    for (int i = lane; i < kHistBins; i += 64) { tab[i] = p.hist_energies[i]; tab[kHistBins + i] = p.hist_bounds[i]; }
-    if (lane == 0) tab[2 * kHistBins] = p.hist_bounds[kHistBins];
+    stage_tables(tab, p.hist_energies, p.hist_bounds, lane, 64, [](int) {});
     const double *en = tab, *bd = tab + kHistBins;
     const double bd0 = p.hist_bounds[0];
     const uint64_t bad_from = first_bad_subblock(p.state, p.channels, p.weights, (uint32_t)lane);
     __syncthreads();
     unsigned long long *gh = reinterpret_cast<unsigned long long *>(p.hist);
-    gate_stream_range(p.subblocks, p.sub_cap, p.channels, p.weights, *p.k, bd, bd0, p.sub_begin, p.sub_end, bad_from, gh, p.out_counts,
-                      (uint32_t)lane);
+    const GateCounts n = gate_range<true, false>(p.subblocks, p.sub_cap, p.channels, p.weights, *p.k, bd, bd0, p.sub_begin, p.sub_end,
+                                                 bad_from, gh, gh + kHistBins, (uint32_t)lane, 64u);
+    if (p.out_counts) {
+        if (n.nb) atomicAdd(&p.out_counts[0], n.nb);
+        if (n.ns) atomicAdd(&p.out_counts[1], n.ns);
+    }
     // the handle's readings behind the update (what the reference's render loop asks for on its next frame): the same wave
     // evaluates the histograms it has just touched — no launch of its own inside a tick
     if (p.readings_out) {
@@ -344,17 +357,7 @@ __global__ __launch_bounds__(64) void k_finalize_stream(FinalizeParams p)
             hb[i] = __hip_atomic_load(&gh[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             hs[i] = __hip_atomic_load(&gh[kHistBins + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (p.readings_peaks_dst) {
-            p.readings_peaks_dst[lane] = p.readings_peaks_src[lane];
-            p.readings_peaks_dst[64 + lane] = p.readings_peaks_src[64 + lane];
-        }
-        __syncthreads();
-        eval_hist(hb, hs, en, bd, &p.readings_out[0], &p.readings_out[1]);
-        if (p.readings_flag) {
-            __threadfence_system();
-            __syncthreads();
-            if (lane == 0) __hip_atomic_store(p.readings_flag, p.readings_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        publish_readings(p.readings, hb, hs, en, bd, p.readings_out);
     }
 }
 
@@ -362,10 +365,11 @@ constexpr uint32_t kFinalizeSmallMax = 64u;      // streams up to which a launch
 hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s)
 {
     if (p.n_streams == 0) return hipSuccess;
+    // batches: slot == sub-block index, and the index a 32-bit number (the direct form of gate_range counts in 32 bits)
+    if (p.sub_begin != 0 || p.sub_end > p.sub_cap || p.sub_end >> 31) return hipErrorInvalidValue;
     // four waves per stream (even a 100-sub-block stream moves two 8 KB histograms in and out of LDS: 64 / 128 / 256 / 512
     // threads at the bench shape: 0.043 / 0.036 / 0.033 / 0.045 ms), sixteen for a long stream
-    const uint64_t nsub = p.sub_end - p.sub_begin;
-    const uint32_t threads = nsub > 2048 ? 1024u : 256u;
+    const uint32_t threads = p.sub_end > 2048 ? 1024u : 256u;
     // a handful of short streams: the launch is a chain of memory round trips, not work -> the form that shortens the chain
     if (p.n_streams <= kFinalizeSmallMax && threads == 256u) hipLaunchKernelGGL(k_finalize<true>, dim3(p.n_streams), dim3(threads), 0, s, p);
     else hipLaunchKernelGGL(k_finalize<false>, dim3(p.n_streams), dim3(threads), 0, s, p);
@@ -398,8 +402,6 @@ __device__ __forceinline__ double window_energy_head(const double *__restrict__ 
     }
     return sum;
 }
-
-__device__ __forceinline__ double energy_to_lufs(double e) { return e <= 0.0 ? -INFINITY : 10.0 * log10(e) - 0.691; }
 
 // (value, j) maximum: a NaN never wins, ties go to the lower j; (-inf, 0xFFFFFFFF) is "none yet" and loses to any value
 __device__ __forceinline__ void max_at(double &v, uint32_t &at, double v2, uint32_t at2)
@@ -437,11 +439,11 @@ __global__ __launch_bounds__(SMALL ? 256 : 1024) void k_loudness_series(Finalize
     uint32_t am = kNone, as = kNone;
     for (uint32_t j = (uint32_t)tid; j < n; j += (uint32_t)nthr) {
         double em, es = __builtin_nan("");
-        if (j >= 3) em = SMALL ? window_energy_eager<4, true>(P, j, cap, C, p.weights) : window_energy<4, true>(P, j, cap, C, p.weights);
+        if (j >= 3) em = block_energy<4, SMALL, true>(P, j, cap, C, p.weights);
         else em = window_energy_head<4>(P, j, C, p.weights);
         em /= 4.0 * S;
         if (st_on) {
-            if (j >= 29) es = SMALL ? window_energy_eager<30, true>(P, j, cap, C, p.weights) : window_energy<30, true>(P, j, cap, C, p.weights);
+            if (j >= 29) es = block_energy<30, SMALL, true>(P, j, cap, C, p.weights);
             else es = window_energy_head<30>(P, j, C, p.weights);
             es /= 30.0 * S;
         }
@@ -486,29 +488,14 @@ __global__ __launch_bounds__(64) void k_hist_eval(const unsigned long long *hist
 {
     __shared__ unsigned long long hb[kHistBins];
     __shared__ unsigned long long hs[kHistBins];
-    __shared__ double tab[2 * kHistBins + 1];               // the two tables beside the histograms: one round trip for all four
-    for (int i = threadIdx.x; i < kHistBins; i += 64) {
-        hb[i] = hist2000[i]; hs[i] = hist2000[kHistBins + i];
-        tab[i] = en[i]; tab[kHistBins + i] = bd[i];
-    }
-    if (threadIdx.x == 0) tab[2 * kHistBins] = bd[kHistBins];
-    if (x.peaks_dst) {
-        x.peaks_dst[threadIdx.x] = x.peaks_src[threadIdx.x];
-        x.peaks_dst[64 + threadIdx.x] = x.peaks_src[64 + threadIdx.x];
-    }
-    __syncthreads();
-    eval_hist(hb, hs, tab, tab + kHistBins, &out2[0], &out2[1]);
-    if (x.flag) {
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(x.flag, x.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    __shared__ double tab[kTabDoubles];                     // the two tables beside the histograms: one round trip for all four
+    stage_tables(tab, en, bd, threadIdx.x, 64, [&](int i) { hb[i] = hist2000[i]; hs[i] = hist2000[kHistBins + i]; });
+    publish_readings(x, hb, hs, tab, tab + kHistBins, out2);
 }
 
 hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, const double *bounds,
                             double *out2, hipStream_t s, const ReadingsExtra *peaks)
 {
-    static_assert(2 * kMaxChannels == 128, "k_hist_eval copies two floats per lane");
     hipLaunchKernelGGL(k_hist_eval, dim3(1), dim3(64), 0, s,
                        reinterpret_cast<const unsigned long long *>(hist2000), energies, bounds, out2,
                        peaks ? *peaks : ReadingsExtra{nullptr, nullptr, nullptr, 0u});
@@ -520,10 +507,8 @@ hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, co
 // Two stages with a fixed reduction shape (bit-reproducible): kRingBlocks partial sums, then one block — in ONE launch: the
 // workgroup that finishes last (a counter behind the partial sums, wrapped back to zero by atomicInc for the next launch)
 // reduces the partial sums.  (Through round 3 the second stage was a launch of its own: one more of a tick's launches.)
-// The window is ONE run of ring elements with at most one wrap (frames <= ring_frames), so an element's position is an add and
-// a compare in 32 bits and its channel advances by a constant step: no division in the loop (the first version divided two
-// 64-bit numbers per element — most of its 9.8 us inside a tick).  256 workgroups: a thread takes four or five elements of the
-// three-second window at 48 kHz stereo, all requested before the first is used.
+// The window is ONE run of ring elements with at most one wrap (frames <= ring_frames): ring_sumsq.  256 workgroups: a thread takes
+// four or five elements of the three-second window at 48 kHz stereo, all requested before the first is used.
 constexpr int kRingBlocks = 256;
 __global__ __launch_bounds__(256) void k_ring_energy(const double *ring, uint32_t ring_elems, uint32_t C, uint32_t begin_elem,
                                                      uint32_t total, double frames,
@@ -531,33 +516,7 @@ __global__ __launch_bounds__(256) void k_ring_energy(const double *ring, uint32_
 {
     __shared__ double red[256];
     __shared__ uint32_t is_last;
-    constexpr uint32_t kStride = (uint32_t)kRingBlocks * 256u;
-    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t cstep = kStride % C;
-    uint32_t c = tid % C;
-    double acc = 0.0;
-    uint32_t i = tid;
-    for (; i + 3u * kStride < total; i += 4u * kStride) {
-        double y[4], w[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            uint32_t e = begin_elem + i + (uint32_t)q * kStride;
-            if (e >= ring_elems) e -= ring_elems;
-            y[q] = ring[e];
-            w[q] = weights[c];
-            c += cstep; if (c >= C) c -= C;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc = w[q] != 0.0 ? fma(w[q] * y[q], y[q], acc) : acc;      // (weight 0: a channel the crate does not
-    }                                                                                              //  filter — its ring stays zero there, whatever the input)
-    for (; i < total; i += kStride) {
-        uint32_t e = begin_elem + i;
-        if (e >= ring_elems) e -= ring_elems;
-        const double y = ring[e];
-        const double wc = weights[c];
-        acc = wc != 0.0 ? fma(wc * y, y, acc) : acc;
-        c += cstep; if (c >= C) c -= C;
-    }
+    double acc = ring_sumsq(ring, ring_elems, C, begin_elem, total, blockIdx.x * 256u + threadIdx.x, (uint32_t)kRingBlocks * 256u, weights, 0.0);
     // workgroup sum: shuffle tree inside each wave, then the four wave sums in a fixed order
     for (int d = 32; d >= 1; d >>= 1) acc += __shfl_down(acc, d, 64);
     if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = acc;
@@ -579,7 +538,7 @@ __global__ __launch_bounds__(256) void k_ring_energy(const double *ring, uint32_
     if (threadIdx.x == 0) {
         const double e = red[0] / frames;
         out[0] = e;
-        out[1] = e <= 0.0 ? -INFINITY : 10.0 * log10(e) - 0.691;   // energy_to_loudness
+        out[1] = energy_to_lufs(e);
     }
 }
 
@@ -600,7 +559,7 @@ hipError_t launch_ring_energy(const double *ring, uint64_t ring_frames, uint32_t
 // ============================================================================
 //  Meter banks: N streaming meters advanced by one launch per stage
 // ============================================================================
-// Gating of every stream's new sub-blocks behind a bank's time-domain launch: one wave per stream, k_finalize_stream's gating
+// Gating of every stream's new sub-blocks behind a bank's time-domain launch: one wave per stream, k_finalize_stream's gate_range
 // (the same window form, hence a handle's histograms bit for bit) over the stream's own range, derived from its frame count.
 // Streams that completed no sub-block leave at once.  The tables are read where they are (L2): a wave has a few blocks to gate.
 // frames_of (ragged adds): what the launch gave each stream; a stream that got nothing leaves before it reads its state.
@@ -616,8 +575,11 @@ __global__ __launch_bounds__(64) void k_meter_bank_gate(MeterBankParams p, uint6
     if (sb1 == sb0) return;
     const uint64_t bad_from = first_bad_subblock(st, p.channels, p.weights, lane);
     unsigned long long *gh = reinterpret_cast<unsigned long long *>(p.hist) + (size_t)stream * 2 * kHistBins;
-    gate_stream_range(p.subblocks + (size_t)stream * p.sub_stride, p.sub_cap, p.channels, p.weights, *p.k, p.hist_bounds,
-                      p.hist_bounds[0], sb0, sb1, bad_from, gh, p.counts + 2 * (size_t)stream, lane);
+    const GateCounts n = gate_range<true, false>(p.subblocks + (size_t)stream * p.sub_stride, p.sub_cap, p.channels, p.weights, *p.k,
+                                                 p.hist_bounds, p.hist_bounds[0], sb0, sb1, bad_from, gh, gh + kHistBins, lane, 64u);
+    uint32_t *counts = p.counts + 2 * (size_t)stream;
+    if (n.nb) atomicAdd(&counts[0], n.nb);
+    if (n.ns) atomicAdd(&counts[1], n.ns);
 }
 
 hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, const uint64_t *frames_of, hipStream_t s)
@@ -652,33 +614,9 @@ __device__ __forceinline__ double bank_window_energy(const MeterBankParams &p, c
         if (k >= q && w != 0.0) e += w * P[(size_t)((k - q) % cap) * C + c];
     }
     if (k >= (uint64_t)N && r != 0u) {
-        // one run of ring elements with at most one wrap (S - r <= ring_frames): an add and a compare per element, the channel
-        // advancing by a constant step; four loads in flight per lane
-        const uint32_t ring_elems = (uint32_t)(p.ring_frames * C);
-        const uint32_t begin = (uint32_t)((((k - N) * S + r) % p.ring_frames) * C);
-        const uint32_t total = (uint32_t)((S - r) * C);
-        const uint32_t cstep = 64u % C;
-        uint32_t c = lane % C, i = lane;
-        for (; i + 3u * 64u < total; i += 4u * 64u) {
-            double y[4], w[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                uint32_t el = begin + i + 64u * (uint32_t)q;
-                if (el >= ring_elems) el -= ring_elems;
-                y[q] = R[el];
-                w[q] = p.weights[c];
-                c += cstep; if (c >= C) c -= C;
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) e = w[q] != 0.0 ? fma(w[q] * y[q], y[q], e) : e;
-        }
-        for (; i < total; i += 64u) {
-            uint32_t el = begin + i;
-            if (el >= ring_elems) el -= ring_elems;
-            const double y = R[el], w = p.weights[c];
-            e = w != 0.0 ? fma(w * y, y, e) : e;
-            c += cstep; if (c >= C) c -= C;
-        }
+        // (S - r <= ring_frames: one run with at most one wrap)
+        e = ring_sumsq(R, (uint32_t)(p.ring_frames * C), C, (uint32_t)((((k - N) * S + r) % p.ring_frames) * C), (uint32_t)((S - r) * C),
+                       lane, 64u, p.weights, e);
     }
     return wave_sum(e);
 }

@@ -9,6 +9,7 @@
 // Nothing here is translated from the reference: the reference has no GPU code.
 #include "ss_kernels.h"
 #include "ss_fft_dev.h"
+#include "ss_loudness_dev.h"
 #include <atomic>
 #include <type_traits>
 #include <cstdlib>
@@ -599,47 +600,21 @@ __device__ __forceinline__ void tick_reading_finish(const TdParams &p, uint32_t 
         const double tot = __builtin_nontemporal_load(p.st_scratch + kRingTickBlocks + 1);
         const double en = (pr + tot) / p.st_frames;
         p.st_out[0] = en;
-        p.st_out[1] = en <= 0.0 ? -INFINITY : 10.0 * log10(en) - 0.691;      // energy_to_loudness
+        p.st_out[1] = energy_to_lufs(en);
         __hip_atomic_store(reinterpret_cast<uint32_t *>(p.st_scratch + kRingTickBlocks), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
 // first part (k_tick's workgroups behind the loudness call's): the weighted energy of the ring over
 // the frames of the window that lie IN FRONT of this call — which the call does not touch, so these workgroups run beside it.
-// One run of ring elements with at most one wrap, like k_ring_energy (ss_loudness.hip); block r of `blocks` leaves its partial
+// ring_sumsq over all these workgroups' threads, like k_ring_energy (ss_loudness.hip); block r of `blocks` leaves its partial
 // sum in scratch[r] and counts itself in behind it.
 __device__ __forceinline__ void ring_window_partial(const TdParams &p, uint32_t r)
 {
     __shared__ double red[kTdSplitWaves];
     const uint32_t stride = p.st_blocks * 64u * kTdSplitWaves;
-    const uint32_t tid = r * 64u * kTdSplitWaves + threadIdx.x;
-    const uint32_t C = p.channels;
-    const uint32_t ring_elems = (uint32_t)(p.ring_frames * C);
-    const uint32_t cstep = stride % C;
-    uint32_t c = tid % C;
-    double acc = 0.0;
-    uint32_t i = tid;
-    for (; i + 3u * stride < p.st_old_total; i += 4u * stride) {
-        double y[4], w[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            uint32_t e = p.st_begin_elem + i + (uint32_t)q * stride;
-            if (e >= ring_elems) e -= ring_elems;
-            y[q] = p.ring[e];
-            w[q] = p.st_weights[c];
-            c += cstep; if (c >= C) c -= C;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc = w[q] != 0.0 ? fma(w[q] * y[q], y[q], acc) : acc;      // (weight 0: the crate does not filter that channel)
-    }
-    for (; i < p.st_old_total; i += stride) {
-        uint32_t e = p.st_begin_elem + i;
-        if (e >= ring_elems) e -= ring_elems;
-        const double y = p.ring[e];
-        const double wc = p.st_weights[c];
-        acc = wc != 0.0 ? fma(wc * y, y, acc) : acc;
-        c += cstep; if (c >= C) c -= C;
-    }
+    double acc = ring_sumsq(p.ring, (uint32_t)(p.ring_frames * p.channels), p.channels, p.st_begin_elem, p.st_old_total,
+                            r * 64u * kTdSplitWaves + threadIdx.x, stride, p.st_weights, 0.0);
     for (int d = 32; d >= 1; d >>= 1) acc += __shfl_down(acc, d, 64);
     if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = acc;
     __syncthreads();
