@@ -599,6 +599,42 @@ int ss_batch_render_spectrum(ss_batch *b, uint32_t cols, int gain_mode, float ga
  * the result. */
 int ss_batch_set_columns_gain(ss_batch *b, int gain_mode, float gain_db);
 int ss_batch_download_spectrum_columns(ss_batch *b, uint32_t stream, float *out, size_t cap_floats);
+/* One curve per stream instead of one row per window: the long-term average spectrum and the peak-hold spectrum of every
+ * (stream s, fft channel r), reduced on the device from the rows a pass left — the v_w that ss_batch_download_fft returns, dB with
+ * the pink compensation — over the stream's own windows w < n_windows_s (ss_batch_stream_shape for ragged batches; rows behind
+ * that count are never read).  For retained bin i:
+ *   - a NaN value is skipped: a refused window's row is all NaN and drops out of every bin of its row, and of no other row; an
+ *     infinity counts as a value;
+ *   - windows_counted[r] = the values not skipped at bin 0;
+ *   - max_db[i] = the largest counted v_w, bit for bit the f32 that was stored;
+ *   - mean_db[i] = the power mean (float)(10 log10((1 / n) sum_w 10^(v_w / 10))), n the values counted at bin i: powers formed in
+ *     f32 (exp2f(v log2(10) / 10)), summed in f64, the logarithm taken in f64;
+ *   - nothing counted (no window, or every window refused): mean_db = max_db = NaN, count 0.
+ * The sums have one fixed order (windows by index, in chunks that are added by index; streams by index for the corpus form; no
+ * floating-point atomics): two reductions of the same rows agree bit for bit, mean_db included.
+ * Device memory (sums, means, maxima and counts per bin of every stream: 20 bytes per bin, 70 MB for 1024 stereo streams at
+ * fft_n = 4096) is allocated at a batch's first ss_batch_spectrum_stats: a batch that never calls it allocates and launches
+ * exactly what it did before.
+ * Status codes: a batch without SS_BATCH_FFT or with SS_BATCH_FFT_COLUMNS (no rows), and a download or the corpus form before
+ * the first reduction, SS_ERR_INVALID_MODE; a null batch or a bad stream index SS_ERR_INVALID_ARG.  n_windows == 0 is valid:
+ * every result is NaN with count 0.
+ * after ss_batch_run: reduce every stream's rows; queued on the batch's stream like ss_batch_render_spectrum, nothing is copied
+ * or waited for */
+int ss_batch_spectrum_stats(ss_batch *b);
+/* one stream: mean_db / max_db are [fft_channels][n_bins] f32 (either may be NULL), windows_counted is [fft_channels] (may be
+ * NULL); cap_floats < fft_channels * n_bins, or cap_channels < fft_channels with windows_counted given: SS_ERR_CAPACITY.  Waits
+ * for the batch's stream. */
+int ss_batch_download_spectrum_stats(ss_batch *b, uint32_t stream, float *mean_db, float *max_db, size_t cap_floats,
+                                     uint32_t *windows_counted, uint32_t cap_channels);
+/* the whole batch pooled, from the last reduction's per-stream sums: the same rule on the f64 power sums and counts of all streams
+ * added up — every counted window of every stream weighs the same — max_db the maximum over the streams, windows_counted[r] the
+ * u64 total of the streams' counts.  One more small launch; waits. */
+int ss_batch_corpus_spectrum(ss_batch *b, float *mean_db, float *max_db, size_t cap_floats,
+                             uint64_t *windows_counted, uint32_t cap_channels);
+/* verification utility: how ss_batch_spectrum_stats cuts this batch's windows — `chunks` runs of `chunk_windows` consecutive
+ * windows per stream (either may be NULL); chunks > 1: partial sums per run, added in run order by a second launch (one long file);
+ * chunks == 1: one launch (many streams).  The results depend on it in the last bits of the f64 sums only. */
+int ss_batch_spectrum_stats_plan(const ss_batch *b, uint32_t *chunks, uint32_t *chunk_windows);
 /* [stream][cols][2] f32 (min, max) of the decimation bins x_min <= i < x_max */
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max);
 int ss_batch_download_waveform_columns(ss_batch *b, uint32_t stream, float *out, size_t cap_floats);

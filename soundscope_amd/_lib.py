@@ -48,6 +48,7 @@ SYMBOLS = [
     "ss_meter_bank_add_ragged", "ss_meter_bank_add_ragged_pcm", "ss_meter_bank_add_ragged_device",
     "ss_meter_bank_reset", "ss_meter_bank_read", "ss_meter_bank_peaks", "ss_meter_bank_histograms",
     "ss_meter_bank_spectrum_enable", "ss_meter_bank_spectrum_layout", "ss_meter_bank_spectrum", "ss_meter_bank_spectrum_columns",
+    "ss_batch_spectrum_stats", "ss_batch_download_spectrum_stats", "ss_batch_corpus_spectrum", "ss_batch_spectrum_stats_plan",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -262,6 +263,10 @@ def _bind(lib):
         "ss_meter_bank_spectrum_layout": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f64p, f64p, C.c_uint32]),
         "ss_meter_bank_spectrum": (C.c_int, [vp, f32p, C.c_size_t, C.POINTER(C.c_int32), C.c_uint32]),
         "ss_meter_bank_spectrum_columns": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_float, f32p, C.c_size_t, C.POINTER(C.c_int32), C.c_uint32]),
+        "ss_batch_spectrum_stats": (C.c_int, [vp]),
+        "ss_batch_download_spectrum_stats": (C.c_int, [vp, C.c_uint32, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32]),
+        "ss_batch_corpus_spectrum": (C.c_int, [vp, f32p, f32p, C.c_size_t, u64p, C.c_uint32]),
+        "ss_batch_spectrum_stats_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

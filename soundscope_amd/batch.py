@@ -192,6 +192,40 @@ class Batch:
         _check(L.lib().ss_batch_download_spectrum_columns(self._h, stream, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
         return out
 
+    # -- one curve per stream: long-term average (power mean) and peak-hold spectrum over the stream's own windows
+    def spectrum_stats(self):
+        """Queue the reduction of every stream's rows behind run() (no copy, no wait)."""
+        _check(L.lib().ss_batch_spectrum_stats(self._h))
+
+    @property
+    def spectrum_stats_plan(self):
+        """(chunks, chunk_windows): how spectrum_stats() cuts the windows of this batch (chunks > 1: partial sums and a second launch)."""
+        c, w = C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_batch_spectrum_stats_plan(self._h, C.byref(c), C.byref(w)))
+        return c.value, w.value
+
+    def _stats_triple(self, count_dtype):
+        lay = self.layout
+        shape = (lay.fft_channels, lay.n_bins)
+        return np.empty(shape, np.float32), np.empty(shape, np.float32), np.empty(lay.fft_channels, count_dtype)
+
+    def spectrum_stats_of(self, stream):
+        """(mean_db[R][n_bins], max_db[R][n_bins], windows_counted[R]) of one stream after spectrum_stats(): NaN values (refused
+        windows) are skipped; nothing counted gives NaN with count 0."""
+        mean, mx, cnt = self._stats_triple(np.uint32)
+        fp = C.POINTER(C.c_float)
+        _check(L.lib().ss_batch_download_spectrum_stats(self._h, stream, mean.ctypes.data_as(fp), mx.ctypes.data_as(fp), mean.size,
+                                                        cnt.ctypes.data_as(C.POINTER(C.c_uint32)), cnt.size))
+        return mean, mx, cnt
+
+    def corpus_spectrum(self):
+        """The same triple for the whole batch pooled (every counted window of every stream weighs the same; counts are u64)."""
+        mean, mx, cnt = self._stats_triple(np.uint64)
+        fp = C.POINTER(C.c_float)
+        _check(L.lib().ss_batch_corpus_spectrum(self._h, mean.ctypes.data_as(fp), mx.ctypes.data_as(fp), mean.size,
+                                                cnt.ctypes.data_as(C.POINTER(C.c_uint64)), cnt.size))
+        return mean, mx, cnt
+
     def render_waveform(self, cols, x_min, x_max):
         _check(L.lib().ss_batch_render_waveform(self._h, cols, int(x_min), int(x_max)))
         self._render_wave_cols = cols

@@ -87,6 +87,17 @@ struct Ragged {
     DevBuf<uint32_t> windows_d, sub_d, wave_window_d;
 };
 
+// per-stream average and peak-hold spectrum (ss_batch_spectrum_stats): all of it allocated at the batch's first reduction, so a
+// batch that never asks holds none of it
+struct SpecStats {
+    bool done = false;                          // a reduction has been queued: there is something to download
+    DevBuf<double> sums, part_sums;             // SpecStatsParams' arrays of these names
+    DevBuf<float> mean, max, part_max;
+    DevBuf<uint32_t> counts, part_counts;
+    DevBuf<float> corpus_mean, corpus_max;      // ss_batch_corpus_spectrum: [fft_channels][fft_bin_stride]
+    DevBuf<unsigned long long> corpus_counts;   // [fft_channels]
+};
+
 }  // namespace
 
 struct ss_batch {
@@ -127,6 +138,7 @@ struct ss_batch {
     DevBuf<uint32_t> col_start;
     uint32_t render_cols = 0, render_wave_cols = 0;
     Columns cols;
+    SpecStats stats;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
     int tp_arith = SS_TP_ARITH_F32;   // SS_TP_ARITH_*: the reference's width unless the caller opts into the f16 split
@@ -235,6 +247,28 @@ ssk::WaveParams batch_wave_params(const ss_batch *b)
     p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * c.channels; p.n_samples = c.frames_per_stream * c.channels;
     p.n_streams = c.n_streams; p.window = b->wave_window; p.out = b->wave.p; p.out_stride = (uint64_t)2 * b->wave_window;
     if (b->ragged.on) { p.samples_of = b->ragged.wave_samples_d.p; p.window_of = b->ragged.wave_window_d.p; }
+    return p;
+}
+
+// how ss_batch_spectrum_stats cuts this batch's rows (fixed with the shape)
+ssk::SpecStatsPlan batch_stats_plan(const ss_batch *b)
+{
+    return ssk::plan_spectrum_stats(b->cfg.n_streams * b->lay.fft_channels, b->lay.fft_bin_stride, b->lay.n_windows);
+}
+
+// the reduction of the rows a pass left (ss_batch_spectrum_stats and what reads its results): the rows, the ragged window counts,
+// the plan, the batch's result arrays
+ssk::SpecStatsParams batch_stats_params(const ss_batch *b)
+{
+    const ss_batch_layout &L = b->lay;
+    const SpecStats &st = b->stats;
+    ssk::SpecStatsParams p{};
+    p.rows = b->fft.p; p.bin_stride = L.fft_bin_stride; p.n_bins = L.n_bins;
+    p.n_streams = b->cfg.n_streams; p.fft_ch = L.fft_channels; p.n_windows = L.n_windows;
+    p.windows_of = b->ragged.on ? b->ragged.windows_d.p : nullptr;
+    p.plan = batch_stats_plan(b);
+    p.sums = st.sums.p; p.mean = st.mean.p; p.max = st.max.p; p.counts = st.counts.p;
+    p.part_sums = st.part_sums.p; p.part_max = st.part_max.p; p.part_counts = st.part_counts.p;
     return p;
 }
 
@@ -1121,6 +1155,87 @@ int ss_batch_download_spectrum_columns(ss_batch *b, uint32_t stream, float *out,
     const size_t per = (size_t)b->lay.n_windows * b->lay.fft_channels * b->render_cols;
     if (cap < per) return SS_ERR_CAPACITY;
     return fetch(b, out, b->render_spec.p + (size_t)stream * per, per);
+}
+
+// ---- per-stream average and peak-hold spectrum ------------------------------------------------------------------
+// a batch whose passes leave rows to reduce (columns-only batches store none)
+static bool has_spectrum_rows(const ss_batch *b) { return (b->cfg.flags & SS_BATCH_FFT) && !b->cols.on; }
+
+int ss_batch_spectrum_stats(ss_batch *b)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (!has_spectrum_rows(b)) return SS_ERR_INVALID_MODE;
+    SpecStats &st = b->stats;
+    const size_t per_stream = (size_t)b->lay.fft_channels * b->lay.fft_bin_stride, all = per_stream * b->cfg.n_streams;
+    const ssk::SpecStatsPlan plan = batch_stats_plan(b);
+    const size_t parts = plan.chunks > 1 ? all * plan.chunks : 0;
+    // (the shape of a batch is fixed at create, so only the first call allocates)
+    HIPCHK(st.sums.ensure(all)); HIPCHK(st.mean.ensure(all)); HIPCHK(st.max.ensure(all)); HIPCHK(st.counts.ensure(all));
+    HIPCHK(st.part_sums.ensure(parts)); HIPCHK(st.part_max.ensure(parts)); HIPCHK(st.part_counts.ensure(parts));
+    HIPCHK(st.corpus_mean.ensure(per_stream)); HIPCHK(st.corpus_max.ensure(per_stream)); HIPCHK(st.corpus_counts.ensure(b->lay.fft_channels));
+    HIPCHK(ssk::launch_spectrum_stats(batch_stats_params(b), b->stream));
+    st.done = true;
+    return SS_OK;
+}
+
+int ss_batch_spectrum_stats_plan(const ss_batch *b, uint32_t *chunks, uint32_t *chunk_windows)
+{
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (!has_spectrum_rows(b)) return SS_ERR_INVALID_MODE;
+    const ssk::SpecStatsPlan plan = batch_stats_plan(b);
+    if (chunks) *chunks = plan.chunks;
+    if (chunk_windows) *chunk_windows = plan.chunk_windows;
+    return SS_OK;
+}
+
+// the compact [fft_channels][n_bins] copies of two [fft_channels][fft_bin_stride] device arrays (either host pointer may be null),
+// queued on the batch's stream
+static int fetch_stats_rows(ss_batch *b, float *mean_db, float *max_db, const float *mean_d, const float *max_d)
+{
+    const ss_batch_layout &L = b->lay;
+    const size_t row = (size_t)L.n_bins * sizeof(float), pitch = (size_t)L.fft_bin_stride * sizeof(float);
+    if (!row) return SS_OK;
+    if (mean_db) HIPCHK(hipMemcpy2DAsync(mean_db, row, mean_d, pitch, row, L.fft_channels, hipMemcpyDeviceToHost, b->stream));
+    if (max_db) HIPCHK(hipMemcpy2DAsync(max_db, row, max_d, pitch, row, L.fft_channels, hipMemcpyDeviceToHost, b->stream));
+    return SS_OK;
+}
+
+int ss_batch_download_spectrum_stats(ss_batch *b, uint32_t stream, float *mean_db, float *max_db, size_t cap_floats,
+                                     uint32_t *windows_counted, uint32_t cap_channels)
+{
+    SS_ON_DEVICE(b);
+    if (!b || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+    if (!has_spectrum_rows(b) || !b->stats.done) return SS_ERR_INVALID_MODE;
+    const ss_batch_layout &L = b->lay;
+    if (cap_floats < (size_t)L.fft_channels * L.n_bins || (windows_counted && cap_channels < L.fft_channels)) return SS_ERR_CAPACITY;
+    const size_t at = (size_t)stream * L.fft_channels * L.fft_bin_stride;
+    int rc = fetch_stats_rows(b, mean_db, max_db, b->stats.mean.p + at, b->stats.max.p + at);
+    if (rc) return rc;
+    // the count of a channel is bin 0's: one u32 of every [fft_bin_stride] row
+    if (windows_counted && L.fft_bin_stride)
+        HIPCHK(hipMemcpy2DAsync(windows_counted, sizeof(uint32_t), b->stats.counts.p + at, (size_t)L.fft_bin_stride * sizeof(uint32_t),
+                                sizeof(uint32_t), L.fft_channels, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return SS_OK;
+}
+
+int ss_batch_corpus_spectrum(ss_batch *b, float *mean_db, float *max_db, size_t cap_floats, uint64_t *windows_counted, uint32_t cap_channels)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (!has_spectrum_rows(b) || !b->stats.done) return SS_ERR_INVALID_MODE;
+    const ss_batch_layout &L = b->lay;
+    if (cap_floats < (size_t)L.fft_channels * L.n_bins || (windows_counted && cap_channels < L.fft_channels)) return SS_ERR_CAPACITY;
+    SpecStats &st = b->stats;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the pooled counts are copied out as they are");
+    HIPCHK(ssk::launch_spectrum_stats_corpus(batch_stats_params(b), st.corpus_mean.p, st.corpus_max.p, st.corpus_counts.p, b->stream));
+    int rc = fetch_stats_rows(b, mean_db, max_db, st.corpus_mean.p, st.corpus_max.p);
+    if (rc) return rc;
+    if (windows_counted && L.fft_bin_stride)
+        HIPCHK(hipMemcpyAsync(windows_counted, st.corpus_counts.p, L.fft_channels * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return SS_OK;
 }
 
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max)

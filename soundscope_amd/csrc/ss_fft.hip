@@ -849,7 +849,10 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
         }
         float *o_mid = outp + (size_t)(w - w_begin) * out_win_stride;
         fft4096_epilogue<true, COLS>(xbuf, t, p.first_bin, p.n_bins, p.db_offset, offp, o_mid, o_mid + p.bin_stride, true, soff, colbuf, coltab, p.col_bins);
-        if (__builtin_expect(zrow_m || zrow_d, 0)) {
+        // Level 0 is a row of zeros — or of zeros and NaN, which fmaxf skipped.  A NaN sample makes every bin of the transform NaN and
+        // the window is refused like any other that holds one: the NaN rows stand, no floor goes over them.  (One published bin, the
+        // same for every thread: the branch is workgroup-uniform; xbuf is not rewritten before the loop-end barrier.)
+        if (__builtin_expect(zrow_m || zrow_d, 0) && xbuf[SPEC_POS(p.first_bin)].x == xbuf[SPEC_POS(p.first_bin)].x) {
             if (!COLS) fft4096_floor_rows(t, p.n_bins, p.db_offset, p.offpink, o_mid, o_mid + p.bin_stride, zrow_m, zrow_d);
             else fft4096_floor_columns(t, p.n_bins, p.db_offset, p.offpink, colbuf, p.bin_col, p.col_init, p.cols, zrow_m, zrow_d);
         }

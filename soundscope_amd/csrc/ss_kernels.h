@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -112,6 +112,33 @@ SpecPlan plan_spectrum(uint32_t n, uint32_t channels, uint32_t hop, uint32_t n_s
 // p: n_streams / n_windows as planned, windows_per_block = plan.windows_per_block
 hipError_t launch_spectrum(const SpecPlan &plan, const FftBatchParams &p, hipStream_t s);
 const char *spectrum_kernel_name(SpecKernel k);         // as rocprofv3 prints it, without template arguments
+
+// ---- spectrum statistics (ss_spectrum_stats.hip): every (stream, fft_channel)'s rows reduced over the stream's windows ------------
+struct SpecStatsPlan {
+    uint32_t slices = 1;             // waves side by side on a row: 64 groups of four bins each
+    uint32_t chunk_windows = 1;      // consecutive windows a wave walks
+    uint32_t chunks = 1;             // chunks per stream slot; > 1: partial sums per chunk and a second launch that adds them in chunk order
+};
+// the one decision for every shape: pairs = n_streams x fft_channels, n_windows of the stream slot
+SpecStatsPlan plan_spectrum_stats(uint32_t pairs, uint32_t bin_stride, uint32_t n_windows);
+struct SpecStatsParams {
+    const float *rows;               // [stream][n_windows][fft_ch][bin_stride] f32 dB: what a pass left (FftBatchParams::out)
+    uint32_t bin_stride, n_bins;
+    uint32_t n_streams, fft_ch, n_windows;
+    const uint32_t *windows_of;      // ragged batches: windows of each stream (nullable = n_windows for all); rows behind it are never read
+    SpecStatsPlan plan;
+    // results, [stream][fft_ch][bin_stride] each; the row padding behind n_bins holds (0, NaN, NaN, 0)
+    double *sums;                    // f64 sums of the counted values' powers 10^(v / 10)
+    float *mean, *max;               // 10 log10(sum / count) and the largest counted value, NaN where nothing was counted
+    uint32_t *counts;                // values counted (not NaN) per bin
+    // plan.chunks > 1: [stream][fft_ch][chunk][bin_stride]
+    double *part_sums;
+    float *part_max;
+    uint32_t *part_counts;
+};
+hipError_t launch_spectrum_stats(const SpecStatsParams &p, hipStream_t s);
+// the batch pooled from p.sums / p.max / p.counts, streams in index order: mean / max [fft_ch][bin_stride], counts [fft_ch] (bin 0's)
+hipError_t launch_spectrum_stats_corpus(const SpecStatsParams &p, float *mean, float *max, unsigned long long *counts, hipStream_t s);
 
 // ---- time domain ------------------------------------------------------------
 struct TdConst {                 // one per (rate, true-peak factor), device resident
