@@ -520,6 +520,63 @@ int ss_meter_bank_spectrum(ss_meter_bank *m, float *rows, size_t cap_floats, int
 int ss_meter_bank_spectrum_columns(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db,
                                    float *out, size_t cap_floats, int32_t *status, uint32_t cap_rows);
 
+/* Tracked spectra of a bank: the two curves every real-time analyser draws over the instantaneous row — an
+ * exponentially averaged trace and a peak-hold trace that falls back after a hold time — kept on the device for every row of
+ * every stream and advanced by ss_meter_bank_spectrum_track on each stream's OWN clock.  The live counterpart of
+ * ss_batch_spectrum_stats.  Not in the reference.
+ *  Definitions.  rate: the bank's sample rate.  v[i]: what ss_meter_bank_spectrum would return at this moment for row (s, r), bin
+ *  i (f32 dBFS before pink compensation).  fed_s: stream s's own frame counter, the one that places its window (what uniform and
+ *  ragged adds gave that stream).  Every row keeps last, the fed_s of its last accepted update, and updates, a u32 count of its
+ *  accepted updates since its reset (it stays at 0xFFFFFFFF).  For one _track call, delta = fed_s - last.
+ *  - Which rows a _track call touches.  A row with state and delta == 0 is not touched at all — nothing arrived for that stream,
+ *    its state stays byte for byte ("a stream given nothing keeps its window").  A row whose status at this moment is a refusal
+ *    (SS_ERR_NAN, SS_ERR_INFINITY, SS_ERR_SCALING) is not touched either: last stays, so the next accepted update decays over the
+ *    whole gap.  Rows are independent: a refused channel row leaves the other rows of its stream alone.
+ *  - First accepted update (updates == 0; delta plays no part): P[i] = p[i], peak[i] = v[i], age[i] = 0 for every bin.
+ *  - Average.  p[i] = exp2f(v[i] * log2(10)/10), the f32 power as ss_batch_spectrum_stats forms it, widened to f64;
+ *    alpha = -expm1(-delta / (rate * average_tau_s)) in f64 (exactly 1 for average_tau_s == 0); P[i] += alpha * (p[i] - P[i]) in
+ *    f64; avg_db[i] = (float)(10 log10 P[i]), the logarithm in f64.
+ *  - Peak hold.  age[i] counts frames in a u32 and stays at 0xFFFFFFFF; hold_frames = (uint64_t)(hold_s * rate + 0.5), and the peak
+ *    never falls for hold_s = +inf.  hold_db[i] = (float)((double)peak - decay_db_per_s * ((double)over / (double)rate)) with
+ *    over = max(0, age - hold_frames): f64, in exactly that order, without a fused multiply-add — the same IEEE expression on
+ *    the host gives the same bits.  Update: age = sat(age + delta); D = hold_db of the new age; v[i] >= D captures (peak = v[i],
+ *    age = 0), otherwise peak and the new age stay.  What is reported afterwards is hold_db of the state as it stands.
+ *  - ss_meter_bank_reset resets the meters, not the display: it leaves the tracked state alone as it leaves the history alone.
+ *    ss_meter_bank_spectrum_enable, with either argument, drops the tracked state and turns tracking off.
+ *    ss_meter_bank_spectrum and _columns neither advance nor read the state: their results and launches are unchanged, and a bank
+ *    that never enables tracking allocates and launches exactly what it did before.
+ *  - Device memory: 16 bytes per bin (P f64, peak f32, age u32), bins rounded up to a multiple of four per row, plus one row
+ *    buffer of the transform — 20 bytes per bin, 6820 bins at 48 kHz: about 224 MB of state and 56 MB of rows for 1024 stereo
+ *    streams.
+ *  - Status codes: before _track_enable SS_ERR_INVALID_MODE; a `cap` too small SS_ERR_CAPACITY; a bad stream index, cols outside
+ *    1 .. 512 or an unknown gain mode SS_ERR_INVALID_ARG. */
+typedef struct ss_spectrum_ballistics {
+    double average_tau_s;    /* time constant of the exponential POWER average, >= 0, finite; 0: the average is the newest row */
+    double hold_s;           /* how long a captured peak stays before it falls, >= 0; +inf: held for ever */
+    double decay_db_per_s;   /* fall rate once the hold has run out, >= 0, finite */
+} ss_spectrum_ballistics;   /* 24 bytes */
+/* cfg != NULL: empty state for every row (enabling again, with the same or new parameters, starts from empty state);
+ * SS_ERR_INVALID_ARG for a negative or NaN parameter, an infinite average_tau_s or decay_db_per_s, then SS_ERR_INVALID_MODE
+ * without the spectrum history — both before anything is allocated.  cfg == NULL: tracking off, the state freed. */
+int ss_meter_bank_spectrum_track_enable(ss_meter_bank *m, const ss_spectrum_ballistics *cfg);
+/* advances every row's state to the windows as they stand: the transform's row launch into a device buffer and one elementwise
+ * launch behind it.  Only queued: no copy, no wait. */
+int ss_meter_bank_spectrum_track(ss_meter_bank *m);
+/* empties the listed streams' rows (streams == NULL: all): updates = 0, the next accepted update seeds them */
+int ss_meter_bank_spectrum_track_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count);
+/* avg_db and hold_db as rows [stream][row][n_bins] f32, before pink compensation like ss_meter_bank_spectrum's (either may be
+ * NULL: that curve is neither formed nor copied), and updates[stream * rows + row] (may be NULL).  A row with updates == 0
+ * reads all NaN.  Waits; one launch and one copy. */
+int ss_meter_bank_spectrum_tracked(ss_meter_bank *m, float *avg_rows, float *hold_rows, size_t cap_floats,
+                                   uint32_t *updates, uint32_t cap_rows);
+/* both curves reduced on the device to `cols` chart columns by ss_meter_bank_spectrum_columns' rule applied to
+ * x = (float)((double)curve[i] + pink[i]): max over the column of clamp(x + gain, -100, 0) in f32, NaN for a column without a
+ * bin or a row without state; gain_mode as there.  avg_cols / hold_cols are [stream][row][cols] (either may be NULL), updates
+ * as above; the full rows never leave the device.  Waits; one launch (two with SS_GAIN_REFERENCE) and one copy. */
+int ss_meter_bank_spectrum_tracked_columns(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db,
+                                           float *avg_cols, float *hold_cols, size_t cap_floats,
+                                           uint32_t *updates, uint32_t cap_rows);
+
 /* ------------------------------------------------------------------------- *
  *  Multi-GPU: one process per GPU, streams sharded over the ranks, and exactly ONE exchange —
  *  the SUM all-reduce of the two 1000-bin u64 histograms for the corpus-level integrated-LUFS gate

@@ -48,6 +48,8 @@ SYMBOLS = [
     "ss_meter_bank_add_ragged", "ss_meter_bank_add_ragged_pcm", "ss_meter_bank_add_ragged_device",
     "ss_meter_bank_reset", "ss_meter_bank_read", "ss_meter_bank_peaks", "ss_meter_bank_histograms",
     "ss_meter_bank_spectrum_enable", "ss_meter_bank_spectrum_layout", "ss_meter_bank_spectrum", "ss_meter_bank_spectrum_columns",
+    "ss_meter_bank_spectrum_track_enable", "ss_meter_bank_spectrum_track", "ss_meter_bank_spectrum_track_reset",
+    "ss_meter_bank_spectrum_tracked", "ss_meter_bank_spectrum_tracked_columns",
     "ss_batch_spectrum_stats", "ss_batch_download_spectrum_stats", "ss_batch_corpus_spectrum", "ss_batch_spectrum_stats_plan",
 ]
 
@@ -115,6 +117,10 @@ class MeterReading(C.Structure):
     _fields_ = [("momentary", C.c_double), ("shortterm", C.c_double), ("integrated", C.c_double),
                 ("loudness_range", C.c_double), ("true_peak", C.c_double * 2), ("sample_peak", C.c_double * 2),
                 ("frames", C.c_uint64)]
+
+
+class SpectrumBallistics(C.Structure):
+    _fields_ = [("average_tau_s", C.c_double), ("hold_s", C.c_double), ("decay_db_per_s", C.c_double)]
 
 
 class BatchLayout(C.Structure):
@@ -263,6 +269,12 @@ def _bind(lib):
         "ss_meter_bank_spectrum_layout": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f64p, f64p, C.c_uint32]),
         "ss_meter_bank_spectrum": (C.c_int, [vp, f32p, C.c_size_t, C.POINTER(C.c_int32), C.c_uint32]),
         "ss_meter_bank_spectrum_columns": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_float, f32p, C.c_size_t, C.POINTER(C.c_int32), C.c_uint32]),
+        "ss_meter_bank_spectrum_track_enable": (C.c_int, [vp, C.POINTER(SpectrumBallistics)]),
+        "ss_meter_bank_spectrum_track": (C.c_int, [vp]),
+        "ss_meter_bank_spectrum_track_reset": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_uint32]),
+        "ss_meter_bank_spectrum_tracked": (C.c_int, [vp, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32]),
+        "ss_meter_bank_spectrum_tracked_columns": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_float, f32p, f32p, C.c_size_t,
+                                                             C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_batch_spectrum_stats": (C.c_int, [vp]),
         "ss_batch_download_spectrum_stats": (C.c_int, [vp, C.c_uint32, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_batch_corpus_spectrum": (C.c_int, [vp, f32p, f32p, C.c_size_t, u64p, C.c_uint32]),

@@ -360,6 +360,37 @@ hipError_t launch_bank_history_append_ragged(float *hist, const float *pcm, uint
                                              uint32_t channels, hipStream_t s);
 hipError_t launch_meter_bank_spectrum(const BankSpectrumParams &p, bool columns, hipStream_t s);
 
+// tracked bank spectra (ss_bank_spectrum_track.hip): an exponentially averaged and a peak-hold curve per row, advanced from the rows
+// and statuses launch_meter_bank_spectrum(columns = false) has stored, on each stream's own frame counter
+struct BankTrackRow { uint64_t last; uint32_t updates; uint32_t pad; };      // a row's clock: fed at its last accepted update; their count
+struct BankTrackParams {
+    const float *rows;               // [row][n_bins] f32 dB, rows n_bins floats apart (the update only)
+    const int32_t *status;           // [row] (the update only)
+    uint64_t fed;                    // the bank-wide frame counter
+    const uint64_t *ahead;           // [stream], nullable: stream s's own counter is fed + ahead[s]
+    uint32_t n_streams, rows_per_stream, n_bins;
+    uint32_t bin_stride;             // n_bins rounded up to a multiple of four
+    unsigned char *state;            // [row]: P f64 [bin_stride], peak f32 [bin_stride], age u32 [bin_stride] — 16 * bin_stride bytes
+    const BankTrackRow *meta_in;     // [row]: the clocks as they stand
+    BankTrackRow *meta_out;          // [row]: the update writes EVERY row's clock here (the host swaps the two; read-outs: unused)
+    double rate, average_tau_s, decay_db_per_s;
+    uint64_t hold_frames;            // (uint64_t)(hold_s * rate + 0.5); ~0: the peak never falls
+};
+// the columns read-out: launch_meter_bank_spectrum's column tables and gain; avg / hold [row][cols] and updates [row] are nullable
+struct BankTrackColumns {
+    const double *pink; const uint16_t *bin_col; const float *col_init;
+    const double *integrated; uint32_t integrated_stride;
+    uint32_t cols; float gain_db;
+    float *avg, *hold; uint32_t *updates;
+};
+hipError_t launch_bank_spectrum_track(const BankTrackParams &p, hipStream_t s);
+// the listed streams' rows lose their state (streams == nullptr: streams 0 .. count - 1); meta: the clocks as they stand
+hipError_t launch_bank_spectrum_track_reset(BankTrackRow *meta, const uint32_t *streams, uint32_t count, uint32_t rows_per_stream,
+                                            hipStream_t s);
+// avg / hold: [row][n_bins] f32 dB (either nullable), updates [row] (nullable)
+hipError_t launch_bank_spectrum_tracked_rows(const BankTrackParams &p, float *avg, float *hold, uint32_t *updates, hipStream_t s);
+hipError_t launch_bank_spectrum_tracked_columns(const BankTrackParams &p, const BankTrackColumns &c, hipStream_t s);
+
 // ---- waveform ---------------------------------------------------------------
 struct WaveParams {
     const float *pcm; uint64_t stream_stride; uint64_t n_samples; // interleaved samples per stream

@@ -36,6 +36,16 @@ struct ss_meter_bank {
     ssh::DevBuf<float> spec_col_init;      // spec_cols
     uint32_t spec_cols = 0;
     ssh::PinBuf<unsigned char> spec_pin;   // page-locked results: floats, then the statuses
+    // tracked spectra (ss_meter_bank_spectrum_track_enable): per row an averaged and a peak-hold curve, advanced behind the
+    // transform's row launch.  A row's clock is kept twice; an update reads trk_meta[trk_cur] and writes the other (ssk::BankTrackParams)
+    bool trk_on = false;
+    ss_spectrum_ballistics trk_cfg{};
+    ssh::DevBuf<unsigned char> trk_state;  // [n][rows]: 16 bytes per bin at a stride of n_bins rounded up to four
+    ssh::DevBuf<ssk::BankTrackRow> trk_meta;   // [2][n][rows]
+    uint32_t trk_cur = 0;
+    ssh::DevBuf<float> trk_rows;           // [n][rows][n_bins]: the row launch of an update
+    ssh::DevBuf<int32_t> trk_status;       // [n][rows]
+    ssh::DevBuf<unsigned char> trk_out;    // a read-out: the curves asked for, then the update counts
 };
 
 static_assert(sizeof(ss_meter_reading) == 72 && sizeof(ssk::MeterReading) == sizeof(ss_meter_reading), "ss_meter_reading layout");
@@ -241,6 +251,45 @@ static_assert(SS_BANK_SPECTRUM_N == ssk::kBankSpecN, "one window length");
 
 uint32_t spec_rows(const ss_meter_bank *m) { return m->meter.channels == 2 ? 2u : m->meter.channels; }
 
+// the transform's launch parameters for the windows as they stand (rows; the caller adds what columns need)
+ssk::BankSpectrumParams spectrum_params(const ss_meter_bank *m, float *out, int32_t *status)
+{
+    ssk::BankSpectrumParams q{};
+    q.f = one_window_fft(ssk::plan_spectrum(SS_BANK_SPECTRUM_N, m->meter.channels, kOneWindowHop, 1, 1), *m->ft, *m->bt);
+    q.hist = m->spec_hist.p;
+    q.start = (uint32_t)((m->spec_fed - SS_BANK_SPECTRUM_N) & (SS_BANK_SPECTRUM_N - 1));
+    q.ahead = m->spec_ahead.p;
+    q.n_streams = m->meter.n; q.channels = m->meter.channels; q.rows = spec_rows(m);
+    q.status = status; q.out = out;
+    return q;
+}
+
+// the chart-column tables of `cols` columns on the device (kept until another count is asked for)
+int column_tables(ss_meter_bank *m, uint32_t cols)
+{
+    if (cols == m->spec_cols) return SS_OK;
+    std::vector<uint16_t> bc(m->bt->count);
+    std::vector<float> cinit(cols, std::numeric_limits<float>::quiet_NaN());
+    for (size_t i = 0; i < bc.size(); i++) {
+        bc[i] = (uint16_t)spectrum_column_of(m->bt->chart_x[i], cols);
+        cinit[bc[i]] = -std::numeric_limits<float>::infinity();
+    }
+    HIPCHK(m->spec_bin_col.upload(bc));
+    HIPCHK(m->spec_col_init.upload(cinit));
+    m->spec_cols = cols;
+    return SS_OK;
+}
+
+// SS_GAIN_REFERENCE: every stream's integrated loudness after the last add — the readings read() returns, on the device
+int reference_gain(ss_meter_bank *m, const double **integrated, uint32_t *stride)
+{
+    HIPCHK(ssk::launch_meter_bank_readings(m->meter.bank_params(), m->readings.p, m->stream));
+    static_assert(sizeof(ssk::MeterReading) % sizeof(double) == 0, "readings as doubles");
+    *integrated = &m->readings.p[0].integrated;
+    *stride = sizeof(ssk::MeterReading) / sizeof(double);
+    return SS_OK;
+}
+
 // the spectrum launch of every (stream, row) and one copy of its results (`per_row` floats each) and statuses into page-locked memory
 int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, float gain_db, uint32_t per_row,
                  float **vals, int32_t **status)
@@ -252,34 +301,13 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
         HIPCHK(bank_sync(m));
         HIPCHK(m->spec_pin.ensure(fbytes + sbytes));
     }
-    ssk::BankSpectrumParams q{};
-    q.f = one_window_fft(ssk::plan_spectrum(SS_BANK_SPECTRUM_N, m->meter.channels, kOneWindowHop, 1, 1), *m->ft, *m->bt);
-    q.hist = m->spec_hist.p;
-    q.start = (uint32_t)((m->spec_fed - SS_BANK_SPECTRUM_N) & (SS_BANK_SPECTRUM_N - 1));
-    q.ahead = m->spec_ahead.p;
-    q.n_streams = m->meter.n; q.channels = m->meter.channels; q.rows = R;
-    q.status = m->spec_status.p; q.out = m->spec_out.p;
+    ssk::BankSpectrumParams q = spectrum_params(m, m->spec_out.p, m->spec_status.p);
     if (columns) {
-        if (cols != m->spec_cols) {
-            std::vector<uint16_t> bc(m->bt->count);
-            std::vector<float> cinit(cols, std::numeric_limits<float>::quiet_NaN());
-            for (size_t i = 0; i < bc.size(); i++) {
-                bc[i] = (uint16_t)spectrum_column_of(m->bt->chart_x[i], cols);
-                cinit[bc[i]] = -std::numeric_limits<float>::infinity();
-            }
-            HIPCHK(m->spec_bin_col.upload(bc));
-            HIPCHK(m->spec_col_init.upload(cinit));
-            m->spec_cols = cols;
-        }
+        int rc = column_tables(m, cols);
+        if (rc) return rc;
         q.pink = m->spec_pink.p; q.bin_col = m->spec_bin_col.p; q.col_init = m->spec_col_init.p;
         q.cols = cols; q.gain_db = gain_db;
-        if (gain_mode == SS_GAIN_REFERENCE) {
-            // every stream's integrated loudness after the last add: the readings read() returns, on the device
-            HIPCHK(ssk::launch_meter_bank_readings(m->meter.bank_params(), m->readings.p, m->stream));
-            static_assert(sizeof(ssk::MeterReading) % sizeof(double) == 0, "readings as doubles");
-            q.integrated = &m->readings.p[0].integrated;
-            q.integrated_stride = sizeof(ssk::MeterReading) / sizeof(double);
-        }
+        if (gain_mode == SS_GAIN_REFERENCE && (rc = reference_gain(m, &q.integrated, &q.integrated_stride))) return rc;
     }
     HIPCHK(ssk::launch_meter_bank_spectrum(q, columns, m->stream));
     char *pin = reinterpret_cast<char *>(m->spec_pin.p);
@@ -288,6 +316,56 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
     HIPCHK(bank_sync(m));
     *vals = reinterpret_cast<float *>(pin);
     *status = reinterpret_cast<int32_t *>(pin + fbytes);
+    return SS_OK;
+}
+
+// ---- tracked spectra ---------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(ss_spectrum_ballistics) == 24, "ss_spectrum_ballistics layout");
+
+size_t track_rows_of(const ss_meter_bank *m) { return (size_t)m->meter.n * spec_rows(m); }
+
+// the tracked state is dropped: nothing on the stream still uses it afterwards
+int track_drop(ss_meter_bank *m)
+{
+    if (!m->trk_on) return SS_OK;
+    HIPCHK(bank_sync(m));
+    m->trk_on = false;
+    m->trk_state.release(); m->trk_meta.release(); m->trk_rows.release(); m->trk_status.release(); m->trk_out.release();
+    return SS_OK;
+}
+
+ssk::BankTrackParams track_params(const ss_meter_bank *m)
+{
+    const size_t rows = track_rows_of(m);
+    const double rate = (double)m->meter.rate, frames = m->trk_cfg.hold_s * rate + 0.5;
+    ssk::BankTrackParams p{};
+    p.rows = m->trk_rows.p; p.status = m->trk_status.p;
+    p.fed = m->spec_fed; p.ahead = m->spec_ahead.p;
+    p.n_streams = m->meter.n; p.rows_per_stream = spec_rows(m);
+    p.n_bins = (uint32_t)m->bt->count; p.bin_stride = (p.n_bins + 3u) & ~3u;
+    p.state = m->trk_state.p;
+    p.meta_in = m->trk_meta.p + m->trk_cur * rows;
+    p.meta_out = m->trk_meta.p + (m->trk_cur ^ 1u) * rows;
+    p.rate = rate; p.average_tau_s = m->trk_cfg.average_tau_s; p.decay_db_per_s = m->trk_cfg.decay_db_per_s;
+    p.hold_frames = frames < 18446744073709551615.0 ? (uint64_t)frames : ~0ull;      // (+inf, or beyond u64: never falls)
+    return p;
+}
+
+// a read-out's results behind its launch: `bytes` of trk_out into page-locked memory, waited for
+int track_fetch(ss_meter_bank *m, size_t bytes, unsigned char **pin)
+{
+    HIPCHK(hipMemcpyAsync(m->spec_pin.p, m->trk_out.p, bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(bank_sync(m));
+    *pin = m->spec_pin.p;
+    return SS_OK;
+}
+
+// room for a read-out of `bytes` on the device and in page-locked memory
+int track_room(ss_meter_bank *m, size_t bytes)
+{
+    if (bytes > m->trk_out.n || bytes > m->spec_pin.n) HIPCHK(bank_sync(m));
+    HIPCHK(m->trk_out.ensure(bytes));
+    HIPCHK(m->spec_pin.ensure(bytes));
     return SS_OK;
 }
 
@@ -450,6 +528,8 @@ int ss_meter_bank_spectrum_enable(ss_meter_bank *m, int enable)
 {
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
+    int rc = track_drop(m);                                                        // the tracked curves belong to the history they followed
+    if (rc) return rc;
     if (!enable) {
         HIPCHK(bank_sync(m));
         m->spec_on = false;
@@ -457,7 +537,7 @@ int ss_meter_bank_spectrum_enable(ss_meter_bank *m, int enable)
         return SS_OK;
     }
     if (20000.0f > (float)m->meter.rate / 2.0f) return SS_ERR_FREQ_LIMIT;         // get_fft's FrequencyLimit check, before any allocation
-    int rc = get_fft_tables(SS_BANK_SPECTRUM_N, &m->ft);
+    rc = get_fft_tables(SS_BANK_SPECTRUM_N, &m->ft);
     if (rc) return rc;
     rc = get_bin_tables(m->meter.rate, SS_BANK_SPECTRUM_N, &m->bt);
     if (rc) return rc;
@@ -521,6 +601,116 @@ int ss_meter_bank_spectrum_columns(ss_meter_bank *m, uint32_t cols, int gain_mod
     if (rc) return rc;
     std::memcpy(out, v, R * cols * sizeof(float));
     std::memcpy(status, st, R * sizeof(int32_t));
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_track_enable(ss_meter_bank *m, const ss_spectrum_ballistics *cfg)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!cfg) return track_drop(m);
+    if (!(cfg->average_tau_s >= 0.0) || std::isinf(cfg->average_tau_s) || !(cfg->hold_s >= 0.0) || !(cfg->decay_db_per_s >= 0.0) ||
+        std::isinf(cfg->decay_db_per_s))
+        return SS_ERR_INVALID_ARG;
+    if (!m->spec_on) return SS_ERR_INVALID_MODE;
+    int rc = track_drop(m);                                                        // enabling again starts from empty state
+    if (rc) return rc;
+    const size_t rows = track_rows_of(m), nb = m->bt->count, stride = (nb + 3u) & ~(size_t)3u;
+    HIPCHK(m->trk_state.alloc(rows * stride * 16u));
+    HIPCHK(m->trk_meta.alloc(2 * rows));
+    HIPCHK(m->trk_rows.alloc(rows * nb));
+    HIPCHK(m->trk_status.alloc(rows));
+    HIPCHK(hipMemsetAsync(m->trk_meta.p, 0, 2 * rows * sizeof(ssk::BankTrackRow), m->stream));     // updates == 0: a row without state
+    m->trk_cfg = *cfg;
+    m->trk_cur = 0;
+    m->trk_on = true;
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_track(ss_meter_bank *m)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->trk_on) return SS_ERR_INVALID_MODE;
+    HIPCHK(ssk::launch_meter_bank_spectrum(spectrum_params(m, m->trk_rows.p, m->trk_status.p), false, m->stream));
+    HIPCHK(ssk::launch_bank_spectrum_track(track_params(m), m->stream));
+    m->trk_cur ^= 1u;
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_track_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->trk_on) return SS_ERR_INVALID_MODE;
+    ssk::BankTrackRow *meta = m->trk_meta.p + m->trk_cur * track_rows_of(m);
+    if (!streams) {
+        HIPCHK(ssk::launch_bank_spectrum_track_reset(meta, nullptr, m->meter.n, spec_rows(m), m->stream));
+        return SS_OK;
+    }
+    for (uint32_t i = 0; i < count; i++) if (streams[i] >= m->meter.n) return SS_ERR_INVALID_ARG;
+    if (!count) return SS_OK;
+    HIPCHK(m->list.ensure(count));
+    int rc = upload(m, m->list.p, streams, count * sizeof(uint32_t));
+    if (rc) return rc;
+    HIPCHK(ssk::launch_bank_spectrum_track_reset(meta, m->list.p, count, spec_rows(m), m->stream));
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_tracked(ss_meter_bank *m, float *avg_rows, float *hold_rows, size_t cap_floats, uint32_t *updates,
+                                   uint32_t cap_rows)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->trk_on) return SS_ERR_INVALID_MODE;
+    const size_t R = track_rows_of(m), plane = R * m->bt->count;
+    if (((avg_rows || hold_rows) && cap_floats < plane) || (updates && cap_rows < R)) return SS_ERR_CAPACITY;
+    // the curves asked for, then the counts: one copy
+    const size_t n_planes = (avg_rows ? 1u : 0u) + (hold_rows ? 1u : 0u), bytes = n_planes * plane * sizeof(float) + R * sizeof(uint32_t);
+    int rc = track_room(m, bytes);
+    if (rc) return rc;
+    float *base = reinterpret_cast<float *>(m->trk_out.p);
+    float *d_avg = avg_rows ? base : nullptr, *d_hold = hold_rows ? base + (avg_rows ? plane : 0) : nullptr;
+    HIPCHK(ssk::launch_bank_spectrum_tracked_rows(track_params(m), d_avg, d_hold, reinterpret_cast<uint32_t *>(base + n_planes * plane),
+                                                  m->stream));
+    unsigned char *pin;
+    rc = track_fetch(m, bytes, &pin);
+    if (rc) return rc;
+    const float *h = reinterpret_cast<const float *>(pin);
+    if (avg_rows) std::memcpy(avg_rows, h, plane * sizeof(float));
+    if (hold_rows) std::memcpy(hold_rows, h + (avg_rows ? plane : 0), plane * sizeof(float));
+    if (updates) std::memcpy(updates, h + n_planes * plane, R * sizeof(uint32_t));
+    return SS_OK;
+}
+
+int ss_meter_bank_spectrum_tracked_columns(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db, float *avg_cols,
+                                           float *hold_cols, size_t cap_floats, uint32_t *updates, uint32_t cap_rows)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (cols == 0 || cols > 512 || (gain_mode != SS_GAIN_FIXED && gain_mode != SS_GAIN_REFERENCE)) return SS_ERR_INVALID_ARG;
+    if (!m->trk_on) return SS_ERR_INVALID_MODE;
+    const size_t R = track_rows_of(m), plane = R * cols;
+    if (((avg_cols || hold_cols) && cap_floats < plane) || (updates && cap_rows < R)) return SS_ERR_CAPACITY;
+    const size_t bytes = 2 * plane * sizeof(float) + R * sizeof(uint32_t);          // both curves (a few KB per stream), then the counts
+    int rc = track_room(m, bytes);
+    if (rc) return rc;
+    rc = column_tables(m, cols);
+    if (rc) return rc;
+    float *base = reinterpret_cast<float *>(m->trk_out.p);
+    ssk::BankTrackColumns c{};
+    c.pink = m->spec_pink.p; c.bin_col = m->spec_bin_col.p; c.col_init = m->spec_col_init.p;
+    c.cols = cols; c.gain_db = gain_db;
+    if (gain_mode == SS_GAIN_REFERENCE && (rc = reference_gain(m, &c.integrated, &c.integrated_stride))) return rc;
+    c.avg = base; c.hold = base + plane; c.updates = reinterpret_cast<uint32_t *>(base + 2 * plane);
+    HIPCHK(ssk::launch_bank_spectrum_tracked_columns(track_params(m), c, m->stream));
+    unsigned char *pin;
+    rc = track_fetch(m, bytes, &pin);
+    if (rc) return rc;
+    const float *h = reinterpret_cast<const float *>(pin);
+    if (avg_cols) std::memcpy(avg_cols, h, plane * sizeof(float));
+    if (hold_cols) std::memcpy(hold_cols, h + plane, plane * sizeof(float));
+    if (updates) std::memcpy(updates, h + 2 * plane, R * sizeof(uint32_t));
     return SS_OK;
 }
 

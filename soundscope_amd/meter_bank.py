@@ -5,6 +5,8 @@ time-domain launch and a gating launch, and `read()` returns every stream's read
 The streams need not move together: `add_ragged()` gives every stream its own number of frames per call, none included.
 With `enable_spectrum()` the bank also keeps every stream's newest 16384 input frames, and `spectrum()` /
 `spectrum_columns()` transform all of them (mid and side for stereo banks) in one launch.
+With `enable_spectrum_tracking()` it keeps, per row, an exponentially averaged and a peak-hold curve on the device;
+`track_spectrum()` advances them on each stream's own clock, `tracked_spectrum()` / `tracked_spectrum_columns()` read them.
 """
 import ctypes as C
 
@@ -149,18 +151,74 @@ class MeterBank:
                                               st.ctypes.data_as(C.POINTER(C.c_int32)), st.size))
         return rows, st
 
+    @staticmethod
+    def _gain(gain):
+        """(gain mode, gain_db) of a gain argument: None (0 dB), a float in dB, or 'reference'"""
+        if isinstance(gain, str):
+            if gain != "reference":
+                raise ValueError(f"gain {gain!r}: None, a number or 'reference'")
+            return L.SS_GAIN_REFERENCE, 0.0
+        return L.SS_GAIN_FIXED, 0.0 if gain is None else float(gain)
+
     def spectrum_columns(self, cols, gain=None):
         """(columns [n_streams, rows, cols] f32, status [n_streams, rows] i32).  gain: None (0 dB), a float in dB, or "reference"
         (-13 - integrated loudness of each stream, tui.rs:1234)."""
         r, _, _ = self.spectrum_layout()
-        if isinstance(gain, str):
-            if gain != "reference":
-                raise ValueError(f"gain {gain!r}: None, a number or 'reference'")
-            mode, g = L.SS_GAIN_REFERENCE, 0.0
-        else:
-            mode, g = L.SS_GAIN_FIXED, 0.0 if gain is None else float(gain)
+        mode, g = self._gain(gain)
         out = np.empty((self.n_streams, r, int(cols)), np.float32)
         st = np.empty((self.n_streams, r), np.int32)
         _check(L.lib().ss_meter_bank_spectrum_columns(self._h, int(cols), mode, g, out.ctypes.data_as(C.POINTER(C.c_float)), out.size,
                                                       st.ctypes.data_as(C.POINTER(C.c_int32)), st.size))
         return out, st
+
+    # ---- tracked spectra (ss_meter_bank_spectrum_track*) -----------------------------------------------------------------------
+    def enable_spectrum_tracking(self, average_tau_s, hold_s, decay_db_per_s):
+        """Keep, per row, an exponentially averaged power spectrum (time constant average_tau_s; 0: the newest row) and a
+        peak-hold spectrum (held hold_s seconds, inf: for ever, then falling decay_db_per_s) on the device.  Needs
+        enable_spectrum(); enabling again starts from empty state."""
+        cfg = L.SpectrumBallistics(float(average_tau_s), float(hold_s), float(decay_db_per_s))
+        _check(L.lib().ss_meter_bank_spectrum_track_enable(self._h, C.byref(cfg)))
+
+    def disable_spectrum_tracking(self):
+        """Tracking off, its device memory freed."""
+        _check(L.lib().ss_meter_bank_spectrum_track_enable(self._h, None))
+
+    def track_spectrum(self):
+        """Advance every row's curves to the windows as they stand, each stream by the frames it has had since its last update
+        (a stream given nothing, or a refused row, is left alone).  Only queued: two launches, no copy, no wait."""
+        _check(L.lib().ss_meter_bank_spectrum_track(self._h))
+
+    def reset_spectrum_tracking(self, streams=None):
+        """Empty the listed streams' curves (None: all); their next update starts them again."""
+        if streams is None:
+            _check(L.lib().ss_meter_bank_spectrum_track_reset(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+        _check(L.lib().ss_meter_bank_spectrum_track_reset(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+
+    def tracked_spectrum(self):
+        """(avg [n_streams, rows, n_bins] f32 dB, hold [n_streams, rows, n_bins] f32 dB, updates [n_streams, rows] u32): both
+        curves before pink compensation, like spectrum(); a row with updates == 0 is all NaN."""
+        r, nb, _ = self.spectrum_layout()
+        avg = np.empty((self.n_streams, r, nb), np.float32)
+        hold = np.empty((self.n_streams, r, nb), np.float32)
+        upd = np.empty((self.n_streams, r), np.uint32)
+        fp = C.POINTER(C.c_float)
+        _check(L.lib().ss_meter_bank_spectrum_tracked(self._h, avg.ctypes.data_as(fp), hold.ctypes.data_as(fp), avg.size,
+                                                      upd.ctypes.data_as(C.POINTER(C.c_uint32)), upd.size))
+        return avg, hold, upd
+
+    def tracked_spectrum_columns(self, cols, gain=None):
+        """(avg [n_streams, rows, cols] f32, hold [n_streams, rows, cols] f32, updates [n_streams, rows] u32): both curves reduced
+        to chart columns on the device by spectrum_columns()'s rule; gain as there.  NaN: a column without a bin, a row without
+        state."""
+        r, _, _ = self.spectrum_layout()
+        mode, g = self._gain(gain)
+        avg = np.empty((self.n_streams, r, int(cols)), np.float32)
+        hold = np.empty((self.n_streams, r, int(cols)), np.float32)
+        upd = np.empty((self.n_streams, r), np.uint32)
+        fp = C.POINTER(C.c_float)
+        _check(L.lib().ss_meter_bank_spectrum_tracked_columns(self._h, int(cols), mode, g, avg.ctypes.data_as(fp),
+                                                              hold.ctypes.data_as(fp), avg.size,
+                                                              upd.ctypes.data_as(C.POINTER(C.c_uint32)), upd.size))
+        return avg, hold, upd
