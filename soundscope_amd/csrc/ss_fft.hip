@@ -51,6 +51,8 @@ constexpr int kX2Stride = 17;    // anyhop kernel: row of 16 padded to 17, confl
 // cycle: the reads go through lds_ld64 (volatile, LDS address space: one ds_read_b64 each, never merged).
 constexpr int kRowB = 17;
 constexpr int kPlaneB = 16 * kRowB;
+#define X1B(ka, tb_, ta_) ((ka) * kPlaneB + (tb_) * kRowB + (ta_))      // exchange 1: element (ka; tb, ta)
+#define X2B(kb, ka_, tb_) ((kb) * kPlaneB + (ka_) * kRowB + (tb_))      // exchange 2: element (kb; ka, tb)
 
 // Published spectrum layout of the N = 4096 kernels: bin k lives at k with bits 1:0 XORed with bits 6:5.  A lane owns four
 // consecutive retained bins k0 + e (k0 = first_bin + 4 g) and reads bin e of all lanes with one ds_read_b64 (32-lane groups,
@@ -383,6 +385,65 @@ __device__ __forceinline__ void read_levels2(const uint32_t (*lv)[2], uint32_t &
     a = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.x, q0.z), umax(q1.x, q1.z)));
     b = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.y, q0.w), umax(q1.y, q1.w)));
 }
+// the 4-wide siblings: four rows a wave, lv[wave][0..3] in rows of eight words (k_fft4096_ms's [wave][4 peaks, 4 energies])
+__device__ __forceinline__ void read_levels4(const uint32_t (*lv)[8], uint32_t (&x)[4])
+{
+    const uint4 q0 = *reinterpret_cast<const uint4 *>(&lv[0][0]), q1 = *reinterpret_cast<const uint4 *>(&lv[1][0]);
+    const uint4 q2 = *reinterpret_cast<const uint4 *>(&lv[2][0]), q3 = *reinterpret_cast<const uint4 *>(&lv[3][0]);
+    x[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.x, q1.x), umax(q2.x, q3.x)));
+    x[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.y, q1.y), umax(q2.y, q3.y)));
+    x[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.z, q1.z), umax(q2.z, q3.z)));
+    x[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.w, q1.w), umax(q2.w, q3.w)));
+}
+__device__ __forceinline__ void read_energies4(const uint32_t (*lv)[8], uint32_t (&g)[4])
+{
+    const uint4 e0 = *reinterpret_cast<const uint4 *>(&lv[0][4]), e1 = *reinterpret_cast<const uint4 *>(&lv[1][4]);
+    const uint4 e2 = *reinterpret_cast<const uint4 *>(&lv[2][4]), e3 = *reinterpret_cast<const uint4 *>(&lv[3][4]);
+    auto fs = [](uint32_t a, uint32_t b, uint32_t c, uint32_t d) -> uint32_t {
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint((__uint_as_float(a) + __uint_as_float(b)) + (__uint_as_float(c) + __uint_as_float(d))));
+    };
+    g[0] = fs(e0.x, e1.x, e2.x, e3.x); g[1] = fs(e0.y, e1.y, e2.y, e3.y);
+    g[2] = fs(e0.z, e1.z, e2.z, e3.z); g[3] = fs(e0.w, e1.w, e2.w, e3.w);
+}
+// The exact block exponent of a window from its rows' peaks xa, xb (0 = the row is empty: no level, exponent 0) and energies ga,
+// gb: energies (see block_exp_energy) when both are normal numbers, peaks when a square under- or overflowed.
+__device__ __forceinline__ int exact_block_exp(uint32_t xa, uint32_t xb, uint32_t ga, uint32_t gb)
+{
+    if (xa == 0u || xb == 0u) return 0;
+    const bool gok = ga != 0u && gb != 0u && ga < 0x7F800000u && gb < 0x7F800000u;
+    return gok ? block_exp_energy(ga, gb) : block_exp(xa, xb);
+}
+
+// ============================================================================
+//  The run of windows a workgroup walks
+// ============================================================================
+struct WindowRun { uint32_t stream, begin, end; };
+// workgroup -> run `begin`..`end` of `stream` (streams outermost), cut to the stream's own window count (ragged batches);
+// false: nothing is left of it
+__device__ __forceinline__ bool window_run(const FftBatchParams &p, WindowRun &r)
+{
+    const uint32_t groups = (p.n_windows + p.windows_per_block - 1) / p.windows_per_block;
+    const uint32_t stream = blockIdx.x / groups;
+    const uint32_t grp = blockIdx.x - stream * groups;
+    const uint32_t begin = grp * p.windows_per_block;
+    uint32_t end = begin + p.windows_per_block;
+    const uint32_t n_win = p.windows_of ? p.windows_of[stream] : p.n_windows;
+    if (begin >= n_win) return false;
+    if (end > n_win) end = n_win;
+    r = WindowRun{stream, begin, end};
+    return true;
+}
+// Logical workgroup id of the kernels that run one workgroup per channel (k_fft4096_pairw, k_fft16k_run: channel innermost,
+// then runs, then streams).  Workgroup ids are dealt round-robin to the 8 XCDs, each with its own L2.  The channels of one run
+// read the same interleaved lines, so they must sit on ONE XCD: logical id = (id mod 8) * ceil(total / 8) + id / 8 makes the
+// ids of an XCD consecutive (the launcher pads the grid to a multiple of 8; surplus ids leave), and the channels of one run are
+// neighbours.  What follows the id — the surplus test, the split into (stream, run, channel), the ragged cut in windows or in
+// pairs — stays in the two kernels: written as a function of window_run's shape it moves instructions in both.
+__device__ __forceinline__ uint32_t xcd_logical_id()
+{
+    const uint32_t per_xcd = gridDim.x >> 3;
+    return (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+}
 
 // HS = hop / 256.  A workgroup iteration transforms TWO consecutive windows: they share the
 // sliding sample registers (16 + HS slots) and every per-thread constant, and every barrier
@@ -406,14 +467,9 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms(FftBatchParams p)
     __shared__ __attribute__((aligned(16))) uint32_t xlev4[4][8];          // [wave][4 peaks, 4 energies]
 
     const int t = threadIdx.x;
-    const uint32_t groups = (p.n_windows + p.windows_per_block - 1) / p.windows_per_block;
-    const uint32_t stream = blockIdx.x / groups;
-    const uint32_t grp = blockIdx.x - stream * groups;
-    const uint32_t w_begin = grp * p.windows_per_block;
-    uint32_t w_end = w_begin + p.windows_per_block;
-    const uint32_t n_win = p.windows_of ? p.windows_of[stream] : p.n_windows;     // ragged batches: this stream's own count
-    if (w_begin >= n_win) return;
-    if (w_end > n_win) w_end = n_win;
+    WindowRun run;
+    if (!window_run(p, run)) return;
+    const uint32_t stream = run.stream, w_begin = run.begin, w_end = run.end;
 
     const float2 *src = reinterpret_cast<const float2 *>(p.pcm) + (size_t)stream * p.frames_per_stream +
                         p.first_start + (size_t)w_begin * p.hop;
@@ -466,28 +522,11 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms(FftBatchParams p)
                 *reinterpret_cast<uint4 *>(&xlev4[wvid][4]) = make_uint4(__float_as_uint(s0), __float_as_uint(s1), __float_as_uint(s2), __float_as_uint(s3));
             }
             __syncthreads();
-            const uint4 q0 = *reinterpret_cast<const uint4 *>(&xlev4[0][0]), q1 = *reinterpret_cast<const uint4 *>(&xlev4[1][0]);
-            const uint4 q2 = *reinterpret_cast<const uint4 *>(&xlev4[2][0]), q3 = *reinterpret_cast<const uint4 *>(&xlev4[3][0]);
-            X[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.x, q1.x), umax(q2.x, q3.x)));
-            X[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.y, q1.y), umax(q2.y, q3.y)));
-            X[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.z, q1.z), umax(q2.z, q3.z)));
-            X[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(q0.w, q1.w), umax(q2.w, q3.w)));
-            const uint4 e0 = *reinterpret_cast<const uint4 *>(&xlev4[0][4]), e1 = *reinterpret_cast<const uint4 *>(&xlev4[1][4]);
-            const uint4 e2 = *reinterpret_cast<const uint4 *>(&xlev4[2][4]), e3 = *reinterpret_cast<const uint4 *>(&xlev4[3][4]);
-            auto fs = [](uint32_t a, uint32_t b, uint32_t c, uint32_t d) -> uint32_t {
-                return (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint((__uint_as_float(a) + __uint_as_float(b)) + (__uint_as_float(c) + __uint_as_float(d))));
-            };
-            G[0] = fs(e0.x, e1.x, e2.x, e3.x); G[1] = fs(e0.y, e1.y, e2.y, e3.y);
-            G[2] = fs(e0.z, e1.z, e2.z, e3.z); G[3] = fs(e0.w, e1.w, e2.w, e3.w);
+            read_levels4(xlev4, X);
+            read_energies4(xlev4, G);
         }
-        // (energies when both are normal numbers, peaks when a square under- or overflowed)
-        auto row_exp = [](uint32_t xa, uint32_t xb, uint32_t ga, uint32_t gb) -> int {
-            if (xa == 0u || xb == 0u) return 0;
-            const bool gok = ga != 0u && gb != 0u && ga < 0x7F800000u && gb < 0x7F800000u;
-            return gok ? block_exp_energy(ga, gb) : block_exp(xa, xb);
-        };
-        const int E0 = row_exp(X[0], X[1], G[0], G[1]);
-        const int E1 = row_exp(X[2], X[3], G[2], G[3]);
+        const int E0 = exact_block_exp(X[0], X[1], G[0], G[1]);
+        const int E1 = exact_block_exp(X[2], X[3], G[2], G[3]);
         const float sc0 = exp2i(E0), sc1 = exp2i(E1);
         // prefetch the 2*HS new slots of the next pair (consumed after the epilogue)
         float2 nx[2 * HS];
@@ -573,27 +612,93 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms(FftBatchParams p)
 #undef X1W
 #undef X2W
 
+// Wave priority by phase: a wave that is exchanging through LDS (writes, barrier, reads) runs at raised priority so
+// its few LDS instructions issue ahead of the other workgroups' butterflies; measured 3.15 -> 3.05 ms (A/B in one process)
+#define SS_PRIO_HI() __builtin_amdgcn_s_setprio(3)
+#define SS_PRIO_LO() __builtin_amdgcn_s_setprio(0)
+// Phase marks of a window loop: NoMark where a kernel has none; PhaseMark is NoMark too but in the development build
+// (-DSS_FFT_PROF), where it keeps per-phase shader-clock totals over all waves (tools/probe_fft_phases.py, probe_fft16k_phases.py).
+struct NoMark {
+    __device__ __forceinline__ void operator()(int) const {}
+    __device__ __forceinline__ void end() const {}
+};
+#ifdef SS_FFT_PROF
+__device__ unsigned long long g_fft_prof[16];
+struct PhaseMark {
+    uint64_t pt = __builtin_amdgcn_s_memtime(), acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    __device__ __forceinline__ void operator()(int i) { const uint64_t n = __builtin_amdgcn_s_memtime(); acc[i] += n - pt; pt = n; }
+    __device__ __forceinline__ void end() const
+    {
+        if ((threadIdx.x & 63) != 0) return;
+#pragma unroll
+        for (int i = 0; i < 12; i++) atomicAdd(&g_fft_prof[i], (unsigned long long)acc[i]);
+        atomicAdd(&g_fft_prof[15], 1ull);
+    }
+};
+#else
+typedef NoMark PhaseMark;
+#endif
+
+// ============================================================================
+//  The pass core of the batch layout (k_fft4096_ms1, k_fft4096_pairw, k_fft16k_run): what stands between two steps in one
+//  kernel (a prefetch, a level exchange, a twiddle request) stays in that kernel, between the calls.  The steps take the
+//  kernel's own row pointers — rebuilt from tb, hi in here the address arithmetic moves — and, as policies, the wave priority
+//  (PRIO) and the phase marks.  Pass 1's twiddles are r16_load_tw1 / r16_pass1_tw (ss_fft_dev.h); its store loop and the publish
+//  behind pass 3 (masked at SPEC_POS(t), or plain at t) are three lines in each kernel: owned by a function here, either one
+//  reorders the kernels' loop-invariant addresses, and the instructions behind them (tools/isa_same.py).
+// ============================================================================
+template <bool PRIO>
+__device__ __forceinline__ void r16_fft(v2f (&z)[16])
+{
+    if (PRIO) SS_PRIO_LO();
+    fft16(z);
+    if (PRIO) SS_PRIO_HI();
+}
+// a thread's row of sixteen (row = &xbuf[X1B(hi, tb, 0)], the same place in both exchanges: pass 2's input and pass 3's) and
+// the barrier that lets the next stores go over it; marks i, i + 1 around the barrier
+template <class Mark>
+__device__ __forceinline__ void r16_row_load(v2f (&z)[16], const v2f *row, Mark &mark, int i)
+{
+#pragma unroll
+    for (int j = 0; j < 16; j++) z[j] = lds_ld64(&row[j]);
+    mark(i);
+    __syncthreads();
+    mark(i + 1);
+}
+// pass 2 (thread = tb + 16 ka) up to its twiddled stores: x2 = &xbuf[X2B(0, hi, tb)], twp = tw2s + tb, the [kb][tb] table
+// (address = tb * 8 + an immediate); marks 2, 3
+template <bool PRIO, class Mark>
+__device__ __forceinline__ void r16_pass2(v2f (&z)[16], const v2f *row, v2f *x2, const v2f *twp, Mark &mark)
+{
+    r16_row_load(z, row, mark, 2);
+    r16_fft<PRIO>(z);
+    x2[0] = z[R16(0)];
+    // the twiddles four at a time, the next four requested before the current four are used
+    v2f twa[4], twb[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) twa[j] = lds_ld64(&twp[16 * (1 + j)]);
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const int kb0 = 1 + 4 * g, nk = g == 3 ? 3 : 4;
+        if (g < 3) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (kb0 + 4 + j < 16) twb[j] = lds_ld64(&twp[16 * (kb0 + 4 + j)]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < nk; j++) x2[(kb0 + j) * kPlaneB] = pk_cmul(z[R16(kb0 + j)], twa[j]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; j++) twa[j] = twb[j];
+    }
+}
+
 // Single-window variant (one window per iteration): built for occupancy — three workgroups per CU instead of two.
 // Of the 15 pass-1 twiddles W^(t ka), TWN stay resident; the others are rebuilt as W^(t ka) = W^(t (ka & 3)) * W^(t (ka & 12)),
 // one extra complex multiply each per window.
 // Resident pass-1 twiddles of k_fft4096_ms1 (6, 9, 12 or all fifteen were built): 168 VGPRs at 12, the three-waves limit.  Both
 // instantiations take this one count: the columns-only rows would otherwise round differently from the stored ones.
 constexpr int kMs1Tw = 12;
-// Wave priority by phase: a wave that is exchanging through LDS (writes, barrier, reads) runs at raised priority so
-// its few LDS instructions issue ahead of the other workgroups' butterflies; measured 3.15 -> 3.05 ms (A/B in one process)
-#define SS_PRIO_HI() __builtin_amdgcn_s_setprio(3)
-#define SS_PRIO_LO() __builtin_amdgcn_s_setprio(0)
-// Development build (-DSS_FFT_PROF): per-phase shader-clock totals of k_fft4096_ms1 over all waves (tools/probe_fft_phases.py)
-#ifdef SS_FFT_PROF
-__device__ unsigned long long g_fft_prof[16];
-#define SS_FPROF_DECL uint64_t pt_ = __builtin_amdgcn_s_memtime(); uint64_t pacc_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define SS_FPROF_MARK(i) do { const uint64_t n_ = __builtin_amdgcn_s_memtime(); pacc_[i] += n_ - pt_; pt_ = n_; } while (0)
-#define SS_FPROF_END do { if ((threadIdx.x & 63) == 0) { _Pragma("unroll") for (int i_ = 0; i_ < 12; i_++) atomicAdd(&g_fft_prof[i_], (unsigned long long)pacc_[i_]); atomicAdd(&g_fft_prof[15], 1ull); } } while (0)
-#else
-#define SS_FPROF_DECL
-#define SS_FPROF_MARK(i)
-#define SS_FPROF_END
-#endif
 template <int HS, int TWN, bool COLS>
 __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
 {
@@ -612,17 +717,10 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
     // (three workgroups per CU leave 53 KB each: 53.4 KB with these)
     __shared__ __attribute__((aligned(16))) uint2 coltab[COLS ? 512 : 1];
     __shared__ __attribute__((aligned(16))) float colbuf[COLS ? 2 * kColStride : 1];
-#define X1W(ka, tb_, ta_) ((ka) * kPlaneB + (tb_) * kRowB + (ta_))
-#define X2W(kb, ka_, tb_) ((kb) * kPlaneB + (ka_) * kRowB + (tb_))
     const int t = threadIdx.x;
-    const uint32_t groups = (p.n_windows + p.windows_per_block - 1) / p.windows_per_block;
-    const uint32_t stream = blockIdx.x / groups;
-    const uint32_t grp = blockIdx.x - stream * groups;
-    const uint32_t w_begin = grp * p.windows_per_block;
-    uint32_t w_end = w_begin + p.windows_per_block;
-    const uint32_t n_win = p.windows_of ? p.windows_of[stream] : p.n_windows;     // ragged batches: this stream's own count
-    if (w_begin >= n_win) return;
-    if (w_end > n_win) w_end = n_win;
+    WindowRun run;
+    if (!window_run(p, run)) return;
+    const uint32_t stream = run.stream, w_begin = run.begin, w_end = run.end;
     const float2 *src = reinterpret_cast<const float2 *>(p.pcm) + (size_t)stream * p.frames_per_stream +
                         p.first_start + (size_t)w_begin * p.hop;
     const v2f *twn = reinterpret_cast<const v2f *>(p.tw_n);
@@ -631,11 +729,7 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
 #pragma unroll
     for (int j = 0; j < 8; j++) hwp[j] = v2f{p.half_window[t + 256 * (2 * j)], p.half_window[t + 256 * (2 * j + 1)]};
     v2f tw1[16];
-    static_assert(TWN == 6 || TWN == 9 || TWN == 12, "resident pass-1 twiddles: 6, 9 or 12");
-    // TWN resident pass-1 twiddles: 6 = {1, 2, 3, 4, 8, 12}; 9 adds {5, 6, 7}; 12 adds {9, 10, 11} (one multiply instead of two each)
-    auto tw_resident = [](int ka) -> bool { return (ka & 3) == 0 || (ka & 12) == 0 || (TWN >= 9 && (ka >> 2) == 1) || (TWN >= 12 && (ka >> 2) == 2); };
-#pragma unroll
-    for (int ka = 1; ka < 16; ka++) if (tw_resident(ka)) tw1[ka] = twn[ka * t];
+    r16_load_tw1<TWN>(tw1, twn, t);
     tw2s[t] = reinterpret_cast<const v2f *>(p.tw_256)[(t & 15) * (t >> 4)];      // [kb][tb]: W_256^(tb kb) at kb * 16 + tb
     if (COLS) {
         for (uint32_t g = (uint32_t)t; 4u * g < p.bin_stride; g += 256u) coltab[g] = p.col_groups[g];
@@ -713,7 +807,7 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
         if (mm != 0u && md != 0u) rescale(block_exp(mm, md));
     };
     presettle();
-    SS_FPROF_DECL
+    PhaseMark mark;
     for (uint32_t w = w_begin; w < w_end; ++w) {
         float2 nx[HS];
         const bool more = (w + 1 < w_end);
@@ -758,78 +852,30 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
             }
         }
         const float soff = soffE;                            // this window's side row rides the transform as side * 2^E
-        SS_PRIO_LO();
-        fft16(z);
-        SS_PRIO_HI();
-        xbuf[X1W(0, tb, hi)] = z[R16(0)];
+        r16_fft<true>(z);
+        xbuf[X1B(0, tb, hi)] = z[R16(0)];
 #pragma unroll
-        for (int ka = 1; ka < 16; ka++) {
-            v2f v = z[R16(ka)];
-            if (!tw_resident(ka)) {
-                // (the product tw1[ka & 3] tw1[ka & 12] formed per window off the data's dependent chain, then ONE multiply of the data:
-                // measured in round 6, six interleaved repetitions: 2.996 vs 2.995 ms — nothing)
-                v = pk_cmul(v, tw1[ka & 3]);
-                v = pk_cmul(v, tw1[ka & 12]);
-            } else {
-                v = pk_cmul(v, tw1[ka]);
-            }
-            xbuf[X1W(ka, tb, hi)] = v;
-        }
+        for (int ka = 1; ka < 16; ka++) xbuf[X1B(ka, tb, hi)] = r16_pass1_tw<TWN>(ka, z[R16(ka)], tw1);
 #pragma unroll
         for (int q = 0; q < HS; q++) {
             nx[q] = make_float2(0.f, 0.f);
             if (more) nx[q] = src[(size_t)(w + 1 - w_begin) * p.hop + t + 256 * (16 - HS + q)];
         }
-        SS_FPROF_MARK(0);
+        mark(0);
         __syncthreads();
-        SS_FPROF_MARK(1);
-#pragma unroll
-        for (int ta = 0; ta < 16; ta++) z[ta] = lds_ld64(&xbuf[X1W(hi, tb, ta)]);
-        SS_FPROF_MARK(2);
+        mark(1);
+        r16_pass2<true>(z, &xbuf[X1B(hi, tb, 0)], &xbuf[X2B(0, hi, tb)], tw2s + tb, mark);
+        mark(4);
         __syncthreads();
-        SS_FPROF_MARK(3);
-        SS_PRIO_LO();
-        fft16(z);
-        SS_PRIO_HI();
-        xbuf[X2W(0, hi, tb)] = z[R16(0)];
-        {   // second-pass twiddles from the [kb][tb] table (address = tb * 8 + an immediate), four at a time, the next four
-            // requested before the current four are used
-            const v2f *twp = tw2s + tb;
-            v2f twa[4], twb[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) twa[j] = lds_ld64(&twp[16 * (1 + j)]);
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const int kb0 = 1 + 4 * g, nk = g == 3 ? 3 : 4;
-                if (g < 3) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) if (kb0 + 4 + j < 16) twb[j] = lds_ld64(&twp[16 * (kb0 + 4 + j)]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < nk; j++) xbuf[X2W(kb0 + j, hi, tb)] = pk_cmul(z[R16(kb0 + j)], twa[j]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; j++) twa[j] = twb[j];
-            }
-        }
-        SS_FPROF_MARK(4);
-        __syncthreads();
-        SS_FPROF_MARK(5);
-#pragma unroll
-        for (int q = 0; q < 16; q++) z[q] = lds_ld64(&xbuf[X2W(hi, tb, q)]);
-        SS_FPROF_MARK(6);
-        __syncthreads();
-        SS_FPROF_MARK(7);
-        SS_PRIO_LO();
-        fft16(z);
-        SS_PRIO_HI();
+        mark(5);
+        r16_row_load(z, &xbuf[X1B(hi, tb, 0)], mark, 6);
+        r16_fft<true>(z);
 #pragma unroll
         for (int kc = 0; kc < 16; kc++)
             if ((p.publish_mask >> kc) & 1u) xbuf[kc * 256 + tsw] = z[R16(kc)];   // blocks with no retained bin or mirror are skipped
-        SS_FPROF_MARK(8);
+        mark(8);
         __syncthreads();
-        SS_FPROF_MARK(9);
+        mark(9);
         SS_PRIO_LO();
         // the sliding registers take the prefetched hop before the epilogue's stores (see fft4096_epilogue); its levels go to
         // the workgroup (read at the next loop top), and the next window's ordinary exponent is settled
@@ -856,14 +902,12 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
             if (!COLS) fft4096_floor_rows(t, p.n_bins, p.db_offset, p.offpink, o_mid, o_mid + p.bin_stride, zrow_m, zrow_d);
             else fft4096_floor_columns(t, p.n_bins, p.db_offset, p.offpink, colbuf, p.bin_col, p.col_init, p.cols, zrow_m, zrow_d);
         }
-        SS_FPROF_MARK(10);
+        mark(10);
         __syncthreads();
-        SS_FPROF_MARK(11);
+        mark(11);
     }
-    SS_FPROF_END;
+    mark.end();
     if (COLS) flush_columns(w_end - 1);                     // (the loop's last barrier closed the last epilogue)
-#undef X1W
-#undef X2W
 }
 
 // One REAL channel (mono buffers, or channel `ch` of an interleaved one) at hop 1024: two consecutive windows w, w + 1
@@ -880,15 +924,11 @@ __global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchP
     // hops that enter per pair, rows 0..4 serve the run's first pair once; xlev[wave] = (first, second) window, exact path
     __shared__ __attribute__((aligned(16))) uint32_t hoplev[5][4];
     __shared__ __attribute__((aligned(16))) uint32_t xlev[4][2];
-#define X1W(ka, tb_, ta_) ((ka) * kPlaneB + (tb_) * kRowB + (ta_))
-#define X2W(kb, ka_, tb_) ((kb) * kPlaneB + (ka_) * kRowB + (tb_))
     const int t = threadIdx.x;
     const uint32_t pairs_per_block = p.windows_per_block >> 1;            // the host keeps windows_per_block even
     const uint32_t n_pairs_max = (p.n_windows + 1) >> 1;
     const uint32_t groups = (n_pairs_max + pairs_per_block - 1) / pairs_per_block;
-    // channels of one run read the same interleaved lines: keep them on one XCD (the mapping is spelled out in k_fft16k_run)
-    const uint32_t per_xcd = gridDim.x >> 3;
-    uint32_t bid = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    uint32_t bid = xcd_logical_id();
     if (bid >= p.n_streams * groups * fft_ch) return;
     const uint32_t ch = bid % fft_ch; bid /= fft_ch;
     const uint32_t grp = bid % groups;
@@ -906,10 +946,11 @@ __global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchP
 #pragma unroll
     for (int j = 0; j < 16; j++) hw2[j] = hw[j] = p.window[t + 256 * j];  // the full Hann window: no mid/side halving here
     v2f tw1[16];
-    tw1[1] = twn[t]; tw1[2] = twn[2 * t]; tw1[3] = twn[3 * t];
-    tw1[4] = twn[4 * t]; tw1[8] = twn[8 * t]; tw1[12] = twn[12 * t];
-    tw1[5] = twn[5 * t]; tw1[6] = twn[6 * t]; tw1[7] = twn[7 * t];               // three more resident (k_fft4096_ms1's TWN = 9; round 6: -3 %,
-                                                                                 // 166 VGPRs; twelve would cost the third wave per SIMD)
+    // Nine resident pass-1 twiddles (round 6: -3 % against six, 166 VGPRs; twelve would cost the third wave per SIMD): the six
+    // factors and the plane ka = 4..7 whole.  Written as the six-factor policy plus that plane, here and at the store: as
+    // r16_load_tw1<9> / r16_pass1_tw<9> the same arithmetic comes out in another instruction order.
+    r16_load_tw1<6>(tw1, twn, t);
+    tw1[5] = twn[5 * t]; tw1[6] = twn[6 * t]; tw1[7] = twn[7 * t];
     tw2s[t] = reinterpret_cast<const v2f *>(p.tw_256)[(t & 15) * (t >> 4)];      // [kb][tb]: W_256^(tb kb) at kb * 16 + tb (see k_fft4096_ms1)
     const int tb = t & 15, hi = t >> 4;
     const int tsw = SPEC_POS(t);
@@ -974,6 +1015,7 @@ __global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchP
         }
     };
     settle();
+    NoMark nomark;
     for (uint32_t pp = pp_begin; pp < pp_end; ++pp) {
         const bool two = (2u * pp + 1u < n_win);
         const bool more = (pp + 1 < pp_end);
@@ -998,63 +1040,27 @@ __global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchP
 #pragma unroll
             for (int j = 0; j < 16; j++) { if (bad_a) z[j].x = 0.0f; else z[j].y = 0.0f; }
         }
-        SS_PRIO_LO();
-        fft16(z);
-        SS_PRIO_HI();
-        xbuf[X1W(0, tb, hi)] = z[R16(0)];
+        r16_fft<true>(z);
+        xbuf[X1B(0, tb, hi)] = z[R16(0)];
 #pragma unroll
-        for (int ka = 1; ka < 16; ka++) {
-            v2f v = z[R16(ka)];
-            if ((ka >> 2) == 1) v = pk_cmul(v, tw1[ka]);
-            else {
-                if (ka & 3) v = pk_cmul(v, tw1[ka & 3]);
-                if (ka & 12) v = pk_cmul(v, tw1[ka & 12]);
-            }
-            xbuf[X1W(ka, tb, hi)] = v;
-        }
+        for (int ka = 1; ka < 16; ka++)
+            xbuf[X1B(ka, tb, hi)] = (ka >> 2) == 1 ? pk_cmul(z[R16(ka)], tw1[ka]) : r16_pass1_tw<6>(ka, z[R16(ka)], tw1);
         __syncthreads();
-#pragma unroll
-        for (int ta = 0; ta < 16; ta++) z[ta] = lds_ld64(&xbuf[X1W(hi, tb, ta)]);
-        __syncthreads();
-        SS_PRIO_LO();
-        fft16(z);
-        SS_PRIO_HI();
-        xbuf[X2W(0, hi, tb)] = z[R16(0)];
-        {
-            const v2f *twp = tw2s + tb;
-            v2f twa[4], twb[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) twa[j] = lds_ld64(&twp[16 * (1 + j)]);
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const int kb0 = 1 + 4 * g, nk = g == 3 ? 3 : 4;
-                if (g < 3) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) if (kb0 + 4 + j < 16) twb[j] = lds_ld64(&twp[16 * (kb0 + 4 + j)]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < nk; j++) xbuf[X2W(kb0 + j, hi, tb)] = pk_cmul(z[R16(kb0 + j)], twa[j]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; j++) twa[j] = twb[j];
-            }
-        }
+        r16_pass2<true>(z, &xbuf[X1B(hi, tb, 0)], &xbuf[X2B(0, hi, tb)], tw2s + tb, nomark);
         {   // the two entering hops' levels to the workgroup (read back behind the next barrier, used at the slide)
             const uint32_t wl0 = hop_level(nx[0], nx[1], nx[2], nx[3]), wl1 = hop_level(nx[4], nx[5], nx[6], nx[7]);
             if (lane63) { hoplev[0][wvid] = wl0; hoplev[1][wvid] = wl1; }
         }
         __syncthreads();
         const uint32_t nP0 = read_level(hoplev[0]), nP1 = read_level(hoplev[1]);
+        // (the kernel's own lines, not r16_row_load: behind the level read the call moves this kernel's address arithmetic)
 #pragma unroll
-        for (int q = 0; q < 16; q++) z[q] = lds_ld64(&xbuf[X2W(hi, tb, q)]);
+        for (int q = 0; q < 16; q++) z[q] = lds_ld64(&xbuf[X2B(hi, tb, q)]);
         __syncthreads();
-        SS_PRIO_LO();
-        fft16(z);
-        SS_PRIO_HI();
+        r16_fft<true>(z);
 #pragma unroll
         for (int kc = 0; kc < 16; kc++)
-            if ((p.publish_mask >> kc) & 1u) xbuf[kc * 256 + tsw] = z[R16(kc)];
+            if ((p.publish_mask >> kc) & 1u) xbuf[kc * 256 + tsw] = z[R16(kc)];   // blocks with no retained bin or mirror are skipped
         __syncthreads();
         SS_PRIO_LO();
         float *o_first = outp + (size_t)(pp - pp_begin) * 2u * row_stride;
@@ -1073,8 +1079,6 @@ __global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchP
         }
         __syncthreads();
     }
-#undef X1W
-#undef X2W
 }
 
 // generic hop (not a multiple of 256 or >= N/2 slots): one window per iteration, full reload
@@ -1085,14 +1089,9 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms_anyhop(FftBatchPa
     __shared__ __attribute__((aligned(16))) uint32_t xlev[4][2];      // exact block exponent: [wave][mid, side] largest windowed magnitude
     __shared__ __attribute__((aligned(16))) uint32_t glev[4][2];      //                        ... and windowed energy
     const int t = threadIdx.x;
-    const uint32_t groups = (p.n_windows + p.windows_per_block - 1) / p.windows_per_block;
-    const uint32_t stream = blockIdx.x / groups;
-    const uint32_t grp = blockIdx.x - stream * groups;
-    const uint32_t w_begin = grp * p.windows_per_block;
-    uint32_t w_end = w_begin + p.windows_per_block;
-    const uint32_t n_win = p.windows_of ? p.windows_of[stream] : p.n_windows;     // ragged batches: this stream's own count
-    if (w_begin >= n_win) return;
-    if (w_end > n_win) w_end = n_win;
+    WindowRun run;
+    if (!window_run(p, run)) return;
+    const uint32_t stream = run.stream, w_begin = run.begin, w_end = run.end;
     const float2 *src = reinterpret_cast<const float2 *>(p.pcm) + (size_t)stream * p.frames_per_stream +
                         p.first_start + (size_t)w_begin * p.hop;
     tw2s[t] = reinterpret_cast<const v2f *>(p.tw_256)[t];
@@ -1126,7 +1125,7 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms_anyhop(FftBatchPa
             read_levels2(xlev, Xm, Xd);
             read_energies2(glev, Gm, Gd);
         }
-        // energies (see block_exp_energy) when both are normal numbers, peaks when a square under- or overflowed
+        // (spelled out, not exact_block_exp: through the call this kernel comes out two instructions longer)
         const bool gok = Gm != 0u && Gd != 0u && Gm < 0x7F800000u && Gd < 0x7F800000u;
         const int E = (Xm != 0u && Xd != 0u) ? (gok ? block_exp_energy(Gm, Gd) : block_exp(Xm, Xd)) : 0;
         {
@@ -1162,16 +1161,8 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms_anyhop(FftBatchPa
     }
 }
 
-// ============================================================================
-//  Spectrum, N = 16384 (the reference's native window, tui.rs:1488), one REAL channel per
-//  512-thread workgroup: real FFT through an 8192-point complex FFT, split by one radix-2
-//  decimation-in-frequency step into two 4096-point problems that reuse the radix-16 machinery:
-//    z[i] = (xw[2i], xw[2i+1]),  y_q[i] = (z[i] + (-1)^q z[i+4096]) W_8192^(i q),  Z[2k+q] = FFT_4096(y_q)[k]
-//    X[b] = (Z[b] + conj Z[8192-b])/2 - (i/2) W_16384^b (Z[b] - conj Z[8192-b])
-//  Threads 0-255 run q = 0, threads 256-511 run q = 1; the mirror 8192-b has the parity of b, so each
-//  half only mirrors inside its own published spectrum.  mode 0: mono buffer, 1: stereo -> mid/side
-//  (audio_player.rs:400-419), 2: channel `ch` of an interleaved buffer.
-// ============================================================================
+// Spectrum, N = 16384, ONE window of one real channel per 512-thread workgroup: the algorithm is spelled out at
+// fft16k_transform (ss_fft_dev.h)
 __global__ __launch_bounds__(512, 2) void k_fft16k(FftBatchParams p, int midside, uint32_t fft_ch)
 {
     __shared__ __attribute__((aligned(16))) unsigned char lds[kFft16kLdsBytes];
@@ -1203,19 +1194,13 @@ __global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_
     __shared__ __attribute__((aligned(16))) v2f xbuf2[2][16 * kPlaneB];      // 2 x 34816 B
     __shared__ __attribute__((aligned(16))) v2f tw2s[256];                    //  2048 B
     __shared__ __attribute__((aligned(16))) float stage[8][256];              //  8192 B: 79872 B per workgroup, two per CU
-#define X1W(ka, tb_, ta_) ((ka) * kPlaneB + (tb_) * kRowB + (ta_))
-#define X2W(kb, ka_, tb_) ((kb) * kPlaneB + (ka_) * kRowB + (tb_))
     const int q = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));   // which half this wave carries
     const int t = threadIdx.x & 255;
     v2f *xbuf = xbuf2[q];
     const uint32_t groups = (p.n_windows + p.windows_per_block - 1) / p.windows_per_block;
-    // Workgroup ids are dealt round-robin to the 8 XCDs, each with its own L2.  The channels of one run read the
-    // same interleaved lines, so they must sit on ONE XCD: logical id = (id mod 8) * ceil(total / 8) + id / 8 makes
-    // the ids of an XCD consecutive (the launcher pads the grid to a multiple of 8; surplus ids leave).
-    const uint32_t per_xcd = gridDim.x >> 3;
-    uint32_t bid = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    uint32_t bid = xcd_logical_id();
     if (bid >= p.n_streams * groups * fft_ch) return;
-    const uint32_t ch = bid % fft_ch; bid /= fft_ch;            // the channels of one run are neighbours in the logical order
+    const uint32_t ch = bid % fft_ch; bid /= fft_ch;
     const uint32_t grp = bid % groups;
     const uint32_t stream = bid / groups;
     const uint32_t w_begin = grp * p.windows_per_block;
@@ -1254,8 +1239,7 @@ __global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_
     const v2f half = {0.5f, 0.5f};
     const v2f we0 = {p.window[ne], p.window[ne + 1]}, we15 = {p.window[15360u + ne], p.window[15360u + ne + 1]};
     v2f twg[16];
-    twg[1] = tw4k[t]; twg[2] = tw4k[2 * t]; twg[3] = tw4k[3 * t];
-    twg[4] = tw4k[4 * t]; twg[8] = tw4k[8 * t]; twg[12] = tw4k[12 * t];
+    r16_load_tw1<6>(twg, tw4k, t);
     const int tb = t & 15, hi = t >> 4;
     const uint32_t ngroups = (p.n_bins + 3) >> 2;
     constexpr float kDb = 3.01029995663981195f;
@@ -1282,7 +1266,7 @@ __global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_
 #pragma unroll
     for (int j = 0; j < 16; j++) asm volatile("" : "+v"(raw[j]));
     __syncthreads();
-    SS_FPROF_DECL      // (-DSS_FFT_PROF: the window loop's phases, tools/probe_fft16k_phases.py)
+    PhaseMark mark;      // (-DSS_FFT_PROF: the window loop's phases, tools/probe_fft16k_phases.py)
 
     for (uint32_t w = w_begin; w < w_end; ++w) {
         const bool more = (w + 1 < w_end);
@@ -1314,53 +1298,18 @@ __global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_
             z[j + 11] = raw[j + 11] * whi; z[j + 3] = raw[j + 3] - raw[j + 3] * whi;
         }
         fft16(z);
-        xbuf[X1W(0, tb, hi)] = z[R16(0)];
+        xbuf[X1B(0, tb, hi)] = z[R16(0)];
 #pragma unroll
-        for (int ka = 1; ka < 16; ka++) {
-            v2f v = z[R16(ka)];
-            if (ka & 3) v = pk_cmul(v, twg[ka & 3]);
-            if (ka & 12) v = pk_cmul(v, twg[ka & 12]);
-            xbuf[X1W(ka, tb, hi)] = v;
-        }
+        for (int ka = 1; ka < 16; ka++) xbuf[X1B(ka, tb, hi)] = r16_pass1_tw<6>(ka, z[R16(ka)], twg);
         if (more) nx = ld2((size_t)(w + 1 - w_begin) * 1024u + n0 + 1024u * 15u);
-        SS_FPROF_MARK(0);
+        mark(0);
         __syncthreads();
-        SS_FPROF_MARK(1);
-#pragma unroll
-        for (int ta = 0; ta < 16; ta++) z[ta] = lds_ld64(&xbuf[X1W(hi, tb, ta)]);
-        SS_FPROF_MARK(2);
+        mark(1);
+        r16_pass2<false>(z, &xbuf[X1B(hi, tb, 0)], &xbuf[X2B(0, hi, tb)], tw2s + tb, mark);
+        mark(4);
         __syncthreads();
-        SS_FPROF_MARK(3);
-        fft16(z);
-        xbuf[X2W(0, hi, tb)] = z[R16(0)];
-        {   // second-pass twiddles from the [kb][tb] table, four at a time, the next four requested before the current four are used
-            const v2f *twp = tw2s + tb;
-            v2f twa[4], twb[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) twa[j] = lds_ld64(&twp[16 * (1 + j)]);
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const int kb0 = 1 + 4 * g, nk = g == 3 ? 3 : 4;
-                if (g < 3) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) if (kb0 + 4 + j < 16) twb[j] = lds_ld64(&twp[16 * (kb0 + 4 + j)]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < nk; j++) xbuf[X2W(kb0 + j, hi, tb)] = pk_cmul(z[R16(kb0 + j)], twa[j]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; j++) twa[j] = twb[j];
-            }
-        }
-        SS_FPROF_MARK(4);
-        __syncthreads();
-        SS_FPROF_MARK(5);
-#pragma unroll
-        for (int qq = 0; qq < 16; qq++) z[qq] = lds_ld64(&xbuf[X2W(hi, tb, qq)]);
-        SS_FPROF_MARK(6);
-        __syncthreads();
-        SS_FPROF_MARK(7);
+        mark(5);
+        r16_row_load(z, &xbuf[X1B(hi, tb, 0)], mark, 6);
         fft16(z);
 #pragma unroll
         for (int kc = 0; kc < 16; kc++) xbuf[kc * 256 + t] = z[R16(kc)];          // Z_q[k] at k (natural order)
@@ -1373,9 +1322,9 @@ __global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_
 #pragma unroll
             for (int e = 0; e < 4; e++) wt[e] = tw16k[(fbq + 256u * wv + 64u * e + lane) & 8191u];
         }
-        SS_FPROF_MARK(8);
+        mark(8);
         __syncthreads();
-        SS_FPROF_MARK(9);
+        mark(9);
         asm volatile("" : "+v"(nx));        // the prefetched hop is claimed in front of the epilogue's stores
 
         // ---- epilogue, all eight waves (both spectra are published).  Iteration `it` covers 2048 retained bins, wave wv the 256
@@ -1456,13 +1405,11 @@ __global__ __launch_bounds__(512, 4) void k_fft16k_run(FftBatchParams p, uint32_
             for (int j = 0; j < 15; j++) raw[j] = raw[j + 1];
             raw[15] = nx;
         }
-        SS_FPROF_MARK(10);
+        mark(10);
         __syncthreads();                    // epilogue reads are done before the next window's pass-1 writes
-        SS_FPROF_MARK(11);
+        mark(11);
     }
-    SS_FPROF_END;
-#undef X1W
-#undef X2W
+    mark.end();
 }
 
 // ============================================================================

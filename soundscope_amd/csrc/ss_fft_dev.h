@@ -140,6 +140,34 @@ __device__ __forceinline__ void fft16(v2f (&a)[16])
     radix4(a[12], a[13], a[14], a[15]);
 }
 
+// ---- pass 1 of a 4096-point transform on radix-16 passes: the twiddles W^(t ka), W = W_4096, of thread t ----------------------
+// TWN of the fifteen are resident in tw[ka]: 6 = {1, 2, 3, 4, 8, 12}, 9 adds {5, 6, 7}, 12 adds {9, 10, 11}.  The others are
+// applied factored, W^(t ka) = W^(t (ka & 3)) * W^(t (ka & 12)): one more complex multiply per window, in THAT order (the order
+// decides the bits).  (The product of the two factors formed off the data's dependent chain, then one multiply of the data:
+// measured in round 6 in k_fft4096_ms1, six interleaved repetitions: 2.996 vs 2.995 ms — nothing.)
+template <int TWN>
+constexpr bool r16_resident(int ka)
+{
+    static_assert(TWN == 6 || TWN == 9 || TWN == 12, "resident pass-1 twiddles: 6, 9 or 12");
+    return (ka & 3) == 0 || (ka & 12) == 0 || (TWN >= 9 && (ka >> 2) == 1) || (TWN >= 12 && (ka >> 2) == 2);
+}
+template <int TWN>
+__device__ __forceinline__ void r16_load_tw1(v2f (&tw)[16], const v2f *w4096, int t)
+{
+#pragma unroll
+    for (int ka = 1; ka < 16; ka++) if (r16_resident<TWN>(ka)) tw[ka] = w4096[ka * t];
+}
+// v W^(t ka), ka = 1..15.  (With six resident every resident one is a factor, which the skips below reach with one multiply
+// too: taken that way because it is the text that leaves every kernel's instructions where they were.)
+template <int TWN>
+__device__ __forceinline__ v2f r16_pass1_tw(int ka, v2f v, const v2f (&tw)[16])
+{
+    if (TWN > 6 && r16_resident<TWN>(ka)) return pk_cmul(v, tw[ka]);
+    if (ka & 3) v = pk_cmul(v, tw[ka & 3]);
+    if (ka & 12) v = pk_cmul(v, tw[ka & 12]);
+    return v;
+}
+
 // dB of a squared magnitude q with dB = 10*log10(2)*log2(q) + off; q == 0 -> -150
 // (scale_to_dbfs, analyzer.rs:11-27: val == 0.0 => -150.0)
 __device__ __forceinline__ float db_from_sq(float q, float off)
@@ -201,20 +229,13 @@ __device__ __forceinline__ void fft16k_transform(const FftBatchParams &p, Src &s
     }
     const int tb = t & 15, hi = t >> 4;
     // ---- the 4096-point transform of y_q (same passes and LDS layouts as k_fft4096_ms)
-    // pass-1 twiddles W^(t ka) from six gathered ones: W^(t ka) = W^(t (ka & 3)) * W^(t (ka & 12))
-    // (scattered 8-byte gathers are the expensive part of this one-window-per-workgroup kernel)
+    // pass-1 twiddles from six gathered ones (scattered 8-byte gathers are the expensive part of this one-window-per-workgroup kernel)
     v2f twg[16];
-    twg[1] = tw4k[t]; twg[2] = tw4k[2 * t]; twg[3] = tw4k[3 * t];
-    twg[4] = tw4k[4 * t]; twg[8] = tw4k[8 * t]; twg[12] = tw4k[12 * t];
+    r16_load_tw1<6>(twg, tw4k, t);
     fft16(z);
     xbuf[X1W(0, tb, hi)] = z[R16(0)];
 #pragma unroll
-    for (int ka = 1; ka < 16; ka++) {
-        v2f v = z[R16(ka)];
-        if (ka & 3) v = pk_cmul(v, twg[ka & 3]);
-        if (ka & 12) v = pk_cmul(v, twg[ka & 12]);
-        xbuf[X1W(ka, tb, hi)] = v;
-    }
+    for (int ka = 1; ka < 16; ka++) xbuf[X1W(ka, tb, hi)] = r16_pass1_tw<6>(ka, z[R16(ka)], twg);
     src.loaded();
     __syncthreads();
 #pragma unroll

@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
-"""Are the kernels of two AMDGPU assembly files the same machine code?  tools/isa_same.py <old.s> <new.s>
+"""Are the kernels of two AMDGPU assembly files the same machine code?  tools/isa_same.py [--allow-renamed] <old.s> <new.s>
 
 The check of a refactor that must not move an instruction.  Make both files from one translation unit with the Makefile's flags
 plus `--offload-device-only -S` (device-only compile, no GPU needed), e.g. in soundscope_amd/csrc:
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize --offload-device-only -S -o new.s ss_fft.hip
 A kernel is the text between its symbol label and the next `.Lfunc_end`; comments and assembler directives are dropped and the
 basic-block labels are renumbered in order of appearance, so that only instructions and operands are compared.
-Prints one line per kernel (name, instructions old, new, SAME / DIFF; MISSING for a kernel only one file has or whose body
-cannot be found) and exits non-zero unless every kernel is SAME."""
+Prints one line per kernel (name, instructions old, new, verdict) and a summary line that counts the verdicts:
+  SAME     the two instruction lists are equal;
+  RENAMED  they are equal once every register operand (vN, sN, aN, v[a:b], s[a:b], a[a:b]) is replaced by its class and width:
+           the same instructions in the same order, the register allocator chose other numbers;
+  DIFF     anything else;
+  MISSING  a kernel only one file has, or whose body cannot be found.
+Exits non-zero unless every kernel is SAME — or, with --allow-renamed, SAME or RENAMED."""
 import re
 import sys
 
@@ -41,24 +46,39 @@ def kernels(path):
     return out
 
 
+REG = re.compile(r"\b([vsa])(?:(\d+)|\[(\d+):(\d+)\])(?![\w\[])")
+
+
+def classes(ins):
+    """the instruction list with every register operand replaced by its class and width: v[4:5] -> v:2, s7 -> s:1"""
+    return [REG.sub(lambda m: "%s:%d" % (m.group(1), 1 if m.group(2) else int(m.group(4)) - int(m.group(3)) + 1), i) for i in ins]
+
+
+def verdict(old, new):
+    if old is None or new is None:
+        return "MISSING"
+    if old == new:
+        return "SAME"
+    return "RENAMED" if classes(old) == classes(new) else "DIFF"
+
+
 def count(ks, name):
     return sum(1 for i in ks[name] if not i.endswith(":")) if ks.get(name) is not None else "-"
 
 
 def main():
-    if len(sys.argv) != 3:
+    args = [a for a in sys.argv[1:] if a != "--allow-renamed"]
+    if len(args) != 2:
         sys.exit(__doc__)
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    bad = 0
+    passing = ("SAME", "RENAMED") if len(args) < len(sys.argv) - 1 else ("SAME",)
+    old, new = kernels(args[0]), kernels(args[1])
+    tally = dict.fromkeys(("SAME", "RENAMED", "DIFF", "MISSING"), 0)
     for name in sorted(set(old) | set(new)):
-        if old.get(name) is None or new.get(name) is None:
-            verdict = "MISSING"
-        else:
-            verdict = "SAME" if old[name] == new[name] else "DIFF"
-        bad += verdict != "SAME"
-        print(f"{name}  {count(old, name)}  {count(new, name)}  {verdict}")
-    print(f"{len(set(old) | set(new))} kernels, {bad} not the same")
-    sys.exit(1 if bad else 0)
+        v = verdict(old.get(name), new.get(name))
+        tally[v] += 1
+        print(f"{name}  {count(old, name)}  {count(new, name)}  {v}")
+    print(f"{len(set(old) | set(new))} kernels: " + ", ".join(f"{n} {v}" for v, n in tally.items()))
+    sys.exit(0 if all(tally[v] == 0 for v in tally if v not in passing) else 1)
 
 
 if __name__ == "__main__":
