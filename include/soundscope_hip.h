@@ -418,6 +418,65 @@ typedef struct ss_loudness_extremes {
     uint32_t max_shortterm_at;
 } ss_loudness_extremes;         /* 24 bytes */
 int ss_batch_loudness_extremes(ss_batch *b, ss_loudness_extremes *out, uint32_t cap_streams);
+/* Loudness regions: the gated loudness of time ranges of the streams of a batch, and of groups of such ranges (programme items in
+ * a transmission log, tracks of a mix, scenes of a reel; a group of whole streams is an album, the loudness_global_multiple /
+ * loudness_range_multiple case).  Not in the reference.  After ss_batch_run, on what the pass left on the device: nothing inside
+ * the pass changes.  With S = s100 and P the stream's sub-block energies (ss_batch_download_subblocks), region (s, a, n):
+ *   - owns the gating blocks of stream s that end with sub-block j, a + 3 <= j < a + n (all four sub-blocks inside the region),
+ *     and the short-term blocks that end with j = a + 29 + 10 m < a + n: the phase is anchored at the region's start, as a meter
+ *     started there would have it, not at the stream's start.  n_gating_blocks = max(n - 3, 0), n_st_blocks = (n - 30) / 10 + 1
+ *     for n >= 30, else 0;
+ *   - every energy is the weighted sum of the 4 (30) sub-block energies ending with j, each channel added oldest first, divided
+ *     by 4 S (30 S): for a = 0 the same expressions and additions as the pass itself, hence the same bits;
+ *   - the K-weighting filter is the stream's continuous one: a region is NOT a fresh meter fed the range, it is the stream's own
+ *     blocks that lie inside the range (a fresh meter's filter would start from rest at a: its first blocks differ by what the
+ *     filter still remembers of the frames in front of a);
+ *   - non-finite input follows the stream: a block that ends behind the stream's first sub-block holding a non-finite sample of a
+ *     weighted channel has a NaN energy; it is counted in n_gating_blocks / n_st_blocks and lands in no bin;
+ *   - blocks at or above the absolute gate (-70 LUFS) are binned like the stream's own (1000 bins of 0.1 LU); integrated_lufs and
+ *     loudness_range are the relative gate at -10 LU and the EBU 3342 percentile walk on the region's own histogram pair: -inf and
+ *     0 where nothing is counted;
+ *   - max_momentary runs over a + 3 <= j < a + n; max_shortterm over EVERY j with a + 29 <= j < a + n (every sub-block, as the
+ *     loudness series has it, not only the histogram's phase).  Values are 10 log10(E) - 0.691 (E <= 0: -inf); NaN is skipped, an
+ *     infinity counts, ties go to the lowest j; *_at is the ABSOLUTE sub-block index in the stream; no such value: -inf at
+ *     0xFFFFFFFF.  At rates without short-term blocks (thirty sub-blocks exceed the crate's 3 s ring) n_st_blocks = 0 and
+ *     max_shortterm is -inf at 0xFFFFFFFF.
+ * Groups: a group's histogram pair is the bin-wise u64 sum of the pairs of the regions that name it, its counts the sums of their
+ * counts, its results the same evaluation of that sum.  Regions may come from any streams, overlap and repeat: each one counts.
+ * A group without regions reads -inf, 0, 0, 0.  Per-region histograms are not kept: give a region a group of its own to read its.
+ * Only integer atomics touch shared histograms and there are no floating-point atomics: two calls on the same pass agree byte for
+ * byte.
+ * ss_batch_loudness_regions copies `regions` before it returns and queues its work on the batch's stream like
+ * ss_batch_spectrum_stats: nothing is copied back or waited for.  A later call replaces the list and every result.  The downloads
+ * and ss_batch_group_histograms (1000 block bins then 1000 short-term bins, as ss_batch_histograms) wait for the stream.
+ * Device memory (16 bytes + 48 bytes per region, 16 KB + 32 bytes per group) is allocated at the first call and grows with a longer
+ * list: a batch that never calls this allocates and launches exactly what it did before.
+ * Status codes, all checked before anything is queued: a batch without SS_BATCH_LUFS, and a download before the first call,
+ * SS_ERR_INVALID_MODE; stream >= n_streams, first_subblock + n_subblocks (in 64 bits) beyond the stream's own n_subblocks
+ * (ss_batch_stream_shape for ragged batches), a group >= n_groups other than SS_REGION_NO_GROUP, a group index >= n_groups in
+ * ss_batch_group_histograms, regions == NULL with n_regions > 0: SS_ERR_INVALID_ARG; a `cap` too small: SS_ERR_CAPACITY.
+ * n_regions == 0 and n_subblocks == 0 are valid. */
+#define SS_REGION_NO_GROUP 0xFFFFFFFFu
+typedef struct ss_loudness_region {
+    uint32_t stream;
+    uint32_t first_subblock;    /* a: index of the region's first 100 ms sub-block in its stream */
+    uint32_t n_subblocks;       /* n: may be 0 */
+    uint32_t group;             /* 0 .. n_groups - 1, or SS_REGION_NO_GROUP */
+} ss_loudness_region;           /* 16 bytes */
+typedef struct ss_region_result {
+    double integrated_lufs, loudness_range;
+    double max_momentary, max_shortterm;            /* LUFS; -inf if none */
+    uint32_t max_momentary_at, max_shortterm_at;    /* ABSOLUTE sub-block index in the stream; 0xFFFFFFFF if none */
+    uint32_t n_gating_blocks, n_st_blocks;
+} ss_region_result;             /* 48 bytes */
+typedef struct ss_group_result {
+    double integrated_lufs, loudness_range;
+    uint64_t n_gating_blocks, n_st_blocks;
+} ss_group_result;              /* 32 bytes */
+int ss_batch_loudness_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups);
+int ss_batch_download_region_results(ss_batch *b, ss_region_result *out, uint32_t cap_regions);
+int ss_batch_download_group_results(ss_batch *b, ss_group_result *out, uint32_t cap_groups);
+int ss_batch_group_histograms(ss_batch *b, uint32_t group, uint64_t *out2000);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

@@ -51,6 +51,7 @@ SYMBOLS = [
     "ss_meter_bank_spectrum_track_enable", "ss_meter_bank_spectrum_track", "ss_meter_bank_spectrum_track_reset",
     "ss_meter_bank_spectrum_tracked", "ss_meter_bank_spectrum_tracked_columns",
     "ss_batch_spectrum_stats", "ss_batch_download_spectrum_stats", "ss_batch_corpus_spectrum", "ss_batch_spectrum_stats_plan",
+    "ss_batch_loudness_regions", "ss_batch_download_region_results", "ss_batch_download_group_results", "ss_batch_group_histograms",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -62,6 +63,7 @@ SS_ERR_CAPACITY, SS_ERR_UNSUPPORTED, SS_ERR_INVALID_ARG, SS_ERR_DEVICE = 20, 21,
 SS_BATCH_FFT, SS_BATCH_LUFS, SS_BATCH_TRUE_PEAK, SS_BATCH_WAVEFORM, SS_BATCH_ALL = 1, 2, 4, 8, 15
 SS_BATCH_FFT_COLUMNS = 16
 SS_BATCH_LOUDNESS_SERIES = 32
+SS_REGION_NO_GROUP = 0xFFFFFFFF
 SS_PCM_U8, SS_PCM_S16, SS_PCM_S24, SS_PCM_S32, SS_PCM_F32, SS_PCM_F64 = 1, 2, 3, 4, 5, 6
 SS_GAIN_FIXED, SS_GAIN_REFERENCE = 0, 1
 SS_COMM_RCCL, SS_COMM_HOST_TCP = 0, 1
@@ -111,6 +113,22 @@ class BatchGeometry(C.Structure):
 class LoudnessExtremes(C.Structure):
     _fields_ = [("max_momentary", C.c_double), ("max_shortterm", C.c_double),
                 ("max_momentary_at", C.c_uint32), ("max_shortterm_at", C.c_uint32)]
+
+
+class LoudnessRegion(C.Structure):
+    _fields_ = [("stream", C.c_uint32), ("first_subblock", C.c_uint32), ("n_subblocks", C.c_uint32), ("group", C.c_uint32)]
+
+
+class RegionResult(C.Structure):
+    _fields_ = [("integrated_lufs", C.c_double), ("loudness_range", C.c_double),
+                ("max_momentary", C.c_double), ("max_shortterm", C.c_double),
+                ("max_momentary_at", C.c_uint32), ("max_shortterm_at", C.c_uint32),
+                ("n_gating_blocks", C.c_uint32), ("n_st_blocks", C.c_uint32)]
+
+
+class GroupResult(C.Structure):
+    _fields_ = [("integrated_lufs", C.c_double), ("loudness_range", C.c_double),
+                ("n_gating_blocks", C.c_uint64), ("n_st_blocks", C.c_uint64)]
 
 
 class MeterReading(C.Structure):
@@ -275,6 +293,10 @@ def _bind(lib):
         "ss_meter_bank_spectrum_tracked": (C.c_int, [vp, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_meter_bank_spectrum_tracked_columns": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_float, f32p, f32p, C.c_size_t,
                                                              C.POINTER(C.c_uint32), C.c_uint32]),
+        "ss_batch_loudness_regions": (C.c_int, [vp, C.POINTER(LoudnessRegion), C.c_uint32, C.c_uint32]),
+        "ss_batch_download_region_results": (C.c_int, [vp, C.POINTER(RegionResult), C.c_uint32]),
+        "ss_batch_download_group_results": (C.c_int, [vp, C.POINTER(GroupResult), C.c_uint32]),
+        "ss_batch_group_histograms": (C.c_int, [vp, C.c_uint32, u64p]),
         "ss_batch_spectrum_stats": (C.c_int, [vp]),
         "ss_batch_download_spectrum_stats": (C.c_int, [vp, C.c_uint32, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_batch_corpus_spectrum": (C.c_int, [vp, f32p, f32p, C.c_size_t, u64p, C.c_uint32]),

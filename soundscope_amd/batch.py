@@ -259,6 +259,41 @@ class Batch:
         _check(L.lib().ss_batch_loudness_extremes(self._h, arr, n))
         return list(arr)
 
+    # -- loudness regions: gated loudness of time ranges of the streams, and of groups of them
+    def loudness_regions(self, regions, n_groups=0):
+        """Queue the gate of `regions` behind the pass: rows (stream, first_subblock, n_subblocks[, group]) in 100 ms sub-blocks,
+        group 0 .. n_groups - 1 or L.SS_REGION_NO_GROUP (the default of a three-column row); a u32 array [n][4] is passed as it is.
+        Replaces the previous list."""
+        rows = regions
+        if not (isinstance(rows, np.ndarray) and rows.dtype == np.uint32 and rows.ndim == 2 and rows.shape[1] == 4):   # (else: as it is)
+            a = np.asarray(regions, dtype=np.int64).reshape(-1, 4 if len(regions) and len(regions[0]) == 4 else 3)
+            if ((a < 0) | (a > 0xFFFFFFFF)).any():
+                raise ValueError("region fields are u32")
+            rows = np.full((a.shape[0], 4), L.SS_REGION_NO_GROUP, np.uint32)
+            rows[:, :a.shape[1]] = a
+        rows = np.ascontiguousarray(rows)
+        _check(L.lib().ss_batch_loudness_regions(self._h, rows.ctypes.data_as(C.POINTER(L.LoudnessRegion)), rows.shape[0], int(n_groups)))
+        self._n_regions, self._n_groups = rows.shape[0], int(n_groups)      # (a refused call leaves the previous list)
+
+    def region_results(self):
+        """Per region of the last list: L.RegionResult (integrated_lufs, loudness_range, max_momentary, max_shortterm and their
+        absolute sub-block indices, n_gating_blocks, n_st_blocks)."""
+        arr = (L.RegionResult * self._n_regions)()
+        _check(L.lib().ss_batch_download_region_results(self._h, arr, self._n_regions))
+        return arr
+
+    def group_results(self):
+        """Per group of the last list: L.GroupResult (integrated_lufs, loudness_range, n_gating_blocks, n_st_blocks)."""
+        arr = (L.GroupResult * self._n_groups)()
+        _check(L.lib().ss_batch_download_group_results(self._h, arr, self._n_groups))
+        return arr
+
+    def group_histograms(self, g):
+        """(block, short-term) histograms of group g: the bin-wise sums of its regions' pairs, 1000 u64 bins each."""
+        out = np.empty(2000, np.uint64)
+        _check(L.lib().ss_batch_group_histograms(self._h, int(g), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[:1000].copy(), out[1000:].copy()
+
     def histograms(self):
         out = np.empty(2000, np.uint64)
         _check(L.lib().ss_batch_histograms(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))

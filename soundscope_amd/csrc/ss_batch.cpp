@@ -98,6 +98,18 @@ struct SpecStats {
     DevBuf<unsigned long long> corpus_counts;   // [fft_channels]
 };
 
+// loudness regions (ss_batch_loudness_regions): all of it allocated at the batch's first call and grown by a longer list, so a
+// batch that never asks holds none of it
+struct Regions {
+    bool done = false;                          // a list has been queued: there is something to download
+    uint32_t n_regions = 0, n_groups = 0;       // of the last call
+    HostStage stage;                            // the caller's list on its way to the device
+    DevBuf<ssk::LoudnessRegion> list;
+    DevBuf<ssk::RegionResult> results;
+    DevBuf<ssk::GroupResult> group_results;
+    DevBuf<unsigned long long> group_hist;      // [group][2][1000]
+};
+
 }  // namespace
 
 struct ss_batch {
@@ -139,6 +151,7 @@ struct ss_batch {
     uint32_t render_cols = 0, render_wave_cols = 0;
     Columns cols;
     SpecStats stats;
+    Regions regions;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
     int tp_arith = SS_TP_ARITH_F32;   // SS_TP_ARITH_*: the reference's width unless the caller opts into the f16 split
@@ -1236,6 +1249,83 @@ int ss_batch_corpus_spectrum(ss_batch *b, float *mean_db, float *max_db, size_t 
         HIPCHK(hipMemcpyAsync(windows_counted, st.corpus_counts.p, L.fft_channels * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return SS_OK;
+}
+
+// ---- loudness regions: gated loudness of time ranges and groups ----------------------------------------------------
+static_assert(sizeof(ss_loudness_region) == 16 && sizeof(ssk::LoudnessRegion) == 16 && offsetof(ssk::LoudnessRegion, group) == offsetof(ss_loudness_region, group),
+              "region layout");
+static_assert(sizeof(ss_region_result) == 48 && sizeof(ssk::RegionResult) == 48 && offsetof(ssk::RegionResult, at_m) == offsetof(ss_region_result, max_momentary_at) &&
+              offsetof(ssk::RegionResult, n_blocks) == offsetof(ss_region_result, n_gating_blocks), "region result layout");
+static_assert(sizeof(ss_group_result) == 32 && sizeof(ssk::GroupResult) == 32 && offsetof(ssk::GroupResult, n_blocks) == offsetof(ss_group_result, n_gating_blocks),
+              "group result layout");
+static_assert(SS_REGION_NO_GROUP == ssk::kRegionNoGroup, "no-group mark");
+
+int ss_batch_loudness_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (!(b->cfg.flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_MODE;
+    if (!regions && n_regions) return SS_ERR_INVALID_ARG;
+    // ---- every check before anything is queued: a refused call leaves the previous list and its results as they were
+    uint32_t longest = 0;
+    for (uint32_t i = 0; i < n_regions; i++) {
+        const ss_loudness_region &r = regions[i];
+        if (r.stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+        const uint64_t n_sub = b->ragged.on ? b->ragged.sub_h[r.stream] : b->lay.n_subblocks;
+        if ((uint64_t)r.first_subblock + r.n_subblocks > n_sub) return SS_ERR_INVALID_ARG;
+        if (r.group != SS_REGION_NO_GROUP && r.group >= n_groups) return SS_ERR_INVALID_ARG;
+        if (r.n_subblocks > longest) longest = r.n_subblocks;
+    }
+    Regions &rg = b->regions;
+    const size_t bytes = (size_t)n_regions * sizeof(ss_loudness_region);
+    // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
+    HIPCHK(rg.list.ensure(n_regions)); HIPCHK(rg.results.ensure(n_regions));
+    HIPCHK(rg.group_results.ensure(n_groups)); HIPCHK(rg.group_hist.ensure((size_t)n_groups * 2 * sst::kHistBins));
+    if (n_regions) {
+        HIPCHK(rg.stage.take(bytes));
+        std::memcpy(rg.stage.buf.p, regions, bytes);
+        HIPCHK(hipMemcpyAsync(rg.list.p, rg.stage.buf.p, bytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(rg.stage.sent(b->stream));
+    }
+    ssk::RegionGateParams p{};
+    p.k = b->td->dev.p; p.subblocks = b->sub.p; p.sub_cap = b->sub_cap(); p.sub_stride = (uint64_t)p.sub_cap * b->cfg.channels;
+    p.hist_energies = b->hist_energies; p.hist_bounds = b->hist_bounds; p.weights = b->weights.p; p.state = b->state.p;
+    p.channels = b->cfg.channels;
+    p.regions = rg.list.p; p.results = rg.results.p; p.n_regions = n_regions; p.n_groups = n_groups; p.longest = longest;
+    p.group_results = rg.group_results.p; p.group_hist = rg.group_hist.p;
+    HIPCHK(ssk::launch_region_gate(p, b->stream));
+    rg.n_regions = n_regions; rg.n_groups = n_groups; rg.done = true;
+    return SS_OK;
+}
+
+int ss_batch_download_region_results(ss_batch *b, ss_region_result *out, uint32_t cap_regions)
+{
+    SS_ON_DEVICE(b);
+    if (!b || (!out && b->regions.n_regions)) return SS_ERR_INVALID_ARG;
+    if (!(b->cfg.flags & SS_BATCH_LUFS) || !b->regions.done) return SS_ERR_INVALID_MODE;
+    if (cap_regions < b->regions.n_regions) return SS_ERR_CAPACITY;
+    if (!b->regions.n_regions) return ss_batch_sync(b);
+    return fetch(b, out, reinterpret_cast<const ss_region_result *>(b->regions.results.p), b->regions.n_regions);
+}
+
+int ss_batch_download_group_results(ss_batch *b, ss_group_result *out, uint32_t cap_groups)
+{
+    SS_ON_DEVICE(b);
+    if (!b || (!out && b->regions.n_groups)) return SS_ERR_INVALID_ARG;
+    if (!(b->cfg.flags & SS_BATCH_LUFS) || !b->regions.done) return SS_ERR_INVALID_MODE;
+    if (cap_groups < b->regions.n_groups) return SS_ERR_CAPACITY;
+    if (!b->regions.n_groups) return ss_batch_sync(b);
+    return fetch(b, out, reinterpret_cast<const ss_group_result *>(b->regions.group_results.p), b->regions.n_groups);
+}
+
+int ss_batch_group_histograms(ss_batch *b, uint32_t group, uint64_t *out2000)
+{
+    SS_ON_DEVICE(b);
+    if (!b || !out2000) return SS_ERR_INVALID_ARG;
+    if (!(b->cfg.flags & SS_BATCH_LUFS) || !b->regions.done) return SS_ERR_INVALID_MODE;
+    if (group >= b->regions.n_groups) return SS_ERR_INVALID_ARG;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the histograms are copied out as they are");
+    return fetch(b, out2000, reinterpret_cast<const uint64_t *>(b->regions.group_hist.p) + (size_t)group * 2 * sst::kHistBins, 2 * sst::kHistBins);
 }
 
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max)

@@ -284,6 +284,31 @@ __attribute__((visibility("hidden"))) hipError_t launch_finalize_stream(const Fi
 struct LoudnessExtremes { double max_m, max_s; uint32_t at_m, at_s; };
 hipError_t launch_loudness_series(const FinalizeParams &p, double *series, uint64_t series_stride, LoudnessExtremes *extremes,
                                   hipStream_t s);
+// Loudness regions (ss_batch_loudness_regions), behind a pass on the same stream: the gated loudness of runs of one stream's
+// sub-blocks, optionally pooled into groups.  The records are laid out as ss_loudness_region / ss_region_result /
+// ss_group_result (include/soundscope_hip.h).
+constexpr uint32_t kRegionNoGroup = 0xFFFFFFFFu;
+struct LoudnessRegion { uint32_t stream, first_subblock, n_subblocks, group; };
+struct RegionResult { double integrated, lra, max_m, max_s; uint32_t at_m, at_s, n_blocks, n_st_blocks; };
+struct GroupResult { double integrated, lra; unsigned long long n_blocks, n_st_blocks; };
+struct RegionGateParams {
+    const TdConst *k;
+    const double *subblocks; uint64_t sub_stride; uint32_t sub_cap;      // batches: slot == sub-block index
+    const double *hist_energies, *hist_bounds, *weights;
+    const TdState *state;            // [stream]: bad_key
+    uint32_t channels;
+    const LoudnessRegion *regions;   // [n_regions], every one inside its stream (the caller has checked)
+    RegionResult *results;           // [n_regions]
+    uint32_t n_regions, n_groups;
+    uint32_t longest;                // sub-blocks of the longest region: region_gate_threads
+    GroupResult *group_results;      // [n_groups]; the launcher clears them and the histograms, the regions add their counts
+    unsigned long long *group_hist;  // [n_groups][2][1000] (block, short-term)
+};
+// threads of a region's workgroup: launch_finalize's rule on the longest region of the list
+constexpr uint32_t kRegionLongSub = 2048;
+inline uint32_t region_gate_threads(uint32_t longest) { return longest > kRegionLongSub ? 1024u : 256u; }
+// clears the groups, gates every region (k_region_gate) and evaluates every group (k_group_eval): three steps queued on s
+hipError_t launch_region_gate(const RegionGateParams &p, hipStream_t s);
 // gate + LRA on explicit histograms (corpus gate after the all-reduce; handle getters)
 // `peaks` (optional): a handle's readings in one launch (ReadingsExtra above)
 hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, const double *bounds,

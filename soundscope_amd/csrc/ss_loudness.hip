@@ -502,6 +502,113 @@ hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, co
     return hipGetLastError();
 }
 
+// ============================================================================
+//  Loudness regions (ss_batch_loudness_regions): the gate of runs of one stream's sub-blocks, pooled into groups
+// ============================================================================
+// One workgroup per region (s, a, n): the stream's own gating blocks that end with j in [a + 3, a + n) and its short-term blocks
+// that end with j = a + 29 + 10 m < a + n (the phase starts with the region), every energy the very block_energy form and division
+// k_finalize and k_loudness_series use (a = 0: the same bits), NaN behind the stream's first bad sub-block.  One loop over j feeds
+// the gating bin and the momentary maximum and, from a + 29 on, the short-term maximum (every j, as the series has it) and every
+// tenth j the short-term bin.  The LDS pair starts from zero; behind the loop its non-zero bins and the block counts (every block
+// counts, binned or not: closed forms of n) go to the region's group with u64 atomics — integers only, so the sums do not depend
+// on the order — and wave 0 evaluates the pair into the region's result.  Indices are 32-bit: slot == sub-block index < 2^31.
+__global__ __launch_bounds__(1024) void k_region_gate(RegionGateParams p)
+{
+    __shared__ unsigned long long hb[kHistBins];
+    __shared__ unsigned long long hs[kHistBins];
+    __shared__ uint32_t bad_from_s;
+    __shared__ double red_v[2][16];
+    __shared__ uint32_t red_at[2][16];
+    const LoudnessRegion rg = p.regions[blockIdx.x];
+    const int tid = threadIdx.x, nthr = (int)blockDim.x;
+    for (int i = tid; i < kHistBins; i += nthr) { hb[i] = 0ull; hs[i] = 0ull; }
+    if (tid < 64) {
+        const uint32_t bf = first_bad_subblock(p.state + rg.stream, p.channels, p.weights, (uint32_t)tid);
+        if (tid == 0) bad_from_s = bf;
+    }
+    const double *bd = p.hist_bounds;
+    const double bd0 = bd[0];
+    const uint32_t C = p.channels, cap = p.sub_cap;
+    const double S = (double)p.k->s100;
+    const bool st_on = !p.k->st_off;
+    const double *P = p.subblocks + (size_t)rg.stream * p.sub_stride;
+    const uint32_t a = rg.first_subblock, n = rg.n_subblocks, end = a + n;
+    __syncthreads();
+    const uint32_t bad_from = bad_from_s;
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    double bm = -INFINITY, bs = -INFINITY;
+    uint32_t am = kNone, as = kNone;
+    for (uint32_t j = a + 3u + (uint32_t)tid; j < end; j += (uint32_t)nthr) {
+        double em = block_energy<4, false, true>(P, j, cap, C, p.weights) / (4.0 * S);
+        if (j > bad_from) em = __builtin_nan("");
+        if (em >= bd0) atomicAdd(&hb[hist_index(bd, em)], 1ull);
+        max_at(bm, am, energy_to_lufs(em), j);
+        if (st_on && j >= a + 29u) {
+            double es = block_energy<30, false, true>(P, j, cap, C, p.weights) / (30.0 * S);
+            if (j > bad_from) es = __builtin_nan("");
+            max_at(bs, as, energy_to_lufs(es), j);
+            if ((j - a - 29u) % 10u == 0u && es >= bd0) atomicAdd(&hs[hist_index(bd, es)], 1ull);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        max_at(bm, am, __shfl_xor(bm, o, 64), (uint32_t)__shfl_xor((int)am, o, 64));
+        max_at(bs, as, __shfl_xor(bs, o, 64), (uint32_t)__shfl_xor((int)as, o, 64));
+    }
+    const int wave = tid >> 6;
+    if ((tid & 63) == 0) { red_v[0][wave] = bm; red_at[0][wave] = am; red_v[1][wave] = bs; red_at[1][wave] = as; }
+    __syncthreads();                                            // (the histograms in LDS are complete as well)
+    RegionResult *out = p.results + blockIdx.x;
+    const uint32_t nb = n > 3u ? n - 3u : 0u, ns = st_on && n >= 30u ? (n - 30u) / 10u + 1u : 0u;
+    GroupResult *grp = rg.group != kRegionNoGroup ? p.group_results + rg.group : nullptr;
+    if (tid == 0) {
+        for (int w = 1; w < (nthr >> 6); w++) { max_at(bm, am, red_v[0][w], red_at[0][w]); max_at(bs, as, red_v[1][w], red_at[1][w]); }
+        out->max_m = bm; out->max_s = bs; out->at_m = am; out->at_s = as;
+        out->n_blocks = nb; out->n_st_blocks = ns;
+        if (grp) {
+            if (nb) atomicAdd(&grp->n_blocks, (unsigned long long)nb);
+            if (ns) atomicAdd(&grp->n_st_blocks, (unsigned long long)ns);
+        }
+    }
+    if (grp) {
+        unsigned long long *gh = p.group_hist + (size_t)rg.group * 2 * kHistBins;
+        for (int i = tid; i < kHistBins; i += nthr) {
+            const unsigned long long db = hb[i], ds = hs[i];
+            if (db) atomicAdd(&gh[i], db);
+            if (ds) atomicAdd(&gh[kHistBins + i], ds);
+        }
+    }
+    if (tid < 64) eval_hist(hb, hs, p.hist_energies, bd, &out->integrated, &out->lra);
+}
+
+// One wave per group behind the regions, shaped like k_hist_eval: the group's summed pair and the two tables into LDS, eval_hist
+// into the group's result (its counts are already there).
+__global__ __launch_bounds__(64) void k_group_eval(RegionGateParams p)
+{
+    __shared__ unsigned long long hb[kHistBins];
+    __shared__ unsigned long long hs[kHistBins];
+    __shared__ double tab[kTabDoubles];
+    const unsigned long long *gh = p.group_hist + (size_t)blockIdx.x * 2 * kHistBins;
+    stage_tables(tab, p.hist_energies, p.hist_bounds, threadIdx.x, 64, [&](int i) { hb[i] = gh[i]; hs[i] = gh[kHistBins + i]; });
+    __syncthreads();
+    GroupResult *out = p.group_results + blockIdx.x;
+    eval_hist(hb, hs, tab, tab + kHistBins, &out->integrated, &out->lra);
+}
+
+hipError_t launch_region_gate(const RegionGateParams &p, hipStream_t s)
+{
+    // slot == sub-block index, a 32-bit number with room for a workgroup's stride behind it; one workgroup per region / group
+    if (p.sub_cap >> 31 || p.n_regions >> 31 || p.n_groups >> 31) return hipErrorInvalidValue;
+    if (p.n_groups) {
+        hipError_t e = hipMemsetAsync(p.group_results, 0, (size_t)p.n_groups * sizeof(GroupResult), s);
+        if (e == hipSuccess) e = hipMemsetAsync(p.group_hist, 0, (size_t)p.n_groups * 2 * kHistBins * sizeof(unsigned long long), s);
+        if (e != hipSuccess) return e;
+    }
+    if (p.n_regions) hipLaunchKernelGGL(k_region_gate, dim3(p.n_regions), dim3(region_gate_threads(p.longest)), 0, s, p);
+    if (p.n_groups) hipLaunchKernelGGL(k_group_eval, dim3(p.n_groups), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+
 // mean square over the last `frames` frames of the filtered ring, channel-weighted
 // (calc_gating_block on the ring "as is": loudness_shortterm / loudness_momentary).
 // Two stages with a fixed reduction shape (bit-reproducible): kRingBlocks partial sums, then one block — in ONE launch: the
