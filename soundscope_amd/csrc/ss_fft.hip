@@ -203,7 +203,9 @@ __device__ __forceinline__ void fft4096_epilogue(const v2f *xb, int t, uint32_t 
             const v2f so2 = {side_off, side_off};
             const v2f osa = v2f{op[i].x, op[i].y} + so2, osb = v2f{op[i].z, op[i].w} + so2;
             const float ops[4] = {osa.x, osa.y, osb.x, osb.y};
-            const float qmin = fminf(fminf(fminf(qm[0], qm[1]), fminf(qm[2], qm[3])), fminf(fminf(qs[0], qs[1]), fminf(qs[2], qs[3])));
+            // (eight values: a chain of three v_min3_f32 and one v_min_f32; left to the compiler the fminf tree was three v_min_f32 and two v_min3_f32)
+            auto min3 = [](float a, float b, float c) -> float { return __builtin_fminf(__builtin_fminf(a, b), c); };
+            const float qmin = fminf(min3(min3(min3(qm[0], qm[1], qm[2]), qm[3], qs[0]), qs[1], qs[2]), qs[3]);
             if (__builtin_expect(__ballot(qmin == 0.0f) == 0ull, 1)) {
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
@@ -816,9 +818,11 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
         // multiplies, which do not wait for them: the window is formed under the exponent the slide settled on
         const uint4 lq0 = *reinterpret_cast<const uint4 *>(&hoplev[0][0][0]), lq1 = *reinterpret_cast<const uint4 *>(&hoplev[0][2][0]);
         __builtin_amdgcn_sched_barrier(0);
+        // the window multiply of the frames j + 8 rides the first adds of pass 1 (radix4_windowed, below): only the products of
+        // the frames 0 .. 7 are formed here, z[j + 8] never is
         v2f z[16];
 #pragma unroll
-        for (int j = 0; j < 16; j++) z[j] = windowed(j);
+        for (int j = 0; j < 8; j++) z[j] = windowed(j);
         __builtin_amdgcn_sched_barrier(0);
         const uint32_t nPm = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(lq0.x, lq0.z), umax(lq1.x, lq1.z)));
         const uint32_t nPd = (uint32_t)__builtin_amdgcn_readfirstlane((int)umax(umax(lq0.y, lq0.w), umax(lq1.y, lq1.w)));
@@ -836,7 +840,7 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
                 // an onset or a decay inside the window: exact, the windowed ENERGY of either row (see block_exp_energy)
                 float xm = 0.0f, xd = 0.0f;
 #pragma unroll
-                for (int j = 0; j < 16; j++) { xm = fmaf(z[j].x, z[j].x, xm); xd = fmaf(z[j].y, z[j].y, xd); }
+                for (int j = 0; j < 16; j++) { const v2f v = j < 8 ? z[j] : windowed(j); xm = fmaf(v.x, v.x, xm); xd = fmaf(v.y, v.y, xd); }
                 const float wm = wave_fsum_lane63(xm), wd = wave_fsum_lane63(xd);
                 if (lane63) *reinterpret_cast<uint2 *>(xlev[wvid]) = make_uint2(__float_as_uint(wm), __float_as_uint(wd));
                 __syncthreads();
@@ -847,12 +851,19 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
                     T = T < -60 ? -60 : (T > 60 ? 60 : T);
                     const float sc = rescale(T);
 #pragma unroll
-                    for (int j = 0; j < 16; j++) z[j].y *= sc;
+                    for (int j = 0; j < 8; j++) z[j].y *= sc;      // (the frames j + 8 are windowed from the rescaled registers)
                 }
             }
         }
         const float soff = soffE;                            // this window's side row rides the transform as side * 2^E
-        r16_fft<true>(z);
+        SS_PRIO_LO();
+#pragma unroll
+        for (int r = 0; r < 4; r++) {                        // stage 1 of fft16 from (z[j], sd[j + 8] hann[j + 8])
+            if (r & 1) radix4_windowed<1>(z[r], z[r + 4], z[r + 8], z[r + 12], sd[r + 8], hwp[(r + 8) >> 1], sd[r + 12], hwp[(r + 12) >> 1]);
+            else radix4_windowed<0>(z[r], z[r + 4], z[r + 8], z[r + 12], sd[r + 8], hwp[(r + 8) >> 1], sd[r + 12], hwp[(r + 12) >> 1]);
+        }
+        fft16_stage2(z);
+        SS_PRIO_HI();
         xbuf[X1B(0, tb, hi)] = z[R16(0)];
 #pragma unroll
         for (int ka = 1; ka < 16; ka++) xbuf[X1B(ka, tb, hi)] = r16_pass1_tw<TWN>(ka, z[R16(ka)], tw1);

@@ -56,16 +56,6 @@ __device__ __forceinline__ v2f pk_cmul(v2f a, v2f w)
         : "=v"(r), "=&v"(m) : "v"(a), "v"(w));
     return r;
 }
-// a * w for a compile-time constant w held in a scalar register pair (the three constants of fft16: left to the "v"
-// constraint of pk_cmul the compiler copies them into vector registers in front of every use, ten v_mov_b64 per window)
-__device__ __forceinline__ v2f pk_cmul_k(v2f a, v2f w)
-{
-    v2f m, r;
-    asm("v_pk_mul_f32 %1, %2, %3 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-        "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_lo:[0,0,1] neg_hi:[0,0,0]"
-        : "=v"(r), "=&v"(m) : "v"(a), "s"(w));
-    return r;
-}
 // (a.x + a.y, a.y - a.x) = a - i a      [times R gives a * W16^2]
 __device__ __forceinline__ v2f pk_w2pre(v2f a) { return pk_sub_ib(a, a); }
 // (a.y - a.x, -(a.x + a.y))             [times R gives a * W16^6]
@@ -75,15 +65,6 @@ __device__ __forceinline__ v2f pk_w6pre(v2f a)
     asm("v_pk_add_f32 %0, %1, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[1,1]" : "=v"(r) : "v"(a));
     return r;
 }
-// a * (-i) = (a.y, -a.x)
-__device__ __forceinline__ v2f pk_mul_mi(v2f a)
-{
-    v2f r;
-    const v2f zero = {0.0f, 0.0f};
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,0] neg_hi:[0,1]" : "=v"(r) : "v"(zero), "v"(a));
-    return r;
-}
-
 // a * w.lo (S = 0) or a * w.hi (S = 1) in both halves: one real weight out of a register pair that holds two
 template <int S>
 __device__ __forceinline__ v2f pk_mul_bcast(v2f a, v2f w)
@@ -111,33 +92,106 @@ __device__ __forceinline__ void radix4(v2f &a0, v2f &a1, v2f &a2, v2f &a3)
     a3 = pk_add_ib(t1, t3);   // t1 + i t3
 }
 
-// Forward 16-point DFT in registers (81 packed instructions).  Input a[j] natural order; output
-// X[k] is left in a[R16(k)] with R16(k) = ((k & 3) << 2) | (k >> 2).
+// Forward 16-point DFT in registers: 72 packed instructions, 64 of the eight radix-4 butterflies and ONE per non-trivial twiddle.
+// Input a[j] natural order; output X[k] is left in a[R16(k)] with R16(k) = ((k & 3) << 2) | (k >> 2).
+// The twiddles W16^(r p) between the stages are applied less their real factor, which the fmas of the stage-2 butterfly carry:
+//   W^2 = R (1 - i), W^6 = -R (1 + i)     the pre-forms pk_w2pre / pk_w6pre, R = sqrt(1/2)
+//   W^4 = -i                              no instruction: the butterfly's first pair is b0 -+ i b2
+//   W^1 = C (1 - i T), W^3 = -i C (1 + i T), W^9 = -C (1 - i T)     C = cos(pi/8), T = tan(pi/8): one fma each, a (1 -+ i T);
+//                                         the two of a column share C, which goes onto their sum and their difference
+// Stage 2 of columns p = 1, 2, 3 is ONE asm statement each (ten or eleven dependent instructions: see pk_cmul on the s_nop
+// the compiler puts behind a statement whose result the next instruction reads), in place, with one temporary pair.
+// The constants stand in scalar register pairs ("s"): left to a "v" constraint the compiler copies them into vector registers in
+// front of every use.  The modifier sets, D = the result:
+#define SS_PK_SUB_IB(D, A, B) "v_pk_add_f32 " D ", " A ", " B " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,0] neg_hi:[0,1]\n\t"          /* A - i B */
+#define SS_PK_ADD_IB(D, A, B) "v_pk_add_f32 " D ", " A ", " B " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,0]\n\t"          /* A + i B */
+#define SS_PK_W6PRE(D, A) "v_pk_add_f32 " D ", " A ", " A " op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[1,1]\n\t"              /* -(1 + i) A */
+#define SS_PK_ADD(D, A, B) "v_pk_add_f32 " D ", " A ", " B "\n\t"
+#define SS_PK_SUB(D, A, B) "v_pk_add_f32 " D ", " A ", " B " neg_lo:[0,1] neg_hi:[0,1]\n\t"
+#define SS_PK_FMA(D, V, K, T) "v_pk_fma_f32 " D ", " V ", " K ", " T "\n\t"                                                            /* T + K V */
+#define SS_PK_FNMA(D, V, K, T) "v_pk_fma_f32 " D ", " V ", " K ", " T " neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"                             /* T - K V */
+#define SS_PK_FMA_SUB_IK(D, V, K, T) "v_pk_fma_f32 " D ", " V ", " K ", " T " op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[0,0,0] neg_hi:[1,0,0]\n\t"   /* T - i K V */
+#define SS_PK_FMA_ADD_IK(D, V, K, T) "v_pk_fma_f32 " D ", " V ", " K ", " T " op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[0,0,0]\n\t"   /* T + i K V */
 #define R16(k) ((((k) & 3) << 2) | ((k) >> 2))
+__device__ __forceinline__ void fft16_stage2(v2f (&a)[16])
+{
+    constexpr float C1 = 0.92387953251128674f, T1 = 0.41421356237309505f, R = 0.70710678118654752f;
+    const v2f kc = {C1, C1}, kt = {T1, T1}, kr = {R, R};
+    v2f tmp;
+    // stage 2: 4-point DFTs over r of a[r + 4p] W16^(r p); result s lands in a[s + 4p] = X[p + 4s]
+    radix4(a[0], a[1], a[2], a[3]);
+    // p = 1: (a4, C q5, R p6, -i C q7);  t0, t1 = a4 +- R p6;  a4, a6 = t0 +- C (q5 - i q7);  a5, a7 = t1 -+ i C (q5 + i q7)
+    asm(SS_PK_FMA_SUB_IK("%1", "%1", "%5", "%1")          // q5
+        SS_PK_FMA_ADD_IK("%3", "%3", "%5", "%3")          // q7
+        SS_PK_SUB_IB("%2", "%2", "%2")                    // p6
+        SS_PK_ADD_IB("%4", "%1", "%3")
+        SS_PK_SUB_IB("%3", "%1", "%3")
+        SS_PK_FNMA("%1", "%2", "%7", "%0")                // t1
+        SS_PK_FMA("%2", "%2", "%7", "%0")                 // t0
+        SS_PK_FMA("%0", "%3", "%6", "%2")
+        SS_PK_FNMA("%2", "%3", "%6", "%2")
+        SS_PK_FMA_ADD_IK("%3", "%4", "%6", "%1")
+        SS_PK_FMA_SUB_IK("%1", "%4", "%6", "%1")
+        : "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "=&v"(tmp) : "s"(kt), "s"(kc), "s"(kr));
+    // p = 2: (a8, R p9, -i a10, R p11);  t0, t1 = a8 -+ i a10;  a8, a10 = t0 +- R (p9 + p11);  a9, a11 = t1 -+ i R (p9 - p11)
+    asm(SS_PK_SUB_IB("%1", "%1", "%1")                    // p9
+        SS_PK_W6PRE("%3", "%3")                           // p11
+        SS_PK_SUB_IB("%4", "%0", "%2")                    // t0
+        SS_PK_ADD_IB("%2", "%0", "%2")                    // t1
+        SS_PK_ADD("%0", "%1", "%3")
+        SS_PK_SUB("%1", "%1", "%3")
+        SS_PK_FNMA("%3", "%0", "%5", "%4")                // (a10, parked in a11's pair)
+        SS_PK_FMA("%0", "%0", "%5", "%4")
+        SS_PK_FMA_ADD_IK("%4", "%1", "%5", "%2")          // (a11, parked in the temporary)
+        SS_PK_FMA_SUB_IK("%1", "%1", "%5", "%2")
+        : "+v"(a[8]), "+v"(a[9]), "+v"(a[10]), "+v"(a[11]), "=&v"(tmp) : "s"(kr));
+    a[10] = a[11];
+    a[11] = tmp;
+    // p = 3: (a12, -i C q13, R p14, -C q15);  t0, t1 = a12 +- R p14;  a12, a14 = t0 -+ C (q15 + i q13);  a13, a15 = t1 -+ i C (q15 - i q13)
+    asm(SS_PK_FMA_ADD_IK("%1", "%1", "%5", "%1")          // q13
+        SS_PK_FMA_SUB_IK("%3", "%3", "%5", "%3")          // q15
+        SS_PK_W6PRE("%2", "%2")                           // p14
+        SS_PK_SUB_IB("%4", "%3", "%1")
+        SS_PK_ADD_IB("%3", "%3", "%1")
+        SS_PK_FNMA("%1", "%2", "%7", "%0")                // t1
+        SS_PK_FMA("%2", "%2", "%7", "%0")                 // t0
+        SS_PK_FNMA("%0", "%3", "%6", "%2")
+        SS_PK_FMA("%2", "%3", "%6", "%2")
+        SS_PK_FMA_ADD_IK("%3", "%4", "%6", "%1")
+        SS_PK_FMA_SUB_IK("%1", "%4", "%6", "%1")
+        : "+v"(a[12]), "+v"(a[13]), "+v"(a[14]), "+v"(a[15]), "=&v"(tmp) : "s"(kt), "s"(kc), "s"(kr));
+}
+
 __device__ __forceinline__ void fft16(v2f (&a)[16])
 {
-    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, R = 0.70710678118654752f;
-    const v2f w1 = {C1, -S1}, w3 = {S1, -C1}, w9 = {-C1, S1};
     // stage 1: 4-point DFTs over q of a[r + 4q]; result p lands in a[r + 4p]
     radix4(a[0], a[4], a[8], a[12]);
     radix4(a[1], a[5], a[9], a[13]);
     radix4(a[2], a[6], a[10], a[14]);
     radix4(a[3], a[7], a[11], a[15]);
-    // twiddle a[r + 4p] *= W16^(r p)
-    a[5] = pk_cmul_k(a[5], w1);            // r=1,p=1: W^1
-    a[9] = pk_w2pre(a[9]) * R;           // r=1,p=2: W^2
-    a[13] = pk_cmul_k(a[13], w3);          // r=1,p=3: W^3
-    a[6] = pk_w2pre(a[6]) * R;           // r=2,p=1: W^2
-    a[10] = pk_mul_mi(a[10]);            // r=2,p=2: W^4 = -i
-    a[14] = pk_w6pre(a[14]) * R;         // r=2,p=3: W^6 = (-R,-R)
-    a[7] = pk_cmul_k(a[7], w3);            // r=3,p=1: W^3
-    a[11] = pk_w6pre(a[11]) * R;         // r=3,p=2: W^6
-    a[15] = pk_cmul_k(a[15], w9);          // r=3,p=3: W^9 = (-C1, +S1)
-    // stage 2: 4-point DFTs over r of a[r + 4p]; result s lands in a[s + 4p] = X[p + 4s]
-    radix4(a[0], a[1], a[2], a[3]);
-    radix4(a[4], a[5], a[6], a[7]);
-    radix4(a[8], a[9], a[10], a[11]);
-    radix4(a[12], a[13], a[14], a[15]);
+    fft16_stage2(a);
+}
+// A stage-1 butterfly of fft16 on WINDOWED samples, the window multiply of its last two inputs inside: with m_a = s_a h_a and
+// m_b = s_b h_b formed (pk_mul_bcast), t0, t1 = m_a +- s_c h_c and t2, t3 = m_b +- s_d h_d are four fmas where two products and four
+// adds were six instructions.  hc, hd: the register pairs that hold the weights in half S.  In: a0 = m_a, a1 = m_b; out: the
+// butterfly's four results.  One asm statement (see pk_cmul).
+template <int S>
+__device__ __forceinline__ void radix4_windowed(v2f &a0, v2f &a1, v2f &a2, v2f &a3, v2f sc, v2f hc, v2f sd, v2f hd)
+{
+#define SS_WIN_FMA(D, V, H, T, NEG) "v_pk_fma_f32 " D ", " V ", " H ", " T " op_sel:[0,%c9,0] op_sel_hi:[1,%c9,1]" NEG "\n\t"
+    v2f o0, m1 = a1;
+    asm(SS_WIN_FMA("%2", "%5", "%6", "%0", "")                                  // t0
+        SS_WIN_FMA("%0", "%5", "%6", "%0", " neg_lo:[1,0,0] neg_hi:[1,0,0]")    // t1
+        SS_WIN_FMA("%3", "%7", "%8", "%1", "")                                  // t2
+        SS_WIN_FMA("%1", "%7", "%8", "%1", " neg_lo:[1,0,0] neg_hi:[1,0,0]")    // t3
+        SS_PK_ADD("%4", "%2", "%3")
+        SS_PK_SUB("%2", "%2", "%3")
+        SS_PK_ADD_IB("%3", "%0", "%1")
+        SS_PK_SUB_IB("%0", "%0", "%1")
+        : "+v"(a0), "+v"(m1), "=&v"(a2), "=&v"(a3), "=&v"(o0) : "v"(sc), "v"(hc), "v"(sd), "v"(hd), "n"(S));
+    a1 = a0;
+    a0 = o0;
+#undef SS_WIN_FMA
 }
 
 // ---- pass 1 of a 4096-point transform on radix-16 passes: the twiddles W^(t ka), W = W_4096, of thread t ----------------------

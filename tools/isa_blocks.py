@@ -2,7 +2,8 @@
 """Basic blocks of ONE kernel of an AMDGPU assembly file with their instruction mix — the static side of a kernel's instruction budget
 (DESIGN 3.2): tools/isa_blocks.py <file.s> <mangled-name substring> [first block] [last block]
 Columns: block index, label, VALU (f64 fma/mul/add | cvt | dpp/readlane/permute moves | other), MFMA, LDS, VMEM, SALU, waits/nops,
-the s_setprio values inside (phase marks of the tile loop), and where the block branches."""
+pk (the packed v_pk_* among the VALU columns) and nop (the s_nop among the waits), the s_setprio values inside (phase marks of the
+tile loop), and where the block branches.  The totals line counts the blocks shown."""
 import re, sys
 s = open(sys.argv[1]).read()
 names = [m for m in re.findall(r'^(\S+):\s*; @', s, re.M) if sys.argv[2] in m]
@@ -31,7 +32,7 @@ def cls(op):
         return 'valu'
     return 'other'
 tot = {}
-print(f"{'#':>4} {'label':<12} {'f64':>4} {'cvt':>4} {'move':>4} {'valu':>4} {'mfma':>4} {'lds':>4} {'vmem':>4} {'salu':>4} {'wait':>4}  notes")
+print(f"{'#':>4} {'label':<12} {'f64':>4} {'cvt':>4} {'move':>4} {'valu':>4} {'mfma':>4} {'lds':>4} {'vmem':>4} {'salu':>4} {'wait':>4} {'pk':>4} {'nop':>4}  notes")
 for k, b in enumerate(blocks):
     if k < lo or k > hi: continue
     c = {}
@@ -41,11 +42,13 @@ for k, b in enumerate(blocks):
         dpp = 'dpp' in ins or 'row_' in ins or 'quad_perm' in ins
         kcls = 'move' if (dpp and op.startswith('v_mov')) else cls(op)
         c[kcls] = c.get(kcls, 0) + 1
+        if op.startswith('v_pk_'): c['pk'] = c.get('pk', 0) + 1
+        if op == 's_nop': c['nop'] = c.get('nop', 0) + 1
         if op == 's_setprio': notes.append('prio' + ins.split()[1])
         m = re.match(r's_cbranch_\w+ (\.LBB\d+_\d+)|s_branch (\.LBB\d+_\d+)', ins)
         if m:
             t = m.group(1) or m.group(2)
             notes.append(('^' if idx.get(t, 1 << 30) <= k else 'v') + str(idx.get(t, '?')))
     for q, v in c.items(): tot[q] = tot.get(q, 0) + v
-    print(f"{k:>4} {b[0]:<12} " + ' '.join(f"{c.get(q, 0):>4}" for q in ('f64', 'cvt', 'move', 'valu', 'mfma', 'lds', 'vmem', 'salu', 'wait')) + '  ' + ' '.join(notes))
+    print(f"{k:>4} {b[0]:<12} " + ' '.join(f"{c.get(q, 0):>4}" for q in ('f64', 'cvt', 'move', 'valu', 'mfma', 'lds', 'vmem', 'salu', 'wait', 'pk', 'nop')) + '  ' + ' '.join(notes))
 print('total', tot)

@@ -1,6 +1,7 @@
 // A/B for north_star's "MFMA only if the FFT is recast as a dense twiddle GEMM and rocprof shows it beating the shuffle path":
 // the radix-16 step of the spectrum kernels (a 16-point complex DFT per lane-thread) done
-//   (A) the way k_fft4096_ms1 / k_fft16k_run do it: 81 packed-f32 VALU instructions in registers, and
+//   (A) the way k_fft4096_ms1 / k_fft16k_run did it at the time: 81 packed-f32 VALU instructions in registers (the kernels' fft16
+//       has its constant twiddles fused into fmas since, 72; this copy keeps the measured form), and
 //   (B) as a dense 16 x 16 complex DFT-matrix product on the matrix cores at f32-equivalent accuracy:
 //       D = W X with W = Wr + i Wi constant, X = 16 points x 16 columns per MFMA tile,
 //       Dr = Wr Xr - Wi Xi, Di = Wr Xi + Wi Xr: four real 16x16x16 products, each as the three-term f16 split
