@@ -477,6 +477,70 @@ int ss_batch_loudness_regions(ss_batch *b, const ss_loudness_region *regions, ui
 int ss_batch_download_region_results(ss_batch *b, ss_region_result *out, uint32_t cap_regions);
 int ss_batch_download_group_results(ss_batch *b, ss_group_result *out, uint32_t cap_groups);
 int ss_batch_group_histograms(ss_batch *b, uint32_t group, uint64_t *out2000);
+/* Peak series and peak regions: the true and sample peak of every 100 ms of every stream of a batch, the frame that attains each,
+ * and their maxima over time ranges and groups of ranges — the second half of a delivery specification (programme loudness and
+ * maximum true peak per item), on the grid of the loudness regions, so one ss_loudness_region list reads both.  Not in the
+ * reference.  ss_batch_peak_series reads the resident f32 corpus alone: it needs no ss_batch_run and no particular flag, and
+ * nothing inside a pass changes.  With S = s100 = (sample_rate + 5) / 10 and F_s stream s's own frame count (ss_batch_set_lengths;
+ * frames behind it are never read), stream s has E_s = ceil(F_s / S) entries; entry j covers frames [j S, min((j + 1) S, F_s)):
+ * entries j < n_subblocks are the sub-blocks the loudness side indexes, a last partial entry covers the tail, so the maximum over
+ * a stream's entries covers every frame.  Per (stream, entry, channel) one ss_peak_entry:
+ *   - the interpolator is the batch's: y_f[n] = sum_t c_f[t] x[n - t] over the taps ss_inspect_true_peak lists (12 per branch at
+ *     factor 4, 24 at factor 2), the factor ss_batch_config::true_peak_factor (0: the crate's rule for the rate; at 192 kHz and
+ *     above there is no interpolation and true_peak equals sample_peak).  Branch 0 is x[n] itself.  One f32 chain of fused
+ *     multiply-adds per output, oldest tap first; it need not equal a pass's true peak bit for bit (the pass's own forms do not
+ *     equal each other either), and lies within the same distance of the exact sum;
+ *   - x[n] = 0 for n < 0: a stream's history is its own, never the tail of the stream in front of it in memory;
+ *   - an output belongs to the entry of its frame n and reaches back up to 11 (23) frames into the entry before;
+ *   - capture is the crate's `if v > max` from 0: a NaN output is never captured (the other branches of its frame still are), an
+ *     infinity is; an all-zero or all-NaN entry reads 0 at 0xFFFFFFFF; ties go to the lowest frame.
+ * The series ([stream][entries_cap][channels] records, 16 * entries_cap * channels * n_streams bytes, entries_cap =
+ * ceil(frames_per_stream / S)) is allocated at the first call; ss_batch_peak_series_plan reports entries_cap and tile_frames, the
+ * frames of an entry one workgroup stages at a time (an entry of more frames is walked in tiles).
+ * ss_batch_peak_regions takes the loudness regions' records, copies them before it returns, and reduces the series over entries
+ * first_subblock <= j < first_subblock + n_subblocks; the bound is the stream's E_s, not n_subblocks, so a region may include the
+ * tail entry.  `ceiling` is linear (+inf: nothing is over).  Ties between equal values: within a region the lowest entry, then the
+ * lowest frame, then the lowest channel; across a group the lowest region index.  Regions may come from any streams, overlap and
+ * repeat: each one counts.  A region or group in which nothing was captured reads 0 with the "none" marks below.  Group maxima use
+ * integer atomics on (value bits, inverted index) words only and there are no floating-point atomics: two calls agree byte for byte.
+ * ss_batch_download_region_channel_peaks returns every region's per-channel maxima, [region][channels] floats each; either pointer
+ * may be NULL.
+ * Both calls queue their work on the batch's stream like ss_batch_spectrum_stats: nothing is copied back or waited for.  A later
+ * call replaces every result; the downloads wait for the stream.  ss_batch_peak_regions reads the series as it is when it runs:
+ * call ss_batch_peak_series again after new input or new lengths.  A batch that never calls any of this allocates and launches
+ * exactly what it did before.
+ * Status codes, all checked before anything is queued: a download before the first computation of its kind, and
+ * ss_batch_peak_regions before ss_batch_peak_series: SS_ERR_INVALID_MODE; stream >= n_streams, first_subblock + n_subblocks (in 64
+ * bits) beyond the stream's E_s, a group >= n_groups other than SS_REGION_NO_GROUP, a NaN or negative ceiling, regions == NULL with
+ * n_regions > 0: SS_ERR_INVALID_ARG; a `cap` too small: SS_ERR_CAPACITY.  n_regions == 0, n_subblocks == 0 and F_s == 0 (no
+ * entries) are valid. */
+typedef struct ss_peak_entry {
+    float true_peak;            /* max over the entry's frames and ALL branches, branch 0 (the sample) included: max(true, sample)
+                                 * like EbuR128::true_peak */
+    float sample_peak;          /* max |x[n]| */
+    uint32_t true_peak_frame;   /* offset in the entry of the frame that attains it first; 0xFFFFFFFF if nothing was captured */
+    uint32_t sample_peak_frame;
+} ss_peak_entry;                /* 16 bytes */
+typedef struct ss_region_peaks {
+    double true_peak, sample_peak;                      /* max over the region's entries and ALL channels (the f32 widened); 0 if none */
+    uint64_t true_peak_frame, sample_peak_frame;        /* ABSOLUTE frame in the stream; UINT64_MAX if none */
+    uint32_t true_peak_channel, sample_peak_channel;    /* 0xFFFFFFFF if none */
+    uint32_t n_over;                                    /* entries whose true_peak of ANY channel is > ceiling */
+    uint32_t first_over;                                /* absolute entry index of the first; 0xFFFFFFFF if none */
+} ss_region_peaks;              /* 48 bytes */
+typedef struct ss_group_peaks {
+    double true_peak, sample_peak;                      /* max over the regions that name the group */
+    uint32_t true_peak_region, sample_peak_region;      /* index into the list; 0xFFFFFFFF if none */
+    uint64_t n_over;                                    /* sum of the regions' n_over (overlaps and repeats each count) */
+} ss_group_peaks;               /* 32 bytes */
+int ss_batch_peak_series(ss_batch *b);
+int ss_batch_peak_series_plan(const ss_batch *b, uint32_t *tile_frames, uint32_t *entries_cap);
+/* stream's entries, [entry][channel]; *n_entries (optional) = E_s; cap_entries counts entries (records / channels) */
+int ss_batch_download_peak_series(ss_batch *b, uint32_t stream, ss_peak_entry *out, size_t cap_entries, uint32_t *n_entries);
+int ss_batch_peak_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups, double ceiling);
+int ss_batch_download_region_peaks(ss_batch *b, ss_region_peaks *out, uint32_t cap_regions);
+int ss_batch_download_group_peaks(ss_batch *b, ss_group_peaks *out, uint32_t cap_groups);
+int ss_batch_download_region_channel_peaks(ss_batch *b, float *true_pk, float *sample_pk, size_t cap_floats);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

@@ -52,6 +52,8 @@ SYMBOLS = [
     "ss_meter_bank_spectrum_tracked", "ss_meter_bank_spectrum_tracked_columns",
     "ss_batch_spectrum_stats", "ss_batch_download_spectrum_stats", "ss_batch_corpus_spectrum", "ss_batch_spectrum_stats_plan",
     "ss_batch_loudness_regions", "ss_batch_download_region_results", "ss_batch_download_group_results", "ss_batch_group_histograms",
+    "ss_batch_peak_series", "ss_batch_peak_series_plan", "ss_batch_download_peak_series", "ss_batch_peak_regions",
+    "ss_batch_download_region_peaks", "ss_batch_download_group_peaks", "ss_batch_download_region_channel_peaks",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -129,6 +131,22 @@ class RegionResult(C.Structure):
 class GroupResult(C.Structure):
     _fields_ = [("integrated_lufs", C.c_double), ("loudness_range", C.c_double),
                 ("n_gating_blocks", C.c_uint64), ("n_st_blocks", C.c_uint64)]
+
+
+class PeakEntry(C.Structure):
+    _fields_ = [("true_peak", C.c_float), ("sample_peak", C.c_float), ("true_peak_frame", C.c_uint32), ("sample_peak_frame", C.c_uint32)]
+
+
+class RegionPeaks(C.Structure):
+    _fields_ = [("true_peak", C.c_double), ("sample_peak", C.c_double),
+                ("true_peak_frame", C.c_uint64), ("sample_peak_frame", C.c_uint64),
+                ("true_peak_channel", C.c_uint32), ("sample_peak_channel", C.c_uint32),
+                ("n_over", C.c_uint32), ("first_over", C.c_uint32)]
+
+
+class GroupPeaks(C.Structure):
+    _fields_ = [("true_peak", C.c_double), ("sample_peak", C.c_double),
+                ("true_peak_region", C.c_uint32), ("sample_peak_region", C.c_uint32), ("n_over", C.c_uint64)]
 
 
 class MeterReading(C.Structure):
@@ -297,6 +315,13 @@ def _bind(lib):
         "ss_batch_download_region_results": (C.c_int, [vp, C.POINTER(RegionResult), C.c_uint32]),
         "ss_batch_download_group_results": (C.c_int, [vp, C.POINTER(GroupResult), C.c_uint32]),
         "ss_batch_group_histograms": (C.c_int, [vp, C.c_uint32, u64p]),
+        "ss_batch_peak_series": (C.c_int, [vp]),
+        "ss_batch_peak_series_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_batch_download_peak_series": (C.c_int, [vp, C.c_uint32, C.POINTER(PeakEntry), C.c_size_t, C.POINTER(C.c_uint32)]),
+        "ss_batch_peak_regions": (C.c_int, [vp, C.POINTER(LoudnessRegion), C.c_uint32, C.c_uint32, C.c_double]),
+        "ss_batch_download_region_peaks": (C.c_int, [vp, C.POINTER(RegionPeaks), C.c_uint32]),
+        "ss_batch_download_group_peaks": (C.c_int, [vp, C.POINTER(GroupPeaks), C.c_uint32]),
+        "ss_batch_download_region_channel_peaks": (C.c_int, [vp, f32p, f32p, C.c_size_t]),
         "ss_batch_spectrum_stats": (C.c_int, [vp]),
         "ss_batch_download_spectrum_stats": (C.c_int, [vp, C.c_uint32, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_batch_corpus_spectrum": (C.c_int, [vp, f32p, f32p, C.c_size_t, u64p, C.c_uint32]),

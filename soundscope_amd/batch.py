@@ -12,6 +12,23 @@ from . import _lib as L
 from .analyzer import _check
 
 
+def _region_rows(regions):
+    """A region list as contiguous u32 [n][4] rows: a u32 array [n][4] as it is, else rows of three or four integers (a missing
+    group is L.SS_REGION_NO_GROUP)."""
+    rows = regions
+    if not (isinstance(rows, np.ndarray) and rows.dtype == np.uint32 and rows.ndim == 2 and rows.shape[1] == 4):   # (else: as it is)
+        a = np.asarray(regions, dtype=np.int64).reshape(-1, 4 if len(regions) and len(regions[0]) == 4 else 3)
+        if ((a < 0) | (a > 0xFFFFFFFF)).any():
+            raise ValueError("region fields are u32")
+        rows = np.full((a.shape[0], 4), L.SS_REGION_NO_GROUP, np.uint32)
+        rows[:, :a.shape[1]] = a
+    return np.ascontiguousarray(rows)
+
+
+PEAK_ENTRY_DTYPE = np.dtype([("true_peak", np.float32), ("sample_peak", np.float32),
+                             ("true_peak_frame", np.uint32), ("sample_peak_frame", np.uint32)])
+
+
 class Batch:
     def __init__(self, sample_rate=48000, channels=2, n_streams=1, frames_per_stream=480000,
                  fft_n=4096, hop_frames=1024, flags=L.SS_BATCH_ALL, true_peak_factor=0,
@@ -264,14 +281,7 @@ class Batch:
         """Queue the gate of `regions` behind the pass: rows (stream, first_subblock, n_subblocks[, group]) in 100 ms sub-blocks,
         group 0 .. n_groups - 1 or L.SS_REGION_NO_GROUP (the default of a three-column row); a u32 array [n][4] is passed as it is.
         Replaces the previous list."""
-        rows = regions
-        if not (isinstance(rows, np.ndarray) and rows.dtype == np.uint32 and rows.ndim == 2 and rows.shape[1] == 4):   # (else: as it is)
-            a = np.asarray(regions, dtype=np.int64).reshape(-1, 4 if len(regions) and len(regions[0]) == 4 else 3)
-            if ((a < 0) | (a > 0xFFFFFFFF)).any():
-                raise ValueError("region fields are u32")
-            rows = np.full((a.shape[0], 4), L.SS_REGION_NO_GROUP, np.uint32)
-            rows[:, :a.shape[1]] = a
-        rows = np.ascontiguousarray(rows)
+        rows = _region_rows(regions)
         _check(L.lib().ss_batch_loudness_regions(self._h, rows.ctypes.data_as(C.POINTER(L.LoudnessRegion)), rows.shape[0], int(n_groups)))
         self._n_regions, self._n_groups = rows.shape[0], int(n_groups)      # (a refused call leaves the previous list)
 
@@ -293,6 +303,57 @@ class Batch:
         out = np.empty(2000, np.uint64)
         _check(L.lib().ss_batch_group_histograms(self._h, int(g), out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out[:1000].copy(), out[1000:].copy()
+
+    # -- peak series and peak regions: true and sample peak per 100 ms entry, and their maxima over ranges and groups
+    def peak_series(self):
+        """Queue the peak series of whatever is resident: per (stream, 100 ms entry, channel) the true and sample peak and the
+        frame of each.  Needs no run() and no particular flag."""
+        _check(L.lib().ss_batch_peak_series(self._h))
+
+    def peak_series_plan(self):
+        """(tile_frames, entries_cap): the frames of an entry a workgroup stages at a time, and the entry slots per stream."""
+        t, e = C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_batch_peak_series_plan(self._h, C.byref(t), C.byref(e)))
+        return t.value, e.value
+
+    def peak_series_of(self, stream):
+        """Stream's entries: a structured array [entries][channels] (true_peak, sample_peak, true_peak_frame, sample_peak_frame;
+        the frames are offsets in the entry, 0xFFFFFFFF where nothing was captured)."""
+        ch, cap = int(self.cfg.channels), self.peak_series_plan()[1]
+        out = np.zeros((cap, ch), PEAK_ENTRY_DTYPE)
+        n = C.c_uint32()
+        _check(L.lib().ss_batch_download_peak_series(self._h, stream, out.ctypes.data_as(C.POINTER(L.PeakEntry)), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def peak_regions(self, regions, n_groups=0, ceiling=float("inf")):
+        """Queue the maxima of the peak series over `regions` (rows as loudness_regions takes them, in 100 ms entries; a region may
+        reach the stream's tail entry) behind peak_series(); `ceiling` (linear) is what n_over / first_over count against.
+        Replaces the previous list."""
+        rows = _region_rows(regions)
+        _check(L.lib().ss_batch_peak_regions(self._h, rows.ctypes.data_as(C.POINTER(L.LoudnessRegion)), rows.shape[0], int(n_groups),
+                                             float(ceiling)))
+        self._n_peak_regions, self._n_peak_groups = rows.shape[0], int(n_groups)      # (a refused call leaves the previous list)
+
+    def region_peaks(self):
+        """Per region of the last peak list: L.RegionPeaks (true_peak, sample_peak, their absolute frames and channels, n_over,
+        first_over)."""
+        arr = (L.RegionPeaks * getattr(self, "_n_peak_regions", 0))()
+        _check(L.lib().ss_batch_download_region_peaks(self._h, arr, len(arr)))
+        return arr
+
+    def group_peaks(self):
+        """Per group of the last peak list: L.GroupPeaks (true_peak, sample_peak, the regions that attain them, n_over)."""
+        arr = (L.GroupPeaks * getattr(self, "_n_peak_groups", 0))()
+        _check(L.lib().ss_batch_download_group_peaks(self._h, arr, len(arr)))
+        return arr
+
+    def region_channel_peaks(self):
+        """(true_peak, sample_peak) of every channel of every region of the last peak list: two f32 arrays [regions][channels]."""
+        ch = int(self.cfg.channels)
+        tp, sp = np.zeros((getattr(self, "_n_peak_regions", 0), ch), np.float32), np.zeros((getattr(self, "_n_peak_regions", 0), ch), np.float32)
+        fp = C.POINTER(C.c_float)
+        _check(L.lib().ss_batch_download_region_channel_peaks(self._h, tp.ctypes.data_as(fp), sp.ctypes.data_as(fp), tp.size))
+        return tp, sp
 
     def histograms(self):
         out = np.empty(2000, np.uint64)

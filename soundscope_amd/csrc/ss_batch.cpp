@@ -110,6 +110,20 @@ struct Regions {
     DevBuf<unsigned long long> group_hist;      // [group][2][1000]
 };
 
+// peak series and peak regions (ss_batch_peak_series, ss_batch_peak_regions): all of it allocated at the batch's first call (the
+// regions' part grown by a longer list), so a batch that never asks holds none of it
+struct Peaks {
+    bool series_done = false, regions_done = false;     // queued at least once: there is something to download
+    uint32_t n_regions = 0, n_groups = 0;               // of the last ss_batch_peak_regions
+    DevBuf<uint4> series;                               // [stream][entries_cap][channels] records (ss_peak_entry)
+    HostStage stage;                                    // the caller's list on its way to the device
+    DevBuf<ssk::LoudnessRegion> list;
+    DevBuf<ssk::RegionPeaks> results;
+    DevBuf<float> ch_true, ch_sample;                   // [region][channels]
+    DevBuf<unsigned long long> group_acc;               // [group][3] (RegionPeaksParams::group_acc)
+    DevBuf<ssk::GroupPeaks> group_results;
+};
+
 }  // namespace
 
 struct ss_batch {
@@ -152,6 +166,7 @@ struct ss_batch {
     Columns cols;
     SpecStats stats;
     Regions regions;
+    Peaks peaks;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
     int tp_arith = SS_TP_ARITH_F32;   // SS_TP_ARITH_*: the reference's width unless the caller opts into the f16 split
@@ -1326,6 +1341,142 @@ int ss_batch_group_histograms(ss_batch *b, uint32_t group, uint64_t *out2000)
     if (group >= b->regions.n_groups) return SS_ERR_INVALID_ARG;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the histograms are copied out as they are");
     return fetch(b, out2000, reinterpret_cast<const uint64_t *>(b->regions.group_hist.p) + (size_t)group * 2 * sst::kHistBins, 2 * sst::kHistBins);
+}
+
+// ---- peak series and peak regions: true and sample peak per 100 ms entry, and their maxima over ranges and groups -----------
+static_assert(sizeof(ss_peak_entry) == 16 && sizeof(uint4) == 16 && offsetof(ss_peak_entry, sample_peak) == 4 && offsetof(ss_peak_entry, true_peak_frame) == 8 &&
+              offsetof(ss_peak_entry, sample_peak_frame) == 12, "peak entry layout");
+static_assert(sizeof(ss_region_peaks) == 48 && sizeof(ssk::RegionPeaks) == 48 && offsetof(ssk::RegionPeaks, true_frame) == offsetof(ss_region_peaks, true_peak_frame) &&
+              offsetof(ssk::RegionPeaks, true_channel) == offsetof(ss_region_peaks, true_peak_channel) && offsetof(ssk::RegionPeaks, n_over) == offsetof(ss_region_peaks, n_over) &&
+              offsetof(ssk::RegionPeaks, first_over) == offsetof(ss_region_peaks, first_over), "region peaks layout");
+static_assert(sizeof(ss_group_peaks) == 32 && sizeof(ssk::GroupPeaks) == 32 && offsetof(ssk::GroupPeaks, true_region) == offsetof(ss_group_peaks, true_peak_region) &&
+              offsetof(ssk::GroupPeaks, n_over) == offsetof(ss_group_peaks, n_over), "group peaks layout");
+
+// the series' time grid and tiling: the batch's rate and slot size alone (no pass, no tables)
+static uint32_t peak_s100(const ss_batch *b) { return (b->cfg.sample_rate + 5u) / 10u; }
+static ssk::PeakSeriesPlan batch_peak_plan(const ss_batch *b) { return ssk::plan_peak_series(b->cfg.channels, peak_s100(b), b->cfg.frames_per_stream); }
+// E_s: entries of a stream of the batch, the tail's partial entry included
+static uint64_t peak_entries_of(const ss_batch *b, uint32_t stream)
+{
+    const uint64_t F = b->ragged.on ? b->ragged.frames_h[stream] : b->cfg.frames_per_stream, S = peak_s100(b);
+    return S ? (F + S - 1) / S : 0;
+}
+
+int ss_batch_peak_series_plan(const ss_batch *b, uint32_t *tile_frames, uint32_t *entries_cap)
+{
+    if (!b) return SS_ERR_INVALID_ARG;
+    const ssk::PeakSeriesPlan plan = batch_peak_plan(b);
+    if (tile_frames) *tile_frames = plan.tile_frames;
+    if (entries_cap) *entries_cap = plan.entries_cap;
+    return SS_OK;
+}
+
+int ss_batch_peak_series(ss_batch *b)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const ss_batch_config &c = b->cfg;
+    const ssk::PeakSeriesPlan plan = batch_peak_plan(b);
+    if (!peak_s100(b) || (uint64_t)plan.entries_cap * peak_s100(b) < c.frames_per_stream) return SS_ERR_UNSUPPORTED;     // (2^32 entries)
+    ssk::PeakSeriesParams p{};
+    p.factor = c.true_peak_factor ? (int)c.true_peak_factor : sst::true_peak_factor_for_rate(c.sample_rate);
+    if (p.factor) {
+        uint32_t len = 0;
+        static_assert(sizeof p.taps / sizeof p.taps[0] == 36, "three branches of 12 taps, or one of 24");
+        int rc = ss_inspect_true_peak(p.factor, p.taps, 36, &len);
+        if (rc) return rc;
+    }
+    // (the shape of a batch is fixed at create, so only the first call allocates)
+    HIPCHK(b->peaks.series.ensure((size_t)c.n_streams * plan.entries_cap * c.channels));
+    p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * c.channels; p.n_frames = c.frames_per_stream;
+    p.frames_of = b->ragged.on ? b->ragged.frames_d.p : nullptr;
+    p.series = b->peaks.series.p;
+    p.n_streams = c.n_streams; p.channels = c.channels; p.s100 = peak_s100(b);
+    p.tile_frames = plan.tile_frames; p.entries_cap = plan.entries_cap;
+    HIPCHK(ssk::launch_peak_series(p, b->stream));
+    b->peaks.series_done = true;
+    return SS_OK;
+}
+
+int ss_batch_download_peak_series(ss_batch *b, uint32_t stream, ss_peak_entry *out, size_t cap_entries, uint32_t *n_entries)
+{
+    SS_ON_DEVICE(b);
+    if (!b || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+    if (!b->peaks.series_done) return SS_ERR_INVALID_MODE;
+    const uint64_t n = peak_entries_of(b, stream);
+    if (!out && n) return SS_ERR_INVALID_ARG;
+    if (cap_entries < n) return SS_ERR_CAPACITY;
+    if (n_entries) *n_entries = (uint32_t)n;
+    if (!n) return ss_batch_sync(b);
+    const size_t C = b->cfg.channels;
+    return fetch(b, reinterpret_cast<uint4 *>(out), b->peaks.series.p + (size_t)stream * batch_peak_plan(b).entries_cap * C, (size_t)n * C);
+}
+
+int ss_batch_peak_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups, double ceiling)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    Peaks &pk = b->peaks;
+    if (!pk.series_done) return SS_ERR_INVALID_MODE;
+    if ((!regions && n_regions) || !(ceiling >= 0.0)) return SS_ERR_INVALID_ARG;        // (NaN fails the comparison)
+    // ---- every check before anything is queued: a refused call leaves the previous list and its results as they were
+    for (uint32_t i = 0; i < n_regions; i++) {
+        const ss_loudness_region &r = regions[i];
+        if (r.stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+        if ((uint64_t)r.first_subblock + r.n_subblocks > peak_entries_of(b, r.stream)) return SS_ERR_INVALID_ARG;
+        if (r.group != SS_REGION_NO_GROUP && r.group >= n_groups) return SS_ERR_INVALID_ARG;
+    }
+    const size_t bytes = (size_t)n_regions * sizeof(ss_loudness_region), C = b->cfg.channels;
+    // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
+    HIPCHK(pk.list.ensure(n_regions)); HIPCHK(pk.results.ensure(n_regions));
+    HIPCHK(pk.ch_true.ensure((size_t)n_regions * C)); HIPCHK(pk.ch_sample.ensure((size_t)n_regions * C));
+    HIPCHK(pk.group_acc.ensure((size_t)n_groups * 3)); HIPCHK(pk.group_results.ensure(n_groups));
+    if (n_regions) {
+        HIPCHK(pk.stage.take(bytes));
+        std::memcpy(pk.stage.buf.p, regions, bytes);
+        HIPCHK(hipMemcpyAsync(pk.list.p, pk.stage.buf.p, bytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(pk.stage.sent(b->stream));
+    }
+    ssk::RegionPeaksParams p{};
+    p.series = pk.series.p; p.entries_cap = batch_peak_plan(b).entries_cap; p.channels = b->cfg.channels; p.s100 = peak_s100(b);
+    p.ceiling = ceiling;
+    p.regions = pk.list.p; p.results = pk.results.p; p.ch_true = pk.ch_true.p; p.ch_sample = pk.ch_sample.p;
+    p.n_regions = n_regions; p.n_groups = n_groups; p.group_acc = pk.group_acc.p; p.group_results = pk.group_results.p;
+    HIPCHK(ssk::launch_region_peaks(p, b->stream));
+    pk.n_regions = n_regions; pk.n_groups = n_groups; pk.regions_done = true;
+    return SS_OK;
+}
+
+int ss_batch_download_region_peaks(ss_batch *b, ss_region_peaks *out, uint32_t cap_regions)
+{
+    SS_ON_DEVICE(b);
+    if (!b || (!out && b->peaks.n_regions)) return SS_ERR_INVALID_ARG;
+    if (!b->peaks.regions_done) return SS_ERR_INVALID_MODE;
+    if (cap_regions < b->peaks.n_regions) return SS_ERR_CAPACITY;
+    if (!b->peaks.n_regions) return ss_batch_sync(b);
+    return fetch(b, out, reinterpret_cast<const ss_region_peaks *>(b->peaks.results.p), b->peaks.n_regions);
+}
+
+int ss_batch_download_group_peaks(ss_batch *b, ss_group_peaks *out, uint32_t cap_groups)
+{
+    SS_ON_DEVICE(b);
+    if (!b || (!out && b->peaks.n_groups)) return SS_ERR_INVALID_ARG;
+    if (!b->peaks.regions_done) return SS_ERR_INVALID_MODE;
+    if (cap_groups < b->peaks.n_groups) return SS_ERR_CAPACITY;
+    if (!b->peaks.n_groups) return ss_batch_sync(b);
+    return fetch(b, out, reinterpret_cast<const ss_group_peaks *>(b->peaks.group_results.p), b->peaks.n_groups);
+}
+
+int ss_batch_download_region_channel_peaks(ss_batch *b, float *true_pk, float *sample_pk, size_t cap_floats)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (!b->peaks.regions_done) return SS_ERR_INVALID_MODE;
+    const size_t n = (size_t)b->peaks.n_regions * b->cfg.channels;
+    if (cap_floats < n) return SS_ERR_CAPACITY;
+    if (n && true_pk) HIPCHK(hipMemcpyAsync(true_pk, b->peaks.ch_true.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    if (n && sample_pk) HIPCHK(hipMemcpyAsync(sample_pk, b->peaks.ch_sample.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    return ss_batch_sync(b);
 }
 
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max)

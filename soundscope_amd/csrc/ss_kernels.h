@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_peak_series.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -309,6 +309,40 @@ constexpr uint32_t kRegionLongSub = 2048;
 inline uint32_t region_gate_threads(uint32_t longest) { return longest > kRegionLongSub ? 1024u : 256u; }
 // clears the groups, gates every region (k_region_gate) and evaluates every group (k_group_eval): three steps queued on s
 hipError_t launch_region_gate(const RegionGateParams &p, hipStream_t s);
+// Peak series (ss_batch_peak_series; ss_peak_series.hip): per (stream, 100 ms entry, channel) the true and sample peak and the
+// frame of each, from the resident corpus alone — no pass, no tables.  A record is laid out as ss_peak_entry
+// (include/soundscope_hip.h): {f32 true_peak, f32 sample_peak, u32 true_peak_frame, u32 sample_peak_frame}.
+struct PeakSeriesPlan { uint32_t tile_frames, entries_cap; };
+// tile_frames: frames of an entry a workgroup stages at a time; entries_cap = ceil(n_frames / s100): record slots per stream
+PeakSeriesPlan plan_peak_series(uint32_t channels, uint32_t s100, uint64_t n_frames);
+struct PeakSeriesParams {
+    const float *pcm;                // [stream][frame][channels] f32, 16-byte aligned
+    uint64_t stream_stride;          // floats between streams
+    uint64_t n_frames;               // frames of a slot
+    const uint64_t *frames_of;       // ragged batches: each stream's own frames (nullable = n_frames for all)
+    void *series;                    // [stream][entries_cap][channels] records of 16 bytes
+    uint32_t n_streams, channels, s100;
+    uint32_t tile_frames, entries_cap;      // plan_peak_series
+    int factor;                      // 4, 2 or 0 (sample peak only)
+    float taps[36];                  // [factor - 1][12 or 24]: branch f + 1's coefficient at delay d (ss_inspect_true_peak's layout)
+};
+hipError_t launch_peak_series(const PeakSeriesParams &p, hipStream_t s);
+// Peak regions (ss_batch_peak_regions), behind a series on the same stream: its maxima over runs of one stream's entries, pooled
+// into groups.  The records are laid out as ss_region_peaks / ss_group_peaks.
+struct RegionPeaks { double true_peak, sample_peak; unsigned long long true_frame, sample_frame; uint32_t true_channel, sample_channel, n_over, first_over; };
+struct GroupPeaks { double true_peak, sample_peak; uint32_t true_region, sample_region; unsigned long long n_over; };
+struct RegionPeaksParams {
+    const void *series; uint32_t entries_cap, channels, s100;
+    double ceiling;                  // linear; an entry counts as over when any channel's true peak exceeds it
+    const LoudnessRegion *regions;   // [n_regions], every one inside its stream's entries (the caller has checked)
+    RegionPeaks *results;            // [n_regions]
+    float *ch_true, *ch_sample;      // [n_regions][channels]
+    uint32_t n_regions, n_groups;
+    unsigned long long *group_acc;   // [n_groups][3]: (true bits, ~region), (sample bits, ~region), overs; the launcher clears them
+    GroupPeaks *group_results;       // [n_groups]
+};
+// clears the groups' words, reduces every region (k_region_peaks) and writes every group's record (k_group_peaks)
+hipError_t launch_region_peaks(const RegionPeaksParams &p, hipStream_t s);
 // gate + LRA on explicit histograms (corpus gate after the all-reduce; handle getters)
 // `peaks` (optional): a handle's readings in one launch (ReadingsExtra above)
 hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, const double *bounds,
