@@ -35,6 +35,8 @@ class Batch:
                  waveform_window=0.0, spectrum_columns=0):
         """spectrum_columns > 0 (with L.SS_BATCH_FFT_COLUMNS in flags, added here if missing): columns-only spectrum — the
         render-side reduction runs inside the spectrum kernel and only that many chart columns per row are kept."""
+        self._ragged = False                # set_lengths() has been called
+        self._listed = {"loudness": (0, 0), "peak": (0, 0)}       # (regions, groups) of the last accepted list of each kind
         if spectrum_columns:
             flags |= L.SS_BATCH_FFT_COLUMNS
             self._render_cols = int(spectrum_columns)
@@ -173,7 +175,7 @@ class Batch:
         lay = self.layout
         out = np.empty((lay.n_windows, lay.fft_channels, lay.n_bins), np.float32)
         _check(L.lib().ss_batch_download_fft(self._h, stream, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
-        return out[:self.stream_shape(stream).n_windows] if getattr(self, "_ragged", False) else out
+        return out[:self.stream_shape(stream).n_windows] if self._ragged else out
 
     def bin_tables(self):
         n = self.layout.n_bins
@@ -186,7 +188,7 @@ class Batch:
         pts = self.layout.n_wave_points
         out = np.empty(pts, np.float32)
         _check(L.lib().ss_batch_download_waveform(self._h, stream, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
-        if getattr(self, "_ragged", False):
+        if self._ragged:
             out = out[:self.stream_shape(stream).n_wave_points]
         return out.reshape(-1, 2)          # [bin] -> (min, max)
 
@@ -276,27 +278,34 @@ class Batch:
         _check(L.lib().ss_batch_loudness_extremes(self._h, arr, n))
         return list(arr)
 
+    # -- follow-up calls on a region list: one setter and two record getters per kind
+    def _set_list(self, kind, call, regions, n_groups, *more):
+        """Queue the library's list setter `call` on `regions` (as _region_rows takes them) and remember the list's counts."""
+        rows = _region_rows(regions)
+        _check(call(self._h, rows.ctypes.data_as(C.POINTER(L.LoudnessRegion)), rows.shape[0], int(n_groups), *more))
+        self._listed[kind] = (rows.shape[0], int(n_groups))                  # (a refused call leaves the previous list)
+
+    def _records(self, kind, per_group, record, call):
+        """One `record` per region (per_group: group) of the last list of `kind`; before any list the library refuses."""
+        arr = (record * self._listed[kind][per_group])()
+        _check(call(self._h, arr, len(arr)))
+        return arr
+
     # -- loudness regions: gated loudness of time ranges of the streams, and of groups of them
     def loudness_regions(self, regions, n_groups=0):
         """Queue the gate of `regions` behind the pass: rows (stream, first_subblock, n_subblocks[, group]) in 100 ms sub-blocks,
         group 0 .. n_groups - 1 or L.SS_REGION_NO_GROUP (the default of a three-column row); a u32 array [n][4] is passed as it is.
         Replaces the previous list."""
-        rows = _region_rows(regions)
-        _check(L.lib().ss_batch_loudness_regions(self._h, rows.ctypes.data_as(C.POINTER(L.LoudnessRegion)), rows.shape[0], int(n_groups)))
-        self._n_regions, self._n_groups = rows.shape[0], int(n_groups)      # (a refused call leaves the previous list)
+        self._set_list("loudness", L.lib().ss_batch_loudness_regions, regions, n_groups)
 
     def region_results(self):
         """Per region of the last list: L.RegionResult (integrated_lufs, loudness_range, max_momentary, max_shortterm and their
         absolute sub-block indices, n_gating_blocks, n_st_blocks)."""
-        arr = (L.RegionResult * self._n_regions)()
-        _check(L.lib().ss_batch_download_region_results(self._h, arr, self._n_regions))
-        return arr
+        return self._records("loudness", 0, L.RegionResult, L.lib().ss_batch_download_region_results)
 
     def group_results(self):
         """Per group of the last list: L.GroupResult (integrated_lufs, loudness_range, n_gating_blocks, n_st_blocks)."""
-        arr = (L.GroupResult * self._n_groups)()
-        _check(L.lib().ss_batch_download_group_results(self._h, arr, self._n_groups))
-        return arr
+        return self._records("loudness", 1, L.GroupResult, L.lib().ss_batch_download_group_results)
 
     def group_histograms(self, g):
         """(block, short-term) histograms of group g: the bin-wise sums of its regions' pairs, 1000 u64 bins each."""
@@ -329,28 +338,21 @@ class Batch:
         """Queue the maxima of the peak series over `regions` (rows as loudness_regions takes them, in 100 ms entries; a region may
         reach the stream's tail entry) behind peak_series(); `ceiling` (linear) is what n_over / first_over count against.
         Replaces the previous list."""
-        rows = _region_rows(regions)
-        _check(L.lib().ss_batch_peak_regions(self._h, rows.ctypes.data_as(C.POINTER(L.LoudnessRegion)), rows.shape[0], int(n_groups),
-                                             float(ceiling)))
-        self._n_peak_regions, self._n_peak_groups = rows.shape[0], int(n_groups)      # (a refused call leaves the previous list)
+        self._set_list("peak", L.lib().ss_batch_peak_regions, regions, n_groups, float(ceiling))
 
     def region_peaks(self):
         """Per region of the last peak list: L.RegionPeaks (true_peak, sample_peak, their absolute frames and channels, n_over,
         first_over)."""
-        arr = (L.RegionPeaks * getattr(self, "_n_peak_regions", 0))()
-        _check(L.lib().ss_batch_download_region_peaks(self._h, arr, len(arr)))
-        return arr
+        return self._records("peak", 0, L.RegionPeaks, L.lib().ss_batch_download_region_peaks)
 
     def group_peaks(self):
         """Per group of the last peak list: L.GroupPeaks (true_peak, sample_peak, the regions that attain them, n_over)."""
-        arr = (L.GroupPeaks * getattr(self, "_n_peak_groups", 0))()
-        _check(L.lib().ss_batch_download_group_peaks(self._h, arr, len(arr)))
-        return arr
+        return self._records("peak", 1, L.GroupPeaks, L.lib().ss_batch_download_group_peaks)
 
     def region_channel_peaks(self):
         """(true_peak, sample_peak) of every channel of every region of the last peak list: two f32 arrays [regions][channels]."""
-        ch = int(self.cfg.channels)
-        tp, sp = np.zeros((getattr(self, "_n_peak_regions", 0), ch), np.float32), np.zeros((getattr(self, "_n_peak_regions", 0), ch), np.float32)
+        shape = (self._listed["peak"][0], int(self.cfg.channels))
+        tp, sp = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
         fp = C.POINTER(C.c_float)
         _check(L.lib().ss_batch_download_region_channel_peaks(self._h, tp.ctypes.data_as(fp), sp.ctypes.data_as(fp), tp.size))
         return tp, sp

@@ -98,13 +98,27 @@ struct SpecStats {
     DevBuf<unsigned long long> corpus_counts;   // [fft_channels]
 };
 
+// The region list of a follow-up call (ss_batch_loudness_regions, ss_batch_peak_regions).  Each of the two holds its own, stage
+// included: a loudness list and a peak list live side by side.
+struct RegionList {
+    bool done = false;                          // a list has been queued: there is something to download
+    uint32_t n_regions = 0, n_groups = 0;       // of the last call that was queued
+    HostStage stage;                            // the caller's list on its way to the device
+    DevBuf<ssk::LoudnessRegion> dev;
+    // the device list becomes the caller's (checked: check_regions), behind whatever is queued on the batch's stream
+    int replace(hipStream_t stream, const ss_loudness_region *regions, uint32_t n)
+    {
+        HIPCHK(dev.ensure(n));                  // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
+        if (n) HIPCHK(stage.send(dev.p, regions, (size_t)n * sizeof(ss_loudness_region), stream));
+        return SS_OK;
+    }
+    void queued(uint32_t n, uint32_t groups) { n_regions = n; n_groups = groups; done = true; }     // ... and its launch is queued
+};
+
 // loudness regions (ss_batch_loudness_regions): all of it allocated at the batch's first call and grown by a longer list, so a
 // batch that never asks holds none of it
 struct Regions {
-    bool done = false;                          // a list has been queued: there is something to download
-    uint32_t n_regions = 0, n_groups = 0;       // of the last call
-    HostStage stage;                            // the caller's list on its way to the device
-    DevBuf<ssk::LoudnessRegion> list;
+    RegionList list;
     DevBuf<ssk::RegionResult> results;
     DevBuf<ssk::GroupResult> group_results;
     DevBuf<unsigned long long> group_hist;      // [group][2][1000]
@@ -113,11 +127,9 @@ struct Regions {
 // peak series and peak regions (ss_batch_peak_series, ss_batch_peak_regions): all of it allocated at the batch's first call (the
 // regions' part grown by a longer list), so a batch that never asks holds none of it
 struct Peaks {
-    bool series_done = false, regions_done = false;     // queued at least once: there is something to download
-    uint32_t n_regions = 0, n_groups = 0;               // of the last ss_batch_peak_regions
+    bool series_done = false;                           // queued at least once: there is something to download
     DevBuf<uint4> series;                               // [stream][entries_cap][channels] records (ss_peak_entry)
-    HostStage stage;                                    // the caller's list on its way to the device
-    DevBuf<ssk::LoudnessRegion> list;
+    RegionList list;                                    // of the last ss_batch_peak_regions
     DevBuf<ssk::RegionPeaks> results;
     DevBuf<float> ch_true, ch_sample;                   // [region][channels]
     DevBuf<unsigned long long> group_acc;               // [group][3] (RegionPeaksParams::group_acc)
@@ -175,6 +187,10 @@ struct ss_batch {
     // sub-block slots per stream in sub and series (a stream shorter than one sub-block still has a slot)
     uint32_t sub_cap() const { return lay.n_subblocks ? lay.n_subblocks : 1; }
     size_t samples_per_stream() const { return (size_t)cfg.frames_per_stream * cfg.channels; }
+    // a stream's own length: what ss_batch_set_lengths gave it, else the slot's (a kernel: the per-stream array, or null for the slot's)
+    uint64_t frames_of(uint32_t s) const { return ragged.on ? ragged.frames_h[s] : cfg.frames_per_stream; }
+    uint32_t subblocks_of(uint32_t s) const { return ragged.on ? ragged.sub_h[s] : lay.n_subblocks; }
+    template <typename T> const T *ragged_ptr(const DevBuf<T> &of_stream) const { return ragged.on ? of_stream.p : nullptr; }
 };
 
 namespace ssi {
@@ -222,7 +238,7 @@ ssk::FftBatchParams batch_fft_params(const ss_batch *b)
     p.pcm = b->pcm.p; p.out = b->fft.p;
     p.frames_per_stream = c.frames_per_stream; p.first_start = b->first_start;
     p.n_streams = c.n_streams; p.channels = c.channels; p.n_windows = b->lay.n_windows; p.hop = c.hop_frames;
-    p.windows_of = b->ragged.on ? b->ragged.windows_d.p : nullptr;
+    p.windows_of = b->ragged_ptr(b->ragged.windows_d);
     if (b->cols.on) {
         p.out_cols = b->render_spec.p; p.bin_col = b->cols.bin_col.p; p.col_groups = b->cols.groups.p; p.col_init = b->cols.init.p; p.col_bins = b->cols.bins.p; p.cols = b->render_cols;
         p.integrated = b->cols.gain_mode == SS_GAIN_REFERENCE ? b->integrated.p : nullptr;
@@ -245,7 +261,7 @@ ssk::TdParams batch_td_params(const ss_batch *b)
     p.s100 = b->td->host.s100; p.nseg = plan.nseg; p.seg_sub = plan.seg_sub;
     p.warm_sub = plan.warm_sub; p.fix_sub = plan.fix_sub; p.split_batch = plan.split_batch;
     if (plan.fixup) p.seg_state = b->seg_state.p;       // (sized with the plan: choose_td_geometry)
-    p.frames_of = b->ragged.on ? b->ragged.frames_d.p : nullptr;
+    p.frames_of = b->ragged_ptr(b->ragged.frames_d);
     p.tp_f32 = b->tp_arith == SS_TP_ARITH_F32 ? 1u : 0u;
     if (b->wave_fused && !b->ragged.on) { p.wave_out = b->wave.p; p.wave_stride = (uint64_t)2 * b->wave_window; p.wave_window = b->wave_window; p.halo_frames = b->wave_halo; }
     return p;
@@ -261,7 +277,7 @@ ssk::FinalizeParams batch_gating_params(const ss_batch *b)
     f.hist_energies = b->hist_energies; f.hist_bounds = b->hist_bounds; f.weights = b->weights.p; f.hist = b->hist.p;
     f.corpus_hist = b->corpus.p; f.n_streams = b->cfg.n_streams; f.channels = C;
     f.sub_begin = 0; f.sub_end = b->lay.n_subblocks;
-    f.sub_end_of = b->ragged.on ? b->ragged.sub_d.p : nullptr;
+    f.sub_end_of = b->ragged_ptr(b->ragged.sub_d);
     f.out_integrated = b->integrated.p; f.out_lra = b->lra.p; f.out_counts = b->counts.p;
     f.state = b->state.p;
     return f;
@@ -274,7 +290,7 @@ ssk::WaveParams batch_wave_params(const ss_batch *b)
     ssk::WaveParams p{};
     p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * c.channels; p.n_samples = c.frames_per_stream * c.channels;
     p.n_streams = c.n_streams; p.window = b->wave_window; p.out = b->wave.p; p.out_stride = (uint64_t)2 * b->wave_window;
-    if (b->ragged.on) { p.samples_of = b->ragged.wave_samples_d.p; p.window_of = b->ragged.wave_window_d.p; }
+    p.samples_of = b->ragged_ptr(b->ragged.wave_samples_d); p.window_of = b->ragged_ptr(b->ragged.wave_window_d);
     return p;
 }
 
@@ -293,7 +309,7 @@ ssk::SpecStatsParams batch_stats_params(const ss_batch *b)
     ssk::SpecStatsParams p{};
     p.rows = b->fft.p; p.bin_stride = L.fft_bin_stride; p.n_bins = L.n_bins;
     p.n_streams = b->cfg.n_streams; p.fft_ch = L.fft_channels; p.n_windows = L.n_windows;
-    p.windows_of = b->ragged.on ? b->ragged.windows_d.p : nullptr;
+    p.windows_of = b->ragged_ptr(b->ragged.windows_d);
     p.plan = batch_stats_plan(b);
     p.sums = st.sums.p; p.mean = st.mean.p; p.max = st.max.p; p.counts = st.counts.p;
     p.part_sums = st.part_sums.p; p.part_max = st.part_max.p; p.part_counts = st.part_counts.p;
@@ -340,9 +356,8 @@ int choose_td_geometry(ss_batch *b)
 {
     if (!b->td) return SS_OK;
     const ss_batch_config *cfg = &b->cfg;
-    const ss_batch_layout &L = b->lay;
     const uint32_t C = cfg->channels;
-    const uint32_t nsub = b->ragged.on ? b->ragged.max_sub : L.n_subblocks;
+    const uint32_t nsub = b->ragged.max_sub;             // (equal lengths: of every stream, ss_batch_create)
     const double W0 = 256.0 * ssk::td_resident_waves_per_cu(C, b->td->host.s100, b->wave_fused ? b->wave_halo : 0);
     // what a segment boundary costs, in sub-blocks of full work: the run-in (mode 1), or the fix-up's re-run of kTdFixSub sub-blocks
     // at about 0.8 of a full tile each (filter and energies are most of a tile) — config 5's sweep seg = 2 ... 10 with the fix-up:
@@ -395,7 +410,7 @@ int choose_td_geometry(ss_batch *b)
     if (forgets && split_ok && b->td_mode == 0 && split == ssk::kTdSplitNone && nsub > min_seg && 8.0 * cfg->n_streams * nseg_min <= W0) {
         split = ssk::kTdSplitSegments; plan.seg_sub = min_seg; plan.nseg = nseg_min;
     }
-    plan.split_batch = b->ragged.on ? ssk::kTdSplitNone : split;
+    if (!b->ragged.on) plan.split_batch = split;          // (ragged lengths: one wave per stream / segment, kTdSplitNone)
     // How segments > 0 start.  The exact hand-over: no run-in, their first kTdFixSub sub-blocks re-run from the true state by a
     // second launch (launch_time_domain_fixup).  Mode 1: the 0.1 s run-in from a zero state of rounds 1-4.  Segments of eight
     // waves (the pass is a latency chain, and a second launch is a fifth of it): every segment runs the FILTER over the kTdFixSub
@@ -497,6 +512,37 @@ int fetch(ss_batch *b, T *dst, const T *src, size_t count, hipMemcpyKind kind = 
     return SS_OK;
 }
 
+// ---- follow-up calls: behind a pass, on a list of regions; they hand back one record per region, group or stream -----------------
+// The download of n records and its status ladder: no destination for n > 0 records, then the mode, then the capacity; nothing to
+// copy means synchronise.  (The caller has checked b.)  Dev is Out as the kernels name it.
+template <class Out, class Dev>
+int fetch_records(ss_batch *b, bool mode_ok, Out *out, uint32_t cap, uint32_t n, const Dev *src)
+{
+    static_assert(sizeof(Out) == sizeof(Dev), "the records are copied out as they are");
+    if (!out && n) return SS_ERR_INVALID_ARG;
+    if (!mode_ok) return SS_ERR_INVALID_MODE;
+    if (cap < n) return SS_ERR_CAPACITY;
+    if (!n) return ss_batch_sync(b);
+    return fetch(b, out, reinterpret_cast<const Out *>(src), n);
+}
+
+// Every check of a region list, before anything is queued or allocated: a refused call leaves the previous list, its counts and its
+// results as they were.  bound_of_stream(s): whole sub-blocks for loudness, entries (the partial tail included) for peaks.
+template <class Bound>
+int check_regions(const ss_batch *b, const ss_loudness_region *regions, uint32_t n, uint32_t n_groups, Bound bound_of_stream, uint32_t *longest)
+{
+    if (!regions && n) return SS_ERR_INVALID_ARG;
+    *longest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const ss_loudness_region &r = regions[i];
+        if (r.stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+        if ((uint64_t)r.first_subblock + r.n_subblocks > bound_of_stream(r.stream)) return SS_ERR_INVALID_ARG;
+        if (r.group != SS_REGION_NO_GROUP && r.group >= n_groups) return SS_ERR_INVALID_ARG;
+        if (r.n_subblocks > *longest) *longest = r.n_subblocks;
+    }
+    return SS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -574,7 +620,7 @@ int ss_batch_create(const ss_batch_config *cfg, ss_batch **out)
         // (A/B in one process: 3.14 vs 3.12 ms), so the rows stay compact.
         L.fft_bin_stride = (L.n_bins + 3u) & ~3u;
     }
-    if (b->td) L.n_subblocks = sh.subblocks;
+    if (b->td) L.n_subblocks = b->ragged.max_sub = sh.subblocks;
 
     // ---- buffers
     if (b->ft) {
@@ -714,7 +760,7 @@ int ss_batch_stream_shape(const ss_batch *b, uint32_t stream, ss_stream_shape *o
 {
     SS_ON_DEVICE(b);
     if (!b || !out || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-    const uint64_t F = b->ragged.on ? b->ragged.frames_h[stream] : b->cfg.frames_per_stream;
+    const uint64_t F = b->frames_of(stream);
     const StreamShape sh = stream_shape(b, F);
     out->frames = F; out->n_windows = sh.windows;
     out->n_subblocks = sh.subblocks; out->n_wave_points = (uint32_t)(2 * sh.wave_bins);
@@ -1065,7 +1111,7 @@ int ss_batch_download_loudness_series(ss_batch *b, uint32_t stream, double *mome
     SS_ON_DEVICE(b);
     if (!b || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
     if (!b->series.p) return SS_ERR_INVALID_MODE;                // the batch was made without SS_BATCH_LOUDNESS_SERIES
-    const size_t n = b->ragged.on ? b->ragged.sub_h[stream] : b->lay.n_subblocks;
+    const size_t n = b->subblocks_of(stream);
     if (cap < n) return SS_ERR_CAPACITY;
     if (!n || (!momentary && !shortterm)) return SS_OK;
     std::vector<double> ms(2 * n);
@@ -1081,11 +1127,7 @@ int ss_batch_download_loudness_series(ss_batch *b, uint32_t stream, double *mome
 int ss_batch_loudness_extremes(ss_batch *b, ss_loudness_extremes *out, uint32_t cap_streams)
 {
     SS_ON_DEVICE(b);
-    if (!b || !out) return SS_ERR_INVALID_ARG;
-    if (!b->extremes.p) return SS_ERR_INVALID_MODE;
-    const uint32_t n = b->cfg.n_streams;
-    if (cap_streams < n) return SS_ERR_CAPACITY;
-    return fetch(b, out, reinterpret_cast<const ss_loudness_extremes *>(b->extremes.p), n);
+    return !b ? SS_ERR_INVALID_ARG : fetch_records(b, b->extremes.p != nullptr, out, cap_streams, b->cfg.n_streams, b->extremes.p);      // (n_streams > 0)
 }
 
 int ss_batch_histograms(ss_batch *b, uint64_t *out2000)
@@ -1280,65 +1322,43 @@ int ss_batch_loudness_regions(ss_batch *b, const ss_loudness_region *regions, ui
     SS_ON_DEVICE(b);
     if (!b) return SS_ERR_INVALID_ARG;
     if (!(b->cfg.flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_MODE;
-    if (!regions && n_regions) return SS_ERR_INVALID_ARG;
-    // ---- every check before anything is queued: a refused call leaves the previous list and its results as they were
     uint32_t longest = 0;
-    for (uint32_t i = 0; i < n_regions; i++) {
-        const ss_loudness_region &r = regions[i];
-        if (r.stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-        const uint64_t n_sub = b->ragged.on ? b->ragged.sub_h[r.stream] : b->lay.n_subblocks;
-        if ((uint64_t)r.first_subblock + r.n_subblocks > n_sub) return SS_ERR_INVALID_ARG;
-        if (r.group != SS_REGION_NO_GROUP && r.group >= n_groups) return SS_ERR_INVALID_ARG;
-        if (r.n_subblocks > longest) longest = r.n_subblocks;
-    }
+    int rc = check_regions(b, regions, n_regions, n_groups, [b](uint32_t s) { return b->subblocks_of(s); }, &longest);
+    if (rc) return rc;
     Regions &rg = b->regions;
-    const size_t bytes = (size_t)n_regions * sizeof(ss_loudness_region);
-    // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
-    HIPCHK(rg.list.ensure(n_regions)); HIPCHK(rg.results.ensure(n_regions));
-    HIPCHK(rg.group_results.ensure(n_groups)); HIPCHK(rg.group_hist.ensure((size_t)n_groups * 2 * sst::kHistBins));
-    if (n_regions) {
-        HIPCHK(rg.stage.take(bytes));
-        std::memcpy(rg.stage.buf.p, regions, bytes);
-        HIPCHK(hipMemcpyAsync(rg.list.p, rg.stage.buf.p, bytes, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(rg.stage.sent(b->stream));
-    }
+    HIPCHK(rg.results.ensure(n_regions)); HIPCHK(rg.group_results.ensure(n_groups)); HIPCHK(rg.group_hist.ensure((size_t)n_groups * 2 * sst::kHistBins));
+    if ((rc = rg.list.replace(b->stream, regions, n_regions))) return rc;
     ssk::RegionGateParams p{};
     p.k = b->td->dev.p; p.subblocks = b->sub.p; p.sub_cap = b->sub_cap(); p.sub_stride = (uint64_t)p.sub_cap * b->cfg.channels;
     p.hist_energies = b->hist_energies; p.hist_bounds = b->hist_bounds; p.weights = b->weights.p; p.state = b->state.p;
     p.channels = b->cfg.channels;
-    p.regions = rg.list.p; p.results = rg.results.p; p.n_regions = n_regions; p.n_groups = n_groups; p.longest = longest;
+    p.regions = rg.list.dev.p; p.results = rg.results.p; p.n_regions = n_regions; p.n_groups = n_groups; p.longest = longest;
     p.group_results = rg.group_results.p; p.group_hist = rg.group_hist.p;
     HIPCHK(ssk::launch_region_gate(p, b->stream));
-    rg.n_regions = n_regions; rg.n_groups = n_groups; rg.done = true;
+    rg.list.queued(n_regions, n_groups);
     return SS_OK;
 }
+
+static bool has_loudness_regions(const ss_batch *b) { return (b->cfg.flags & SS_BATCH_LUFS) && b->regions.list.done; }
 
 int ss_batch_download_region_results(ss_batch *b, ss_region_result *out, uint32_t cap_regions)
 {
     SS_ON_DEVICE(b);
-    if (!b || (!out && b->regions.n_regions)) return SS_ERR_INVALID_ARG;
-    if (!(b->cfg.flags & SS_BATCH_LUFS) || !b->regions.done) return SS_ERR_INVALID_MODE;
-    if (cap_regions < b->regions.n_regions) return SS_ERR_CAPACITY;
-    if (!b->regions.n_regions) return ss_batch_sync(b);
-    return fetch(b, out, reinterpret_cast<const ss_region_result *>(b->regions.results.p), b->regions.n_regions);
+    return !b ? SS_ERR_INVALID_ARG : fetch_records(b, has_loudness_regions(b), out, cap_regions, b->regions.list.n_regions, b->regions.results.p);
 }
 
 int ss_batch_download_group_results(ss_batch *b, ss_group_result *out, uint32_t cap_groups)
 {
     SS_ON_DEVICE(b);
-    if (!b || (!out && b->regions.n_groups)) return SS_ERR_INVALID_ARG;
-    if (!(b->cfg.flags & SS_BATCH_LUFS) || !b->regions.done) return SS_ERR_INVALID_MODE;
-    if (cap_groups < b->regions.n_groups) return SS_ERR_CAPACITY;
-    if (!b->regions.n_groups) return ss_batch_sync(b);
-    return fetch(b, out, reinterpret_cast<const ss_group_result *>(b->regions.group_results.p), b->regions.n_groups);
+    return !b ? SS_ERR_INVALID_ARG : fetch_records(b, has_loudness_regions(b), out, cap_groups, b->regions.list.n_groups, b->regions.group_results.p);
 }
 
 int ss_batch_group_histograms(ss_batch *b, uint32_t group, uint64_t *out2000)
 {
     SS_ON_DEVICE(b);
     if (!b || !out2000) return SS_ERR_INVALID_ARG;
-    if (!(b->cfg.flags & SS_BATCH_LUFS) || !b->regions.done) return SS_ERR_INVALID_MODE;
-    if (group >= b->regions.n_groups) return SS_ERR_INVALID_ARG;
+    if (!has_loudness_regions(b)) return SS_ERR_INVALID_MODE;
+    if (group >= b->regions.list.n_groups) return SS_ERR_INVALID_ARG;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the histograms are copied out as they are");
     return fetch(b, out2000, reinterpret_cast<const uint64_t *>(b->regions.group_hist.p) + (size_t)group * 2 * sst::kHistBins, 2 * sst::kHistBins);
 }
@@ -1358,8 +1378,8 @@ static ssk::PeakSeriesPlan batch_peak_plan(const ss_batch *b) { return ssk::plan
 // E_s: entries of a stream of the batch, the tail's partial entry included
 static uint64_t peak_entries_of(const ss_batch *b, uint32_t stream)
 {
-    const uint64_t F = b->ragged.on ? b->ragged.frames_h[stream] : b->cfg.frames_per_stream, S = peak_s100(b);
-    return S ? (F + S - 1) / S : 0;
+    const uint64_t S = peak_s100(b);
+    return S ? (b->frames_of(stream) + S - 1) / S : 0;
 }
 
 int ss_batch_peak_series_plan(const ss_batch *b, uint32_t *tile_frames, uint32_t *entries_cap)
@@ -1389,7 +1409,7 @@ int ss_batch_peak_series(ss_batch *b)
     // (the shape of a batch is fixed at create, so only the first call allocates)
     HIPCHK(b->peaks.series.ensure((size_t)c.n_streams * plan.entries_cap * c.channels));
     p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * c.channels; p.n_frames = c.frames_per_stream;
-    p.frames_of = b->ragged.on ? b->ragged.frames_d.p : nullptr;
+    p.frames_of = b->ragged_ptr(b->ragged.frames_d);
     p.series = b->peaks.series.p;
     p.n_streams = c.n_streams; p.channels = c.channels; p.s100 = peak_s100(b);
     p.tile_frames = plan.tile_frames; p.entries_cap = plan.entries_cap;
@@ -1418,61 +1438,42 @@ int ss_batch_peak_regions(ss_batch *b, const ss_loudness_region *regions, uint32
     if (!b) return SS_ERR_INVALID_ARG;
     Peaks &pk = b->peaks;
     if (!pk.series_done) return SS_ERR_INVALID_MODE;
-    if ((!regions && n_regions) || !(ceiling >= 0.0)) return SS_ERR_INVALID_ARG;        // (NaN fails the comparison)
-    // ---- every check before anything is queued: a refused call leaves the previous list and its results as they were
-    for (uint32_t i = 0; i < n_regions; i++) {
-        const ss_loudness_region &r = regions[i];
-        if (r.stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
-        if ((uint64_t)r.first_subblock + r.n_subblocks > peak_entries_of(b, r.stream)) return SS_ERR_INVALID_ARG;
-        if (r.group != SS_REGION_NO_GROUP && r.group >= n_groups) return SS_ERR_INVALID_ARG;
-    }
-    const size_t bytes = (size_t)n_regions * sizeof(ss_loudness_region), C = b->cfg.channels;
-    // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
-    HIPCHK(pk.list.ensure(n_regions)); HIPCHK(pk.results.ensure(n_regions));
-    HIPCHK(pk.ch_true.ensure((size_t)n_regions * C)); HIPCHK(pk.ch_sample.ensure((size_t)n_regions * C));
+    if (!(ceiling >= 0.0)) return SS_ERR_INVALID_ARG;        // (NaN fails the comparison)
+    uint32_t longest = 0;
+    int rc = check_regions(b, regions, n_regions, n_groups, [b](uint32_t s) { return peak_entries_of(b, s); }, &longest);
+    if (rc) return rc;
+    const size_t C = b->cfg.channels;
+    HIPCHK(pk.results.ensure(n_regions)); HIPCHK(pk.ch_true.ensure((size_t)n_regions * C)); HIPCHK(pk.ch_sample.ensure((size_t)n_regions * C));
     HIPCHK(pk.group_acc.ensure((size_t)n_groups * 3)); HIPCHK(pk.group_results.ensure(n_groups));
-    if (n_regions) {
-        HIPCHK(pk.stage.take(bytes));
-        std::memcpy(pk.stage.buf.p, regions, bytes);
-        HIPCHK(hipMemcpyAsync(pk.list.p, pk.stage.buf.p, bytes, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(pk.stage.sent(b->stream));
-    }
+    if ((rc = pk.list.replace(b->stream, regions, n_regions))) return rc;
     ssk::RegionPeaksParams p{};
     p.series = pk.series.p; p.entries_cap = batch_peak_plan(b).entries_cap; p.channels = b->cfg.channels; p.s100 = peak_s100(b);
     p.ceiling = ceiling;
-    p.regions = pk.list.p; p.results = pk.results.p; p.ch_true = pk.ch_true.p; p.ch_sample = pk.ch_sample.p;
+    p.regions = pk.list.dev.p; p.results = pk.results.p; p.ch_true = pk.ch_true.p; p.ch_sample = pk.ch_sample.p;
     p.n_regions = n_regions; p.n_groups = n_groups; p.group_acc = pk.group_acc.p; p.group_results = pk.group_results.p;
     HIPCHK(ssk::launch_region_peaks(p, b->stream));
-    pk.n_regions = n_regions; pk.n_groups = n_groups; pk.regions_done = true;
+    pk.list.queued(n_regions, n_groups);
     return SS_OK;
 }
 
 int ss_batch_download_region_peaks(ss_batch *b, ss_region_peaks *out, uint32_t cap_regions)
 {
     SS_ON_DEVICE(b);
-    if (!b || (!out && b->peaks.n_regions)) return SS_ERR_INVALID_ARG;
-    if (!b->peaks.regions_done) return SS_ERR_INVALID_MODE;
-    if (cap_regions < b->peaks.n_regions) return SS_ERR_CAPACITY;
-    if (!b->peaks.n_regions) return ss_batch_sync(b);
-    return fetch(b, out, reinterpret_cast<const ss_region_peaks *>(b->peaks.results.p), b->peaks.n_regions);
+    return !b ? SS_ERR_INVALID_ARG : fetch_records(b, b->peaks.list.done, out, cap_regions, b->peaks.list.n_regions, b->peaks.results.p);
 }
 
 int ss_batch_download_group_peaks(ss_batch *b, ss_group_peaks *out, uint32_t cap_groups)
 {
     SS_ON_DEVICE(b);
-    if (!b || (!out && b->peaks.n_groups)) return SS_ERR_INVALID_ARG;
-    if (!b->peaks.regions_done) return SS_ERR_INVALID_MODE;
-    if (cap_groups < b->peaks.n_groups) return SS_ERR_CAPACITY;
-    if (!b->peaks.n_groups) return ss_batch_sync(b);
-    return fetch(b, out, reinterpret_cast<const ss_group_peaks *>(b->peaks.group_results.p), b->peaks.n_groups);
+    return !b ? SS_ERR_INVALID_ARG : fetch_records(b, b->peaks.list.done, out, cap_groups, b->peaks.list.n_groups, b->peaks.group_results.p);
 }
 
 int ss_batch_download_region_channel_peaks(ss_batch *b, float *true_pk, float *sample_pk, size_t cap_floats)
 {
     SS_ON_DEVICE(b);
     if (!b) return SS_ERR_INVALID_ARG;
-    if (!b->peaks.regions_done) return SS_ERR_INVALID_MODE;
-    const size_t n = (size_t)b->peaks.n_regions * b->cfg.channels;
+    if (!b->peaks.list.done) return SS_ERR_INVALID_MODE;
+    const size_t n = (size_t)b->peaks.list.n_regions * b->cfg.channels;
     if (cap_floats < n) return SS_ERR_CAPACITY;
     if (n && true_pk) HIPCHK(hipMemcpyAsync(true_pk, b->peaks.ch_true.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     if (n && sample_pk) HIPCHK(hipMemcpyAsync(sample_pk, b->peaks.ch_sample.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));

@@ -126,6 +126,20 @@ struct HostStage {
         return e;
     }
     void idle() { busy = false; }        // the owner has synchronised the stream
+    // the first `bytes` of the buffer, filled behind a take, on their way to `dst` on the device: one DMA, the event behind it
+    hipError_t queue(void *dst, size_t bytes, hipStream_t stream)
+    {
+        hipError_t e = hipMemcpyAsync(dst, buf.p, bytes, hipMemcpyHostToDevice, stream);
+        return e == hipSuccess ? sent(stream) : e;
+    }
+    // the staged upload in one call: `bytes` at `src` through the buffer to `dst`; `src` is free again when this returns
+    hipError_t send(void *dst, const void *src, size_t bytes, hipStream_t stream)
+    {
+        hipError_t e = take(bytes);
+        if (e != hipSuccess) return e;
+        std::memcpy(buf.p, src, bytes);
+        return queue(dst, bytes, stream);
+    }
 };
 
 // what ssk::launch_pcm_to_f32's wide reads of 24-bit samples may touch behind the last sample: every raw PCM buffer on the device is

@@ -62,20 +62,11 @@ hipError_t bank_sync(ss_meter_bank *m)
     return e;
 }
 
-// the first `bytes` of the staging buffer on their way to the device: one DMA, the event behind it
-int stage_send(ss_meter_bank *m, void *dst, size_t bytes)
-{
-    HIPCHK(hipMemcpyAsync(dst, m->stage.buf.p, bytes, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(m->stage.sent(m->stream));
-    return SS_OK;
-}
-
 // stage host bytes on the device through the page-locked copy
 int upload(ss_meter_bank *m, void *dst, const void *src, size_t bytes)
 {
-    HIPCHK(m->stage.take(bytes));
-    std::memcpy(m->stage.buf.p, src, bytes);
-    return stage_send(m, dst, bytes);
+    HIPCHK(m->stage.send(dst, src, bytes, m->stream));
+    return SS_OK;
 }
 
 // the f32 input of a call whose `samples` samples stand on the device at `bytes`: raw PCM is converted into m->in (the caller has
@@ -222,8 +213,7 @@ int add_ragged_host(ss_meter_bank *m, const void *const *pcm, const uint64_t *fr
         if (bytes) std::memcpy(dst, pcm[s], bytes);
         std::memset(dst + bytes, 0, padded - bytes);
     }
-    rc = stage_send(m, m->rag.p, head + body);
-    if (rc) return rc;
+    HIPCHK(m->stage.queue(m->rag.p, head + body, m->stream));
     const uint64_t *arr = reinterpret_cast<const uint64_t *>(m->rag.p);
     const float *in = nullptr;
     rc = device_input(m, m->rag.p + head, pl.total, format, &in);
@@ -231,15 +221,25 @@ int add_ragged_host(ss_meter_bank *m, const void *const *pcm, const uint64_t *fr
     return advance(m, pl, arr, in, arr + n, 0);
 }
 
+// the stream list of a reset: every index checked, then the list on the device at *dev (streams null — every stream: nothing to
+// check or send, *dev null)
+int stream_list(ss_meter_bank *m, const uint32_t *streams, uint32_t count, const uint32_t **dev)
+{
+    *dev = nullptr;
+    if (!streams) return SS_OK;
+    for (uint32_t i = 0; i < count; i++) if (streams[i] >= m->meter.n) return SS_ERR_INVALID_ARG;
+    HIPCHK(m->list.ensure(count));
+    *dev = m->list.p;
+    return upload(m, m->list.p, streams, count * sizeof(uint32_t));
+}
+
+// streams null: every stream
 int bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
 {
-    const uint32_t *dev = nullptr;
-    if (streams) {
-        HIPCHK(m->list.ensure(count));
-        int rc = upload(m, m->list.p, streams, count * sizeof(uint32_t));
-        if (rc) return rc;
-        dev = m->list.p;
-    }
+    const uint32_t *dev;
+    int rc = stream_list(m, streams, count, &dev);
+    if (rc) return rc;
+    if (!streams) count = m->meter.n;
     HIPCHK(ssk::launch_meter_bank_reset(m->meter.bank_params(), dev, count, m->stream));
     for (uint32_t i = 0; i < count; i++) m->fed[streams ? streams[i] : i] = 0;
     return SS_OK;
@@ -280,19 +280,27 @@ int column_tables(ss_meter_bank *m, uint32_t cols)
     return SS_OK;
 }
 
-// SS_GAIN_REFERENCE: every stream's integrated loudness after the last add — the readings read() returns, on the device
-int reference_gain(ss_meter_bank *m, const double **integrated, uint32_t *stride)
+// The column fold of a launch (ssk::BankSpectrumParams, ssk::BankTrackColumns: the seven fields have one name in both): the tables
+// of `cols` columns, the pink compensation and the gain — SS_GAIN_REFERENCE: every stream's integrated loudness after the last add,
+// the readings read() returns, left on the device by a launch of their own.
+template <class P>
+int column_fold(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db, P *q)
 {
+    int rc = column_tables(m, cols);
+    if (rc) return rc;
+    q->pink = m->spec_pink.p; q->bin_col = m->spec_bin_col.p; q->col_init = m->spec_col_init.p;
+    q->cols = cols; q->gain_db = gain_db;
+    if (gain_mode != SS_GAIN_REFERENCE) return SS_OK;
     HIPCHK(ssk::launch_meter_bank_readings(m->meter.bank_params(), m->readings.p, m->stream));
     static_assert(sizeof(ssk::MeterReading) % sizeof(double) == 0, "readings as doubles");
-    *integrated = &m->readings.p[0].integrated;
-    *stride = sizeof(ssk::MeterReading) / sizeof(double);
+    q->integrated = &m->readings.p[0].integrated;
+    q->integrated_stride = sizeof(ssk::MeterReading) / sizeof(double);
     return SS_OK;
 }
 
-// the spectrum launch of every (stream, row) and one copy of its results (`per_row` floats each) and statuses into page-locked memory
-int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, float gain_db, uint32_t per_row,
-                 float **vals, int32_t **status)
+// the spectrum launch of every (stream, row), one copy of its results (`per_row` floats each) and statuses into page-locked memory,
+// and from there to the caller
+int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, float gain_db, uint32_t per_row, float *vals, int32_t *status)
 {
     const uint32_t R = spec_rows(m);
     const size_t rows = (size_t)m->meter.n * R, fbytes = rows * per_row * sizeof(float), sbytes = rows * sizeof(int32_t);
@@ -302,20 +310,15 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
         HIPCHK(m->spec_pin.ensure(fbytes + sbytes));
     }
     ssk::BankSpectrumParams q = spectrum_params(m, m->spec_out.p, m->spec_status.p);
-    if (columns) {
-        int rc = column_tables(m, cols);
-        if (rc) return rc;
-        q.pink = m->spec_pink.p; q.bin_col = m->spec_bin_col.p; q.col_init = m->spec_col_init.p;
-        q.cols = cols; q.gain_db = gain_db;
-        if (gain_mode == SS_GAIN_REFERENCE && (rc = reference_gain(m, &q.integrated, &q.integrated_stride))) return rc;
-    }
+    int rc = columns ? column_fold(m, cols, gain_mode, gain_db, &q) : SS_OK;
+    if (rc) return rc;
     HIPCHK(ssk::launch_meter_bank_spectrum(q, columns, m->stream));
-    char *pin = reinterpret_cast<char *>(m->spec_pin.p);
+    unsigned char *pin = m->spec_pin.p;
     HIPCHK(hipMemcpyAsync(pin, m->spec_out.p, fbytes, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(pin + fbytes, m->spec_status.p, sbytes, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(bank_sync(m));
-    *vals = reinterpret_cast<float *>(pin);
-    *status = reinterpret_cast<int32_t *>(pin + fbytes);
+    std::memcpy(vals, pin, fbytes);
+    std::memcpy(status, pin + fbytes, sbytes);
     return SS_OK;
 }
 
@@ -351,12 +354,23 @@ ssk::BankTrackParams track_params(const ss_meter_bank *m)
     return p;
 }
 
-// a read-out's results behind its launch: `bytes` of trk_out into page-locked memory, waited for
-int track_fetch(ss_meter_bank *m, size_t bytes, unsigned char **pin)
+// Where a read-out's results stand in trk_out, in floats: the averaged curve at 0 and the peak-hold curve at `hold_at`, `plane` floats
+// each, then the update counts of the `rows` rows at `counts_at`.
+struct TrackOut {
+    size_t plane, hold_at, counts_at, rows;
+    size_t bytes() const { return counts_at * sizeof(float) + rows * sizeof(uint32_t); }
+};
+
+// a read-out's results behind its launch: trk_out into page-locked memory in one copy, waited for, and from there what the caller
+// asked for (a null pointer: not that one)
+int track_fetch(ss_meter_bank *m, const TrackOut &o, float *avg, float *hold, uint32_t *updates)
 {
-    HIPCHK(hipMemcpyAsync(m->spec_pin.p, m->trk_out.p, bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(m->spec_pin.p, m->trk_out.p, o.bytes(), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(bank_sync(m));
-    *pin = m->spec_pin.p;
+    const float *h = reinterpret_cast<const float *>(m->spec_pin.p);
+    if (avg) std::memcpy(avg, h, o.plane * sizeof(float));
+    if (hold) std::memcpy(hold, h + o.hold_at, o.plane * sizeof(float));
+    if (updates) std::memcpy(updates, h + o.counts_at, o.rows * sizeof(uint32_t));
     return SS_OK;
 }
 
@@ -481,8 +495,6 @@ int ss_meter_bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t coun
 {
     SS_ON_DEVICE(m);
     if (!m) return null_bank();
-    if (!streams) return bank_reset(m, nullptr, m->meter.n);
-    for (uint32_t i = 0; i < count; i++) if (streams[i] >= m->meter.n) return SS_ERR_INVALID_ARG;
     return bank_reset(m, streams, count);
 }
 
@@ -578,12 +590,7 @@ int ss_meter_bank_spectrum(ss_meter_bank *m, float *rows, size_t cap_floats, int
     const uint32_t nb = (uint32_t)m->bt->count;
     const size_t R = (size_t)m->meter.n * spec_rows(m);
     if (cap_floats < R * nb || cap_rows < R) return SS_ERR_CAPACITY;
-    float *v; int32_t *st;
-    int rc = spectrum_run(m, false, 0, SS_GAIN_FIXED, 0.0f, nb, &v, &st);
-    if (rc) return rc;
-    std::memcpy(rows, v, R * nb * sizeof(float));
-    std::memcpy(status, st, R * sizeof(int32_t));
-    return SS_OK;
+    return spectrum_run(m, false, 0, SS_GAIN_FIXED, 0.0f, nb, rows, status);
 }
 
 int ss_meter_bank_spectrum_columns(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db, float *out, size_t cap_floats,
@@ -596,12 +603,7 @@ int ss_meter_bank_spectrum_columns(ss_meter_bank *m, uint32_t cols, int gain_mod
     if (!m->spec_on) return SS_ERR_INVALID_MODE;
     const size_t R = (size_t)m->meter.n * spec_rows(m);
     if (cap_floats < R * cols || cap_rows < R) return SS_ERR_CAPACITY;
-    float *v; int32_t *st;
-    int rc = spectrum_run(m, true, cols, gain_mode, gain_db, cols, &v, &st);
-    if (rc) return rc;
-    std::memcpy(out, v, R * cols * sizeof(float));
-    std::memcpy(status, st, R * sizeof(int32_t));
-    return SS_OK;
+    return spectrum_run(m, true, cols, gain_mode, gain_db, cols, out, status);
 }
 
 int ss_meter_bank_spectrum_track_enable(ss_meter_bank *m, const ss_spectrum_ballistics *cfg)
@@ -644,16 +646,11 @@ int ss_meter_bank_spectrum_track_reset(ss_meter_bank *m, const uint32_t *streams
     if (!m) return null_bank();
     if (!m->trk_on) return SS_ERR_INVALID_MODE;
     ssk::BankTrackRow *meta = m->trk_meta.p + m->trk_cur * track_rows_of(m);
-    if (!streams) {
-        HIPCHK(ssk::launch_bank_spectrum_track_reset(meta, nullptr, m->meter.n, spec_rows(m), m->stream));
-        return SS_OK;
-    }
-    for (uint32_t i = 0; i < count; i++) if (streams[i] >= m->meter.n) return SS_ERR_INVALID_ARG;
-    if (!count) return SS_OK;
-    HIPCHK(m->list.ensure(count));
-    int rc = upload(m, m->list.p, streams, count * sizeof(uint32_t));
+    if (streams && !count) return SS_OK;                                           // (an empty list: nothing is staged)
+    const uint32_t *dev;
+    int rc = stream_list(m, streams, count, &dev);
     if (rc) return rc;
-    HIPCHK(ssk::launch_bank_spectrum_track_reset(meta, m->list.p, count, spec_rows(m), m->stream));
+    HIPCHK(ssk::launch_bank_spectrum_track_reset(meta, dev, streams ? count : m->meter.n, spec_rows(m), m->stream));
     return SS_OK;
 }
 
@@ -666,21 +663,14 @@ int ss_meter_bank_spectrum_tracked(ss_meter_bank *m, float *avg_rows, float *hol
     const size_t R = track_rows_of(m), plane = R * m->bt->count;
     if (((avg_rows || hold_rows) && cap_floats < plane) || (updates && cap_rows < R)) return SS_ERR_CAPACITY;
     // the curves asked for, then the counts: one copy
-    const size_t n_planes = (avg_rows ? 1u : 0u) + (hold_rows ? 1u : 0u), bytes = n_planes * plane * sizeof(float) + R * sizeof(uint32_t);
-    int rc = track_room(m, bytes);
+    const size_t hold_at = avg_rows ? plane : 0;
+    const TrackOut o{plane, hold_at, hold_at + (hold_rows ? plane : 0), R};
+    int rc = track_room(m, o.bytes());
     if (rc) return rc;
     float *base = reinterpret_cast<float *>(m->trk_out.p);
-    float *d_avg = avg_rows ? base : nullptr, *d_hold = hold_rows ? base + (avg_rows ? plane : 0) : nullptr;
-    HIPCHK(ssk::launch_bank_spectrum_tracked_rows(track_params(m), d_avg, d_hold, reinterpret_cast<uint32_t *>(base + n_planes * plane),
-                                                  m->stream));
-    unsigned char *pin;
-    rc = track_fetch(m, bytes, &pin);
-    if (rc) return rc;
-    const float *h = reinterpret_cast<const float *>(pin);
-    if (avg_rows) std::memcpy(avg_rows, h, plane * sizeof(float));
-    if (hold_rows) std::memcpy(hold_rows, h + (avg_rows ? plane : 0), plane * sizeof(float));
-    if (updates) std::memcpy(updates, h + n_planes * plane, R * sizeof(uint32_t));
-    return SS_OK;
+    HIPCHK(ssk::launch_bank_spectrum_tracked_rows(track_params(m), avg_rows ? base : nullptr, hold_rows ? base + o.hold_at : nullptr,
+                                                  reinterpret_cast<uint32_t *>(base + o.counts_at), m->stream));
+    return track_fetch(m, o, avg_rows, hold_rows, updates);
 }
 
 int ss_meter_bank_spectrum_tracked_columns(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db, float *avg_cols,
@@ -692,26 +682,15 @@ int ss_meter_bank_spectrum_tracked_columns(ss_meter_bank *m, uint32_t cols, int 
     if (!m->trk_on) return SS_ERR_INVALID_MODE;
     const size_t R = track_rows_of(m), plane = R * cols;
     if (((avg_cols || hold_cols) && cap_floats < plane) || (updates && cap_rows < R)) return SS_ERR_CAPACITY;
-    const size_t bytes = 2 * plane * sizeof(float) + R * sizeof(uint32_t);          // both curves (a few KB per stream), then the counts
-    int rc = track_room(m, bytes);
+    const TrackOut o{plane, plane, 2 * plane, R};                                    // both curves (a few KB per stream), then the counts
+    int rc = track_room(m, o.bytes());
     if (rc) return rc;
-    rc = column_tables(m, cols);
-    if (rc) return rc;
-    float *base = reinterpret_cast<float *>(m->trk_out.p);
     ssk::BankTrackColumns c{};
-    c.pink = m->spec_pink.p; c.bin_col = m->spec_bin_col.p; c.col_init = m->spec_col_init.p;
-    c.cols = cols; c.gain_db = gain_db;
-    if (gain_mode == SS_GAIN_REFERENCE && (rc = reference_gain(m, &c.integrated, &c.integrated_stride))) return rc;
-    c.avg = base; c.hold = base + plane; c.updates = reinterpret_cast<uint32_t *>(base + 2 * plane);
+    if ((rc = column_fold(m, cols, gain_mode, gain_db, &c))) return rc;
+    float *base = reinterpret_cast<float *>(m->trk_out.p);
+    c.avg = base; c.hold = base + o.hold_at; c.updates = reinterpret_cast<uint32_t *>(base + o.counts_at);
     HIPCHK(ssk::launch_bank_spectrum_tracked_columns(track_params(m), c, m->stream));
-    unsigned char *pin;
-    rc = track_fetch(m, bytes, &pin);
-    if (rc) return rc;
-    const float *h = reinterpret_cast<const float *>(pin);
-    if (avg_cols) std::memcpy(avg_cols, h, plane * sizeof(float));
-    if (hold_cols) std::memcpy(hold_cols, h + plane, plane * sizeof(float));
-    if (updates) std::memcpy(updates, h + 2 * plane, R * sizeof(uint32_t));
-    return SS_OK;
+    return track_fetch(m, o, avg_cols, hold_cols, updates);
 }
 
 }  // extern "C"
