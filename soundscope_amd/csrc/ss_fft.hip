@@ -94,7 +94,7 @@ typedef __attribute__((address_space(3))) char lds_char;
 __device__ __forceinline__ void lds_fmax(lds_f32 *p, float v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }   // ds_max_f32
 template <bool LDS_TABLE = false, bool COLS = false>
 __device__ __forceinline__ void fft4096_epilogue(const v2f *xb, int t, uint32_t first_bin, uint32_t n_bins,
-                                                 float db_offset, const float *__restrict__ offpink,
+                                                 float lg0, const float *__restrict__ offpink,
                                                  float *o_mid, float *o_side, bool store_side = true,
                                                  float side_off = 0.0f, float *colbuf = nullptr, const uint2 *coltab = nullptr,
                                                  const uint2 *colbins = nullptr)
@@ -110,18 +110,18 @@ __device__ __forceinline__ void fft4096_epilogue(const v2f *xb, int t, uint32_t 
     // per-phase clock profile (-DSS_FFT_PROF) this order takes a fifth off the epilogue's wave time; the kernel time does
     // not move (the other two workgroups of the CU cover the wait), it is kept because it also frees two spilled registers.
     constexpr float kDb = 3.01029995663981195f;
-    // (wave-uniform, but a VALU division: pinned to a scalar register instead of a vector register held across the window loop)
-    const float lg0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint((-150.0f - db_offset) / kDb)));
+    // lg0 = (-150 - db_offset) / kDb is a launch constant (FftBatchParams::lg0, ssk::fft4096_lg0): it arrives in a scalar register
     float4 op[2];
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const uint32_t g = (uint32_t)t + 256u * i;
+        if (LDS_TABLE) continue;                    // (read from LDS inside the group, below)
         op[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         // byte offset recomputed per window (opaque to the optimiser): hoisted out of the window loop the two 64-bit row
         // addresses cost four vector registers for its whole length — this kernel sits at the three-waves-per-SIMD edge
         uint32_t boff = 16u * g;
         asm volatile("" : "+v"(boff));
-        if (!LDS_TABLE && g < ngroups) op[i] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(offpink) + boff);   // table padded to the row stride
+        if (g < ngroups) op[i] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(offpink) + boff);   // table padded to the row stride
     }
     float rm[2][4], rs[2][4];
     // COLS: a group's eight values are folded as soon as they exist (nothing is stored, so nothing has to wait for the loads of
@@ -203,27 +203,32 @@ __device__ __forceinline__ void fft4096_epilogue(const v2f *xb, int t, uint32_t 
             const v2f so2 = {side_off, side_off};
             const v2f osa = v2f{op[i].x, op[i].y} + so2, osb = v2f{op[i].z, op[i].w} + so2;
             const float ops[4] = {osa.x, osa.y, osb.x, osb.y};
-            // (eight values: a chain of three v_min3_f32 and one v_min_f32; left to the compiler the fminf tree was three v_min_f32 and two v_min3_f32)
-            auto min3 = [](float a, float b, float c) -> float { return __builtin_fminf(__builtin_fminf(a, b), c); };
-            const float qmin = fminf(min3(min3(min3(qm[0], qm[1], qm[2]), qm[3], qs[0]), qs[1], qs[2]), qs[3]);
-            if (__builtin_expect(__ballot(qmin == 0.0f) == 0ull, 1)) {
+            // (eight values: three v_min3_f32 and one v_min_f32, written out: from fminf the compiler puts a v_max_f32 x, x, x in front
+            // of the first operands to quiet a signalling NaN, which the result of a packed fma never is)
+            auto min3 = [](float a, float b, float c) -> float { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; };
+            auto min2 = [](float a, float b) -> float { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; };
+            const float qmin = min2(min3(min3(min3(qm[0], qm[1], qm[2]), qm[3], qs[0]), qs[1], qs[2]), qs[3]);
+#if defined(__HIP_DEVICE_COMPILE__)
+            __builtin_amdgcn_sched_barrier(0);          // the logarithms stay behind the packed arithmetic, as they always stood
+#endif
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                rm[i][e] = fmaf(__log2f(qm[e]), kDb, opv[e]);
+                rs[i][e] = fmaf(__log2f(qs[e]), kDb, ops[e]);
+            }
+            // the rare wave rewrites its zero bins in place (log2(0) = -inf stood there): the two paths share every register, so
+            // nothing is copied where they meet
+            if (__builtin_expect(__ballot(qmin == 0.0f) != 0ull, 0)) {
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    rm[i][e] = fmaf(__log2f(qm[e]), kDb, opv[e]);
-                    rs[i][e] = fmaf(__log2f(qs[e]), kDb, ops[e]);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    rm[i][e] = fmaf(qm[e] == 0.0f ? lg0 : __log2f(qm[e]), kDb, opv[e]);
-                    rs[i][e] = qs[e] == 0.0f ? fmaf(lg0, kDb, opv[e]) : fmaf(__log2f(qs[e]), kDb, ops[e]);      // a zero is -150 whatever the exponent
+                    const float fl = fmaf(lg0, kDb, opv[e]);                    // a zero is -150 whatever the exponent
+                    rm[i][e] = qm[e] == 0.0f ? fl : rm[i][e];
+                    rs[i][e] = qs[e] == 0.0f ? fl : rs[i][e];
                 }
             }
             if (COLS) fold_group(i, g);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) { rm[i][e] = 0.0f; rs[i][e] = 0.0f; }
         }
+        // (a lane without a group forms no values: its stores stand under the same test)
     }
     if (COLS) return;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -376,6 +381,17 @@ __device__ __forceinline__ int block_exp(uint32_t a, uint32_t b)
     const int e = ((int)a - (int)b + (1 << 22)) >> 23;
     return e < -60 ? -60 : (e > 60 ? 60 : e);
 }
+// The same two for WAVE-UNIFORM levels, on the scalar unit (k_fft4096_ms1 settles an exponent per window from levels that already
+// stand in scalar registers).  The pin between the two comparisons keeps them from being merged into v_med3_i32, which has no scalar
+// form and took the exponent, and every comparison against it, to the vector unit.
+__device__ __forceinline__ int clamp60_uniform(int e)
+{
+    e = e < -60 ? -60 : e;
+    asm("" : "+s"(e));
+    return e > 60 ? 60 : e;
+}
+__device__ __forceinline__ int block_exp_uniform(uint32_t a, uint32_t b) { return clamp60_uniform(((int)a - (int)b + (1 << 22)) >> 23); }
+__device__ __forceinline__ int block_exp_energy_uniform(uint32_t a, uint32_t b) { return clamp60_uniform(((int)a - (int)b + (1 << 23)) >> 24); }
 __device__ __forceinline__ float exp2i(int e) { return __uint_as_float((uint32_t)(127 + e) << 23); }      // |e| <= 126
 __device__ __forceinline__ float uniform_f(float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
 // side_off of a block exponent
@@ -591,8 +607,8 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms(FftBatchParams p)
         __syncthreads();
         // ---- epilogue: groups of four consecutive bins per thread, 16-byte stores
         float *o_mid = outp + (size_t)(w - w_begin) * out_win_stride;
-        fft4096_epilogue(xbuf[0], t, p.first_bin, p.n_bins, p.db_offset, p.offpink, o_mid, o_mid + p.bin_stride, true, block_off(E0));
-        if (two) fft4096_epilogue(xbuf[1], t, p.first_bin, p.n_bins, p.db_offset, p.offpink, o_mid + out_win_stride,
+        fft4096_epilogue(xbuf[0], t, p.first_bin, p.n_bins, p.lg0, p.offpink, o_mid, o_mid + p.bin_stride, true, block_off(E0));
+        if (two) fft4096_epilogue(xbuf[1], t, p.first_bin, p.n_bins, p.lg0, p.offpink, o_mid + out_win_stride,
                                   o_mid + out_win_stride + p.bin_stride, true, block_off(E1));
         // a row whose WINDOWED samples are all zero reads the reference's floor (the transform of zeros, analyzer.rs:20-22)
         if (__builtin_expect(X[0] == 0u || X[1] == 0u, 0))
@@ -806,7 +822,7 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
         for (int g = 2; g < NH; g++) { mm = umax(mm, Pm[g]); md = umax(md, Pd[g]); }
         thr_m = mm + 0x800000u; thr_d = md + 0x800000u;
         inner_ok = mm != 0u && md != 0u && Pm[1] <= thr_m && Pd[1] <= thr_d;
-        if (mm != 0u && md != 0u) rescale(block_exp(mm, md));
+        if (mm != 0u && md != 0u) rescale(block_exp_uniform(mm, md));
     };
     presettle();
     PhaseMark mark;
@@ -847,8 +863,7 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
                 uint32_t Xm, Xd;
                 read_energies2(xlev, Xm, Xd);
                 if (Xm != 0u && Xd != 0u && Xm < 0x7F800000u && Xd < 0x7F800000u) {      // (a square that under- or overflowed: E stays)
-                    int T = E + block_exp_energy(Xm, Xd);    // (the side halves carry 2^E already)
-                    T = T < -60 ? -60 : (T > 60 ? 60 : T);
+                    const int T = clamp60_uniform(E + block_exp_energy_uniform(Xm, Xd));    // (the side halves carry 2^E already)
                     const float sc = rescale(T);
 #pragma unroll
                     for (int j = 0; j < 8; j++) z[j].y *= sc;      // (the frames j + 8 are windowed from the rescaled registers)
@@ -867,10 +882,29 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
         xbuf[X1B(0, tb, hi)] = z[R16(0)];
 #pragma unroll
         for (int ka = 1; ka < 16; ka++) xbuf[X1B(ka, tb, hi)] = r16_pass1_tw<TWN>(ka, z[R16(ka)], tw1);
+        // (nx is read under `more` alone.  The entering hop's requests are 2048 bytes apart and an immediate reaches 4095: one
+        // scalar base per pair of requests, pinned to a scalar register pair, plus the lane's 32-bit byte offset — left alone the
+        // compiler forms the addresses with two 64-bit vector additions per pair and window)
+        if (more) {
+            // (a pointer to GLOBAL memory by type: behind the pin the compiler no longer sees where it came from)
+#if defined(__HIP_DEVICE_COMPILE__)
+            typedef __attribute__((address_space(1))) const char global_char;
+            typedef __attribute__((address_space(1))) const float2 global_float2;
+#else
+            typedef const char global_char;
+            typedef const float2 global_float2;
+#endif
+            global_char *nb = (global_char *)(src + (size_t)(w + 1 - w_begin) * p.hop + 256 * (16 - HS));
+            uint32_t toff = 8u * (uint32_t)t;           // (opaque per window: hoisted, it comes back widened to a 64-bit register pair)
+            asm volatile("" : "+v"(toff));
 #pragma unroll
-        for (int q = 0; q < HS; q++) {
-            nx[q] = make_float2(0.f, 0.f);
-            if (more) nx[q] = src[(size_t)(w + 1 - w_begin) * p.hop + t + 256 * (16 - HS + q)];
+            for (int q = 0; q < HS; q++) {
+                if ((q & 1) == 0) {
+                    if (q) nb += 4096;
+                    asm("" : "+s"(nb));
+                }
+                nx[q] = *(global_float2 *)(nb + toff + 2048 * (q & 1));
+            }
         }
         mark(0);
         __syncthreads();
@@ -905,7 +939,7 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
             presettle();
         }
         float *o_mid = outp + (size_t)(w - w_begin) * out_win_stride;
-        fft4096_epilogue<true, COLS>(xbuf, t, p.first_bin, p.n_bins, p.db_offset, offp, o_mid, o_mid + p.bin_stride, true, soff, colbuf, coltab, p.col_bins);
+        fft4096_epilogue<true, COLS>(xbuf, t, p.first_bin, p.n_bins, p.lg0, offp, o_mid, o_mid + p.bin_stride, true, soff, colbuf, coltab, p.col_bins);
         // Level 0 is a row of zeros — or of zeros and NaN, which fmaxf skipped.  A NaN sample makes every bin of the transform NaN and
         // the window is refused like any other that holds one: the NaN rows stand, no floor goes over them.  (One published bin, the
         // same for every thread: the branch is workgroup-uniform; xbuf is not rewritten before the loop-end barrier.)
@@ -1075,7 +1109,7 @@ __global__ __launch_bounds__(256, kFftPairwWaves) void k_fft4096_pairw(FftBatchP
         __syncthreads();
         SS_PRIO_LO();
         float *o_first = outp + (size_t)(pp - pp_begin) * 2u * row_stride;
-        fft4096_epilogue(xbuf, t, p.first_bin, p.n_bins, p.db_offset, p.offpink, o_first, o_first + row_stride, two, block_off(E));
+        fft4096_epilogue(xbuf, t, p.first_bin, p.n_bins, p.lg0, p.offpink, o_first, o_first + row_stride, two, block_off(E));
         if (__builtin_expect(zrow_a || (two && zrow_b), 0))
             fft4096_floor_rows(t, p.n_bins, p.db_offset, p.offpink, o_first, o_first + row_stride, zrow_a, two && zrow_b);
         if (__builtin_expect(bad_a || bad_b, 0))
@@ -1166,7 +1200,7 @@ __global__ __launch_bounds__(256, kFftWaves) void k_fft4096_ms_anyhop(FftBatchPa
         for (int kc = 0; kc < 16; kc++) xbuf[kc * 256 + SPEC_POS(t)] = z[R16(kc)];
         __syncthreads();
         float *o_mid = outp + (size_t)(w - w_begin) * out_win_stride;
-        fft4096_epilogue(xbuf, t, p.first_bin, p.n_bins, p.db_offset, p.offpink, o_mid, o_mid + p.bin_stride, true, block_off(E));
+        fft4096_epilogue(xbuf, t, p.first_bin, p.n_bins, p.lg0, p.offpink, o_mid, o_mid + p.bin_stride, true, block_off(E));
         if (__builtin_expect(Xm == 0u || Xd == 0u, 0))
             fft4096_floor_rows(t, p.n_bins, p.db_offset, p.offpink, o_mid, o_mid + p.bin_stride, Xm == 0u, Xd == 0u);
     }

@@ -316,6 +316,7 @@ ssk::FftBatchParams spectrum_params(const ssk::SpecPlan &plan, const FftTables &
     if (plan.kernel == SpecKernel::ms1 || plan.kernel == SpecKernel::ms || plan.kernel == SpecKernel::ms_anyhop ||
         plan.kernel == SpecKernel::pairw) {
         p.db_offset = (float)(10.0 * std::log10(4.0 / ((double)ft.n * (double)ft.n)));
+        p.lg0 = ssk::fft4096_lg0(p.db_offset);
         p.offpink = pink ? bt.offpink4096_dev.p : bt.off4096_dev.p;
         p.publish_mask = ssk::fft4096_publish_mask(p.first_bin, p.n_bins);
     } else {

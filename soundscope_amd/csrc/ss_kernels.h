@@ -56,6 +56,7 @@ struct FftBatchParams {
     uint32_t bin_stride;         // floats between output rows (n_bins rounded up to 4: 16-B aligned rows)
     uint32_t windows_per_block;  // 4096 kernel
     float db_offset;             // 10*log10(4/N^2) (4096) or 20*log10(4/N) (generic)
+    float lg0;                   // 4096 kernels: fft4096_lg0(db_offset), the log operand of an exactly-zero squared magnitude
     uint32_t publish_mask;       // 4096 kernels: bit kc set when bins [256kc, 256kc+255] hold a retained bin or a mirror
     const uint32_t *windows_of;   // ragged batches: windows of each stream (nullable = n_windows for all)
     // columns-only spectrum (N3 fused into the epilogue; N = 4096 stereo at hop 1024): the rows are never stored, each
@@ -76,6 +77,10 @@ struct FftBatchParams {
     uint32_t done_value;
 };
 
+// N = 4096 kernels: the value that stands in for log2(q) where a squared magnitude q is exactly zero, so that the dB epilogue's
+// fma(lg0, 10 log10(2), db_offset + pink) lands on -150 + pink.  A launch constant, formed once on the host: the correctly
+// rounded f32 quotient (host code is built without fast-math), the bits the kernels' own division gave per window before.
+inline float fft4096_lg0(float db_offset) { return (-150.0f - db_offset) / 3.01029995663981195f; }
 // N = 4096 kernels: bit kc set when bins [256 kc, 256 kc + 255] hold a retained bin or the mirror 4096 - k of one (the other
 // blocks of the transform are not published to LDS)
 inline uint32_t fft4096_publish_mask(uint32_t first_bin, uint32_t n_bins)
