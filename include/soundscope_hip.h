@@ -815,6 +815,54 @@ int ss_batch_corpus_spectrum(ss_batch *b, float *mean_db, float *max_db, size_t 
  * windows per stream (either may be NULL); chunks > 1: partial sums per run, added in run order by a second launch (one long file);
  * chunks == 1: one launch (many streams).  The results depend on it in the last bits of the f64 sums only. */
 int ss_batch_spectrum_stats_plan(const ss_batch *b, uint32_t *chunks, uint32_t *chunk_windows);
+/* A spectrogram per stream: time on one axis, the chart's log frequency on the other, reduced on the device from the rows a pass
+ * left to a picture the size of the screen — [stream][fft_channel][t_cols][f_cols] f32.  Not in the reference (it shows one
+ * spectrum at a time); the waveform side has this shape already (ss_batch_render_waveform).
+ * Cell (s, r, t, c) is the maximum of clamp(v + gain, -100, 0), in f32, over
+ *   - the windows w of stream s with w_min <= w < min(w_max, n_windows_s) and floor((w - w_min) * t_cols / (w_max - w_min)) == t
+ *     (64-bit integers; the rule of the waveform columns), n_windows_s the stream's own count (ss_batch_stream_shape for ragged
+ *     batches; rows behind that count are never read), and
+ *   - the bins i of row (s, w, r) with floor(chart_x[i] / 100 * f_cols) == c, the last column closed: the column map of
+ *     ss_batch_render_spectrum.
+ * v is the value ss_batch_download_fft returns; gain is gain_db, or -13 - (float)integrated of stream s for SS_GAIN_REFERENCE, as
+ * in ss_batch_render_spectrum.  A NaN value is skipped: a refused window's row is all NaN and drops out of its own row's cells and
+ * of nothing else.  An infinity is clamped like any value.  A cell without a window, without a bin, or with only NaN values is
+ * NaN.  x -> clamp(x + gain) is monotone, so the device takes the maxima first and applies the gain once per cell; a maximum is
+ * exact in any order, so two calls (and the two plans below) agree value for value.
+ * Beside ss_batch_render_spectrum: every cell equals the maximum over its windows of ss_batch_render_spectrum(f_cols, the same
+ * gain)'s columns, NaN positions included — except for a refused window, whose NaN values ss_batch_render_spectrum draws at the
+ * chart's floor (-100 in every column that owns a bin) and this call skips.
+ * SS_BATCH_FFT_COLUMNS batches: the pass has reduced frequency and applied its gain (ss_batch_set_columns_gain), so the
+ * spectrogram is the time maximum of the stored columns: f_cols must equal spectrum_columns (SS_ERR_INVALID_ARG otherwise),
+ * gain_mode and gain_db are not read, and the result equals a full-row batch's of the same input under the same gain — except
+ * that a refused window reads -100 there, as it does in the stored columns.
+ * ss_batch_spectrogram copies the view and queues on the batch's stream like ss_batch_spectrum_stats: nothing is copied back or
+ * waited for; a later call replaces the result.  The result's buffer is the call's own (not ss_batch_render_spectrum's), allocated
+ * at a batch's first call and grown by a larger view: a batch that never calls it allocates and launches exactly what it did before.
+ * Status codes, all checked before anything is queued: a null batch or view, t_cols or f_cols out of range, w_max <= w_min, an
+ * unknown gain mode, first_stream + count > n_streams: SS_ERR_INVALID_ARG; a batch without SS_BATCH_FFT, SS_GAIN_REFERENCE
+ * without SS_BATCH_LUFS, a download before the first call: SS_ERR_INVALID_MODE; cap_floats too small: SS_ERR_CAPACITY.
+ * n_windows == 0 is valid: every cell is NaN. */
+typedef struct ss_spectrogram_view {
+    uint32_t t_cols;     /* time columns, 1 .. 4096                                                     */
+    uint32_t f_cols;     /* frequency columns, 1 .. 512 (ss_batch_render_spectrum's chart columns)       */
+    uint32_t w_min;      /* first window of the view                                                     */
+    uint32_t w_max;      /* one past the last; > w_min; may lie beyond a stream's windows                */
+    int32_t gain_mode;   /* SS_GAIN_FIXED / SS_GAIN_REFERENCE                                            */
+    float gain_db;
+} ss_spectrogram_view;   /* 24 bytes */
+/* after ss_batch_run: reduce every stream's rows to the view's cells */
+int ss_batch_spectrogram(ss_batch *b, const ss_spectrogram_view *v);
+/* verification utility: how ss_batch_spectrogram cuts this view — `runs` workgroups of `run_windows` consecutive windows per time
+ * column (either may be NULL); runs > 1: partial maxima per run, joined by a second launch (one long file, few time columns);
+ * runs == 1: one launch (many streams).  The results do not depend on it. */
+int ss_batch_spectrogram_plan(const ss_batch *b, const ss_spectrogram_view *v, uint32_t *runs, uint32_t *run_windows);
+/* `count` streams from first_stream on, [count][fft_channels][t_cols][f_cols] of the last view, in one transfer.  Waits for the
+ * batch's stream. */
+int ss_batch_download_spectrogram(ss_batch *b, uint32_t first_stream, uint32_t count, float *out, size_t cap_floats);
+/* the windows [*first, *end) time column t of a view owns, before the cut at a stream's own window count: the arithmetic of the
+ * device; host arithmetic.  (0, 0) for a null view, t_cols out of range, w_max <= w_min and for t >= t_cols. */
+void ss_spectrogram_column_windows(const ss_spectrogram_view *v, uint32_t t, uint32_t *first, uint32_t *end);
 /* [stream][cols][2] f32 (min, max) of the decimation bins x_min <= i < x_max */
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max);
 int ss_batch_download_waveform_columns(ss_batch *b, uint32_t stream, float *out, size_t cap_floats);

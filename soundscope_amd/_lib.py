@@ -54,6 +54,7 @@ SYMBOLS = [
     "ss_batch_loudness_regions", "ss_batch_download_region_results", "ss_batch_download_group_results", "ss_batch_group_histograms",
     "ss_batch_peak_series", "ss_batch_peak_series_plan", "ss_batch_download_peak_series", "ss_batch_peak_regions",
     "ss_batch_download_region_peaks", "ss_batch_download_group_peaks", "ss_batch_download_region_channel_peaks",
+    "ss_batch_spectrogram", "ss_batch_spectrogram_plan", "ss_batch_download_spectrogram", "ss_spectrogram_column_windows",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -147,6 +148,11 @@ class RegionPeaks(C.Structure):
 class GroupPeaks(C.Structure):
     _fields_ = [("true_peak", C.c_double), ("sample_peak", C.c_double),
                 ("true_peak_region", C.c_uint32), ("sample_peak_region", C.c_uint32), ("n_over", C.c_uint64)]
+
+
+class SpectrogramView(C.Structure):
+    _fields_ = [("t_cols", C.c_uint32), ("f_cols", C.c_uint32), ("w_min", C.c_uint32), ("w_max", C.c_uint32),
+                ("gain_mode", C.c_int32), ("gain_db", C.c_float)]
 
 
 class MeterReading(C.Structure):
@@ -326,6 +332,10 @@ def _bind(lib):
         "ss_batch_download_spectrum_stats": (C.c_int, [vp, C.c_uint32, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_batch_corpus_spectrum": (C.c_int, [vp, f32p, f32p, C.c_size_t, u64p, C.c_uint32]),
         "ss_batch_spectrum_stats_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_batch_spectrogram": (C.c_int, [vp, C.POINTER(SpectrogramView)]),
+        "ss_batch_spectrogram_plan": (C.c_int, [vp, C.POINTER(SpectrogramView), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_batch_download_spectrogram": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, C.c_size_t]),
+        "ss_spectrogram_column_windows": (None, [C.POINTER(SpectrogramView), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

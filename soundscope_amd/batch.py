@@ -245,6 +245,55 @@ class Batch:
                                                 cnt.ctypes.data_as(C.POINTER(C.c_uint64)), cnt.size))
         return mean, mx, cnt
 
+    # -- one picture per stream: time columns x chart columns, the maximum of every cell's windows and bins
+    def _spectrogram_view(self, t_cols, f_cols, w_min, w_max, gain_db):
+        mode = L.SS_GAIN_REFERENCE if gain_db is None else L.SS_GAIN_FIXED
+        return L.SpectrogramView(int(t_cols), int(f_cols), int(w_min), int(self.layout.n_windows if w_max is None else w_max),
+                                 mode, 0.0 if gain_db is None else float(gain_db))
+
+    def spectrogram(self, t_cols, f_cols, w_min=0, w_max=None, gain_db=None):
+        """Queue the reduction of the windows [w_min, w_max) of every stream to t_cols x f_cols cells behind run() (no copy, no
+        wait): time column t owns the windows with floor((w - w_min) * t_cols / (w_max - w_min)) == t, frequency column c the bins
+        render_spectrum(f_cols) gives it; a cell is the maximum of clamp(dB + gain, -100, 0), NaN where it holds no value.
+        w_max=None: the layout's n_windows; gain_db=None: the reference's per-file rule -13 - integrated.  Columns-only batches:
+        f_cols must be spectrum_columns, and the gain is the pass's own."""
+        v = self._spectrogram_view(t_cols, f_cols, w_min, w_max, gain_db)
+        _check(L.lib().ss_batch_spectrogram(self._h, C.byref(v)))
+        self._spectrogram_shape = (int(self.layout.fft_channels), int(t_cols), int(f_cols))
+
+    def spectrogram_plan(self, t_cols, f_cols, w_min=0, w_max=None, gain_db=None):
+        """(runs, run_windows): how spectrogram() cuts the windows of a time column of this view (runs > 1: partial maxima and a
+        second launch)."""
+        v = self._spectrogram_view(t_cols, f_cols, w_min, w_max, gain_db)
+        r, w = C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_batch_spectrogram_plan(self._h, C.byref(v), C.byref(r), C.byref(w)))
+        return r.value, w.value
+
+    def spectrograms(self, first=0, count=None):
+        """[count][fft_channels][t_cols][f_cols] f32 of the last spectrogram(): `count` streams from `first` on (None: all that
+        follow) in one copy.  Before any spectrogram() the library refuses."""
+        count = int(self.cfg.n_streams) - int(first) if count is None else int(count)
+        out = np.empty((max(count, 0),) + getattr(self, "_spectrogram_shape", (0, 0, 0)), np.float32)
+        _check(L.lib().ss_batch_download_spectrogram(self._h, int(first), count, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def spectrogram_of(self, stream):
+        """[fft_channels][t_cols][f_cols] f32 of one stream after spectrogram()."""
+        return self.spectrograms(stream, 1)[0]
+
+    def windows_between(self, t0_s, t1_s):
+        """(w_min, w_max): the windows that lie wholly inside the time range [t0_s, t1_s] seconds — window w covers the frames
+        [first + w * hop, first + w * hop + fft_n), first = (fft_n // hop + 1) * hop - fft_n (where the pass puts window 0) —
+        cut to the layout's n_windows; w_max == w_min where none does."""
+        rate, n, hop = int(self.cfg.sample_rate), int(self.cfg.fft_n), int(self.cfg.hop_frames)
+        first = (n // hop + 1) * hop - n
+        # whole frames inside the range (a millionth of a frame forgives the rounding of seconds x rate)
+        f0, f1 = max(0, int(np.ceil(float(t0_s) * rate - 1e-6))), int(np.floor(float(t1_s) * rate + 1e-6))
+        lo = max(0, -((first - f0) // hop))                                  # smallest w with first + w * hop >= f0
+        hi = (f1 - n - first) // hop + 1 if f1 >= first + n else 0          # one past the largest w with first + w * hop + n <= f1
+        lo, hi = min(lo, int(self.layout.n_windows)), min(hi, int(self.layout.n_windows))
+        return lo, max(lo, hi)
+
     def render_waveform(self, cols, x_min, x_max):
         _check(L.lib().ss_batch_render_waveform(self._h, cols, int(x_min), int(x_max)))
         self._render_wave_cols = cols

@@ -136,6 +136,18 @@ struct Peaks {
     DevBuf<ssk::GroupPeaks> group_results;
 };
 
+// spectrogram (ss_batch_spectrogram): all of it allocated at the batch's first call and grown by a larger view, so a batch that
+// never asks holds none of it
+struct Spectrogram {
+    bool done = false;                          // a view has been queued: there is something to download
+    ss_spectrogram_view view{};                 // of the last call that was queued
+    uint32_t map_cols = 0;                      // the f_cols bin_col was built for (0: not yet)
+    HostStage stage;                            // bin_col on its way to the device
+    DevBuf<uint16_t> bin_col;                   // SpectrogramParams::bin_col (full-row batches)
+    DevBuf<float> out;                          // [stream][fft_channel][t_cols][f_cols]
+    DevBuf<uint32_t> part;                      // SpectrogramParams::part (plans with runs)
+};
+
 }  // namespace
 
 struct ss_batch {
@@ -179,6 +191,7 @@ struct ss_batch {
     SpecStats stats;
     Regions regions;
     Peaks peaks;
+    Spectrogram spectrogram;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
     int tp_arith = SS_TP_ARITH_F32;   // SS_TP_ARITH_*: the reference's width unless the caller opts into the f16 split
@@ -455,6 +468,22 @@ int upload_column_tables(ss_batch *b)
     HIPCHK(b->cols.init.upload(cinit));
     HIPCHK(b->cols.groups.upload(cg));
     return SS_OK;
+}
+
+// the chart's column map (ss_batch_render_spectrum, ss_batch_spectrogram): column c owns the bins [start[c], start[c + 1]) — the
+// column of a bin is floor(chart_x / 100 * cols), the last column closed on the right; chart_x ascends
+std::vector<uint32_t> spectrum_col_start(const ss_batch *b, uint32_t cols)
+{
+    const uint32_t n_bins = b->lay.n_bins;
+    std::vector<uint32_t> start(cols + 1, n_bins);
+    uint32_t c = 0;
+    start[0] = 0;
+    for (uint32_t i = 0; i < n_bins; i++) {
+        const uint32_t ci = spectrum_column_of(b->bt->chart_x[i], cols);
+        while (c < ci) start[++c] = i;
+    }
+    while (c < cols) start[++c] = n_bins;
+    return start;
 }
 
 // the decimation is fused into the time-domain pass when that pass runs and a bin (plus its shared edge sample)
@@ -1185,17 +1214,7 @@ int ss_batch_render_spectrum(ss_batch *b, uint32_t cols, int gain_mode, float ga
     const ss_batch_layout &L = b->lay;
     if (!(b->cfg.flags & SS_BATCH_FFT) || !L.n_windows || !L.n_bins || b->cols.on) return SS_ERR_INVALID_MODE;   // (columns-only: no rows to reduce)
     if (gain_mode == SS_GAIN_REFERENCE && !(b->cfg.flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_MODE;
-    // column of a bin: floor(chart_x / 100 * cols), the last column closed on the right; chart_x ascends
-    std::vector<uint32_t> start(cols + 1, L.n_bins);
-    {
-        uint32_t c = 0;
-        start[0] = 0;
-        for (uint32_t i = 0; i < L.n_bins; i++) {
-            const uint32_t ci = spectrum_column_of(b->bt->chart_x[i], cols);
-            while (c < ci) start[++c] = i;
-        }
-        while (c < cols) start[++c] = L.n_bins;
-    }
+    const std::vector<uint32_t> start = spectrum_col_start(b, cols);
     const uint64_t rows = (uint64_t)b->cfg.n_streams * L.n_windows * L.fft_channels;
     HIPCHK(b->col_start.ensure(cols + 1));
     HIPCHK(hipMemcpyAsync(b->col_start.p, start.data(), (cols + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
@@ -1306,6 +1325,106 @@ int ss_batch_corpus_spectrum(ss_batch *b, float *mean_db, float *max_db, size_t 
         HIPCHK(hipMemcpyAsync(windows_counted, st.corpus_counts.p, L.fft_channels * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return SS_OK;
+}
+
+// ---- spectrogram: time x frequency chart tiles ---------------------------------------------------------------------
+static_assert(sizeof(ss_spectrogram_view) == 24, "view layout");
+
+// every check of a view, before anything is queued or allocated
+static int check_spectrogram_view(const ss_batch *b, const ss_spectrogram_view *v)
+{
+    if (!b || !v) return SS_ERR_INVALID_ARG;
+    if (v->t_cols == 0 || v->t_cols > ssk::kSpectrogramMaxTCols || v->f_cols == 0 || v->f_cols > ssk::kSpectrogramMaxFCols) return SS_ERR_INVALID_ARG;
+    if (v->w_max <= v->w_min) return SS_ERR_INVALID_ARG;
+    if (b->cols.on) {           // the pass has reduced frequency and applied its gain: the view's gain is not read
+        if (v->f_cols != b->cfg.spectrum_columns) return SS_ERR_INVALID_ARG;
+    } else if (v->gain_mode != SS_GAIN_FIXED && v->gain_mode != SS_GAIN_REFERENCE) return SS_ERR_INVALID_ARG;
+    if (!(b->cfg.flags & SS_BATCH_FFT)) return SS_ERR_INVALID_MODE;
+    if (!b->cols.on && v->gain_mode == SS_GAIN_REFERENCE && !(b->cfg.flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_MODE;
+    return SS_OK;
+}
+
+// how ss_batch_spectrogram cuts a (checked) view of this batch
+static ssk::SpectrogramPlan batch_spectrogram_plan(const ss_batch *b, const ss_spectrogram_view &v)
+{
+    // the most windows a time column holds inside the slot: ceil(span / t_cols) of the view, never more than the slot has behind w_min
+    const uint64_t span = (uint64_t)v.w_max - v.w_min;
+    const uint64_t widest = (span + v.t_cols - 1) / v.t_cols, held = b->lay.n_windows > v.w_min ? b->lay.n_windows - v.w_min : 0;
+    return ssk::plan_spectrogram((uint64_t)b->cfg.n_streams * b->lay.fft_channels * v.t_cols, (uint32_t)(widest < held ? widest : held));
+}
+
+int ss_batch_spectrogram(ss_batch *b, const ss_spectrogram_view *v)
+{
+    SS_ON_DEVICE(b);
+    int rc = check_spectrogram_view(b, v);
+    if (rc) return rc;
+    const ss_batch_layout &L = b->lay;
+    Spectrogram &sg = b->spectrogram;
+    ssk::SpectrogramParams p{};
+    p.plan = batch_spectrogram_plan(b, *v);
+    const size_t cells = (size_t)b->cfg.n_streams * L.fft_channels * v->t_cols * v->f_cols;
+    HIPCHK(sg.out.ensure(cells));               // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
+    HIPCHK(sg.part.ensure(p.plan.runs > 1 ? cells * p.plan.runs : 0));
+    if (!b->cols.on && sg.map_cols != v->f_cols) {
+        // the column of every bin, from the column map ss_batch_render_spectrum uses; staged, so that the call waits for nothing
+        const std::vector<uint32_t> start = spectrum_col_start(b, v->f_cols);
+        const size_t bytes = (size_t)L.fft_bin_stride * sizeof(uint16_t);
+        HIPCHK(sg.bin_col.ensure(L.fft_bin_stride));
+        HIPCHK(sg.stage.take(bytes));
+        uint16_t *bc = reinterpret_cast<uint16_t *>(sg.stage.buf.p);
+        for (uint32_t i = 0; i < L.fft_bin_stride; i++) bc[i] = 0xFFFF;
+        for (uint32_t c = 0; c < v->f_cols; c++)
+            for (uint32_t i = start[c]; i < start[c + 1]; i++) bc[i] = (uint16_t)c;
+        if (bytes) HIPCHK(sg.stage.queue(sg.bin_col.p, bytes, b->stream));
+        sg.map_cols = v->f_cols;
+    }
+    p.columns_form = b->cols.on ? 1u : 0u;
+    p.rows = b->fft.p; p.cols = b->cols.on ? b->render_spec.p : nullptr; p.bin_stride = L.fft_bin_stride;
+    p.n_streams = b->cfg.n_streams; p.fft_ch = L.fft_channels; p.n_windows = L.n_windows;
+    p.windows_of = b->ragged_ptr(b->ragged.windows_d);
+    p.bin_col = sg.bin_col.p;
+    p.t_cols = v->t_cols; p.f_cols = v->f_cols; p.w_min = v->w_min; p.w_max = v->w_max;
+    p.integrated = !b->cols.on && v->gain_mode == SS_GAIN_REFERENCE ? b->integrated.p : nullptr;
+    p.gain_db = v->gain_db;
+    p.out = sg.out.p; p.part = sg.part.p;
+    HIPCHK(ssk::launch_spectrogram(p, b->stream));
+    sg.view = *v;
+    sg.done = true;
+    return SS_OK;
+}
+
+int ss_batch_spectrogram_plan(const ss_batch *b, const ss_spectrogram_view *v, uint32_t *runs, uint32_t *run_windows)
+{
+    int rc = check_spectrogram_view(b, v);
+    if (rc) return rc;
+    const ssk::SpectrogramPlan plan = batch_spectrogram_plan(b, *v);
+    if (runs) *runs = plan.runs;
+    if (run_windows) *run_windows = plan.run_windows;
+    return SS_OK;
+}
+
+int ss_batch_download_spectrogram(ss_batch *b, uint32_t first_stream, uint32_t count, float *out, size_t cap_floats)
+{
+    SS_ON_DEVICE(b);
+    if (!b || (uint64_t)first_stream + count > b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+    const Spectrogram &sg = b->spectrogram;
+    if (!(b->cfg.flags & SS_BATCH_FFT) || !sg.done) return SS_ERR_INVALID_MODE;
+    const size_t per = (size_t)b->lay.fft_channels * sg.view.t_cols * sg.view.f_cols;
+    if (!out && count) return SS_ERR_INVALID_ARG;
+    if (cap_floats < per * count) return SS_ERR_CAPACITY;
+    if (!count) return ss_batch_sync(b);
+    return fetch(b, out, sg.out.p + (size_t)first_stream * per, per * count);
+}
+
+void ss_spectrogram_column_windows(const ss_spectrogram_view *v, uint32_t t, uint32_t *first, uint32_t *end)
+{
+    uint32_t a = 0, e = 0;
+    if (v && v->t_cols && v->t_cols <= ssk::kSpectrogramMaxTCols && v->w_max > v->w_min && t < v->t_cols) {
+        a = ssk::spectrogram_column_first(v->w_min, v->w_max - v->w_min, v->t_cols, t);
+        e = ssk::spectrogram_column_first(v->w_min, v->w_max - v->w_min, v->t_cols, t + 1);
+    }
+    if (first) *first = a;
+    if (end) *end = e;
 }
 
 // ---- loudness regions: gated loudness of time ranges and groups ----------------------------------------------------

@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_peak_series.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -144,6 +144,37 @@ struct SpecStatsParams {
 hipError_t launch_spectrum_stats(const SpecStatsParams &p, hipStream_t s);
 // the batch pooled from p.sums / p.max / p.counts, streams in index order: mean / max [fft_ch][bin_stride], counts [fft_ch] (bin 0's)
 hipError_t launch_spectrum_stats_corpus(const SpecStatsParams &p, float *mean, float *max, unsigned long long *counts, hipStream_t s);
+
+// batch spectrogram (ss_spectrogram.hip): time x frequency chart tiles of the rows (or of a columns-only pass's columns)
+constexpr uint32_t kSpectrogramMaxTCols = 4096, kSpectrogramMaxFCols = 512;
+// first window of time column t of the view [w_min, w_min + span) cut into t_cols columns: the smallest w with
+// floor((w - w_min) * t_cols / span) >= t; t == t_cols gives w_min + span.  (t <= 4096, span < 2^32: the product fits 64 bits.)
+__host__ __device__ inline uint32_t spectrogram_column_first(uint32_t w_min, uint32_t span, uint32_t t_cols, uint32_t t)
+{
+    return w_min + (uint32_t)(((uint64_t)t * span + t_cols - 1u) / t_cols);
+}
+struct SpectrogramPlan {
+    uint32_t runs = 1;               // workgroups side by side on a time column; > 1: partial maxima per run and a second launch that joins them
+    uint32_t run_windows = 1;        // consecutive windows of a time column a run walks
+};
+// units = (stream, fft_channel) pairs x time columns; column_windows = the most windows a time column of the view holds inside the slot
+SpectrogramPlan plan_spectrogram(uint64_t units, uint32_t column_windows);
+struct SpectrogramParams {
+    const float *rows;               // rows form: [stream][n_windows][fft_ch][bin_stride] f32 dB (FftBatchParams::out)
+    const float *cols;               // columns form: [stream][n_windows][fft_ch][f_cols] f32, gain and clamp applied (FftBatchParams::out_cols)
+    uint32_t columns_form;           // 0: reduce `rows`, 1: reduce `cols`
+    uint32_t bin_stride;             // rows form
+    uint32_t n_streams, fft_ch, n_windows;
+    const uint32_t *windows_of;      // [stream], nullable: ragged batches read min(windows_of[s], n_windows) windows of stream s
+    const uint16_t *bin_col;         // rows form: [bin_stride] chart column of every bin, 0xFFFF for the row padding
+    uint32_t t_cols, f_cols, w_min, w_max;
+    const double *integrated;        // rows form, SS_GAIN_REFERENCE: gain = -13 - (float)integrated[stream]; nullptr: gain_db
+    float gain_db;
+    SpectrogramPlan plan;
+    float *out;                      // [stream][fft_ch][t_cols][f_cols]
+    uint32_t *part;                  // plan.runs > 1: [stream][fft_ch][t_cols][run][f_cols] order-preserving images of the runs' maxima, 0 = none
+};
+hipError_t launch_spectrogram(const SpectrogramParams &p, hipStream_t s);
 
 // ---- time domain ------------------------------------------------------------
 struct TdConst {                 // one per (rate, true-peak factor), device resident
