@@ -541,6 +541,73 @@ int ss_batch_peak_regions(ss_batch *b, const ss_loudness_region *regions, uint32
 int ss_batch_download_region_peaks(ss_batch *b, ss_region_peaks *out, uint32_t cap_regions);
 int ss_batch_download_group_peaks(ss_batch *b, ss_group_peaks *out, uint32_t cap_groups);
 int ss_batch_download_region_channel_peaks(ss_batch *b, float *true_pk, float *sample_pk, size_t cap_floats);
+/* Signal scan: whether every stream of a batch holds sound at all, whether it is clipped, and whether it carries a DC offset or
+ * non-finite samples — what an ingest or QC chain checks before it trusts the loudness and peak figures.  Not in the reference.
+ * ss_batch_signal_scan reads the resident f32 corpus alone, like ss_batch_peak_series: it needs no ss_batch_run and no particular
+ * flag, nothing inside a pass changes, and the corpus is only read.  F_s is stream s's own frame count (ss_batch_set_lengths);
+ * frames behind it, and the neighbouring slots, are never read.  Predicates on single samples, f32 comparisons as written:
+ *   - frame n is SILENT iff fabsf(x[n][c]) <= silence_threshold for every channel c: a NaN is never silent, threshold 0 is digital
+ *     silence (-0.0 counts), and at threshold +inf an infinity is silent;
+ *   - sample (n, c) is CLIPPED iff fabsf(x[n][c]) >= clip_level: an infinity is clipped, a NaN is not;
+ *   - a RUN is a maximal sequence of consecutive frames of one stream on which a predicate holds.  Silence runs are counted per
+ *     stream, clip runs per channel of a stream.
+ * Every result except the two f64 sums is an integer defined by these predicates.  The sums widen every finite sample to f64 (its
+ * square is formed in f64, so it is exact) and add in an order fixed by the kernel plan, not by timing; there are no floating-point
+ * atomics: two calls agree byte for byte.  The caller forms DC = sum / (F_s - nonfinite) and RMS = sqrt(sum_sq / (F_s - nonfinite)).
+ * Two lists per stream hold the runs themselves: the silence list has the runs of at least silence_min_frames, ascending by
+ * first_frame, with channel = 0xFFFFFFFF; the clip list has the runs of at least clip_min_samples, ordered by (channel,
+ * first_frame).  A list keeps its first max_events events in that order; the counts in the records are always the true totals, so
+ * a caller sees truncation as count > max_events.
+ * The call copies cfg, queues its work on the batch's stream and waits for nothing; a later call replaces every result; the
+ * downloads wait for the stream.  Call it again after new input or new lengths.  Device memory is allocated at the first call:
+ * 80 bytes per (tile, channel) and 48 per tile of ss_batch_signal_scan_plan's tile_frames frames (a multiple of 64), the records,
+ * and 48 * max_events bytes of lists per stream, which grow with max_events.  A batch that never calls this allocates and launches
+ * exactly what it did before.
+ * Status codes, all checked before anything is queued, so a refused call leaves the previous results as they were: cfg == NULL, a
+ * NaN or negative silence_threshold, clip_level NaN or <= 0, a minimum of 0, max_events > 65536, reserved != 0, stream >=
+ * n_streams, an unknown kind: SS_ERR_INVALID_ARG; a download before the first scan: SS_ERR_INVALID_MODE; a `cap` too small:
+ * SS_ERR_CAPACITY, with nothing written.  F_s == 0 is valid: every field is zero or "none" and both lists are empty. */
+typedef struct ss_signal_scan_config {
+    float    silence_threshold;   /* linear, >= 0, not NaN (+inf allowed) */
+    float    clip_level;          /* linear, > 0, not NaN */
+    uint32_t silence_min_frames;  /* >= 1: runs at least this long are counted and listed */
+    uint32_t clip_min_samples;    /* >= 1 */
+    uint32_t max_events;          /* list slots per stream and kind, 0 .. 65536 */
+    uint32_t reserved;            /* 0 */
+} ss_signal_scan_config;          /* 24 bytes */
+typedef struct ss_stream_scan {
+    uint64_t silent_frames;       /* every silent frame, in runs of any length */
+    uint64_t leading_silence;     /* frames of the run that holds frame 0, else 0: any length, not subject to the minimum */
+    uint64_t trailing_silence;    /* the same for the run that holds frame F_s - 1; in an all-silent stream both equal F_s */
+    uint64_t longest_silence;     /* frames of the longest run of any length; ties go to the lowest frame; 0 if none */
+    uint64_t longest_silence_at;  /* its first frame; UINT64_MAX if none */
+    uint64_t silence_runs;        /* runs of at least silence_min_frames */
+    uint64_t clip_runs;           /* the sum over channels of ss_channel_scan::clip_runs */
+} ss_stream_scan;                 /* 56 bytes */
+typedef struct ss_channel_scan {
+    double   sum, sum_sq;         /* over the channel's finite samples of the stream */
+    uint64_t nonfinite;           /* NaN and infinite samples */
+    uint64_t first_nonfinite;     /* frame of the first; UINT64_MAX if none */
+    uint64_t clipped_samples;
+    uint64_t longest_clip;        /* any length; ties go to the lowest frame; 0 if none */
+    uint64_t longest_clip_at;     /* UINT64_MAX if none */
+    uint64_t clip_runs;           /* the channel's runs of at least clip_min_samples */
+} ss_channel_scan;                /* 64 bytes */
+typedef struct ss_signal_event {
+    uint64_t first_frame;
+    uint64_t frames;
+    uint32_t channel;             /* 0xFFFFFFFF in the silence list */
+    uint32_t reserved;            /* 0 */
+} ss_signal_event;                /* 24 bytes */
+enum { SS_SIGNAL_SILENCE = 0, SS_SIGNAL_CLIP = 1 };
+int ss_batch_signal_scan(ss_batch *b, const ss_signal_scan_config *cfg);
+/* tile_frames: the frames one workgroup scans (runs are carried across tiles); tiles_cap = ceil(frames_per_stream / tile_frames) */
+int ss_batch_signal_scan_plan(const ss_batch *b, uint32_t *tile_frames, uint32_t *tiles_cap);
+int ss_batch_download_stream_scans(ss_batch *b, ss_stream_scan *out, uint32_t cap_streams);
+/* [stream][channel] */
+int ss_batch_download_channel_scans(ss_batch *b, ss_channel_scan *out, size_t cap_records);
+/* one list of one stream; *n_events (optional) = min(count, max_events) */
+int ss_batch_download_signal_events(ss_batch *b, uint32_t stream, int kind, ss_signal_event *out, size_t cap_events, uint32_t *n_events);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

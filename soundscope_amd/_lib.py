@@ -55,6 +55,8 @@ SYMBOLS = [
     "ss_batch_peak_series", "ss_batch_peak_series_plan", "ss_batch_download_peak_series", "ss_batch_peak_regions",
     "ss_batch_download_region_peaks", "ss_batch_download_group_peaks", "ss_batch_download_region_channel_peaks",
     "ss_batch_spectrogram", "ss_batch_spectrogram_plan", "ss_batch_download_spectrogram", "ss_spectrogram_column_windows",
+    "ss_batch_signal_scan", "ss_batch_signal_scan_plan", "ss_batch_download_stream_scans", "ss_batch_download_channel_scans",
+    "ss_batch_download_signal_events",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -67,6 +69,7 @@ SS_BATCH_FFT, SS_BATCH_LUFS, SS_BATCH_TRUE_PEAK, SS_BATCH_WAVEFORM, SS_BATCH_ALL
 SS_BATCH_FFT_COLUMNS = 16
 SS_BATCH_LOUDNESS_SERIES = 32
 SS_REGION_NO_GROUP = 0xFFFFFFFF
+SS_SIGNAL_SILENCE, SS_SIGNAL_CLIP = 0, 1
 SS_PCM_U8, SS_PCM_S16, SS_PCM_S24, SS_PCM_S32, SS_PCM_F32, SS_PCM_F64 = 1, 2, 3, 4, 5, 6
 SS_GAIN_FIXED, SS_GAIN_REFERENCE = 0, 1
 SS_COMM_RCCL, SS_COMM_HOST_TCP = 0, 1
@@ -148,6 +151,25 @@ class RegionPeaks(C.Structure):
 class GroupPeaks(C.Structure):
     _fields_ = [("true_peak", C.c_double), ("sample_peak", C.c_double),
                 ("true_peak_region", C.c_uint32), ("sample_peak_region", C.c_uint32), ("n_over", C.c_uint64)]
+
+
+class SignalScanConfig(C.Structure):
+    _fields_ = [("silence_threshold", C.c_float), ("clip_level", C.c_float), ("silence_min_frames", C.c_uint32),
+                ("clip_min_samples", C.c_uint32), ("max_events", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class StreamScan(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("silent_frames", "leading_silence", "trailing_silence", "longest_silence",
+                                          "longest_silence_at", "silence_runs", "clip_runs")]
+
+
+class ChannelScan(C.Structure):
+    _fields_ = [("sum", C.c_double), ("sum_sq", C.c_double)] + [(n, C.c_uint64) for n in (
+        "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs")]
+
+
+class SignalEvent(C.Structure):
+    _fields_ = [("first_frame", C.c_uint64), ("frames", C.c_uint64), ("channel", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class SpectrogramView(C.Structure):
@@ -336,6 +358,11 @@ def _bind(lib):
         "ss_batch_spectrogram_plan": (C.c_int, [vp, C.POINTER(SpectrogramView), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_batch_download_spectrogram": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, C.c_size_t]),
         "ss_spectrogram_column_windows": (None, [C.POINTER(SpectrogramView), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_batch_signal_scan": (C.c_int, [vp, C.POINTER(SignalScanConfig)]),
+        "ss_batch_signal_scan_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_batch_download_stream_scans": (C.c_int, [vp, C.POINTER(StreamScan), C.c_uint32]),
+        "ss_batch_download_channel_scans": (C.c_int, [vp, C.POINTER(ChannelScan), C.c_size_t]),
+        "ss_batch_download_signal_events": (C.c_int, [vp, C.c_uint32, C.c_int, C.POINTER(SignalEvent), C.c_size_t, C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

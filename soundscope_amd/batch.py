@@ -27,6 +27,13 @@ def _region_rows(regions):
 
 PEAK_ENTRY_DTYPE = np.dtype([("true_peak", np.float32), ("sample_peak", np.float32),
                              ("true_peak_frame", np.uint32), ("sample_peak_frame", np.uint32)])
+# the signal scan's records (ss_stream_scan, ss_channel_scan, ss_signal_event)
+STREAM_SCAN_DTYPE = np.dtype([(n, np.uint64) for n in ("silent_frames", "leading_silence", "trailing_silence", "longest_silence",
+                                                       "longest_silence_at", "silence_runs", "clip_runs")])
+CHANNEL_SCAN_DTYPE = np.dtype([("sum", np.float64), ("sum_sq", np.float64)] + [(n, np.uint64) for n in (
+    "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs")])
+SIGNAL_EVENT_DTYPE = np.dtype([("first_frame", np.uint64), ("frames", np.uint64), ("channel", np.uint32), ("reserved", np.uint32)])
+SIGNAL_SILENCE, SIGNAL_CLIP = L.SS_SIGNAL_SILENCE, L.SS_SIGNAL_CLIP
 
 
 class Batch:
@@ -405,6 +412,47 @@ class Batch:
         fp = C.POINTER(C.c_float)
         _check(L.lib().ss_batch_download_region_channel_peaks(self._h, tp.ctypes.data_as(fp), sp.ctypes.data_as(fp), tp.size))
         return tp, sp
+
+    # -- signal scan: silence, clip runs, DC and non-finite samples of every stream, and the lists of the runs
+    def signal_scan(self, silence_threshold=0.0, clip_level=1.0, silence_min_frames=None, clip_min_samples=3, max_events=256):
+        """Queue the scan of whatever is resident (no run(), no particular flag): a frame is silent iff |x| <= silence_threshold on
+        every channel, a sample is clipped iff |x| >= clip_level (both linear); runs of at least silence_min_frames frames (None:
+        100 ms) and clip_min_samples samples are counted and listed, max_events per stream and kind.  Replaces the previous scan."""
+        if silence_min_frames is None:
+            silence_min_frames = (int(self.cfg.sample_rate) + 5) // 10
+        cfg = L.SignalScanConfig(float(silence_threshold), float(clip_level), int(silence_min_frames), int(clip_min_samples),
+                                 int(max_events), 0)
+        _check(L.lib().ss_batch_signal_scan(self._h, C.byref(cfg)))
+        self._scan_events = int(max_events)
+
+    def signal_scan_plan(self):
+        """(tile_frames, tiles_cap): the frames one workgroup scans (a multiple of 64), and the tile slots per stream."""
+        t, n = C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_batch_signal_scan_plan(self._h, C.byref(t), C.byref(n)))
+        return t.value, n.value
+
+    def stream_scans(self):
+        """One record per stream, a structured array [n_streams] of STREAM_SCAN_DTYPE (UINT64_MAX where there is no run)."""
+        out = np.zeros(int(self.cfg.n_streams), STREAM_SCAN_DTYPE)
+        _check(L.lib().ss_batch_download_stream_scans(self._h, out.ctypes.data_as(C.POINTER(L.StreamScan)), out.size))
+        return out
+
+    def channel_scans(self):
+        """One record per channel of every stream, a structured array [n_streams][channels] of CHANNEL_SCAN_DTYPE: DC is
+        sum / (frames - nonfinite)."""
+        out = np.zeros((int(self.cfg.n_streams), int(self.cfg.channels)), CHANNEL_SCAN_DTYPE)
+        _check(L.lib().ss_batch_download_channel_scans(self._h, out.ctypes.data_as(C.POINTER(L.ChannelScan)), out.size))
+        return out
+
+    def signal_events(self, stream, kind):
+        """The stream's listed runs of `kind` (SIGNAL_SILENCE: by first_frame, channel 0xFFFFFFFF; SIGNAL_CLIP: by (channel,
+        first_frame)): a structured array of SIGNAL_EVENT_DTYPE, the first max_events of them."""
+        cap = getattr(self, "_scan_events", 0)
+        out = np.zeros(cap, SIGNAL_EVENT_DTYPE)
+        n = C.c_uint32()
+        _check(L.lib().ss_batch_download_signal_events(self._h, int(stream), int(kind), out.ctypes.data_as(C.POINTER(L.SignalEvent)),
+                                                       cap, C.byref(n)))
+        return out[:n.value].copy()
 
     def histograms(self):
         out = np.empty(2000, np.uint64)

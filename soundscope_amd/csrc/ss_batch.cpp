@@ -136,6 +136,20 @@ struct Peaks {
     DevBuf<ssk::GroupPeaks> group_results;
 };
 
+// signal scan (ss_batch_signal_scan): all of it allocated at the batch's first call (the lists grown by a larger max_events), so a
+// batch that never asks holds none of it
+struct SignalScan {
+    bool done = false;                                  // queued at least once: there is something to download
+    ss_signal_scan_config cfg{};                        // of the last call that was queued
+    DevBuf<ssk::SignalTileRuns> tile_runs;              // [stream][tiles_cap][channels + 1]
+    DevBuf<ssk::SignalTileChannel> tile_channels;       // [stream][tiles_cap][channels]
+    DevBuf<ssk::SignalTileCarry> tile_carry;            // [stream][tiles_cap][channels + 1]
+    DevBuf<uint32_t> list_base;                         // [stream][channels + 1]
+    DevBuf<ssk::StreamScan> streams;                    // [stream] records (ss_stream_scan)
+    DevBuf<ssk::ChannelScan> channels;                  // [stream][channels] records (ss_channel_scan)
+    DevBuf<ssk::SignalEvent> events;                    // [stream][2][max_events] records (ss_signal_event)
+};
+
 // spectrogram (ss_batch_spectrogram): all of it allocated at the batch's first call and grown by a larger view, so a batch that
 // never asks holds none of it
 struct Spectrogram {
@@ -191,6 +205,7 @@ struct ss_batch {
     SpecStats stats;
     Regions regions;
     Peaks peaks;
+    SignalScan scan;
     Spectrogram spectrogram;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
@@ -1597,6 +1612,92 @@ int ss_batch_download_region_channel_peaks(ss_batch *b, float *true_pk, float *s
     if (n && true_pk) HIPCHK(hipMemcpyAsync(true_pk, b->peaks.ch_true.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     if (n && sample_pk) HIPCHK(hipMemcpyAsync(sample_pk, b->peaks.ch_sample.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     return ss_batch_sync(b);
+}
+
+// ---- signal scan: silence, clip runs, DC and non-finite samples of every stream, and the lists of the runs --------------------
+static_assert(sizeof(ss_signal_scan_config) == 24, "scan config layout");
+static_assert(sizeof(ss_stream_scan) == 56 && sizeof(ssk::StreamScan) == 56 && offsetof(ssk::StreamScan, longest_silence_at) == offsetof(ss_stream_scan, longest_silence_at) &&
+              offsetof(ssk::StreamScan, clip_runs) == offsetof(ss_stream_scan, clip_runs), "stream scan layout");
+static_assert(sizeof(ss_channel_scan) == 64 && sizeof(ssk::ChannelScan) == 64 && offsetof(ssk::ChannelScan, first_nonfinite) == offsetof(ss_channel_scan, first_nonfinite) &&
+              offsetof(ssk::ChannelScan, longest_clip_at) == offsetof(ss_channel_scan, longest_clip_at) && offsetof(ssk::ChannelScan, clip_runs) == offsetof(ss_channel_scan, clip_runs),
+              "channel scan layout");
+static_assert(sizeof(ss_signal_event) == 24 && sizeof(ssk::SignalEvent) == 24 && offsetof(ssk::SignalEvent, channel) == offsetof(ss_signal_event, channel), "signal event layout");
+
+// the scan's tiling: the batch's channel count and slot size alone (no pass, no tables)
+static ssk::SignalScanPlan batch_scan_plan(const ss_batch *b) { return ssk::plan_signal_scan(b->cfg.channels, b->cfg.frames_per_stream); }
+
+int ss_batch_signal_scan_plan(const ss_batch *b, uint32_t *tile_frames, uint32_t *tiles_cap)
+{
+    if (!b) return SS_ERR_INVALID_ARG;
+    const ssk::SignalScanPlan plan = batch_scan_plan(b);
+    if (tile_frames) *tile_frames = plan.tile_frames;
+    if (tiles_cap) *tiles_cap = plan.tiles_cap;
+    return SS_OK;
+}
+
+int ss_batch_signal_scan(ss_batch *b, const ss_signal_scan_config *cfg)
+{
+    SS_ON_DEVICE(b);
+    if (!b || !cfg) return SS_ERR_INVALID_ARG;
+    if (!(cfg->silence_threshold >= 0.f) || !(cfg->clip_level > 0.f)) return SS_ERR_INVALID_ARG;        // (NaN fails the comparison)
+    if (!cfg->silence_min_frames || !cfg->clip_min_samples || cfg->max_events > 65536u || cfg->reserved) return SS_ERR_INVALID_ARG;
+    const ss_batch_config &c = b->cfg;
+    const ssk::SignalScanPlan plan = batch_scan_plan(b);
+    const size_t tiles = (size_t)c.n_streams * plan.tiles_cap, Q = (size_t)c.channels + 1;
+    if ((uint64_t)plan.tiles_cap * plan.tile_frames < c.frames_per_stream || tiles > 0x7FFFFFFFull) return SS_ERR_UNSUPPORTED;      // (2^31 tiles)
+    SignalScan &sc = b->scan;
+    // (the shape of a batch is fixed at create, so only the first call allocates; the lists grow with max_events)
+    HIPCHK(sc.tile_runs.ensure(tiles * Q)); HIPCHK(sc.tile_channels.ensure(tiles * c.channels)); HIPCHK(sc.tile_carry.ensure(tiles * Q));
+    HIPCHK(sc.list_base.ensure(c.n_streams * Q)); HIPCHK(sc.streams.ensure(c.n_streams)); HIPCHK(sc.channels.ensure((size_t)c.n_streams * c.channels));
+    HIPCHK(sc.events.ensure((size_t)c.n_streams * 2 * cfg->max_events));
+    ssk::SignalScanParams p{};
+    p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * c.channels; p.n_frames = c.frames_per_stream;
+    p.frames_of = b->ragged_ptr(b->ragged.frames_d);
+    p.n_streams = c.n_streams; p.channels = c.channels; p.tile_frames = plan.tile_frames; p.tiles_cap = plan.tiles_cap;
+    p.silence_threshold = cfg->silence_threshold; p.clip_level = cfg->clip_level;
+    p.silence_min = cfg->silence_min_frames; p.clip_min = cfg->clip_min_samples; p.max_events = cfg->max_events;
+    p.tile_runs = sc.tile_runs.p; p.tile_channels = sc.tile_channels.p; p.tile_carry = sc.tile_carry.p; p.list_base = sc.list_base.p;
+    p.streams = sc.streams.p; p.channel_scans = sc.channels.p; p.events = sc.events.p;
+    HIPCHK(ssk::launch_signal_scan(p, b->stream));
+    sc.cfg = *cfg;
+    sc.done = true;
+    return SS_OK;
+}
+
+int ss_batch_download_stream_scans(ss_batch *b, ss_stream_scan *out, uint32_t cap_streams)
+{
+    SS_ON_DEVICE(b);
+    return !b ? SS_ERR_INVALID_ARG : fetch_records(b, b->scan.done, out, cap_streams, b->cfg.n_streams, b->scan.streams.p);
+}
+
+int ss_batch_download_channel_scans(ss_batch *b, ss_channel_scan *out, size_t cap_records)
+{
+    SS_ON_DEVICE(b);
+    if (!b || !out) return SS_ERR_INVALID_ARG;
+    if (!b->scan.done) return SS_ERR_INVALID_MODE;
+    const size_t n = (size_t)b->cfg.n_streams * b->cfg.channels;
+    if (cap_records < n) return SS_ERR_CAPACITY;
+    return fetch(b, out, reinterpret_cast<const ss_channel_scan *>(b->scan.channels.p), n);
+}
+
+int ss_batch_download_signal_events(ss_batch *b, uint32_t stream, int kind, ss_signal_event *out, size_t cap_events, uint32_t *n_events)
+{
+    SS_ON_DEVICE(b);
+    if (!b || stream >= b->cfg.n_streams || (kind != SS_SIGNAL_SILENCE && kind != SS_SIGNAL_CLIP)) return SS_ERR_INVALID_ARG;
+    const SignalScan &sc = b->scan;
+    if (!sc.done) return SS_ERR_INVALID_MODE;
+    // how many there are is the stream's own record: the count, cut at the lists' slots
+    ssk::StreamScan rec;
+    int rc = fetch(b, &rec, sc.streams.p + stream, 1);
+    if (rc) return rc;
+    const uint64_t count = kind == SS_SIGNAL_CLIP ? rec.clip_runs : rec.silence_runs;
+    const uint32_t n = count < sc.cfg.max_events ? (uint32_t)count : sc.cfg.max_events;
+    if (!out && n) return SS_ERR_INVALID_ARG;
+    if (cap_events < n) return SS_ERR_CAPACITY;
+    if (n_events) *n_events = n;
+    if (!n) return SS_OK;
+    const ssk::SignalEvent *src = sc.events.p + ((size_t)stream * 2 + (kind == SS_SIGNAL_CLIP ? 1 : 0)) * sc.cfg.max_events;
+    return fetch(b, out, reinterpret_cast<const ss_signal_event *>(src), n);
 }
 
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max)

@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -379,6 +379,56 @@ struct RegionPeaksParams {
 };
 // clears the groups' words, reduces every region (k_region_peaks) and writes every group's record (k_group_peaks)
 hipError_t launch_region_peaks(const RegionPeaksParams &p, hipStream_t s);
+// Signal scan (ss_batch_signal_scan; ss_signal_scan.hip): silence runs per stream, clip runs, sums and non-finite samples per
+// channel, and the lists of the runs, from the resident corpus alone — no pass, no tables.  A stream has C + 1 predicate
+// sequences: 0 is "the frame is silent", 1 + c is "the sample of channel c is clipped".  Three launches: k_signal_tiles (one
+// workgroup per (stream, tile): the tile's sums and run summaries), k_signal_carry (one wave per stream: the runs that cross
+// tiles, the records, every tile's place in the lists), k_signal_events (the lists; only with max_events > 0).
+struct SignalScanPlan { uint32_t tile_frames, tiles_cap; };
+// tile_frames: a multiple of 64 frames whose floats fit the peak series' tile; tiles_cap = ceil(n_frames / tile_frames) per stream
+SignalScanPlan plan_signal_scan(uint32_t channels, uint64_t n_frames);
+// one tile's view of one sequence: the run at its first frame, the run at its last frame, and the runs that touch neither edge
+struct alignas(16) SignalTileRuns {
+    uint32_t head, tail;             // frames of the run that holds the tile's first / last frame (both the tile's frames when all_true)
+    uint32_t all_true;
+    uint32_t count;                  // inner runs of at least the minimum
+    uint32_t longest, longest_at;    // the longest inner run and its first frame in the tile (the lowest of equals); 0: none
+    uint32_t total;                  // frames of the tile on which the predicate holds
+    uint32_t pad;
+};
+struct alignas(16) SignalTileChannel {   // one tile's view of one channel
+    double sum, sum_sq;              // over its finite samples
+    uint32_t clipped, nonfinite;
+    uint32_t first_nonfinite;        // frame in the tile, 0xFFFFFFFF: none
+    uint32_t pad;
+};
+struct alignas(16) SignalTileCarry {     // what k_signal_carry tells k_signal_events about (tile, sequence)
+    unsigned long long carry_in;     // frames of the run open at the tile's first frame that lie in front of the tile
+    uint32_t ev_off;                 // qualifying runs of the sequence that end in earlier tiles (at most max_events)
+    uint32_t owned;                  // ... that end in this tile (a run belongs to the tile that holds its last frame)
+};
+// the records, laid out as ss_stream_scan / ss_channel_scan / ss_signal_event (include/soundscope_hip.h)
+struct StreamScan { unsigned long long silent_frames, leading_silence, trailing_silence, longest_silence, longest_silence_at, silence_runs, clip_runs; };
+struct ChannelScan { double sum, sum_sq; unsigned long long nonfinite, first_nonfinite, clipped_samples, longest_clip, longest_clip_at, clip_runs; };
+struct SignalEvent { unsigned long long first_frame, frames; uint32_t channel, reserved; };
+struct SignalScanParams {
+    const float *pcm;                // [stream][frame][channels] f32, 16-byte aligned
+    uint64_t stream_stride;          // floats between streams
+    uint64_t n_frames;               // frames of a slot
+    const uint64_t *frames_of;       // ragged batches: each stream's own frames (nullable = n_frames for all)
+    uint32_t n_streams, channels;
+    uint32_t tile_frames, tiles_cap; // plan_signal_scan
+    float silence_threshold, clip_level;
+    uint32_t silence_min, clip_min, max_events;
+    SignalTileRuns *tile_runs;       // [stream][tiles_cap][channels + 1]
+    SignalTileChannel *tile_channels;// [stream][tiles_cap][channels]
+    SignalTileCarry *tile_carry;     // [stream][tiles_cap][channels + 1]
+    uint32_t *list_base;             // [stream][channels + 1]: where a sequence's runs start in its list (at most max_events)
+    StreamScan *streams;             // [stream]
+    ChannelScan *channel_scans;      // [stream][channels]
+    SignalEvent *events;             // [stream][2][max_events]: the silence list, the clip list (max_events == 0: unused)
+};
+hipError_t launch_signal_scan(const SignalScanParams &p, hipStream_t s);
 // gate + LRA on explicit histograms (corpus gate after the all-reduce; handle getters)
 // `peaks` (optional): a handle's readings in one launch (ReadingsExtra above)
 hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, const double *bounds,
