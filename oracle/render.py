@@ -14,10 +14,28 @@ def gain_db(integrated):
     return float(np.float32(-13.0) - np.float32(integrated))
 
 
+def chart_column_of(chart_x, cols):
+    """The chart column of every bin: floor(chart_x / 100 * cols), the last column closed on the right, negative values to 0."""
+    c = np.minimum(np.floor(np.asarray(chart_x, np.float64) / 100.0 * cols), cols - 1).astype(np.int64)
+    c[c < 0] = 0
+    return c
+
+
+def spectrum_columns_f32(v, chart_x, gain, cols):
+    """The header's rule in f32 on the values v = (float)((double)row + pink): max over the column of clamp(v + gain, -100, 0);
+    a column without a bin is NaN."""
+    c = chart_column_of(chart_x, cols)
+    g = np.float32(gain)
+    w = np.minimum(np.maximum(v.astype(np.float32) + g, np.float32(-100.0)), np.float32(0.0))
+    out = np.full(cols, np.nan, np.float32)
+    np.fmax.at(out, c, w)
+    return out
+
+
 def spectrum_columns(xy, gain, cols):
     """xy: get_fft output [(chart_x, dB)] -> cols values: max over the column of clamp(dB + gain, -100, 0)."""
     x, y = np.asarray(xy)[:, 0], np.asarray(xy)[:, 1]
-    c = np.minimum(np.floor(x / 100.0 * cols), cols - 1).astype(np.int64)
+    c = chart_column_of(x, cols)
     v = np.clip(y + float(gain), -100.0, 0.0)
     out = np.full(cols, np.nan)
     for ci in np.unique(c):

@@ -11,6 +11,7 @@
 // copy and writes the other, for EVERY row (an untouched row is copied through), and the host swaps the two — no wave can see the
 // clock another wave of the same launch has advanced.
 #include "ss_kernels.h"
+#include "ss_chart_dev.h"
 
 // hold_db must equal the same IEEE expression evaluated on the host bit for bit: no fused multiply-add anywhere in this file
 #pragma clang fp contract(off)
@@ -20,7 +21,6 @@ namespace ssk {
 namespace {
 
 constexpr float kLog2Of10Over10 = 0.33219280948873623f;      // 10^(v / 10) = 2^(v log2(10) / 10), as k_spectrum_stats forms it
-typedef __attribute__((address_space(3))) float lds_f32;
 
 // the three planes of a row's state, from the row's group of four bins `g` on
 struct TrackPlanes { double *P; float *peak; uint32_t *age; };
@@ -167,9 +167,9 @@ __global__ __launch_bounds__(256) void k_bank_spectrum_tracked_rows(BankTrackPar
     if (hold) row_store4(hold, at, bin, p.n_bins, h);
 }
 
-// The two curves folded into chart columns by k_meter_bank_spectrum<true>'s rule: one workgroup per row, x = (float)((double)dB +
-// pink) of every bin into its column with an LDS ds_max_f32 (a maximum has no order: the result is exact), gain and clamp once
-// per column at the flush — max(clamp(x + g)) == clamp(max(x) + g).  A column without a bin and a row without state are NaN.
+// The two curves folded into chart columns by k_meter_bank_spectrum<true>'s rule (ss_chart_dev.h): one workgroup per row, x =
+// (float)((double)dB + pink) of every bin into its column with lds_fmax (a maximum has no order: the result is exact), gain and
+// clamp once per column at the flush.  A column without a bin and a row without state are NaN.
 __global__ __launch_bounds__(256) void k_bank_spectrum_tracked_columns(BankTrackParams p, BankTrackColumns c)
 {
     __shared__ float acc_mem[2 * 512];
@@ -177,26 +177,26 @@ __global__ __launch_bounds__(256) void k_bank_spectrum_tracked_columns(BankTrack
     const uint32_t row = blockIdx.x;
     const uint32_t n = p.meta_in[row].updates;
     if (threadIdx.x == 0 && c.updates) c.updates[row] = n;
-    for (uint32_t k = threadIdx.x; k < c.cols; k += 256u) acc[k] = acc[512u + k] = c.col_init[k];
+    for (uint32_t k = threadIdx.x; k < c.fold.cols; k += 256u) acc[k] = acc[512u + k] = c.fold.col_init[k];
     __syncthreads();
     if (n) {
         const TrackPlanes s = track_planes(p, row, 0u);
         for (uint32_t i = threadIdx.x; i < p.n_bins; i += 256u) {
-            const double pink = c.pink[i];
-            const uint32_t col = c.bin_col[i];
+            const double pink = c.fold.pink[i];
+            const uint32_t col = c.fold.bin_col[i];
             const float a = track_avg_db(s.P[i]), h = track_hold_db(p, s.peak[i], s.age[i]);
-            (void)__hip_atomic_fetch_max(acc + col, (float)((double)a + pink), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            (void)__hip_atomic_fetch_max(acc + 512u + col, (float)((double)h + pink), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            lds_fmax(acc + col, (float)((double)a + pink));
+            lds_fmax(acc + 512u + col, (float)((double)h + pink));
         }
     }
     __syncthreads();
-    const float gain = c.integrated ? -13.0f - (float)c.integrated[(size_t)(row / p.rows_per_stream) * c.integrated_stride] : c.gain_db;
-    for (uint32_t k = threadIdx.x; k < c.cols; k += 256u) {
+    const float gain = chart_gain(c.fold, row / p.rows_per_stream);
+    for (uint32_t k = threadIdx.x; k < c.fold.cols; k += 256u) {
         const float ka = acc[k], kh = acc[512u + k];
         const bool none = !n || ka != ka;                              // NaN: the column owns no bin
-        const size_t at = (size_t)row * c.cols + k;
-        if (c.avg) c.avg[at] = none ? __builtin_nanf("") : fminf(fmaxf(ka + gain, -100.0f), 0.0f);
-        if (c.hold) c.hold[at] = none ? __builtin_nanf("") : fminf(fmaxf(kh + gain, -100.0f), 0.0f);
+        const size_t at = (size_t)row * c.fold.cols + k;
+        if (c.avg) c.avg[at] = none ? __builtin_nanf("") : chart_clamp(ka + gain);
+        if (c.hold) c.hold[at] = none ? __builtin_nanf("") : chart_clamp(kh + gain);
     }
 }
 
@@ -244,7 +244,7 @@ hipError_t launch_bank_spectrum_tracked_columns(const BankTrackParams &p, const 
 {
     const uint32_t n_rows = p.n_streams * p.rows_per_stream;
     if (!n_rows || !p.n_bins) return hipSuccess;
-    if (!track_shape_ok(p) || c.cols == 0 || c.cols > 512u) return hipErrorInvalidValue;
+    if (!track_shape_ok(p) || c.fold.cols == 0 || c.fold.cols > 512u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bank_spectrum_tracked_columns, dim3(n_rows), dim3(256), 0, s, p, c);
     return hipGetLastError();
 }

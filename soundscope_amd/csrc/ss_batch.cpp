@@ -454,17 +454,14 @@ int choose_td_geometry(ss_batch *b)
     return SS_OK;
 }
 
-// the columns-only spectrum's tables: the chart column of every retained bin, per bin and packed per group of four
+// the columns-only spectrum's tables: the shared column tables (ssh::column_tables), and the columns packed per group of four bins
 int upload_column_tables(ss_batch *b)
 {
     const ss_batch_layout &L = b->lay;
-    const uint32_t cols = b->cfg.spectrum_columns;
-    std::vector<uint16_t> bc(L.fft_bin_stride, (uint16_t)0xFFFF);
-    for (uint32_t i = 0; i < L.n_bins; i++) bc[i] = (uint16_t)spectrum_column_of(b->bt->chart_x[i], cols);
+    const ColumnTables t = column_tables(*b->bt, b->cfg.spectrum_columns, L.fft_bin_stride);
+    const std::vector<uint16_t> &bc = t.bin_col;
     HIPCHK(b->cols.bin_col.upload(bc));
     std::vector<uint2> cg(L.fft_bin_stride / 4), cbins(L.fft_bin_stride / 4);
-    std::vector<float> cinit(cols, std::numeric_limits<float>::quiet_NaN());
-    for (uint32_t i = 0; i < L.n_bins; i++) cinit[bc[i]] = -std::numeric_limits<float>::infinity();
     for (uint32_t g = 0; g < cg.size(); g++) {
         uint32_t o[4];
         bool general = false;
@@ -480,25 +477,9 @@ int upload_column_tables(ss_batch *b)
         cbins[g] = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
     }
     HIPCHK(b->cols.bins.upload(cbins));
-    HIPCHK(b->cols.init.upload(cinit));
+    HIPCHK(b->cols.init.upload(t.col_init));
     HIPCHK(b->cols.groups.upload(cg));
     return SS_OK;
-}
-
-// the chart's column map (ss_batch_render_spectrum, ss_batch_spectrogram): column c owns the bins [start[c], start[c + 1]) — the
-// column of a bin is floor(chart_x / 100 * cols), the last column closed on the right; chart_x ascends
-std::vector<uint32_t> spectrum_col_start(const ss_batch *b, uint32_t cols)
-{
-    const uint32_t n_bins = b->lay.n_bins;
-    std::vector<uint32_t> start(cols + 1, n_bins);
-    uint32_t c = 0;
-    start[0] = 0;
-    for (uint32_t i = 0; i < n_bins; i++) {
-        const uint32_t ci = spectrum_column_of(b->bt->chart_x[i], cols);
-        while (c < ci) start[++c] = i;
-    }
-    while (c < cols) start[++c] = n_bins;
-    return start;
 }
 
 // the decimation is fused into the time-domain pass when that pass runs and a bin (plus its shared edge sample)
@@ -1229,7 +1210,7 @@ int ss_batch_render_spectrum(ss_batch *b, uint32_t cols, int gain_mode, float ga
     const ss_batch_layout &L = b->lay;
     if (!(b->cfg.flags & SS_BATCH_FFT) || !L.n_windows || !L.n_bins || b->cols.on) return SS_ERR_INVALID_MODE;   // (columns-only: no rows to reduce)
     if (gain_mode == SS_GAIN_REFERENCE && !(b->cfg.flags & SS_BATCH_LUFS)) return SS_ERR_INVALID_MODE;
-    const std::vector<uint32_t> start = spectrum_col_start(b, cols);
+    const std::vector<uint32_t> start = column_starts(*b->bt, cols);
     const uint64_t rows = (uint64_t)b->cfg.n_streams * L.n_windows * L.fft_channels;
     HIPCHK(b->col_start.ensure(cols + 1));
     HIPCHK(hipMemcpyAsync(b->col_start.p, start.data(), (cols + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
@@ -1381,16 +1362,10 @@ int ss_batch_spectrogram(ss_batch *b, const ss_spectrogram_view *v)
     HIPCHK(sg.out.ensure(cells));               // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
     HIPCHK(sg.part.ensure(p.plan.runs > 1 ? cells * p.plan.runs : 0));
     if (!b->cols.on && sg.map_cols != v->f_cols) {
-        // the column of every bin, from the column map ss_batch_render_spectrum uses; staged, so that the call waits for nothing
-        const std::vector<uint32_t> start = spectrum_col_start(b, v->f_cols);
-        const size_t bytes = (size_t)L.fft_bin_stride * sizeof(uint16_t);
-        HIPCHK(sg.bin_col.ensure(L.fft_bin_stride));
-        HIPCHK(sg.stage.take(bytes));
-        uint16_t *bc = reinterpret_cast<uint16_t *>(sg.stage.buf.p);
-        for (uint32_t i = 0; i < L.fft_bin_stride; i++) bc[i] = 0xFFFF;
-        for (uint32_t c = 0; c < v->f_cols; c++)
-            for (uint32_t i = start[c]; i < start[c + 1]; i++) bc[i] = (uint16_t)c;
-        if (bytes) HIPCHK(sg.stage.queue(sg.bin_col.p, bytes, b->stream));
+        // the column of every bin (ssh::column_tables); staged, so that the call waits for nothing
+        const std::vector<uint16_t> bc = column_tables(*b->bt, v->f_cols, L.fft_bin_stride).bin_col;
+        HIPCHK(sg.bin_col.ensure(bc.size()));
+        if (!bc.empty()) HIPCHK(sg.stage.send(sg.bin_col.p, bc.data(), bc.size() * sizeof(uint16_t), b->stream));
         sg.map_cols = v->f_cols;
     }
     p.columns_form = b->cols.on ? 1u : 0u;

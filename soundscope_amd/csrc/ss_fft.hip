@@ -5,6 +5,7 @@
 // Nothing here is translated from the reference: the reference has no GPU code.
 #include "ss_kernels.h"
 #include "ss_fft_dev.h"
+#include "ss_chart_dev.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -70,11 +71,9 @@ constexpr int kPlaneB = 16 * kRowB;
 // LDS_TABLE: `offpink` is the workgroup's LDS copy of the table (k_fft4096_ms1 / k_fft4096_pairw stage it once per run of
 // windows): the rows are read right where they are used instead of being requested from global memory a whole epilogue
 // ahead (eight registers held across it, and as many vector-memory requests per window as the samples themselves).
-// COLS: nothing is stored — every dB value is folded into its chart column in LDS (tui.rs:49-51, :801-821; the column rule is
-// the library's, include/soundscope_hip.h).  The accumulators hold plain dB values: the gain and the chart's [-100, 0] clamp
-// are monotone, so they commute with the maximum and are applied ONCE per column when a window's columns are flushed —
-// max(clamp(v + gain)) == clamp(max(v) + gain) to the bit.  Folding is an LDS float atomic (ds_max_f32, which ignores a NaN
-// operand like IEEE maxNum) at a byte offset from a host-built table — no per-bin branch, key conversion or clamp in the vector
+// COLS: nothing is stored — every dB value is folded into its chart column in LDS and gain and clamp are applied ONCE per column
+// when a window's columns are flushed (the rule: ss_chart_dev.h).  Folding is an LDS float atomic (lds_fmax) at a byte offset
+// from a host-built table — no per-bin branch, key conversion or clamp in the vector
 // ALU, which is what bounds this kernel (the divergent per-bin ds_min_u32 form of rounds 3-4: 3.30 ms; this one 3.00).
 //   * Chart columns are monotone in the bin index and, above the lowest few dozen bins, at least four bins wide: a lane's four
 //     consecutive bins lie in ONE column or straddle one boundary.  coltab[g] = (o0 | o3 << 16, n): the offsets
@@ -84,14 +83,11 @@ constexpr int kPlaneB = 16 * kRowB;
 //     one LDS address (SQ_LDS_BANK_CONFLICT 40 % of the LDS cycles), profiles/r05_ab_columns.txt.
 //   * Groups the two-run form cannot express (three or four columns inside the group: the lowest bins; the row padding in the
 //     last group, whose offsets point at a spare slot) carry n = 0 and fold bin by bin from colbins — a wave-uniform branch.
-//   * An accumulator starts at -inf where the column owns a bin and at NaN where it owns none (p.col_init); the flush turns NaN
-//     into "no bin" and -inf (every bin of the column was NaN) into the -100 the two-pass kernel gives.
+//   * The accumulators start from p.col_init; the flush resets those that own a bin to -inf.
 // `side_off` (wave-uniform): the second row rode the transform multiplied by 2^E (its block exponent, see "Two rows, one
 // transform" below); side_off = -E * 20 log10(2) takes the factor out again in dB.
 constexpr uint32_t kColStride = 516;            // floats between the two rows' accumulators (512 columns + the spare slot)
-typedef __attribute__((address_space(3))) float lds_f32;
 typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ void lds_fmax(lds_f32 *p, float v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }   // ds_max_f32
 template <bool LDS_TABLE = false, bool COLS = false>
 __device__ __forceinline__ void fft4096_epilogue(const v2f *xb, int t, uint32_t first_bin, uint32_t n_bins,
                                                  float lg0, const float *__restrict__ offpink,
@@ -757,8 +753,9 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
     for (uint32_t g = (uint32_t)t; 4u * g < p.bin_stride; g += 256u)
         reinterpret_cast<float4 *>(offp)[g] = reinterpret_cast<const float4 *>(p.offpink)[g];
     // columns-only mode: gain of this stream, and where a finished window's columns go (flushed one window late, behind the
-    // loop-end barrier that closes its epilogue's atomics, by the threads that idle least: all of them, one column pair each)
-    const float cgain = COLS ? (p.integrated ? -13.0f - (float)p.integrated[stream] : p.gain_db) : 0.0f;
+    // loop-end barrier that closes its epilogue's atomics, by the threads that idle least: all of them, one column pair each).
+    // ss_chart_dev.h's chart_gain and chart_cell, spelled with their parts: with the tests inside the helpers this kernel's code moves.
+    const float cgain = COLS ? (p.integrated ? chart_reference_gain(p.integrated[stream]) : p.gain_db) : 0.0f;
     auto flush_columns = [&](uint32_t wdone) {
         float *oc = p.out_cols + ((size_t)stream * p.n_windows + wdone) * 2u * p.cols;
         for (uint32_t c = (uint32_t)t; c < 2u * p.cols; c += 256u) {
@@ -766,7 +763,7 @@ __global__ __launch_bounds__(256, 3) void k_fft4096_ms1(FftBatchParams p)
             const float k = colbuf[i];
             const bool none = k != k;                                 // NaN: the column owns no bin (never written, never reset)
             if (!none) colbuf[i] = -INFINITY;
-            oc[c] = none ? k : fminf(fmaxf(k + cgain, -100.0f), 0.0f);
+            oc[c] = none ? k : chart_clamp(k + cgain);
         }
     };
     const int tb = t & 15, hi = t >> 4;
@@ -1670,8 +1667,8 @@ const char *spectrum_kernel_name(SpecKernel k)
 //  included) -> SS_ERR_NAN, else an infinity -> SS_ERR_INFINITY, else a non-finite dB value (the magnitude's square overflowed)
 //  -> SS_ERR_SCALING.  The loader's two flags are folded per wave into LDS ahead of the transform's first barrier and read behind
 //  the workgroup's last one, which the SS_ERR_SCALING flag and the column flush need anyway.  A refused row is all NaN.
-//  COLS: the rows are never stored.  v = (float)((double)dB + pink) is folded into its chart column (LDS ds_max_f32, like
-//  k_fft4096_ms1's columns) and gain and clamp are applied once per column at the flush: max(clamp(v + g)) == clamp(max(v) + g).
+//  COLS: the rows are never stored.  v = (float)((double)dB + pink) is folded into its chart column (lds_fmax) and gain and
+//  clamp are applied once per column at the flush (ss_chart_dev.h).
 // ============================================================================
 constexpr int32_t kBankStNan = 11, kBankStInf = 12, kBankStScaling = 15;   // SS_ERR_NAN, SS_ERR_INFINITY, SS_ERR_SCALING
 constexpr uint32_t kBankSpecMask = kBankSpecN - 1u;
@@ -1722,7 +1719,7 @@ struct BankWindow {
         return [self, o](uint32_t idx, float r, float pk) {
             const float v = r + pk;                                        // (pk = 0: the value k_fft16k stores for ss_get_fft)
             self->bad |= (__builtin_fabsf(v) <= 3.402823466e38f) ? 0u : 1u;
-            if (COLS) lds_fmax(self->acc + self->q.bin_col[idx], (float)((double)v + self->q.pink[idx]));
+            if (COLS) lds_fmax(self->acc + self->q.fold.bin_col[idx], (float)((double)v + self->q.fold.pink[idx]));
             else o[idx] = v;
         };
     }
@@ -1739,7 +1736,7 @@ __global__ __launch_bounds__(512, 2) void k_meter_bank_spectrum(BankSpectrumPara
     uint32_t *flags = reinterpret_cast<uint32_t *>(lds + kFft16kLdsBytes + kAccBytes);      // [0, 8): loads, [8, 16): dB values
     const uint32_t stream = blockIdx.x / q.rows, row = blockIdx.x % q.rows;
     if (COLS)
-        for (uint32_t c = threadIdx.x; c < q.cols; c += 512u) acc[c] = q.col_init[c];   // (ordered by the transform's barriers)
+        for (uint32_t c = threadIdx.x; c < q.fold.cols; c += 512u) acc[c] = q.fold.col_init[c];   // (ordered by the transform's barriers)
     BankWindow<COLS> src{q, acc, flags, stream, row};
     fft16k_transform(q.f, src, lds);
     if (__ballot(src.bad) && (threadIdx.x & 63u) == 0) flags[8 + (threadIdx.x >> 6)] = 1u;
@@ -1751,12 +1748,11 @@ __global__ __launch_bounds__(512, 2) void k_meter_bank_spectrum(BankSpectrumPara
     const int32_t st = (nf & 1u) ? kBankStNan : (nf & 2u) ? kBankStInf : sc ? kBankStScaling : 0;
     if (threadIdx.x == 0) q.status[blockIdx.x] = st;
     if (COLS) {
-        const float gain = q.integrated ? -13.0f - (float)q.integrated[(size_t)stream * q.integrated_stride] : q.gain_db;   // tui.rs:1234
-        float *oc = q.out + (size_t)blockIdx.x * q.cols;
-        for (uint32_t c = threadIdx.x; c < q.cols; c += 512u) {
+        const float gain = chart_gain(q.fold, stream);
+        float *oc = q.out + (size_t)blockIdx.x * q.fold.cols;
+        for (uint32_t c = threadIdx.x; c < q.fold.cols; c += 512u) {
             const float k = acc[c];
-            const bool none = k != k;                                      // NaN: the column owns no bin
-            oc[c] = (st || none) ? __builtin_nanf("") : fminf(fmaxf(k + gain, -100.0f), 0.0f);
+            oc[c] = (st || k != k) ? __builtin_nanf("") : chart_cell(k, gain);      // (a refused row is all NaN)
         }
     } else if (st) {
         float *o = q.out + (size_t)blockIdx.x * q.f.n_bins;

@@ -180,6 +180,27 @@ int get_bin_tables(uint32_t rate, size_t n, BinTables **out)
     return SS_OK;
 }
 
+std::vector<uint32_t> column_starts(const BinTables &bt, uint32_t cols)
+{
+    std::vector<uint32_t> start(cols + 1, (uint32_t)bt.count);
+    start[0] = 0;
+    for (uint32_t i = 0, c = 0; i < bt.count; i++) {
+        const uint32_t ci = spectrum_column_of(bt.chart_x[i], cols);
+        while (c < ci) start[++c] = i;
+    }
+    return start;
+}
+
+ColumnTables column_tables(const BinTables &bt, uint32_t cols, size_t stride)
+{
+    ColumnTables t{std::vector<uint16_t>(stride, (uint16_t)0xFFFF), std::vector<float>(cols, std::numeric_limits<float>::quiet_NaN())};
+    for (size_t i = 0; i < bt.count; i++) {
+        t.bin_col[i] = (uint16_t)spectrum_column_of(bt.chart_x[i], cols);
+        t.col_init[t.bin_col[i]] = -std::numeric_limits<float>::infinity();
+    }
+    return t;
+}
+
 int get_td_tables(uint32_t rate, int factor, uint32_t channels, TdTables **out)
 {
     Ctx &c = ctx();

@@ -239,6 +239,12 @@ inline uint32_t spectrum_column_of(double chart_x, uint32_t cols)
     if (f < 0) f = 0;
     return f >= (double)cols ? cols - 1 : (uint32_t)f;
 }
+// The chart's column map of bt's bins (chart_x ascends).  Starts: column c owns the bins [start[c], start[c + 1]), cols <= 65536.
+// Tables, cols <= 512: bin_col[stride], the column of bins [0, count) and 0xFFFF behind them; col_init[cols], -inf where the column
+// owns a bin and a quiet NaN where it owns none (ss_chart_dev.h).
+SS_HIDDEN std::vector<uint32_t> column_starts(const BinTables &bt, uint32_t cols);
+struct ColumnTables { std::vector<uint16_t> bin_col; std::vector<float> col_init; };
+SS_HIDDEN ColumnTables column_tables(const BinTables &bt, uint32_t cols, size_t stride);
 
 // run-in of a time segment that starts from a zero filter state, in 100 ms sub-blocks.  What the missing history would
 // have contributed to the OUTPUT is the tail of the K-weighting impulse response: the slowest pole pair (38 Hz high-pass,

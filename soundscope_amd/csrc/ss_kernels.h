@@ -476,6 +476,15 @@ hipError_t launch_meter_bank_reset(const MeterBankParams &p, const uint32_t *str
 
 // meter-bank spectra (ss_fft.hip): every stream's newest 16384 frames, kept in a ring, transformed in one launch
 constexpr uint32_t kBankSpecN = 16384;
+// the column fold of a bank kernel (the rule: ss_chart_dev.h): the tables of ssh::column_tables with stride = n_bins, and the gain
+struct ChartFold {
+    const double *pink;              // n_bins f64 pink compensation
+    const uint16_t *bin_col;         // n_bins: chart column of every retained bin
+    const float *col_init;           // cols: -inf where the column owns a bin, NaN where it owns none
+    const double *integrated;        // SS_GAIN_REFERENCE: stream s's integrated loudness at integrated[s * integrated_stride]
+    uint32_t integrated_stride;      // (doubles)
+    uint32_t cols; float gain_db;    // cols: 1 .. 512
+};
 struct BankSpectrumParams {
     FftBatchParams f;                // the transform's tables, first_bin / n_bins / db_offset (pink = nullptr, out unused)
     const float *hist;               // [stream][kBankSpecN][channels] f32 ring, frame j at slot j & (kBankSpecN - 1)
@@ -485,14 +494,7 @@ struct BankSpectrumParams {
     uint32_t n_streams, channels, rows;   // rows per stream: 2 (mid, side) for stereo, otherwise channels
     int32_t *status;                 // [stream][row]
     float *out;                      // rows: [stream][row][n_bins]; columns: [stream][row][cols]
-    // columns (k_meter_bank_spectrum<true>)
-    const double *pink;              // n_bins f64 pink compensation
-    const uint16_t *bin_col;         // n_bins: chart column of every retained bin
-    const float *col_init;           // cols: -inf where the column owns a bin, NaN where it owns none
-    const double *integrated;        // SS_GAIN_REFERENCE: stream s's integrated loudness at integrated[s * integrated_stride]
-    uint32_t integrated_stride;      // (doubles)
-    uint32_t cols;                   // 1 .. 512
-    float gain_db;
+    ChartFold fold;                  // columns (k_meter_bank_spectrum<true>)
 };
 // frames [frames - take, frames) of every stream's input (stream s at pcm + s * stride) into the ring at slots (fed + f) & mask;
 // ahead (nullable): stream s's own counter is fed + ahead[s]
@@ -523,9 +525,7 @@ struct BankTrackParams {
 };
 // the columns read-out: launch_meter_bank_spectrum's column tables and gain; avg / hold [row][cols] and updates [row] are nullable
 struct BankTrackColumns {
-    const double *pink; const uint16_t *bin_col; const float *col_init;
-    const double *integrated; uint32_t integrated_stride;
-    uint32_t cols; float gain_db;
+    ChartFold fold;
     float *avg, *hold; uint32_t *updates;
 };
 hipError_t launch_bank_spectrum_track(const BankTrackParams &p, hipStream_t s);

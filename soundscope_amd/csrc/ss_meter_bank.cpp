@@ -268,23 +268,16 @@ ssk::BankSpectrumParams spectrum_params(const ss_meter_bank *m, float *out, int3
 int column_tables(ss_meter_bank *m, uint32_t cols)
 {
     if (cols == m->spec_cols) return SS_OK;
-    std::vector<uint16_t> bc(m->bt->count);
-    std::vector<float> cinit(cols, std::numeric_limits<float>::quiet_NaN());
-    for (size_t i = 0; i < bc.size(); i++) {
-        bc[i] = (uint16_t)spectrum_column_of(m->bt->chart_x[i], cols);
-        cinit[bc[i]] = -std::numeric_limits<float>::infinity();
-    }
-    HIPCHK(m->spec_bin_col.upload(bc));
-    HIPCHK(m->spec_col_init.upload(cinit));
+    const ColumnTables t = ssh::column_tables(*m->bt, cols, m->bt->count);
+    HIPCHK(m->spec_bin_col.upload(t.bin_col));
+    HIPCHK(m->spec_col_init.upload(t.col_init));
     m->spec_cols = cols;
     return SS_OK;
 }
 
-// The column fold of a launch (ssk::BankSpectrumParams, ssk::BankTrackColumns: the seven fields have one name in both): the tables
-// of `cols` columns, the pink compensation and the gain — SS_GAIN_REFERENCE: every stream's integrated loudness after the last add,
-// the readings read() returns, left on the device by a launch of their own.
-template <class P>
-int column_fold(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db, P *q)
+// The column fold of a launch: the tables of `cols` columns, the pink compensation and the gain — SS_GAIN_REFERENCE: every stream's
+// integrated loudness after the last add, the readings read() returns, left on the device by a launch of their own.
+int column_fold(ss_meter_bank *m, uint32_t cols, int gain_mode, float gain_db, ssk::ChartFold *q)
 {
     int rc = column_tables(m, cols);
     if (rc) return rc;
@@ -310,7 +303,7 @@ int spectrum_run(ss_meter_bank *m, bool columns, uint32_t cols, int gain_mode, f
         HIPCHK(m->spec_pin.ensure(fbytes + sbytes));
     }
     ssk::BankSpectrumParams q = spectrum_params(m, m->spec_out.p, m->spec_status.p);
-    int rc = columns ? column_fold(m, cols, gain_mode, gain_db, &q) : SS_OK;
+    int rc = columns ? column_fold(m, cols, gain_mode, gain_db, &q.fold) : SS_OK;
     if (rc) return rc;
     HIPCHK(ssk::launch_meter_bank_spectrum(q, columns, m->stream));
     unsigned char *pin = m->spec_pin.p;
@@ -686,7 +679,7 @@ int ss_meter_bank_spectrum_tracked_columns(ss_meter_bank *m, uint32_t cols, int 
     int rc = track_room(m, o.bytes());
     if (rc) return rc;
     ssk::BankTrackColumns c{};
-    if ((rc = column_fold(m, cols, gain_mode, gain_db, &c))) return rc;
+    if ((rc = column_fold(m, cols, gain_mode, gain_db, &c.fold))) return rc;
     float *base = reinterpret_cast<float *>(m->trk_out.p);
     c.avg = base; c.hold = base + o.hold_at; c.updates = reinterpret_cast<uint32_t *>(base + o.counts_at);
     HIPCHK(ssk::launch_bank_spectrum_tracked_columns(track_params(m), c, m->stream));

@@ -1,6 +1,7 @@
 // ss_session.cpp — the tick drivers: the per-file / per-device state of the reference's App and its
 // per-tick analysis with the audio resident in HBM (/root/reference/src/tui.rs:1207-1241, :1427-1552, :1586-1614).
 #include "ss_host.h"
+#include "ss_chart_dev.h"
 
 using namespace ssh;
 
@@ -309,7 +310,7 @@ int ss_session_open_file(const float *interleaved, size_t n_samples, uint32_t ch
     // fft_gain_compensation_db (tui.rs:1229-1238), f32 arithmetic
     double integrated = 0.0;
     rc = integrated_oneshot(sample_rate, 2, s->pcm.p, n_samples, true, &integrated);
-    s->gain_db = rc ? 0.0f : (-13.0f - (float)integrated);
+    s->gain_db = rc ? 0.0f : ssk::chart_reference_gain(integrated);
     HIPCHK(s->stage.ensure((size_t)2 * s->bin_stride));
     *out = s.release();
     return SS_OK;

@@ -8,9 +8,10 @@
 // flight (a wave-instruction reads 1 KB of one row), carrying fmaxf maxima (maxNum: a NaN value is skipped).  The four maxima are
 // then folded into the unit's chart columns in LDS — at most 512 slots and a spare one for the row padding, whatever n_bins is —
 // as integer maxima of an order-preserving image of the f32 bits (ds_max_u32; no floating-point atomics).  Gain and clamp are
-// monotone, so they are applied once per cell behind the fold: max(clamp(v + gain)) == clamp(max(v) + gain).
+// applied once per cell behind the fold (ss_chart_dev.h, the NaN-keeping clamp).
 // A maximum is exact in any order: runs, their join and two calls agree value for value.
 #include "ss_kernels.h"
+#include "ss_chart_dev.h"
 
 namespace ssk {
 
@@ -31,19 +32,6 @@ __device__ __forceinline__ uint32_t key_of(float v)
 __device__ __forceinline__ float value_of(uint32_t k)
 {
     return k ? __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)) : __builtin_nanf("");
-}
-
-// clamp(v + gain, -100, 0) as numpy's clip has it: a NaN (no value, or inf - inf) stays NaN
-__device__ __forceinline__ float chart_db(float v, float gain)
-{
-    float x = v + gain;
-    x = x < -100.0f ? -100.0f : x;
-    return x > 0.0f ? 0.0f : x;
-}
-
-__device__ __forceinline__ float gain_of(const SpectrogramParams &p, uint32_t stream)
-{
-    return p.integrated ? -13.0f - (float)p.integrated[stream] : p.gain_db;      // tui.rs:1234
 }
 
 // windows of a stream: its own count under ss_batch_set_lengths, never more than the slot holds
@@ -126,9 +114,9 @@ __global__ __launch_bounds__(256) void k_spectrogram_rows(SpectrogramParams p)
     }
     __syncthreads();
     if (runs == 1u) {
-        const float gain = gain_of(p, stream);
+        const float gain = chart_gain(p.integrated, stream, p.gain_db);
         float *o = p.out + (size_t)unit * p.f_cols;
-        for (uint32_t c = threadIdx.x; c < p.f_cols; c += 256u) o[c] = chart_db(value_of(slot[c]), gain);
+        for (uint32_t c = threadIdx.x; c < p.f_cols; c += 256u) o[c] = chart_cell_keep_nan(value_of(slot[c]), gain);
     } else {
         uint32_t *o = p.part + ((size_t)unit * runs + run) * p.f_cols;
         for (uint32_t c = threadIdx.x; c < p.f_cols; c += 256u) o[c] = slot[c];
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(256) void k_spectrogram_join(SpectrogramParams p)
 #pragma unroll 4
     for (uint32_t r = 0; r < p.plan.runs; r++) { const uint32_t x = src[(size_t)r * p.f_cols]; k = x > k ? x : k; }
     const float v = value_of(k);
-    p.out[idx] = p.columns_form ? v : chart_db(v, gain_of(p, unit / p.t_cols / p.fft_ch));
+    p.out[idx] = p.columns_form ? v : chart_cell_keep_nan(v, chart_gain(p.integrated, unit / p.t_cols / p.fft_ch, p.gain_db));
 }
 
 // How the sweep cuts a view: a workgroup per unit, and the windows of a time column in runs where the units alone would leave

@@ -4,6 +4,7 @@
 // arithmetic of ebur128 0.1.10 / spectrum-analyzer 1.7.0 / microfft 0.6.0 as restated in DESIGN.md.
 // Nothing here is translated from the reference: the reference has no GPU code.
 #include "ss_kernels.h"
+#include "ss_chart_dev.h"
 
 namespace ssk {
 // ============================================================================
@@ -118,10 +119,9 @@ hipError_t launch_nonfinite_pairs(const float *interleaved, size_t pairs, uint32
 
 // ============================================================================
 //  Render-side reductions (tui.rs:49-51, :801-821, :664-681)
-//  Spectrum: y + gain, clamped to the chart's [-100, 0] dB, reduced to chart columns on the log-x axis
-//  (column c owns the contiguous bin range [col_start[c], col_start[c+1]); value = maximum; no bin -> NaN).
-//  One wave per spectrum row: the row is staged in wave-private LDS with coalesced loads, then lane c
-//  walks its bins.  gain: fixed, or the reference's per-file rule FFT_TARGET_LUFS - integrated (f32).
+//  Spectrum: the chart-column rule of ss_chart_dev.h, gain and clamp per bin (column c owns the contiguous bin range
+//  [col_start[c], col_start[c+1]); no bin -> NaN).  One wave per spectrum row: the row is staged in wave-private LDS with
+//  coalesced loads, then lane c walks its bins.
 // ============================================================================
 __global__ __launch_bounds__(256) void k_render_spectrum(const float *rows, uint32_t bin_stride, uint32_t n_bins,
                                                          uint64_t n_rows, uint32_t rows_per_stream,
@@ -136,17 +136,12 @@ __global__ __launch_bounds__(256) void k_render_spectrum(const float *rows, uint
     const float4 *src = reinterpret_cast<const float4 *>(rows + row * bin_stride);
     for (uint32_t i = lane; i < bin_stride / 4; i += 64u) reinterpret_cast<float4 *>(mine)[i] = src[i];
     __builtin_amdgcn_wave_barrier();
-    float gain = gain_db;
-    if (integrated) gain = -13.0f - (float)integrated[row / rows_per_stream];      // tui.rs:1234
+    const float gain = chart_gain(integrated, row / rows_per_stream, gain_db);
     float *o = out + row * cols;
     for (uint32_t c = lane; c < cols; c += 64u) {
         const uint32_t b0 = col_start[c], b1 = col_start[c + 1];
         float m = __builtin_nanf("");
-        for (uint32_t b = b0; b < b1 && b < n_bins; b++) {
-            float v = mine[b] + gain;
-            v = fminf(fmaxf(v, -100.0f), 0.0f);
-            m = fmaxf(m, v);                 // maxNum: the NaN seed disappears with the first bin
-        }
+        for (uint32_t b = b0; b < b1 && b < n_bins; b++) m = fmaxf(m, chart_clamp(mine[b] + gain));      // maxNum: the NaN seed disappears with the first bin
         o[c] = m;
     }
 }

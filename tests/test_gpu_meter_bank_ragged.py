@@ -19,6 +19,7 @@ from soundscope_amd import _lib as L
 from soundscope_amd.meter_bank import MeterBank
 
 from conftest import make_multich, make_stereo
+from oracle.render import spectrum_columns_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -317,16 +318,6 @@ def handle_fft(an, x):
     return rc, out[:n.value].copy()
 
 
-def host_columns(v, chart_x, gain, cols):
-    """The header's rule in f32 (the reduction tests/test_gpu_meter_bank_spectrum.py uses)."""
-    c = np.minimum(np.floor(chart_x / 100.0 * cols), cols - 1).astype(np.int64)
-    c[c < 0] = 0
-    w = np.minimum(np.maximum(v.astype(np.float32) + np.float32(gain), np.float32(-100.0)), np.float32(0.0))
-    out = np.full(cols, np.nan, np.float32)
-    np.fmax.at(out, c, w)
-    return out
-
-
 def check_rows_against_handle(bank, hist, an, streams, tag, columns=True):
     rows, st = bank.spectrum()
     pink = bank.spectrum_pink()
@@ -345,7 +336,7 @@ def check_rows_against_handle(bank, hist, an, streams, tag, columns=True):
             assert np.array_equal(ref[:, 0], chart_x) and np.array_equal(got, ref[:, 1]), (tag, s, r, hist.fed(s))
             if columns:
                 g = np.float32(-13.0) - np.float32(integ[s])
-                assert np.array_equal(cols[s, r], host_columns(got.astype(np.float32), chart_x, g, 160), equal_nan=True), (tag, s, r)
+                assert np.array_equal(cols[s, r], spectrum_columns_f32(got.astype(np.float32), chart_x, g, 160), equal_nan=True), (tag, s, r)
     return st
 
 

@@ -11,6 +11,7 @@ from soundscope_amd import _lib as L
 from soundscope_amd.meter_bank import MeterBank
 
 from conftest import db_close, make_multich, make_stereo
+from oracle.render import spectrum_columns_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -67,17 +68,6 @@ def oracle_fft(rate, x):
         return L.SS_OK, po.get_fft(rate, x)
     except po.OracleError as e:
         return e.code, None
-
-
-def host_columns(v, chart_x, gain, cols):
-    """The header's rule in f32 on the values v = (float)((double)row + pink): max over the column of clamp(v + gain, -100, 0)."""
-    c = np.minimum(np.floor(chart_x / 100.0 * cols), cols - 1).astype(np.int64)
-    c[c < 0] = 0
-    g = np.float32(gain)
-    w = np.minimum(np.maximum(v.astype(np.float32) + g, np.float32(-100.0)), np.float32(0.0))
-    out = np.full(cols, np.nan, np.float32)
-    np.fmax.at(out, c, w)
-    return out
 
 
 def check_rows(bank, hist, rate, tag):
@@ -224,7 +214,7 @@ def test_columns(cols):
                 g = np.float32(-13.0) - np.float32(integ[s]) if gain == "reference" else np.float32(gain)
                 for r, sig in enumerate(signals(hist.window(s))):
                     v = (rows[s, r].astype(np.float64) + pink).astype(np.float32)
-                    want = host_columns(v, chart_x, g, cols)
+                    want = spectrum_columns_f32(v, chart_x, g, cols)
                     assert np.array_equal(got[s, r], want, equal_nan=True), (i, gain, s, r)
                     ref = render.spectrum_columns(po.get_fft(rate, sig), float(g), cols)
                     inside = (ref > -100) & (ref < 0) & (got[s, r] > -100) & (got[s, r] < 0)
@@ -322,4 +312,4 @@ def test_scale_1024_streams():
     for s in range(n):
         g = np.float32(-13.0) - np.float32(integ[s])
         for r in range(2):
-            assert np.array_equal(cols[s, r], host_columns(v[s, r], chart_x, g, 160), equal_nan=True), (s, r)
+            assert np.array_equal(cols[s, r], spectrum_columns_f32(v[s, r], chart_x, g, 160), equal_nan=True), (s, r)

@@ -22,7 +22,7 @@ import soundscope_amd as ssa
 from soundscope_amd import _lib as L
 from soundscope_amd.meter_bank import MeterBank
 
-from test_gpu_meter_bank_spectrum import host_columns
+from oracle.render import spectrum_columns_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -315,7 +315,7 @@ def test_columns(columns_bank, cols):
             for r in range(2):
                 for got, curve in ((cavg, avg), (chold, hold)):
                     x = (curve[s, r].astype(np.float64) + pink).astype(np.float32)
-                    want = host_columns(x, chart_x, g, cols)
+                    want = spectrum_columns_f32(x, chart_x, g, cols)
                     assert same_values(got[s, r], want), (cols, gain, s, r)
                     assert np.array_equal(np.isnan(got[s, r]), np.isnan(want))
         if cols == 512:

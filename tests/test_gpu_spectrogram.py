@@ -15,6 +15,7 @@ import pytest
 import soundscope_amd as ssa
 from soundscope_amd import _lib as L
 from conftest import make_multich, make_stereo
+from oracle.render import chart_column_of
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +53,7 @@ def time_fold(per_window, t_cols, w_min, w_max):
 
 def reference(rows, chart_x, t_cols, f_cols, w_min, w_max, gain):
     """the yardstick, in numpy: rows[window][R][bin] f32 of one stream (its own windows only) -> [R][t_cols][f_cols] f32"""
-    col = np.minimum(np.floor(chart_x / 100.0 * f_cols), f_cols - 1).astype(np.int64)
+    col = chart_column_of(chart_x, f_cols)
     assert (np.diff(col) >= 0).all()
     with np.errstate(invalid="ignore"):                          # (inf - inf, NaN: they stay NaN, which is what is wanted)
         y = np.clip(rows + np.float32(gain), np.float32(-100), np.float32(0))
