@@ -930,6 +930,63 @@ int ss_batch_download_spectrogram(ss_batch *b, uint32_t first_stream, uint32_t c
 /* the windows [*first, *end) time column t of a view owns, before the cut at a stream's own window count: the arithmetic of the
  * device; host arithmetic.  (0, 0) for a null view, t_cols out of range, w_max <= w_min and for t >= t_cols. */
 void ss_spectrogram_column_windows(const ss_spectrogram_view *v, uint32_t t, uint32_t *first, uint32_t *end);
+/* Spectrum regions: the average and the peak-hold spectrum of time ranges of the streams — each item of a transmission log, each
+ * track of a continuous mix, each scene of a reel — and of groups of them (an album's pooled curve), reduced on the device from the
+ * rows a pass left.  Not in the reference.  The list is the loudness regions' (ss_loudness_region: stream, first 100 ms sub-block,
+ * count, group), so one list reads the loudness, the peaks and the tonal balance of a delivery.
+ * Grid: S = (sample_rate + 5) / 10 frames and E_s = ceil(F_s / S) entries, the peak series' grid — every list that
+ * ss_batch_peak_regions or ss_batch_loudness_regions accepts is accepted here, and a batch with SS_BATCH_FFT but without
+ * SS_BATCH_LUFS works too.  The bound is first_subblock + n_subblocks <= E_s, in 64 bits.
+ * Windows of a region: window w of a stream covers the frames [first + w hop, first + w hop + fft_n), first = (fft_n / hop + 1) hop
+ * - fft_n (where a pass puts window 0).  Region (s, a, n) owns the windows that lie wholly inside [a S, (a + n) S), cut to the
+ * stream's own n_windows_s (ss_batch_stream_shape); a window that straddles a boundary belongs to neither neighbour, like the
+ * gating blocks of a loudness region.  With 64-bit integers, f0 = a S and f1 = (a + n) S:
+ *   lo = f0 <= first ? 0 : ceil((f0 - first) / hop),  hi = f1 >= first + fft_n ? (f1 - fft_n - first) / hop + 1 : 0,
+ *   end = max(lo, hi), then lo and end are cut to n_windows_s.
+ * (48 kHz, fft_n 4096, hop 1024: region (16, 1) owns window 74 alone, (0, 1) owns none, (0, 20) of a 96 000-frame stream all 89.)
+ * ss_region_windows is this rule before the cut, as host arithmetic: it saturates at 0xFFFFFFFF and gives (0, 0) for fft_n == 0
+ * or hop_frames == 0; the device path runs on its arithmetic.
+ * Per region, fft channel r and retained bin i, the rules of ss_batch_spectrum_stats on the region's windows: a NaN value is
+ * skipped (a refused window's row drops out of its own row's bins and of nothing else), an infinity counts as a value; max_db is
+ * the largest counted value, bit for bit the stored f32; mean_db = (float)(10 log10((1 / n) sum 10^(v / 10))), powers formed in f32
+ * by exp2f, summed in f64, the logarithm taken in f64; windows_counted[r] = the values counted at bin 0; nothing counted
+ * (n_subblocks == 0, a region too short to hold a window, every window refused): mean_db = max_db = NaN, count 0.
+ * Groups: a group's power sums and counts are those of the regions that name it, added in region index order; its max_db is the
+ * maximum of their maxima, its mean_db the same expression on the pooled sums, its windows_counted[r] a u64.  Regions may come from
+ * any streams, may overlap and may repeat: each one counts.  A group without regions reads NaN, NaN, 0.
+ * Order: windows by index inside a chunk, chunks by index, regions by index inside a group; no floating-point atomics — two calls
+ * on the same rows agree byte for byte, mean_db included.  The results depend on the plan (below) in the last bits of the f64 sums
+ * only; max_db, the counts and the NaN positions do not depend on it at all.
+ * ss_batch_spectrum_regions runs after ss_batch_run on the rows the pass left: it copies the list before it returns, queues on the
+ * batch's stream and waits for nothing; a later call replaces the list and every result.  The downloads wait for the stream.
+ * Device memory, allocated at a batch's first call and grown by a longer list (a batch that never calls it allocates and launches
+ * exactly what it did before): 20 bytes per bin of every (region, fft channel) — f64 sum, f32 mean, f32 max, u32 count — i.e.
+ * 14 KB x 2 x 20 B = 68 KB per stereo region at fft_n = 4096, 700 MB for 10 240 regions; 8 bytes per bin of every (group, fft
+ * channel) and a u64 per (group, fft channel); 16 bytes more per bin, region, fft channel and chunk where the plan has chunks.
+ * Status codes, all checked before anything is queued or allocated, so a refused call leaves the previous list and results as they
+ * were: a batch without SS_BATCH_FFT or with SS_BATCH_FFT_COLUMNS (no rows), a download or the plan before the first call:
+ * SS_ERR_INVALID_MODE; a null batch, regions == NULL with n_regions > 0, stream >= n_streams, first_subblock + n_subblocks beyond
+ * E_s, a group >= n_groups other than SS_REGION_NO_GROUP, first + count beyond the list: SS_ERR_INVALID_ARG; a cap too small:
+ * SS_ERR_CAPACITY, with nothing written; a list whose grid or result size does not fit one launch (the limits of
+ * ss_batch_spectrum_stats' own grid: about 1.2e9 (region, fft channel) pairs, or 1e9 (group, fft channel) pairs, at fft_n = 4096):
+ * SS_ERR_UNSUPPORTED.  n_regions == 0 is valid. */
+int ss_batch_spectrum_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups);
+/* `count` regions of the last list from first_region on: mean_db / max_db [count][fft_channels][n_bins] f32 (device rows are
+ * fft_bin_stride apart, these are dense), windows_counted [count][fft_channels]; any of the three may be NULL.  cap_floats counts
+ * for mean_db and max_db each, cap_counts for windows_counted.  Waits for the batch's stream. */
+int ss_batch_download_region_spectra(ss_batch *b, uint32_t first_region, uint32_t count, float *mean_db, float *max_db, size_t cap_floats,
+                                     uint32_t *windows_counted, size_t cap_counts);
+/* the same for `count` groups from first_group on; the counts are u64 */
+int ss_batch_download_group_spectra(ss_batch *b, uint32_t first_group, uint32_t count, float *mean_db, float *max_db, size_t cap_floats,
+                                    uint64_t *windows_counted, size_t cap_counts);
+/* verification utility: how the last queued list was cut — ss_batch_spectrum_stats' rule on (regions x fft_channels) pairs and the
+ * longest region's window count: `chunks` runs of `chunk_windows` consecutive windows per region (either may be NULL); chunks > 1:
+ * partial sums per run, added in run order by a second launch (a few long regions); chunks == 1: one launch. */
+int ss_batch_spectrum_regions_plan(const ss_batch *b, uint32_t *chunks, uint32_t *chunk_windows);
+/* the windows [*first, *end) the sub-blocks [first_subblock, first_subblock + n_subblocks) own, before the cut at a stream's own
+ * window count (either pointer may be NULL); host arithmetic */
+void ss_region_windows(uint32_t sample_rate, uint32_t fft_n, uint32_t hop_frames, uint32_t first_subblock, uint32_t n_subblocks,
+                       uint32_t *first, uint32_t *end);
 /* [stream][cols][2] f32 (min, max) of the decimation bins x_min <= i < x_max */
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max);
 int ss_batch_download_waveform_columns(ss_batch *b, uint32_t stream, float *out, size_t cap_floats);

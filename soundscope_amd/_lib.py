@@ -57,6 +57,8 @@ SYMBOLS = [
     "ss_batch_spectrogram", "ss_batch_spectrogram_plan", "ss_batch_download_spectrogram", "ss_spectrogram_column_windows",
     "ss_batch_signal_scan", "ss_batch_signal_scan_plan", "ss_batch_download_stream_scans", "ss_batch_download_channel_scans",
     "ss_batch_download_signal_events",
+    "ss_batch_spectrum_regions", "ss_batch_download_region_spectra", "ss_batch_download_group_spectra",
+    "ss_batch_spectrum_regions_plan", "ss_region_windows",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -363,6 +365,11 @@ def _bind(lib):
         "ss_batch_download_stream_scans": (C.c_int, [vp, C.POINTER(StreamScan), C.c_uint32]),
         "ss_batch_download_channel_scans": (C.c_int, [vp, C.POINTER(ChannelScan), C.c_size_t]),
         "ss_batch_download_signal_events": (C.c_int, [vp, C.c_uint32, C.c_int, C.POINTER(SignalEvent), C.c_size_t, C.POINTER(C.c_uint32)]),
+        "ss_batch_spectrum_regions": (C.c_int, [vp, C.POINTER(LoudnessRegion), C.c_uint32, C.c_uint32]),
+        "ss_batch_download_region_spectra": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
+        "ss_batch_download_group_spectra": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, f32p, C.c_size_t, u64p, C.c_size_t]),
+        "ss_batch_spectrum_regions_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_region_windows": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -43,7 +43,7 @@ class Batch:
         """spectrum_columns > 0 (with L.SS_BATCH_FFT_COLUMNS in flags, added here if missing): columns-only spectrum — the
         render-side reduction runs inside the spectrum kernel and only that many chart columns per row are kept."""
         self._ragged = False                # set_lengths() has been called
-        self._listed = {"loudness": (0, 0), "peak": (0, 0)}       # (regions, groups) of the last accepted list of each kind
+        self._listed = {"loudness": (0, 0), "peak": (0, 0), "spectrum": (0, 0)}   # (regions, groups) of the last accepted list of each kind
         if spectrum_columns:
             flags |= L.SS_BATCH_FFT_COLUMNS
             self._render_cols = int(spectrum_columns)
@@ -412,6 +412,50 @@ class Batch:
         fp = C.POINTER(C.c_float)
         _check(L.lib().ss_batch_download_region_channel_peaks(self._h, tp.ctypes.data_as(fp), sp.ctypes.data_as(fp), tp.size))
         return tp, sp
+
+    # -- spectrum regions: average and peak-hold spectrum of time ranges of the streams, and of groups of them
+    def spectrum_regions(self, regions, n_groups=0):
+        """Queue the reduction of `regions` (rows as loudness_regions takes them, on the peak series' grid: a region may reach the
+        stream's tail entry) behind run(): each owns the windows that lie wholly inside it (region_windows).  Replaces the
+        previous list."""
+        self._set_list("spectrum", L.lib().ss_batch_spectrum_regions, regions, n_groups)
+
+    def _spectra(self, per_group, call, count_dtype, first, count):
+        lay = self.layout
+        count = self._listed["spectrum"][per_group] - int(first) if count is None else int(count)
+        shape = (max(count, 0), int(lay.fft_channels), int(lay.n_bins))
+        mean, mx, cnt = np.empty(shape, np.float32), np.empty(shape, np.float32), np.empty(shape[:2], count_dtype)
+        fp = C.POINTER(C.c_float)
+        _check(call(self._h, int(first), count, mean.ctypes.data_as(fp), mx.ctypes.data_as(fp), mean.size,
+                    cnt.ctypes.data_as(C.POINTER(C.c_uint32 if count_dtype == np.uint32 else C.c_uint64)), cnt.size))
+        return mean, mx, cnt
+
+    def region_spectra(self, first=0, count=None):
+        """(mean_db[count][R][n_bins], max_db[count][R][n_bins], windows_counted[count][R]) of `count` regions of the last
+        spectrum list from `first` on (None: all that follow): NaN values (refused windows) are skipped; nothing counted gives NaN
+        with count 0."""
+        return self._spectra(0, L.lib().ss_batch_download_region_spectra, np.uint32, first, count)
+
+    def group_spectra(self, first=0, count=None):
+        """The same triple per group of the last spectrum list: its regions pooled, every counted window of every region weighing
+        the same; the counts are u64."""
+        return self._spectra(1, L.lib().ss_batch_download_group_spectra, np.uint64, first, count)
+
+    @property
+    def spectrum_regions_plan(self):
+        """(chunks, chunk_windows): how the last spectrum_regions() list was cut (chunks > 1: partial sums and a second launch)."""
+        c, w = C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_batch_spectrum_regions_plan(self._h, C.byref(c), C.byref(w)))
+        return c.value, w.value
+
+    def region_windows(self, region):
+        """(w_first, w_end): the windows region (stream, first_subblock, n_subblocks[, group]) owns — ss_region_windows, cut to the
+        stream's own window count."""
+        a, e = C.c_uint32(), C.c_uint32()
+        cfg = self.cfg
+        L.lib().ss_region_windows(cfg.sample_rate, cfg.fft_n, cfg.hop_frames, int(region[1]), int(region[2]), C.byref(a), C.byref(e))
+        nw = int(self.stream_shape(int(region[0])).n_windows)
+        return min(a.value, nw), min(e.value, nw)
 
     # -- signal scan: silence, clip runs, DC and non-finite samples of every stream, and the lists of the runs
     def signal_scan(self, silence_threshold=0.0, clip_level=1.0, silence_min_frames=None, clip_min_samples=3, max_events=256):

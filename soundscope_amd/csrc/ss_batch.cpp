@@ -98,8 +98,8 @@ struct SpecStats {
     DevBuf<unsigned long long> corpus_counts;   // [fft_channels]
 };
 
-// The region list of a follow-up call (ss_batch_loudness_regions, ss_batch_peak_regions).  Each of the two holds its own, stage
-// included: a loudness list and a peak list live side by side.
+// The region list of a follow-up call (ss_batch_loudness_regions, ss_batch_peak_regions, ss_batch_spectrum_regions).  Each of the
+// three holds its own, stage included: a loudness list, a peak list and a spectrum list live side by side.
 struct RegionList {
     bool done = false;                          // a list has been queued: there is something to download
     uint32_t n_regions = 0, n_groups = 0;       // of the last call that was queued
@@ -134,6 +134,20 @@ struct Peaks {
     DevBuf<float> ch_true, ch_sample;                   // [region][channels]
     DevBuf<unsigned long long> group_acc;               // [group][3] (RegionPeaksParams::group_acc)
     DevBuf<ssk::GroupPeaks> group_results;
+};
+
+// spectrum regions (ss_batch_spectrum_regions): all of it allocated at the batch's first call and grown by a longer list, so a
+// batch that never asks holds none of it.  The kernels read the list as the host resolved it — `table`: the ssk::SpecRegion
+// records, then the groups' member lists — which goes through the list's stage in one upload; the list's own `dev` stays empty.
+struct SpectrumRegions {
+    RegionList list;
+    ssk::SpecStatsPlan plan;                            // of the last list that was queued
+    DevBuf<uint32_t> table;                             // 4 words per region, member_start [n_groups + 1], members [grouped regions]
+    DevBuf<double> sums, part_sums;                     // SpecRegionsParams::s' arrays of these names
+    DevBuf<float> mean, max, part_max;
+    DevBuf<uint32_t> counts, part_counts;
+    DevBuf<float> group_mean, group_max;                // [group][fft_channels][fft_bin_stride]
+    DevBuf<unsigned long long> group_counts;            // [group][fft_channels]
 };
 
 // signal scan (ss_batch_signal_scan): all of it allocated at the batch's first call (the lists grown by a larger max_events), so a
@@ -205,6 +219,7 @@ struct ss_batch {
     SpecStats stats;
     Regions regions;
     Peaks peaks;
+    SpectrumRegions spec_regions;
     SignalScan scan;
     Spectrogram spectrogram;
     Overlap ov;
@@ -1274,15 +1289,15 @@ int ss_batch_spectrum_stats_plan(const ss_batch *b, uint32_t *chunks, uint32_t *
     return SS_OK;
 }
 
-// the compact [fft_channels][n_bins] copies of two [fft_channels][fft_bin_stride] device arrays (either host pointer may be null),
-// queued on the batch's stream
-static int fetch_stats_rows(ss_batch *b, float *mean_db, float *max_db, const float *mean_d, const float *max_d)
+// the compact [rows][n_bins] copies of two [rows][fft_bin_stride] device arrays (either host pointer may be null), queued on the
+// batch's stream; rows: fft_channels per stream, region or group
+static int fetch_stats_rows(ss_batch *b, float *mean_db, float *max_db, const float *mean_d, const float *max_d, size_t rows)
 {
     const ss_batch_layout &L = b->lay;
     const size_t row = (size_t)L.n_bins * sizeof(float), pitch = (size_t)L.fft_bin_stride * sizeof(float);
     if (!row) return SS_OK;
-    if (mean_db) HIPCHK(hipMemcpy2DAsync(mean_db, row, mean_d, pitch, row, L.fft_channels, hipMemcpyDeviceToHost, b->stream));
-    if (max_db) HIPCHK(hipMemcpy2DAsync(max_db, row, max_d, pitch, row, L.fft_channels, hipMemcpyDeviceToHost, b->stream));
+    if (mean_db) HIPCHK(hipMemcpy2DAsync(mean_db, row, mean_d, pitch, row, rows, hipMemcpyDeviceToHost, b->stream));
+    if (max_db) HIPCHK(hipMemcpy2DAsync(max_db, row, max_d, pitch, row, rows, hipMemcpyDeviceToHost, b->stream));
     return SS_OK;
 }
 
@@ -1295,7 +1310,7 @@ int ss_batch_download_spectrum_stats(ss_batch *b, uint32_t stream, float *mean_d
     const ss_batch_layout &L = b->lay;
     if (cap_floats < (size_t)L.fft_channels * L.n_bins || (windows_counted && cap_channels < L.fft_channels)) return SS_ERR_CAPACITY;
     const size_t at = (size_t)stream * L.fft_channels * L.fft_bin_stride;
-    int rc = fetch_stats_rows(b, mean_db, max_db, b->stats.mean.p + at, b->stats.max.p + at);
+    int rc = fetch_stats_rows(b, mean_db, max_db, b->stats.mean.p + at, b->stats.max.p + at, L.fft_channels);
     if (rc) return rc;
     // the count of a channel is bin 0's: one u32 of every [fft_bin_stride] row
     if (windows_counted && L.fft_bin_stride)
@@ -1315,7 +1330,7 @@ int ss_batch_corpus_spectrum(ss_batch *b, float *mean_db, float *max_db, size_t 
     SpecStats &st = b->stats;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the pooled counts are copied out as they are");
     HIPCHK(ssk::launch_spectrum_stats_corpus(batch_stats_params(b), st.corpus_mean.p, st.corpus_max.p, st.corpus_counts.p, b->stream));
-    int rc = fetch_stats_rows(b, mean_db, max_db, st.corpus_mean.p, st.corpus_max.p);
+    int rc = fetch_stats_rows(b, mean_db, max_db, st.corpus_mean.p, st.corpus_max.p, L.fft_channels);
     if (rc) return rc;
     if (windows_counted && L.fft_bin_stride)
         HIPCHK(hipMemcpyAsync(windows_counted, st.corpus_counts.p, L.fft_channels * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
@@ -1586,6 +1601,146 @@ int ss_batch_download_region_channel_peaks(ss_batch *b, float *true_pk, float *s
     if (cap_floats < n) return SS_ERR_CAPACITY;
     if (n && true_pk) HIPCHK(hipMemcpyAsync(true_pk, b->peaks.ch_true.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     if (n && sample_pk) HIPCHK(hipMemcpyAsync(sample_pk, b->peaks.ch_sample.p, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    return ss_batch_sync(b);
+}
+
+// ---- spectrum regions: average and peak-hold spectrum of time ranges and groups -----------------------------------------------------
+static_assert(sizeof(ssk::SpecRegion) == 16, "resolved region layout");
+
+// The windows [first, end) that lie wholly inside the sub-blocks [a, a + n) of S frames, before the cut at a stream's window count:
+// window w covers the frames [first_start + w hop, first_start + w hop + fft_n), first_start where stream_shape puts window 0.
+// (a, n < 2^32, S < 2^29, fft_n + hop < 2^33: everything fits 64 bits.)
+struct WindowRange { uint64_t first, end; };
+static WindowRange region_windows(uint64_t S, uint64_t fft_n, uint64_t hop, uint64_t a, uint64_t n)
+{
+    if (!fft_n || !hop) return {0, 0};
+    const uint64_t f0 = a * S, f1 = (a + n) * S, first_start = (fft_n / hop + 1) * hop - fft_n;
+    const uint64_t lo = f0 <= first_start ? 0 : (f0 - first_start + hop - 1) / hop;
+    const uint64_t hi = f1 >= first_start + fft_n ? (f1 - fft_n - first_start) / hop + 1 : 0;
+    return {lo, lo > hi ? lo : hi};
+}
+
+void ss_region_windows(uint32_t sample_rate, uint32_t fft_n, uint32_t hop_frames, uint32_t first_subblock, uint32_t n_subblocks,
+                       uint32_t *first, uint32_t *end)
+{
+    const WindowRange r = region_windows(((uint64_t)sample_rate + 5u) / 10u, fft_n, hop_frames, first_subblock, n_subblocks);
+    if (first) *first = (uint32_t)std::min<uint64_t>(r.first, 0xFFFFFFFFull);
+    if (end) *end = (uint32_t)std::min<uint64_t>(r.end, 0xFFFFFFFFull);
+}
+
+int ss_batch_spectrum_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (!has_spectrum_rows(b)) return SS_ERR_INVALID_MODE;
+    uint32_t longest_sub = 0;
+    int rc = check_regions(b, regions, n_regions, n_groups, [b](uint32_t s) { return peak_entries_of(b, s); }, &longest_sub);
+    if (rc) return rc;
+    const ss_batch_layout &L = b->lay;
+    // every region as the kernels read it: its windows, cut to its stream's own count; the longest one makes the plan
+    std::vector<uint32_t> own(b->cfg.n_streams, L.n_windows);
+    if (b->ragged.on)
+        for (uint32_t s = 0; s < b->cfg.n_streams; s++) own[s] = std::min(stream_shape(b, b->frames_of(s)).windows, L.n_windows);
+    std::vector<ssk::SpecRegion> resolved(n_regions);
+    uint32_t longest = 0, grouped = 0;
+    for (uint32_t i = 0; i < n_regions; i++) {
+        const ss_loudness_region &r = regions[i];
+        const WindowRange w = region_windows(peak_s100(b), b->cfg.fft_n, b->cfg.hop_frames, r.first_subblock, r.n_subblocks);
+        const uint32_t nw = own[r.stream];
+        resolved[i] = {r.stream, (uint32_t)std::min<uint64_t>(w.first, nw), (uint32_t)std::min<uint64_t>(w.end, nw), r.group};
+        longest = std::max(longest, resolved[i].w_end - resolved[i].w_first);
+        grouped += r.group != SS_REGION_NO_GROUP;
+    }
+    SpectrumRegions &sr = b->spec_regions;
+    ssk::SpecStatsPlan plan;
+    if (!ssk::spectrum_regions_fit(n_regions, n_groups, L.fft_channels, L.fft_bin_stride, longest, &plan)) return SS_ERR_UNSUPPORTED;
+    const size_t per = (size_t)L.fft_channels * L.fft_bin_stride, all = per * n_regions, parts = plan.chunks > 1 ? all * plan.chunks : 0;
+    HIPCHK(sr.sums.ensure(all)); HIPCHK(sr.mean.ensure(all)); HIPCHK(sr.max.ensure(all)); HIPCHK(sr.counts.ensure(all));
+    HIPCHK(sr.part_sums.ensure(parts)); HIPCHK(sr.part_max.ensure(parts)); HIPCHK(sr.part_counts.ensure(parts));
+    HIPCHK(sr.group_mean.ensure(per * n_groups)); HIPCHK(sr.group_max.ensure(per * n_groups));
+    HIPCHK(sr.group_counts.ensure((size_t)L.fft_channels * n_groups));
+    // the table, built in the stage: the records, then member_start (a counting sort's prefix sums) and every group's members in
+    // region index order
+    const size_t start_at = (size_t)4 * n_regions, members_at = start_at + n_groups + 1, words = members_at + grouped;
+    HIPCHK(sr.table.ensure(words));
+    HIPCHK(sr.list.stage.take(words * sizeof(uint32_t)));
+    uint32_t *t = reinterpret_cast<uint32_t *>(sr.list.stage.buf.p);
+    if (n_regions) std::memcpy(t, resolved.data(), (size_t)n_regions * sizeof(ssk::SpecRegion));
+    std::vector<uint32_t> next((size_t)n_groups + 1, 0u);           // a group's next free place among the members
+    for (const ssk::SpecRegion &r : resolved) if (r.group != SS_REGION_NO_GROUP) next[r.group + 1]++;
+    for (uint32_t g = 0; g < n_groups; g++) next[g + 1] += next[g];
+    std::memcpy(t + start_at, next.data(), next.size() * sizeof(uint32_t));
+    for (uint32_t i = 0; i < n_regions; i++) if (resolved[i].group != SS_REGION_NO_GROUP) t[members_at + next[resolved[i].group]++] = i;
+    HIPCHK(sr.list.stage.queue(sr.table.p, words * sizeof(uint32_t), b->stream));
+    ssk::SpecRegionsParams q{};
+    q.s = batch_stats_params(b);
+    q.s.n_streams = n_regions; q.s.windows_of = nullptr; q.s.plan = plan;
+    q.s.sums = sr.sums.p; q.s.mean = sr.mean.p; q.s.max = sr.max.p; q.s.counts = sr.counts.p;
+    q.s.part_sums = sr.part_sums.p; q.s.part_max = sr.part_max.p; q.s.part_counts = sr.part_counts.p;
+    q.regions = reinterpret_cast<const ssk::SpecRegion *>(sr.table.p);
+    q.n_groups = n_groups; q.member_start = sr.table.p + start_at; q.members = sr.table.p + members_at;
+    q.group_mean = sr.group_mean.p; q.group_max = sr.group_max.p; q.group_counts = sr.group_counts.p;
+    HIPCHK(ssk::launch_spectrum_regions(q, b->stream));
+    sr.plan = plan;
+    sr.list.queued(n_regions, n_groups);
+    return SS_OK;
+}
+
+static bool has_spectrum_regions(const ss_batch *b) { return has_spectrum_rows(b) && b->spec_regions.list.done; }
+
+int ss_batch_spectrum_regions_plan(const ss_batch *b, uint32_t *chunks, uint32_t *chunk_windows)
+{
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (!has_spectrum_regions(b)) return SS_ERR_INVALID_MODE;
+    if (chunks) *chunks = b->spec_regions.plan.chunks;
+    if (chunk_windows) *chunk_windows = b->spec_regions.plan.chunk_windows;
+    return SS_OK;
+}
+
+// the status ladder of the two downloads, `listed` the regions or groups of the last list: the mode, the range, the capacities
+static int check_spectra_range(const ss_batch *b, uint32_t listed, uint32_t first, uint32_t count, bool floats, size_t cap_floats,
+                               bool counts, size_t cap_counts)
+{
+    if (!has_spectrum_regions(b)) return SS_ERR_INVALID_MODE;
+    if ((uint64_t)first + count > listed) return SS_ERR_INVALID_ARG;
+    const size_t rows = (size_t)count * b->lay.fft_channels;
+    if ((floats && cap_floats < rows * b->lay.n_bins) || (counts && cap_counts < rows)) return SS_ERR_CAPACITY;
+    return SS_OK;
+}
+
+int ss_batch_download_region_spectra(ss_batch *b, uint32_t first_region, uint32_t count, float *mean_db, float *max_db, size_t cap_floats,
+                                     uint32_t *windows_counted, size_t cap_counts)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const SpectrumRegions &sr = b->spec_regions;
+    int rc = check_spectra_range(b, sr.list.n_regions, first_region, count, mean_db || max_db, cap_floats, windows_counted != nullptr, cap_counts);
+    if (rc) return rc;
+    const ss_batch_layout &L = b->lay;
+    const size_t rows = (size_t)count * L.fft_channels, at = (size_t)first_region * L.fft_channels * L.fft_bin_stride;
+    if (rows && (rc = fetch_stats_rows(b, mean_db, max_db, sr.mean.p + at, sr.max.p + at, rows))) return rc;
+    // the count of a (region, channel) is bin 0's: one u32 of every [fft_bin_stride] row
+    if (rows && windows_counted && L.fft_bin_stride)
+        HIPCHK(hipMemcpy2DAsync(windows_counted, sizeof(uint32_t), sr.counts.p + at, (size_t)L.fft_bin_stride * sizeof(uint32_t),
+                                sizeof(uint32_t), rows, hipMemcpyDeviceToHost, b->stream));
+    return ss_batch_sync(b);
+}
+
+int ss_batch_download_group_spectra(ss_batch *b, uint32_t first_group, uint32_t count, float *mean_db, float *max_db, size_t cap_floats,
+                                    uint64_t *windows_counted, size_t cap_counts)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const SpectrumRegions &sr = b->spec_regions;
+    int rc = check_spectra_range(b, sr.list.n_groups, first_group, count, mean_db || max_db, cap_floats, windows_counted != nullptr, cap_counts);
+    if (rc) return rc;
+    const ss_batch_layout &L = b->lay;
+    const size_t rows = (size_t)count * L.fft_channels, at = (size_t)first_group * L.fft_channels * L.fft_bin_stride;
+    if (rows && (rc = fetch_stats_rows(b, mean_db, max_db, sr.group_mean.p + at, sr.group_max.p + at, rows))) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the pooled counts are copied out as they are");
+    if (rows && windows_counted && L.fft_bin_stride)
+        HIPCHK(hipMemcpyAsync(windows_counted, sr.group_counts.p + (size_t)first_group * L.fft_channels, rows * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost, b->stream));
     return ss_batch_sync(b);
 }
 

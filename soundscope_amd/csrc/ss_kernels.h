@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -144,6 +144,27 @@ struct SpecStatsParams {
 hipError_t launch_spectrum_stats(const SpecStatsParams &p, hipStream_t s);
 // the batch pooled from p.sums / p.max / p.counts, streams in index order: mean / max [fft_ch][bin_stride], counts [fft_ch] (bin 0's)
 hipError_t launch_spectrum_stats_corpus(const SpecStatsParams &p, float *mean, float *max, unsigned long long *counts, hipStream_t s);
+// Spectrum regions (ss_batch_spectrum_regions; ss_spectrum_regions.hip): the same reduction over time ranges of the streams, pooled into groups.  The host
+// resolves a region to the windows [w_first, w_end) of its stream, w_end no larger than the stream's own window count, so the kernels
+// divide nothing and never read a row behind it.
+struct SpecRegion { uint32_t stream, w_first, w_end, group; };
+struct SpecRegionsParams {
+    // the sweep's block with (region, fft_channel) for its pairs: rows, bin_stride, n_bins, fft_ch and n_windows (of the stream slot)
+    // as in ss_batch_spectrum_stats; n_streams = the REGIONS, windows_of unused; plan = plan_spectrum_stats(regions x fft_ch,
+    // bin_stride, the longest region's windows); sums / mean / max / counts [region][fft_ch][bin_stride], the parts
+    // [region][fft_ch][chunk][bin_stride]
+    SpecStatsParams s;
+    const SpecRegion *regions;       // [regions]
+    uint32_t n_groups;
+    const uint32_t *member_start;    // [n_groups + 1]: group g's members are members[member_start[g] .. member_start[g + 1])
+    const uint32_t *members;         // region indices, ascending inside a group
+    float *group_mean, *group_max;   // [group][fft_ch][bin_stride]
+    unsigned long long *group_counts;// [group][fft_ch]: the pooled count at bin 0
+};
+// whether a list fits the launch limits (launch_spectrum_stats' own, on the regions' and the groups' grids), and its plan
+bool spectrum_regions_fit(uint64_t n_regions, uint64_t n_groups, uint32_t fft_ch, uint32_t bin_stride, uint32_t longest_windows, SpecStatsPlan *plan);
+// k_spectrum_regions, k_spectrum_regions_combine where the plan has chunks, k_spectrum_region_groups where there are groups
+hipError_t launch_spectrum_regions(const SpecRegionsParams &q, hipStream_t s);
 
 // batch spectrogram (ss_spectrogram.hip): time x frequency chart tiles of the rows (or of a columns-only pass's columns)
 constexpr uint32_t kSpectrogramMaxTCols = 4096, kSpectrogramMaxFCols = 512;
