@@ -1,11 +1,14 @@
-"""Plain f64 restatements, from the published definitions, that the time-domain tests hold the device path to (a helper
-module, not a test file): none of it calls the product or the oracle.
+"""Plain f64 restatements, from the published definitions, that the time-domain, gating and spectrum tests hold the device path
+to (a helper module, not a test file): none of it calls the product or the oracle.
 
   * K-weighting: libebur128's design (ebur128_init_filter: a high shelf, then the 38 Hz high-pass, each by bilinear transform,
     numerators and denominators convolved into one 4th-order section) for any rate, run as a sequential f64 filter;
   * the crate's true-peak interpolator: 49 Hann-windowed sinc taps rounded to f32, a zero-stuffed polyphase convolution in f64;
   * ebur128's channel weights, and the momentary / short-term series as `loudness_momentary()` / `loudness_shortterm()` return
     them after every 100 ms sub-block (zeros before the start);
+  * the gate (BS.1770-4, EBU Tech 3342, ebur128's histogram mode): the bin tables, gating and short-term block energies from
+    sub-block energies with the additions in a fixed order, their histograms, integrated loudness and loudness range of a
+    histogram, and the reading of a sliding window;
   * get_waveform's min-max decimation (analyzer.rs:107-137);
   * the spectrum rows (analyzer.rs:11-27, :55-105): the retained-bin rule, mid / side formed in f32, one row of any mono window
     with the transform in f64, and `row_error`, the metric the spectrum forms are held to.
@@ -74,6 +77,135 @@ def loudness_series(sub, rate, channels):
     S = subblock_frames(rate)
     e = sub @ channel_weights(channels)
     return _window_loudness(e, 4, S), _window_loudness(e, 30, S)
+
+
+# ---- the gate: BS.1770-4 gating blocks, EBU Tech 3342 short-term blocks, ebur128's histogram mode
+HIST_BINS = 1000
+
+
+def histogram_tables():
+    """(energies[1000], bounds[1001]) of ebur128's histogram mode: bin i spans [-70 + i / 10, -70 + (i + 1) / 10) LUFS and stands
+    for the energy of its centre."""
+    i = np.arange(HIST_BINS + 1, dtype=np.float64)
+    return 10.0 ** ((-69.95 + i[:-1] / 10.0 + 0.691) / 10.0), 10.0 ** ((-70.0 + i / 10.0 + 0.691) / 10.0)
+
+
+def _window_energies(sub, w, k, ends, S):
+    """Energy of the k sub-blocks that end with each sub-block of `ends`: over the weighted channels in order, w_c times the
+    channel's k sub-blocks added oldest first, the channels' terms added in order, then one division by k S — every step one
+    rounded f64 operation, so the same inputs give the same bits wherever these operations run in this order."""
+    ends = np.asarray(ends, np.int64)
+    total = np.zeros(ends.size)
+    for c in np.flatnonzero(w):
+        cs = sub[ends - (k - 1), c].astype(np.float64)
+        for q in range(k - 2, -1, -1):
+            cs = cs + sub[ends - q, c]
+        total = total + w[c] * cs
+    return total / (float(k) * S)
+
+
+def gate_blocks(sub, rate, channels, first=0, n=None):
+    """(gating-block energies, short-term energies) of the sub-blocks [first, first + n) of `sub` ([sub-block][channel] energies;
+    n=None: all from `first` on).  A gating block ends with every sub-block j >= first + 3 (400 ms, 75 % overlap), a short-term
+    block with j = first + 29 + 10 m (3 s every second: the crate's cadence, its phase at the start of the range)."""
+    sub = np.asarray(sub, np.float64).reshape(-1, channels)
+    n = sub.shape[0] - first if n is None else n
+    assert 0 <= first and n >= 0 and first + n <= sub.shape[0], (first, n, sub.shape)
+    S = float(subblock_frames(rate))
+    w = channel_weights(channels)
+    return (_window_energies(sub, w, 4, np.arange(first + 3, first + n), S),
+            _window_energies(sub, w, 30, np.arange(first + 29, first + n, 10), S))
+
+
+def hist_bins_of(energies):
+    """bin of every energy: i with bounds[i] <= e < bounds[i + 1], the top bin open above; -1 for what is never counted (an
+    energy under bounds[0], a NaN)"""
+    _, bd = histogram_tables()
+    e = np.asarray(energies, np.float64).reshape(-1)
+    idx = np.minimum(np.searchsorted(bd, e, side="right") - 1, HIST_BINS - 1)      # (NaN sorts behind every bound: excluded below)
+    return np.where(e >= bd[0], idx, -1)
+
+
+def gate_histograms(blocks, st):
+    """(block histogram, short-term histogram), u64[1000] each, of the energies gate_blocks returns"""
+    out = []
+    for e in (blocks, st):
+        idx = hist_bins_of(e)
+        out.append(np.bincount(idx[idx >= 0], minlength=HIST_BINS).astype(np.uint64))
+    return out[0], out[1]
+
+
+def hist_moments(h):
+    """(count, mean energy) of a histogram, its bins standing for their centre energies; the sum is exact (fsum)"""
+    import math
+    en, _ = histogram_tables()
+    h = np.asarray(h, np.uint64)
+    cnt = int(h.sum(dtype=np.uint64))
+    return cnt, (math.fsum(h.astype(np.float64) * en) / cnt if cnt else 0.0)
+
+
+def gate_start_bin(threshold):
+    """First bin a relative threshold (an energy) admits: the bin that holds it, plus one if it exceeds that bin's energy — a
+    bin counts only if the energy it stands for reaches the threshold.  (holding bin, start bin); (0, 0) under the first bound."""
+    en, bd = histogram_tables()
+    if threshold < bd[0]:
+        return 0, 0
+    i = int(hist_bins_of([threshold])[0])
+    return i, i + 1 if threshold > en[i] else i
+
+
+def integrated_from_hist(hb, start=None):
+    """Gated loudness of a block histogram (BS.1770-4 in the crate's histogram mode): the mean of the bins from the relative
+    gate's start bin on — 0.1 x the mean of all counted blocks; -inf for an empty histogram or an empty gate.  `start`: another
+    start bin, for telling two readings of the gate rule apart."""
+    import math
+    en, _ = histogram_tables()
+    cnt, mean = hist_moments(hb)
+    if cnt == 0:
+        return -np.inf
+    if start is None:
+        start = gate_start_bin(0.1 * mean)[1]
+    cnt, mean = hist_moments(np.concatenate([np.zeros(start, np.uint64), np.asarray(hb, np.uint64)[start:]]))
+    return 10.0 * math.log10(mean) - 0.691 if cnt else -np.inf
+
+
+def lra_entries_from_hist(hs, start=None):
+    """(gate start bin, gated count, bin of the 10 % entry, bin of the 95 % entry) of a short-term histogram, None for the bins
+    of an empty gate: EBU Tech 3342 in the crate's histogram mode — relative gate 0.01 x the mean of all counted values, the
+    entries of ranks floor((n - 1) p + 0.5) among the n gated ones (the product in f64, as the crate forms it).  `start`: another
+    start bin, as integrated_from_hist takes one."""
+    hs = np.asarray(hs, np.uint64)
+    cnt, mean = hist_moments(hs)
+    if cnt == 0:
+        return 0, 0, None, None
+    if start is None:
+        start = gate_start_bin(0.01 * mean)[1]
+    cum = np.cumsum(hs[start:], dtype=np.uint64)
+    n = int(cum[-1]) if cum.size else 0
+    if n == 0:
+        return start, 0, None, None
+    lo, hi = (int(float(n - 1) * p + 0.5) for p in (0.1, 0.95))
+    return (start, n, start + int(np.searchsorted(cum, np.uint64(lo), side="right")),
+            start + int(np.searchsorted(cum, np.uint64(hi), side="right")))
+
+
+def lra_from_hist(hs, start=None):
+    """Loudness range of a short-term histogram: the 95 % entry's bin over the 10 % entry's, in LU; 0 where nothing is gated"""
+    import math
+    en, _ = histogram_tables()
+    _, n, lo, hi = lra_entries_from_hist(hs, start)
+    return 10.0 * math.log10(en[hi]) - 10.0 * math.log10(en[lo]) if n else 0.0
+
+
+def window_reading(y, weights, F, frames):
+    """The reading of a sliding window at frame F: -0.691 + 10 log10 of the channel-weighted mean square of the filtered signal
+    y ([frame][channel]) over the frames [F - frames, F), zeros in front of frame 0 (the divisor is `frames` throughout, as a
+    meter's zeroed ring has it); -inf for silence."""
+    import math
+    y = np.asarray(y, np.float64)
+    seg = y[max(F - frames, 0):F]
+    e = float(((seg * seg).sum(axis=0) * np.asarray(weights, np.float64)).sum()) / frames
+    return 10.0 * math.log10(e) - 0.691 if e > 0.0 else -np.inf
 
 
 def interpolator_taps(factor):

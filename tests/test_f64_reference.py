@@ -154,3 +154,113 @@ def test_oracle_get_fft_against_the_f64_row(oracle):
                 assert db_close(got, ref, 0.01), (rate, n)
                 worst = max(worst, R.row_error(got, ref, R.pink_db(rate, n)))
     assert worst <= 1e-6, worst
+
+
+# ---- the gate of tests/test_gpu_gating_forms.py
+
+def test_histogram_tables_equal_the_product():
+    """the reference's own bin energies and boundaries against the tables the kernels receive, at test_product_tables' bound"""
+    import ctypes as C
+    from soundscope_amd import _lib as L
+    e, b = np.empty(1000), np.empty(1001)
+    f64p = C.POINTER(C.c_double)
+    assert L.lib().ss_inspect_histogram(e.ctypes.data_as(f64p), b.ctypes.data_as(f64p)) == 0
+    en, bd = R.histogram_tables()
+    assert en.shape == (1000,) and bd.shape == (1001,)
+    assert np.allclose(en, e, rtol=1e-14, atol=0.0) and np.allclose(bd, b, rtol=1e-14, atol=0.0)
+    assert np.all((en > bd[:-1]) & (en < bd[1:]))
+
+
+def _random_histograms():
+    """a few hundred histograms: sparse (one to six bins anywhere, or within a lane or two of each other) and dense (every bin,
+    or a band), counts of 1 ... 2^40 spread over the magnitudes"""
+    rng = np.random.default_rng(3342)
+    for k in range(360):
+        h = np.zeros(1000, np.uint64)
+        top = int(rng.integers(1, 41))
+        if k % 3 == 0:
+            bins = rng.integers(0, 1000, int(rng.integers(1, 7)))
+        elif k % 3 == 1:
+            lo = int(rng.integers(0, 960))
+            bins = lo + rng.integers(0, 40, int(rng.integers(1, 7)))
+        else:
+            lo = int(rng.integers(0, 700))
+            bins = np.arange(lo, 1000 if k % 2 else lo + int(rng.integers(20, 300)))
+        h[bins] = (2.0 ** rng.uniform(0, top, len(bins))).astype(np.uint64)
+        yield h
+
+
+def _close_lu(got, want, tol):
+    return got == want if np.isinf(want) or want == 0.0 else abs(got - want) <= tol
+
+
+def test_histogram_evaluation_agrees_with_the_oracle(oracle):
+    """integrated_from_hist / lra_from_hist against the oracle's evaluation of the same histogram.  1e-11 LU is derived, not
+    measured: either side adds at most 1000 positive f64 terms in some order (relative error at most 1000 x 2^-53 = 1.1e-13,
+    4.8e-13 LU), which leaves a tenfold margin for the log10 and the tables' last bits."""
+    import _gating_plants as P
+    hists = list(_random_histograms()) + [np.zeros(1000, np.uint64)]
+    for p in P.PLANTS:
+        ref = P.reference(P.signal_of(p))
+        hists += [ref.hb, ref.hs]
+    seen = [0, 0]
+    for k, h in enumerate(hists):
+        gi, wi = R.integrated_from_hist(h), oracle.gated_loudness_hist(h)
+        gl, wl = R.lra_from_hist(h), oracle.loudness_range_hist(h)
+        assert _close_lu(gi, wi, 1e-11), (k, gi, wi)
+        assert _close_lu(gl, wl, 1e-11), (k, gl, wl)
+        seen[0] += np.isfinite(wi)
+        seen[1] += wl > 0.0
+    assert seen[0] > 300 and seen[1] > 200, seen
+    assert R.integrated_from_hist(np.zeros(1000, np.uint64)) == -np.inf and R.lra_from_hist(np.zeros(1000, np.uint64)) == 0.0
+
+
+def test_gate_reference_edges():
+    """the reference's own rules on hand-made cases: the bins' half-open edges, the open top bin, what is never counted, the
+    start-bin rule on either side of a bin's energy, the short-term phase of a range, the order of the additions"""
+    en, bd = R.histogram_tables()
+    e = np.array([bd[0], np.nextafter(bd[0], 0.0), bd[1], np.nextafter(bd[1], 0.0), bd[999], bd[1000], 1e30, np.inf, np.nan, 0.0, -1.0])
+    assert list(R.hist_bins_of(e)) == [0, -1, 1, 0, 999, 999, 999, 999, -1, -1, -1]
+    hb, hs = R.gate_histograms(e, e[:0])
+    assert hb.sum() == 7 and hb[999] == 4 and hs.sum() == 0
+    assert R.gate_start_bin(en[500]) == (500, 500) and R.gate_start_bin(np.nextafter(en[500], 1.0)) == (500, 501)
+    assert R.gate_start_bin(bd[500]) == (500, 500) and R.gate_start_bin(np.nextafter(bd[0], 0.0)) == (0, 0)
+    sub = np.arange(1.0, 61.0)[:, None] * np.array([[1.0, 0.5, 0.25, 1e6, 2.0, 4.0]])
+    blocks, st = R.gate_blocks(sub, 8000, 6, first=7, n=40)
+    w = np.array([1.0, 0.5, 0.25, 0.0, 2.82, 5.64]).sum()
+    assert blocks.size == 37 and st.size == 2
+    assert np.allclose(blocks, w * np.array([sum(range(j - 2, j + 2)) for j in range(10, 47)]) / 3200.0, rtol=1e-15)
+    assert np.allclose(st, w * np.array([sum(range(j - 28, j + 2)) for j in (36, 46)]) / 24000.0, rtol=1e-15)
+    assert [a.size for a in R.gate_blocks(sub, 8000, 6, first=3, n=3)] == [0, 0] and [a.size for a in R.gate_blocks(sub, 8000, 6, 0, 30)] == [27, 1]
+    # the ranks floor((n - 1) p + 0.5): two entries are ranks 0 and 1, eleven 1 and 10
+    h = np.zeros(1000, np.uint64); h[[300, 310]] = 1
+    assert R.lra_entries_from_hist(h)[1:] == (2, 300, 310)
+    h[:] = 0; h[400:411] = 1
+    assert R.lra_entries_from_hist(h)[1:] == (11, 401, 410)
+    y = np.ones((100, 2))
+    assert R.window_reading(y, [1.0, 1.0], 10, 40) == 10.0 * np.log10(20.0 / 40.0) - 0.691
+    assert R.window_reading(y, [1.0, 0.0], 100, 40) == -0.691 and R.window_reading(0 * y, [1.0, 1.0], 50, 40) == -np.inf
+
+
+def _plants():
+    import _gating_plants as P
+    return P.PLANTS
+
+
+@pytest.mark.parametrize("plant", _plants(), ids=[p.name for p in _plants()])
+def test_planted_signals_against_the_meter(oracle, plant):
+    """every planted signal of the gating forms test: its condition holds in the reference, no value of the reference lies within
+    1e-5 LU of a bin edge, and gate_blocks over the f64 sub-blocks agrees with the oracle's meter fed the same samples — the same
+    bins (hence block counts), integrated loudness and range within 1e-6 LU"""
+    import _gating_plants as P
+    x = P.signal_of(plant)
+    ref = P.reference(x)
+    plant.check(ref)
+    assert ref.n_sub == sum(n for n, _ in plant.segments) and ref.blocks.size == ref.n_sub - 3
+    assert P.edge_clearance(ref) >= 1e-5, P.edge_clearance(ref)
+    m = oracle.Meter(1, P.RATE)
+    m.add_frames(x)
+    assert m.block_hist().sum() == ref.hb.sum() and m.st_hist().sum() == ref.hs.sum()
+    assert np.array_equal(m.block_hist(), ref.hb) and np.array_equal(m.st_hist(), ref.hs)
+    assert _close_lu(m.integrated(), ref.integrated, 1e-6), (m.integrated(), ref.integrated)
+    assert _close_lu(m.loudness_range(), ref.lra, 1e-6), (m.loudness_range(), ref.lra)
