@@ -767,6 +767,69 @@ int ss_meter_bank_spectrum_tracked_columns(ss_meter_bank *m, uint32_t cols, int 
                                            float *avg_cols, float *hold_cols, size_t cap_floats,
                                            uint32_t *updates, uint32_t cap_rows);
 
+/* Signal watch of a bank: the live counterpart of ss_batch_signal_scan — is this input silent and since when, is
+ * it clipping now, how often and for how long at a time, did a non-finite sample arrive, is a DC offset building up — kept on the
+ * device for every stream and advanced by every add call, whichever of the six forms it has.  Not in the reference.
+ *  The definition is the batch scan's, so there is one: after any sequence of adds, stream s's records equal what
+ *  ss_batch_signal_scan defines for ONE stream that is the concatenation of every frame stream s was given since its watch was last
+ *  reset, with F_s = frames.  The predicates, runs and minima are those of the batch scan's comment above, unchanged: a frame is
+ *  silent iff fabsf(x) <= silence_threshold on every channel, a sample clipped iff fabsf(x) >= clip_level, f32 comparisons as
+ *  written, a NaN holds neither predicate, a run is a maximal stretch of frames on which a predicate holds.  Frame numbers count
+ *  from the stream's watch reset.  Consequences:
+ *  - The run open at the newest frame is a run: it counts in silence_runs / clip_runs where it reaches the minimum, it is
+ *    trailing_silence (the dead-air figure) / trailing_clip, and it takes part in longest_*; ties go to the lowest frame.
+ *  - How the material was cut into calls changes no integer: one call, 10 ms blocks, one frame at a time and ragged calls agree.
+ *  - The two f64 sums add the kernel's tiles (ss_meter_bank_signal_watch_plan's tile_frames frames of one call at most) in
+ *    ascending order behind the state.  Their order is fixed by the call sequence and the plan, not by timing; there are no
+ *    floating-point atomics: two banks fed the same calls agree byte for byte.  Differently cut feeds agree within the bound of
+ *    f64 summation — (N - 1) u / (1 - (N - 1) u) times the sum of |x| (of x^2), u = 2^-53 — not in bits.
+ *  - DC or RMS of the last interval: difference two reads (sum, sum_sq, frames and nonfinite are all running totals).
+ *  - For the PCM forms the predicates see the f32 values the meter sees, ss_pcm_decode's.
+ *  - A stream given 0 frames in a call is not touched, its state and records stay byte for byte, and an all-zero call launches
+ *    nothing.  A non-finite sample touches its own stream's counters only.
+ *  - ss_meter_bank_reset resets the meters, not the watch: it leaves the watch alone as it leaves the spectrum history and the
+ *    tracked state alone.  The watch moves nothing else: readings, peaks, histograms and spectra are byte for byte what they are
+ *    without it, and a bank that never enables it allocates and launches exactly what it did before.
+ *  - Cost: one launch per add call (one workgroup per stream walks the stream's frames of that call tile by tile: a long call is
+ *    walked serially), none for a read.  Device memory: 112 bytes of state per (stream, channels + 1), and the records.
+ *  Configuration is ss_signal_scan_config with ss_batch_signal_scan's refusals; max_events must be 0 — there is no event list yet,
+ *  a polling host reads trailing_*, last_clip_frame and the counters — a non-zero max_events is SS_ERR_INVALID_ARG.
+ *  Status codes: _plan, _reset or the read before _enable SS_ERR_INVALID_MODE; a bad stream index SS_ERR_INVALID_ARG with nothing
+ *  reset; a `cap` too small SS_ERR_CAPACITY with nothing written. */
+typedef struct ss_stream_watch {
+    uint64_t silent_frames;       /* the seven fields of ss_stream_scan, over the frames watched */
+    uint64_t leading_silence;
+    uint64_t trailing_silence;    /* frames of the silence run that holds the newest frame, else 0: dead air since then */
+    uint64_t longest_silence;
+    uint64_t longest_silence_at;
+    uint64_t silence_runs;
+    uint64_t clip_runs;
+    uint64_t frames;              /* frames watched since this stream's watch reset */
+} ss_stream_watch;                /* 64 bytes */
+typedef struct ss_channel_watch {
+    double   sum, sum_sq;         /* the eight fields of ss_channel_scan, over the frames watched */
+    uint64_t nonfinite;
+    uint64_t first_nonfinite;
+    uint64_t clipped_samples;
+    uint64_t longest_clip;
+    uint64_t longest_clip_at;
+    uint64_t clip_runs;
+    uint64_t trailing_clip;       /* frames of the clip run that holds the newest frame, else 0 */
+    uint64_t last_clip_frame;     /* frame of the newest clipped sample; UINT64_MAX if none */
+} ss_channel_watch;               /* 80 bytes */
+/* cfg != NULL: empty state for every stream (enabling again, with the same or new parameters, starts empty); cfg == NULL: the watch
+ * off, its state freed.  Refusals before anything is allocated or changed, so a refused call leaves the previous watch as it was.
+ * With frames == 0 every field of a record is zero or "none". */
+int ss_meter_bank_signal_watch_enable(ss_meter_bank *m, const ss_signal_scan_config *cfg);
+/* frames one tile of the kernel holds (ss_batch_signal_scan_plan's rule for the bank's channel count) */
+int ss_meter_bank_signal_watch_plan(const ss_meter_bank *m, uint32_t *tile_frames);
+/* empties the listed streams' watch (streams == NULL: all); the others are untouched */
+int ss_meter_bank_signal_watch_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count);
+/* the records for the state after the last add; either array may be NULL; channel records are [stream][channel].  Waits; no
+ * launch (the adds leave the records behind) and one copy. */
+int ss_meter_bank_signal_watch(ss_meter_bank *m, ss_stream_watch *streams_out, uint32_t cap_streams,
+                               ss_channel_watch *channels_out, size_t cap_records);
+
 /* ------------------------------------------------------------------------- *
  *  Multi-GPU: one process per GPU, streams sharded over the ranks, and exactly ONE exchange —
  *  the SUM all-reduce of the two 1000-bin u64 histograms for the corpus-level integrated-LUFS gate

@@ -50,6 +50,8 @@ SYMBOLS = [
     "ss_meter_bank_spectrum_enable", "ss_meter_bank_spectrum_layout", "ss_meter_bank_spectrum", "ss_meter_bank_spectrum_columns",
     "ss_meter_bank_spectrum_track_enable", "ss_meter_bank_spectrum_track", "ss_meter_bank_spectrum_track_reset",
     "ss_meter_bank_spectrum_tracked", "ss_meter_bank_spectrum_tracked_columns",
+    "ss_meter_bank_signal_watch_enable", "ss_meter_bank_signal_watch_plan", "ss_meter_bank_signal_watch_reset",
+    "ss_meter_bank_signal_watch",
     "ss_batch_spectrum_stats", "ss_batch_download_spectrum_stats", "ss_batch_corpus_spectrum", "ss_batch_spectrum_stats_plan",
     "ss_batch_loudness_regions", "ss_batch_download_region_results", "ss_batch_download_group_results", "ss_batch_group_histograms",
     "ss_batch_peak_series", "ss_batch_peak_series_plan", "ss_batch_download_peak_series", "ss_batch_peak_regions",
@@ -168,6 +170,14 @@ class StreamScan(C.Structure):
 class ChannelScan(C.Structure):
     _fields_ = [("sum", C.c_double), ("sum_sq", C.c_double)] + [(n, C.c_uint64) for n in (
         "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs")]
+
+
+class StreamWatch(C.Structure):            # ss_stream_watch: the batch record, then the live field
+    _fields_ = StreamScan._fields_ + [("frames", C.c_uint64)]
+
+
+class ChannelWatch(C.Structure):           # ss_channel_watch
+    _fields_ = ChannelScan._fields_ + [("trailing_clip", C.c_uint64), ("last_clip_frame", C.c_uint64)]
 
 
 class SignalEvent(C.Structure):
@@ -360,6 +370,10 @@ def _bind(lib):
         "ss_batch_spectrogram_plan": (C.c_int, [vp, C.POINTER(SpectrogramView), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_batch_download_spectrogram": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, C.c_size_t]),
         "ss_spectrogram_column_windows": (None, [C.POINTER(SpectrogramView), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_meter_bank_signal_watch_enable": (C.c_int, [vp, C.POINTER(SignalScanConfig)]),
+        "ss_meter_bank_signal_watch_plan": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "ss_meter_bank_signal_watch_reset": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_uint32]),
+        "ss_meter_bank_signal_watch": (C.c_int, [vp, C.POINTER(StreamWatch), C.c_uint32, C.POINTER(ChannelWatch), C.c_size_t]),
         "ss_batch_signal_scan": (C.c_int, [vp, C.POINTER(SignalScanConfig)]),
         "ss_batch_signal_scan_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_batch_download_stream_scans": (C.c_int, [vp, C.POINTER(StreamScan), C.c_uint32]),

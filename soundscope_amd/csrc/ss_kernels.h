@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_bank_signal_watch.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -556,6 +556,43 @@ hipError_t launch_bank_spectrum_track_reset(BankTrackRow *meta, const uint32_t *
 // avg / hold: [row][n_bins] f32 dB (either nullable), updates [row] (nullable)
 hipError_t launch_bank_spectrum_tracked_rows(const BankTrackParams &p, float *avg, float *hold, uint32_t *updates, hipStream_t s);
 hipError_t launch_bank_spectrum_tracked_columns(const BankTrackParams &p, const BankTrackColumns &c, hipStream_t s);
+
+// signal watch of a bank (ss_meter_bank_signal_watch*; ss_bank_signal_watch.hip): the batch signal scan's records of everything a
+// stream was given since its watch reset, advanced by one launch per add call.  What sequence q of a stream (0: the frame is
+// silent, 1 + c: channel c is clipped) carries from call to call:
+struct alignas(16) BankWatchSeq {
+    unsigned long long frames;       // frames watched so far (every sequence keeps its own copy: its owning lane reads no other's)
+    unsigned long long open;         // frames of the run that holds the newest frame; 0: none
+    unsigned long long runs;         // closed runs of at least the minimum
+    unsigned long long best, best_at;// the longest closed run and its first frame (the lowest of equals; ~0: none)
+    unsigned long long total;        // frames on which the predicate held
+    unsigned long long lead;         // the run that held frame 0, once it has closed
+    unsigned long long lead_set;     // 0: the predicate has held on every frame so far
+    double sum, sum_sq;              // channel q - 1 (sequence 0: unused): over its finite samples, tile by tile behind the state
+    unsigned long long clipped, nonfinite, first_nonfinite, last_clip;   // (~0: none)
+};                                   // 112 bytes
+// the records, laid out as ss_stream_watch / ss_channel_watch (include/soundscope_hip.h): the batch records, then the live fields
+struct StreamWatch { unsigned long long silent_frames, leading_silence, trailing_silence, longest_silence, longest_silence_at, silence_runs, clip_runs, frames; };
+struct ChannelWatch { double sum, sum_sq; unsigned long long nonfinite, first_nonfinite, clipped_samples, longest_clip, longest_clip_at, clip_runs, trailing_clip, last_clip_frame; };
+struct BankWatchParams {
+    const float *pcm;                // f32 input of this call, any 4-byte alignment: stream s at pcm + offset_of[s], or pcm + s * stride
+    uint64_t stride;                 // floats between streams (offset_of == nullptr)
+    const uint64_t *offset_of;       // [stream], nullable
+    const uint64_t *frames_of;       // [stream], nullable: every stream gets `frames`; a stream of 0 frames is not touched
+    uint64_t frames;
+    uint32_t n_streams, channels;
+    uint32_t tile_frames;            // plan_signal_scan's
+    float silence_threshold, clip_level;
+    uint32_t silence_min, clip_min;
+    BankWatchSeq *state;             // [stream][channels + 1]
+    StreamWatch *streams;            // [stream]
+    ChannelWatch *channel_watches;   // [stream][channels]
+};
+// one workgroup per stream walks its frames of this call in tiles and leaves the state and both records behind
+hipError_t launch_bank_signal_watch(const BankWatchParams &p, hipStream_t s);
+// the listed streams' state and records are empty (streams == nullptr: streams 0 .. count - 1)
+hipError_t launch_bank_signal_watch_reset(BankWatchSeq *state, StreamWatch *stream_watches, ChannelWatch *channel_watches,
+                                          const uint32_t *streams, uint32_t count, uint32_t channels, hipStream_t s);
 
 // ---- waveform ---------------------------------------------------------------
 struct WaveParams {

@@ -46,6 +46,13 @@ struct ss_meter_bank {
     ssh::DevBuf<float> trk_rows;           // [n][rows][n_bins]: the row launch of an update
     ssh::DevBuf<int32_t> trk_status;       // [n][rows]
     ssh::DevBuf<unsigned char> trk_out;    // a read-out: the curves asked for, then the update counts
+    // signal watch (ss_meter_bank_signal_watch_enable): the batch signal scan's records of what every stream was given, advanced by
+    // one launch per add (ssk::BankWatchParams).  The records stand behind each other so that a read is one copy
+    bool watch_on = false;
+    ss_signal_scan_config watch_cfg{};
+    ssh::DevBuf<ssk::BankWatchSeq> watch_state;    // [n][channels + 1]
+    ssh::DevBuf<unsigned char> watch_rec;  // [n] ssk::StreamWatch, then [n][channels] ssk::ChannelWatch
+    ssh::PinBuf<unsigned char> watch_pin;
 };
 
 static_assert(sizeof(ss_meter_reading) == 72 && sizeof(ssk::MeterReading) == sizeof(ss_meter_reading), "ss_meter_reading layout");
@@ -146,6 +153,41 @@ int bank_plan(const ss_meter_bank *m, const uint64_t *frames, uint64_t each, boo
     return SS_OK;
 }
 
+// ---- signal watch ------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(ss_stream_watch) == 64 && sizeof(ssk::StreamWatch) == 64 && sizeof(ss_channel_watch) == 80 && sizeof(ssk::ChannelWatch) == 80,
+              "watch record layout");
+// both records begin with the batch scan's
+static_assert(offsetof(ss_stream_watch, silent_frames) == offsetof(ss_stream_scan, silent_frames) &&
+              offsetof(ss_stream_watch, longest_silence_at) == offsetof(ss_stream_scan, longest_silence_at) &&
+              offsetof(ss_stream_watch, clip_runs) == offsetof(ss_stream_scan, clip_runs) && offsetof(ss_stream_watch, frames) == sizeof(ss_stream_scan) &&
+              offsetof(ssk::StreamWatch, frames) == offsetof(ss_stream_watch, frames), "ss_stream_watch begins with ss_stream_scan");
+static_assert(offsetof(ss_channel_watch, sum) == offsetof(ss_channel_scan, sum) && offsetof(ss_channel_watch, first_nonfinite) == offsetof(ss_channel_scan, first_nonfinite) &&
+              offsetof(ss_channel_watch, longest_clip_at) == offsetof(ss_channel_scan, longest_clip_at) &&
+              offsetof(ss_channel_watch, clip_runs) == offsetof(ss_channel_scan, clip_runs) && offsetof(ss_channel_watch, trailing_clip) == sizeof(ss_channel_scan) &&
+              offsetof(ssk::ChannelWatch, trailing_clip) == offsetof(ss_channel_watch, trailing_clip) &&
+              offsetof(ssk::ChannelWatch, last_clip_frame) == offsetof(ss_channel_watch, last_clip_frame), "ss_channel_watch begins with ss_channel_scan");
+
+ssk::StreamWatch *watch_streams(const ss_meter_bank *m) { return reinterpret_cast<ssk::StreamWatch *>(m->watch_rec.p); }
+ssk::ChannelWatch *watch_channels(const ss_meter_bank *m) { return reinterpret_cast<ssk::ChannelWatch *>(watch_streams(m) + m->meter.n); }
+size_t watch_rec_bytes(const ss_meter_bank *m)
+{
+    return (size_t)m->meter.n * (sizeof(ssk::StreamWatch) + (size_t)m->meter.channels * sizeof(ssk::ChannelWatch));
+}
+
+// the watch's launch behind the staging of an add: every stream by its own frames of the WHOLE call (frames_of null: `frames` each)
+int watch_advance(ss_meter_bank *m, const float *pcm, const uint64_t *offset_of, uint64_t stride, const uint64_t *frames_of, uint64_t frames)
+{
+    ssk::BankWatchParams p{};
+    p.pcm = pcm; p.stride = stride; p.offset_of = offset_of; p.frames_of = frames_of; p.frames = frames;
+    p.n_streams = m->meter.n; p.channels = m->meter.channels;
+    p.tile_frames = ssk::plan_signal_scan(m->meter.channels, 0).tile_frames;
+    p.silence_threshold = m->watch_cfg.silence_threshold; p.clip_level = m->watch_cfg.clip_level;
+    p.silence_min = m->watch_cfg.silence_min_frames; p.clip_min = m->watch_cfg.clip_min_samples;
+    p.state = m->watch_state.p; p.streams = watch_streams(m); p.channel_watches = watch_channels(m);
+    HIPCHK(ssk::launch_bank_signal_watch(p, m->stream));
+    return SS_OK;
+}
+
 // the launches of an add behind its staging.  Stream s's input stands at pcm + offset_of[s] (offset_of null: pcm + s * stride); `arr`:
 // a ragged plan's arrays on the device (null: a uniform call)
 int advance(ss_meter_bank *m, const BankPlan &pl, const uint64_t *arr, const float *pcm, const uint64_t *offset_of, uint64_t stride)
@@ -161,6 +203,10 @@ int advance(ss_meter_bank *m, const BankPlan &pl, const uint64_t *arr, const flo
             HIPCHK(hipMemsetAsync(m->spec_ahead.p, 0, n * sizeof(uint64_t), m->stream));
         }
         HIPCHK(ssk::launch_bank_history_append_ragged(m->spec_hist.p, pcm, stride, offset_of, arr, m->spec_fed, m->spec_ahead.p, n, C, m->stream));
+    }
+    if (m->watch_on) {                                                   // one launch for the whole call, not one per piece
+        int rc = watch_advance(m, pcm, offset_of, stride, arr, pl.longest);
+        if (rc) return rc;
     }
     const uint64_t piece_frames = 32 * ms.s100;
     const ssk::MeterBankParams q = ms.bank_params();
@@ -684,6 +730,71 @@ int ss_meter_bank_spectrum_tracked_columns(ss_meter_bank *m, uint32_t cols, int 
     c.avg = base; c.hold = base + o.hold_at; c.updates = reinterpret_cast<uint32_t *>(base + o.counts_at);
     HIPCHK(ssk::launch_bank_spectrum_tracked_columns(track_params(m), c, m->stream));
     return track_fetch(m, o, avg_cols, hold_cols, updates);
+}
+
+int ss_meter_bank_signal_watch_enable(ss_meter_bank *m, const ss_signal_scan_config *cfg)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!cfg) {
+        if (!m->watch_on) return SS_OK;
+        HIPCHK(bank_sync(m));                                                       // nothing on the stream still uses the state
+        m->watch_on = false;
+        m->watch_state.release(); m->watch_rec.release(); m->watch_pin.release();
+        return SS_OK;
+    }
+    // ss_batch_signal_scan's refusals, and no event list yet
+    if (!(cfg->silence_threshold >= 0.f) || !(cfg->clip_level > 0.f)) return SS_ERR_INVALID_ARG;        // (NaN fails the comparison)
+    if (!cfg->silence_min_frames || !cfg->clip_min_samples || cfg->max_events || cfg->reserved) return SS_ERR_INVALID_ARG;
+    const size_t n = m->meter.n, Q = (size_t)m->meter.channels + 1;
+    HIPCHK(m->watch_state.ensure(n * Q));                                           // (enabling again keeps the allocations)
+    HIPCHK(m->watch_rec.ensure(watch_rec_bytes(m)));
+    HIPCHK(m->watch_pin.ensure(watch_rec_bytes(m)));
+    HIPCHK(ssk::launch_bank_signal_watch_reset(m->watch_state.p, watch_streams(m), watch_channels(m), nullptr, m->meter.n, m->meter.channels,
+                                               m->stream));
+    m->watch_cfg = *cfg;
+    m->watch_on = true;
+    return SS_OK;
+}
+
+int ss_meter_bank_signal_watch_plan(const ss_meter_bank *m, uint32_t *tile_frames)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->watch_on) return SS_ERR_INVALID_MODE;
+    if (tile_frames) *tile_frames = ssk::plan_signal_scan(m->meter.channels, 0).tile_frames;
+    return SS_OK;
+}
+
+int ss_meter_bank_signal_watch_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->watch_on) return SS_ERR_INVALID_MODE;
+    if (streams && !count) return SS_OK;                                           // (an empty list: nothing is staged)
+    const uint32_t *dev;
+    int rc = stream_list(m, streams, count, &dev);
+    if (rc) return rc;
+    HIPCHK(ssk::launch_bank_signal_watch_reset(m->watch_state.p, watch_streams(m), watch_channels(m), dev, streams ? count : m->meter.n,
+                                               m->meter.channels, m->stream));
+    return SS_OK;
+}
+
+int ss_meter_bank_signal_watch(ss_meter_bank *m, ss_stream_watch *streams_out, uint32_t cap_streams, ss_channel_watch *channels_out,
+                               size_t cap_records)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->watch_on) return SS_ERR_INVALID_MODE;
+    const size_t n = m->meter.n, sbytes = n * sizeof(ssk::StreamWatch), cbytes = n * m->meter.channels * sizeof(ssk::ChannelWatch);
+    if ((streams_out && cap_streams < n) || (channels_out && cap_records < n * m->meter.channels)) return SS_ERR_CAPACITY;
+    // the add calls left the records as they stand: no launch, one copy of what was asked for
+    const size_t from = streams_out ? 0 : sbytes, to = channels_out ? sbytes + cbytes : sbytes;
+    if (to > from) HIPCHK(hipMemcpyAsync(m->watch_pin.p + from, m->watch_rec.p + from, to - from, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(bank_sync(m));
+    if (streams_out) std::memcpy(streams_out, m->watch_pin.p, sbytes);
+    if (channels_out) std::memcpy(channels_out, m->watch_pin.p + sbytes, cbytes);
+    return SS_OK;
 }
 
 }  // extern "C"

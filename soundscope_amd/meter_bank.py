@@ -7,6 +7,8 @@ With `enable_spectrum()` the bank also keeps every stream's newest 16384 input f
 `spectrum_columns()` transform all of them (mid and side for stereo banks) in one launch.
 With `enable_spectrum_tracking()` it keeps, per row, an exponentially averaged and a peak-hold curve on the device;
 `track_spectrum()` advances them on each stream's own clock, `tracked_spectrum()` / `tracked_spectrum_columns()` read them.
+With `enable_signal_watch()` every add also advances, per stream, the records `Batch.signal_scan` defines for everything the
+stream was given: silence and since when, clip runs, DC sums and non-finite samples; `signal_watch()` reads them.
 """
 import ctypes as C
 
@@ -18,6 +20,13 @@ from .analyzer import _check
 READING_DTYPE = np.dtype([("momentary", "<f8"), ("shortterm", "<f8"), ("integrated", "<f8"), ("loudness_range", "<f8"),
                           ("true_peak", "<f8", (2,)), ("sample_peak", "<f8", (2,)), ("frames", "<u8")])
 assert READING_DTYPE.itemsize == C.sizeof(L.MeterReading) == 72
+# ss_stream_watch / ss_channel_watch: the batch scan's records (batch.STREAM_SCAN_DTYPE / CHANNEL_SCAN_DTYPE), then the live fields
+STREAM_WATCH_DTYPE = np.dtype([(n, "<u8") for n in ("silent_frames", "leading_silence", "trailing_silence", "longest_silence",
+                                                    "longest_silence_at", "silence_runs", "clip_runs", "frames")])
+CHANNEL_WATCH_DTYPE = np.dtype([("sum", "<f8"), ("sum_sq", "<f8")] + [(n, "<u8") for n in (
+    "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs", "trailing_clip",
+    "last_clip_frame")])
+assert STREAM_WATCH_DTYPE.itemsize == C.sizeof(L.StreamWatch) == 64 and CHANNEL_WATCH_DTYPE.itemsize == C.sizeof(L.ChannelWatch) == 80
 
 
 class MeterBank:
@@ -222,3 +231,40 @@ class MeterBank:
                                                               hold.ctypes.data_as(fp), avg.size,
                                                               upd.ctypes.data_as(C.POINTER(C.c_uint32)), upd.size))
         return avg, hold, upd
+
+    # ---- signal watch (ss_meter_bank_signal_watch*) ----------------------------------------------------------------------------
+    def enable_signal_watch(self, silence_threshold=0.0, clip_level=1.0, silence_min_frames=None, clip_min_samples=3):
+        """Watch every stream's input from now on: silent frames (|x| <= silence_threshold on every channel) and clipped samples
+        (|x| >= clip_level), their runs of at least silence_min_frames (None: 100 ms, as Batch.signal_scan) / clip_min_samples, the
+        DC sums and the non-finite samples.  Enabling again starts empty."""
+        if silence_min_frames is None:
+            silence_min_frames = (self.rate + 5) // 10
+        cfg = L.SignalScanConfig(float(silence_threshold), float(clip_level), int(silence_min_frames), int(clip_min_samples), 0, 0)
+        _check(L.lib().ss_meter_bank_signal_watch_enable(self._h, C.byref(cfg)))
+
+    def disable_signal_watch(self):
+        """The watch off, its device memory freed."""
+        _check(L.lib().ss_meter_bank_signal_watch_enable(self._h, None))
+
+    def signal_watch_plan(self):
+        """Frames one tile of the watch kernel holds (a multiple of 64)."""
+        t = C.c_uint32()
+        _check(L.lib().ss_meter_bank_signal_watch_plan(self._h, C.byref(t)))
+        return t.value
+
+    def reset_signal_watch(self, streams=None):
+        """Empty the listed streams' watch (None: all); the others are untouched."""
+        if streams is None:
+            _check(L.lib().ss_meter_bank_signal_watch_reset(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+        _check(L.lib().ss_meter_bank_signal_watch_reset(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+
+    def signal_watch(self):
+        """(streams [n_streams] of STREAM_WATCH_DTYPE, channels [n_streams, channels] of CHANNEL_WATCH_DTYPE) for everything each
+        stream was given since its watch reset; frame numbers count from there."""
+        st = np.empty(self.n_streams, STREAM_WATCH_DTYPE)
+        ch = np.empty((self.n_streams, self.channels), CHANNEL_WATCH_DTYPE)
+        _check(L.lib().ss_meter_bank_signal_watch(self._h, st.ctypes.data_as(C.POINTER(L.StreamWatch)), st.size,
+                                                  ch.ctypes.data_as(C.POINTER(L.ChannelWatch)), ch.size))
+        return st, ch
