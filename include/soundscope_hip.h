@@ -608,6 +608,82 @@ int ss_batch_download_stream_scans(ss_batch *b, ss_stream_scan *out, uint32_t ca
 int ss_batch_download_channel_scans(ss_batch *b, ss_channel_scan *out, size_t cap_records);
 /* one list of one stream; *n_events (optional) = min(count, max_events) */
 int ss_batch_download_signal_events(ss_batch *b, uint32_t stream, int kind, ss_signal_event *out, size_t cap_events, uint32_t *n_events);
+/* Pair series and pair regions: how two channels of a stream relate in the time domain, per 100 ms and per time range — the
+ * correlation (phase) meter, the channel balance and the level a mono fold-down loses.  A stereo item whose channels are out of
+ * phase disappears in a mono fold-down; delivery specifications reject it.  Not in the reference.
+ * ss_batch_pair_series reads the resident f32 corpus alone, like ss_batch_peak_series: it needs no ss_batch_run and no particular
+ * flag, nothing inside a pass changes, and the corpus is only read.  The grid is the peak series': with S = s100 = (sample_rate +
+ * 5) / 10 and F_s stream s's own frame count (ss_batch_set_lengths; frames behind it, and the neighbouring slots, are never read),
+ * stream s has E_s = ceil(F_s / S) entries; entry j covers frames [j S, min((j + 1) S, F_s)), a last partial entry covers the tail.
+ * Per (stream, entry, pair (a, b)) one ss_pair_entry: a frame in which x_a or x_b is NaN or infinite is SKIPPED and adds to no sum;
+ * every other frame is counted, its two samples widened to f64, and x_a^2, x_b^2 and x_a x_b (exact in f64: 24 x 24 bits) added to
+ * s_aa, s_bb and s_ab.  The additions follow an order fixed by the kernel plan, not by timing: a lane adds its own frames in
+ * ascending order, the 64 lanes of a wave meet in a fixed tree, the four waves are added in wave order; there are no floating-point
+ * atomics, so two calls agree byte for byte.  The caller forms, per entry or region,
+ *   correlation  = s_ab / sqrt(s_aa s_bb)                              (NaN where a power is 0)
+ *   balance (dB) = 10 log10(s_bb / s_aa)
+ *   mono loss (dB) = 10 log10((s_aa + 2 s_ab + s_bb) / (2 (s_aa + s_bb)))   ((a + b) / 2 against the mean channel power: 0 for b = a)
+ * pairs == NULL with n_pairs == 0 is the one pair (0, 1); a == b is allowed (s_ab == s_aa == s_bb).  The call copies `pairs`, queues
+ * its work on the batch's stream and waits for nothing; a later call replaces every result (the pair list included); the downloads
+ * wait for the stream.  Call it again after new input or new lengths.  Device memory, 32 * entries_cap * n_pairs * n_streams bytes
+ * (entries_cap = ceil(frames_per_stream / S)), is allocated at the first call and grows with a longer pair list.
+ * ss_batch_pair_series_plan reports tile_frames (the frames a workgroup has in flight at a time: it fixes which lane adds which
+ * frame), entries_cap and the pairs of the last call that was queued (before the first: those of the default list, 1).
+ * ss_batch_pair_regions takes the loudness regions' records under ss_batch_peak_regions' rules (the bound is the stream's E_s, so a
+ * region may hold the tail entry; regions may overlap, repeat and come from any stream), copies them before it returns, and
+ * reduces the series as it is when the call runs, per (region, pair):
+ *   - the sums, frames and skipped of the region's entries, added in ascending entry order from 0;
+ *   - an entry is ACTIVE iff s_aa + s_bb > power_floor * frames (one f64 addition, one f64 multiplication by the frames counted);
+ *   - an entry is BELOW iff its correlation is under `threshold`, decided without a square root or a division: with p = s_aa * s_bb,
+ *     q = s_ab, t = threshold, every product one rounded f64 multiplication (none contracted into a fused multiply-add),
+ *         t >= 0:  BELOW iff q < 0 || q * q < (t * t) * p
+ *         t <  0:  BELOW iff q < 0 && q * q > (t * t) * p
+ *     so an entry with p == 0 is never BELOW when t <= 0, and when t > 0 only if q < 0 || q * q < 0 holds (it does not for a finite
+ *     q >= 0; a silent entry is inactive anyway);
+ *   - n_below, first_below and the runs take ACTIVE BELOW entries only: a run is a maximal sequence of consecutive entries of the
+ *     region that are both, so an inactive entry ends a run as an entry that is not below does.
+ * A group's record adds the records of the regions that name it in ascending region index order from 0 (ss_batch_spectrum_regions'
+ * rule); its counts are integer sums.  Two calls agree byte for byte.  A batch that never calls any of this allocates and launches
+ * exactly what it did before.
+ * Status codes, all checked before anything is queued, so a refused call leaves the previous results as they were: a or b >=
+ * channels, n_pairs > 16, pairs == NULL with n_pairs > 0, the default pair on a mono batch, stream >= n_streams, cfg == NULL, a NaN
+ * threshold or |threshold| >= 1, a NaN or negative power_floor, min_run == 0, reserved != 0, and the list errors of
+ * ss_batch_peak_regions: SS_ERR_INVALID_ARG; a download before the first computation of its kind, and ss_batch_pair_regions before
+ * ss_batch_pair_series: SS_ERR_INVALID_MODE; a `cap` too small: SS_ERR_CAPACITY, with nothing written.  F_s == 0 (no entries),
+ * n_regions == 0 and n_subblocks == 0 are valid. */
+typedef struct ss_channel_pair { uint32_t a, b; } ss_channel_pair;      /* 8 bytes; a, b < channels */
+typedef struct ss_pair_entry {
+    double   s_aa, s_bb, s_ab;    /* sums of x_a^2, x_b^2, x_a x_b over the counted frames of the entry */
+    uint32_t frames;              /* frames counted */
+    uint32_t skipped;             /* frames of the entry in which x_a or x_b is NaN or infinite: they add to no sum */
+} ss_pair_entry;                  /* 32 bytes */
+typedef struct ss_pair_region_config {
+    double   threshold;           /* an entry is BELOW iff its correlation < threshold; -1 < threshold < 1 */
+    double   power_floor;         /* an entry is ACTIVE iff s_aa + s_bb > power_floor * frames (linear power per frame, >= 0) */
+    uint32_t min_run;             /* >= 1: runs of consecutive active BELOW entries at least this long are counted */
+    uint32_t reserved;            /* 0 */
+} ss_pair_region_config;          /* 24 bytes */
+typedef struct ss_region_pair {
+    double   s_aa, s_bb, s_ab;    /* the entries' sums added in entry order */
+    uint64_t frames, skipped;
+    uint32_t n_active, n_below;   /* n_below counts active entries only */
+    uint32_t first_below;         /* ABSOLUTE entry index of the first active BELOW entry; 0xFFFFFFFF if none */
+    uint32_t longest_below;       /* entries of the longest run, of any length; ties go to the lowest entry; 0 if none */
+    uint32_t longest_below_at;    /* ABSOLUTE entry index of its first entry; 0xFFFFFFFF if none */
+    uint32_t below_runs;          /* runs of at least min_run */
+} ss_region_pair;                 /* 64 bytes */
+typedef struct ss_group_pair {
+    double   s_aa, s_bb, s_ab;    /* the regions' sums added in region index order */
+    uint64_t frames, skipped, n_active, n_below, below_runs;      /* overlaps and repeats each count */
+} ss_group_pair;                  /* 64 bytes */
+int ss_batch_pair_series(ss_batch *b, const ss_channel_pair *pairs, uint32_t n_pairs);
+int ss_batch_pair_series_plan(const ss_batch *b, uint32_t *tile_frames, uint32_t *entries_cap, uint32_t *n_pairs);
+/* stream's entries, [entry][pair]; *n_entries (optional) = E_s; cap_entries counts entries (records / n_pairs) */
+int ss_batch_download_pair_series(ss_batch *b, uint32_t stream, ss_pair_entry *out, size_t cap_entries, uint32_t *n_entries);
+int ss_batch_pair_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups, const ss_pair_region_config *cfg);
+/* [region][pair] and [group][pair] of the last list, the pairs those of the series it read; cap_records counts records */
+int ss_batch_download_region_pairs(ss_batch *b, ss_region_pair *out, size_t cap_records);
+int ss_batch_download_group_pairs(ss_batch *b, ss_group_pair *out, size_t cap_records);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

@@ -61,6 +61,8 @@ SYMBOLS = [
     "ss_batch_download_signal_events",
     "ss_batch_spectrum_regions", "ss_batch_download_region_spectra", "ss_batch_download_group_spectra",
     "ss_batch_spectrum_regions_plan", "ss_region_windows",
+    "ss_batch_pair_series", "ss_batch_pair_series_plan", "ss_batch_download_pair_series", "ss_batch_pair_regions",
+    "ss_batch_download_region_pairs", "ss_batch_download_group_pairs",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -182,6 +184,28 @@ class ChannelWatch(C.Structure):           # ss_channel_watch
 
 class SignalEvent(C.Structure):
     _fields_ = [("first_frame", C.c_uint64), ("frames", C.c_uint64), ("channel", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ChannelPair(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
+
+
+class PairEntry(C.Structure):
+    _fields_ = [("s_aa", C.c_double), ("s_bb", C.c_double), ("s_ab", C.c_double), ("frames", C.c_uint32), ("skipped", C.c_uint32)]
+
+
+class PairRegionConfig(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("power_floor", C.c_double), ("min_run", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RegionPair(C.Structure):
+    _fields_ = [("s_aa", C.c_double), ("s_bb", C.c_double), ("s_ab", C.c_double), ("frames", C.c_uint64), ("skipped", C.c_uint64)] + [
+        (n, C.c_uint32) for n in ("n_active", "n_below", "first_below", "longest_below", "longest_below_at", "below_runs")]
+
+
+class GroupPair(C.Structure):
+    _fields_ = [("s_aa", C.c_double), ("s_bb", C.c_double), ("s_ab", C.c_double)] + [
+        (n, C.c_uint64) for n in ("frames", "skipped", "n_active", "n_below", "below_runs")]
 
 
 class SpectrogramView(C.Structure):
@@ -384,6 +408,12 @@ def _bind(lib):
         "ss_batch_download_group_spectra": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p, f32p, C.c_size_t, u64p, C.c_size_t]),
         "ss_batch_spectrum_regions_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_region_windows": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_batch_pair_series": (C.c_int, [vp, C.POINTER(ChannelPair), C.c_uint32]),
+        "ss_batch_pair_series_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_batch_download_pair_series": (C.c_int, [vp, C.c_uint32, C.POINTER(PairEntry), C.c_size_t, C.POINTER(C.c_uint32)]),
+        "ss_batch_pair_regions": (C.c_int, [vp, C.POINTER(LoudnessRegion), C.c_uint32, C.c_uint32, C.POINTER(PairRegionConfig)]),
+        "ss_batch_download_region_pairs": (C.c_int, [vp, C.POINTER(RegionPair), C.c_size_t]),
+        "ss_batch_download_group_pairs": (C.c_int, [vp, C.POINTER(GroupPair), C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -34,6 +34,35 @@ CHANNEL_SCAN_DTYPE = np.dtype([("sum", np.float64), ("sum_sq", np.float64)] + [(
     "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs")])
 SIGNAL_EVENT_DTYPE = np.dtype([("first_frame", np.uint64), ("frames", np.uint64), ("channel", np.uint32), ("reserved", np.uint32)])
 SIGNAL_SILENCE, SIGNAL_CLIP = L.SS_SIGNAL_SILENCE, L.SS_SIGNAL_CLIP
+# the pair series' records (ss_pair_entry, ss_region_pair, ss_group_pair)
+_PAIR_SUMS = [("s_aa", np.float64), ("s_bb", np.float64), ("s_ab", np.float64)]
+PAIR_ENTRY_DTYPE = np.dtype(_PAIR_SUMS + [("frames", np.uint32), ("skipped", np.uint32)])
+REGION_PAIR_DTYPE = np.dtype(_PAIR_SUMS + [("frames", np.uint64), ("skipped", np.uint64)] + [(n, np.uint32) for n in (
+    "n_active", "n_below", "first_below", "longest_below", "longest_below_at", "below_runs")])
+GROUP_PAIR_DTYPE = np.dtype(_PAIR_SUMS + [(n, np.uint64) for n in ("frames", "skipped", "n_active", "n_below", "below_runs")])
+
+
+# what a caller reads off pair records (entries, regions or groups: anything with s_aa, s_bb, s_ab), as plain numpy
+def pair_correlation(rec):
+    """s_ab / sqrt(s_aa s_bb): +1 in phase, -1 out of phase; NaN where a power is 0."""
+    aa, bb, ab = (np.asarray(rec[n], np.float64) for n in ("s_aa", "s_bb", "s_ab"))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where((aa > 0) & (bb > 0), ab / np.sqrt(aa * bb), np.nan)
+
+
+def pair_balance_db(rec):
+    """10 log10(s_bb / s_aa): positive where channel b is the louder."""
+    aa, bb = np.asarray(rec["s_aa"], np.float64), np.asarray(rec["s_bb"], np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 10.0 * np.log10(bb / aa)
+
+
+def pair_mono_loss_db(rec):
+    """10 log10((s_aa + 2 s_ab + s_bb) / (2 (s_aa + s_bb))): the power of the fold-down (a + b) / 2 against the mean channel power —
+    0 for b = a, -inf for b = -a, about -3 for unrelated channels."""
+    aa, bb, ab = (np.asarray(rec[n], np.float64) for n in ("s_aa", "s_bb", "s_ab"))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 10.0 * np.log10((aa + 2.0 * ab + bb) / (2.0 * (aa + bb)))
 
 
 class Batch:
@@ -43,7 +72,7 @@ class Batch:
         """spectrum_columns > 0 (with L.SS_BATCH_FFT_COLUMNS in flags, added here if missing): columns-only spectrum — the
         render-side reduction runs inside the spectrum kernel and only that many chart columns per row are kept."""
         self._ragged = False                # set_lengths() has been called
-        self._listed = {"loudness": (0, 0), "peak": (0, 0), "spectrum": (0, 0)}   # (regions, groups) of the last accepted list of each kind
+        self._listed = {"loudness": (0, 0), "peak": (0, 0), "spectrum": (0, 0), "pair": (0, 0)}   # (regions, groups) of the last accepted list of each kind
         if spectrum_columns:
             flags |= L.SS_BATCH_FFT_COLUMNS
             self._render_cols = int(spectrum_columns)
@@ -497,6 +526,55 @@ class Batch:
         _check(L.lib().ss_batch_download_signal_events(self._h, int(stream), int(kind), out.ctypes.data_as(C.POINTER(L.SignalEvent)),
                                                        cap, C.byref(n)))
         return out[:n.value].copy()
+
+    # -- pair series and pair regions: sums of x_a^2, x_b^2, x_a x_b per 100 ms entry, and over ranges and groups
+    def pair_series(self, pairs=None):
+        """Queue the pair series of whatever is resident (no run(), no particular flag): per (stream, 100 ms entry, pair) the f64
+        sums over the frames in which both samples are finite.  `pairs`: up to 16 (a, b) channel pairs, None: the one pair (0, 1).
+        Replaces the previous series, pair list included."""
+        if pairs is None:
+            _check(L.lib().ss_batch_pair_series(self._h, None, 0))
+        else:
+            a = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+            _check(L.lib().ss_batch_pair_series(self._h, a.ctypes.data_as(C.POINTER(L.ChannelPair)), a.shape[0]))
+
+    def pair_series_plan(self):
+        """(tile_frames, entries_cap, n_pairs): the frames a workgroup has in flight at a time, the entry slots per stream, the
+        pairs of the last series."""
+        t, e, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_batch_pair_series_plan(self._h, C.byref(t), C.byref(e), C.byref(n)))
+        return t.value, e.value, n.value
+
+    def pair_entries(self, stream):
+        """Stream's entries: a structured array [entries][pairs] of PAIR_ENTRY_DTYPE (pair_correlation and its neighbours read it)."""
+        _, cap, pairs = self.pair_series_plan()
+        out = np.zeros((cap, pairs), PAIR_ENTRY_DTYPE)
+        n = C.c_uint32()
+        _check(L.lib().ss_batch_download_pair_series(self._h, int(stream), out.ctypes.data_as(C.POINTER(L.PairEntry)), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def pair_regions(self, regions, n_groups=0, threshold=0.0, power_floor=0.0, min_run=1):
+        """Queue the reduction of the pair series over `regions` (rows as loudness_regions takes them, on the peak series' grid: a
+        region may reach the stream's tail entry) behind pair_series().  An entry is active iff s_aa + s_bb > power_floor * frames
+        and below iff its correlation < threshold; runs of at least min_run active below entries are counted.  Replaces the
+        previous list."""
+        cfg = L.PairRegionConfig(float(threshold), float(power_floor), int(min_run), 0)
+        self._set_list("pair", L.lib().ss_batch_pair_regions, regions, n_groups, C.byref(cfg))
+        self._listed_pairs = self.pair_series_plan()[2]
+
+    def _pair_records(self, per_group, dtype, record, call):
+        pairs = getattr(self, "_listed_pairs", 0)
+        out = np.zeros((self._listed["pair"][per_group], pairs), dtype)
+        _check(call(self._h, out.ctypes.data_as(C.POINTER(record)), out.size))
+        return out
+
+    def region_pairs(self):
+        """Per region of the last pair list: a structured array [regions][pairs] of REGION_PAIR_DTYPE."""
+        return self._pair_records(0, REGION_PAIR_DTYPE, L.RegionPair, L.lib().ss_batch_download_region_pairs)
+
+    def group_pairs(self):
+        """Per group of the last pair list: a structured array [groups][pairs] of GROUP_PAIR_DTYPE."""
+        return self._pair_records(1, GROUP_PAIR_DTYPE, L.GroupPair, L.lib().ss_batch_download_group_pairs)
 
     def histograms(self):
         out = np.empty(2000, np.uint64)

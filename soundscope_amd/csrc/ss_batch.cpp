@@ -98,8 +98,9 @@ struct SpecStats {
     DevBuf<unsigned long long> corpus_counts;   // [fft_channels]
 };
 
-// The region list of a follow-up call (ss_batch_loudness_regions, ss_batch_peak_regions, ss_batch_spectrum_regions).  Each of the
-// three holds its own, stage included: a loudness list, a peak list and a spectrum list live side by side.
+// The region list of a follow-up call (ss_batch_loudness_regions, ss_batch_peak_regions, ss_batch_spectrum_regions,
+// ss_batch_pair_regions).  Each of the
+// four holds its own, stage included: a loudness list, a peak list, a spectrum list and a pair list live side by side.
 struct RegionList {
     bool done = false;                          // a list has been queued: there is something to download
     uint32_t n_regions = 0, n_groups = 0;       // of the last call that was queued
@@ -164,6 +165,19 @@ struct SignalScan {
     DevBuf<ssk::SignalEvent> events;                    // [stream][2][max_events] records (ss_signal_event)
 };
 
+// pair series and pair regions (ss_batch_pair_series, ss_batch_pair_regions): all of it allocated at the batch's first call (the
+// series grown by a longer pair list, the regions' part by a longer region list), so a batch that never asks holds none of it
+struct Pairs {
+    bool series_done = false;                           // queued at least once: there is something to download
+    uint32_t n_pairs = 0;                               // of the last series that was queued
+    ssk::ChannelPair pairs[ssk::kMaxPairs] = {};
+    DevBuf<ssk::PairEntry> series;                      // [stream][entries_cap][n_pairs] records (ss_pair_entry)
+    RegionList list;                                    // of the last ss_batch_pair_regions
+    uint32_t list_pairs = 0;                            // pairs of the series that list was reduced from
+    DevBuf<ssk::RegionPair> results;                    // [region][list_pairs] records (ss_region_pair)
+    DevBuf<ssk::GroupPair> group_results;               // [group][list_pairs] records (ss_group_pair)
+};
+
 // spectrogram (ss_batch_spectrogram): all of it allocated at the batch's first call and grown by a larger view, so a batch that
 // never asks holds none of it
 struct Spectrogram {
@@ -221,6 +235,7 @@ struct ss_batch {
     Peaks peaks;
     SpectrumRegions spec_regions;
     SignalScan scan;
+    Pairs pair;
     Spectrogram spectrogram;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
@@ -1828,6 +1843,131 @@ int ss_batch_download_signal_events(ss_batch *b, uint32_t stream, int kind, ss_s
     if (!n) return SS_OK;
     const ssk::SignalEvent *src = sc.events.p + ((size_t)stream * 2 + (kind == SS_SIGNAL_CLIP ? 1 : 0)) * sc.cfg.max_events;
     return fetch(b, out, reinterpret_cast<const ss_signal_event *>(src), n);
+}
+
+// ---- pair series and pair regions: sums of x_a^2, x_b^2 and x_a x_b per 100 ms entry, and over ranges and groups ------------------
+static_assert(sizeof(ss_channel_pair) == 8 && sizeof(ssk::ChannelPair) == 8 && offsetof(ss_channel_pair, b) == offsetof(ssk::ChannelPair, b), "channel pair layout");
+static_assert(sizeof(ss_pair_entry) == 32 && sizeof(ssk::PairEntry) == 32 && offsetof(ss_pair_entry, s_ab) == offsetof(ssk::PairEntry, s_ab) &&
+              offsetof(ss_pair_entry, frames) == offsetof(ssk::PairEntry, frames) && offsetof(ss_pair_entry, skipped) == offsetof(ssk::PairEntry, skipped), "pair entry layout");
+static_assert(sizeof(ss_pair_region_config) == 24, "pair region config layout");
+static_assert(sizeof(ss_region_pair) == 64 && sizeof(ssk::RegionPair) == 64 && offsetof(ss_region_pair, frames) == offsetof(ssk::RegionPair, frames) &&
+              offsetof(ss_region_pair, n_active) == offsetof(ssk::RegionPair, n_active) && offsetof(ss_region_pair, first_below) == offsetof(ssk::RegionPair, first_below) &&
+              offsetof(ss_region_pair, longest_below_at) == offsetof(ssk::RegionPair, longest_below_at) && offsetof(ss_region_pair, below_runs) == offsetof(ssk::RegionPair, below_runs),
+              "region pair layout");
+static_assert(sizeof(ss_group_pair) == 64 && sizeof(ssk::GroupPair) == 64 && offsetof(ss_group_pair, frames) == offsetof(ssk::GroupPair, frames) &&
+              offsetof(ss_group_pair, n_active) == offsetof(ssk::GroupPair, n_active) && offsetof(ss_group_pair, below_runs) == offsetof(ssk::GroupPair, below_runs), "group pair layout");
+
+// the pair list a call means: the caller's, or the one pair (0, 1); checked against the batch's channels
+static int pair_list_of(const ss_batch *b, const ss_channel_pair *pairs, uint32_t n_pairs, ssk::ChannelPair (&list)[ssk::kMaxPairs], uint32_t *n)
+{
+    const uint32_t C = b->cfg.channels;
+    if (n_pairs > ssk::kMaxPairs || (!pairs && n_pairs)) return SS_ERR_INVALID_ARG;
+    if (!pairs || !n_pairs) {                                   // the default pair needs two channels
+        if (C < 2u) return SS_ERR_INVALID_ARG;
+        list[0].a = 0u; list[0].b = 1u;
+        *n = 1u;
+        return SS_OK;
+    }
+    for (uint32_t k = 0; k < n_pairs; k++) {
+        if (pairs[k].a >= C || pairs[k].b >= C) return SS_ERR_INVALID_ARG;
+        list[k].a = pairs[k].a; list[k].b = pairs[k].b;
+    }
+    *n = n_pairs;
+    return SS_OK;
+}
+
+int ss_batch_pair_series_plan(const ss_batch *b, uint32_t *tile_frames, uint32_t *entries_cap, uint32_t *n_pairs)
+{
+    if (!b) return SS_ERR_INVALID_ARG;
+    const ssk::ChannelPair dflt = {0u, 1u};                      // before the first call: the default list's plan
+    const bool called = b->pair.series_done;
+    const ssk::PairSeriesPlan plan = ssk::plan_pair_series(b->cfg.channels, peak_s100(b), b->cfg.frames_per_stream, called ? b->pair.pairs : &dflt, called ? b->pair.n_pairs : 1u);
+    if (tile_frames) *tile_frames = plan.sweep_frames;
+    if (entries_cap) *entries_cap = plan.entries_cap;
+    if (n_pairs) *n_pairs = called ? b->pair.n_pairs : 1u;
+    return SS_OK;
+}
+
+int ss_batch_pair_series(ss_batch *b, const ss_channel_pair *pairs, uint32_t n_pairs)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const ss_batch_config &c = b->cfg;
+    ssk::PairSeriesParams p{};
+    int rc = pair_list_of(b, pairs, n_pairs, p.pairs, &p.n_pairs);
+    if (rc) return rc;
+    const ssk::PairSeriesPlan plan = ssk::plan_pair_series(c.channels, peak_s100(b), c.frames_per_stream, p.pairs, p.n_pairs);
+    if (!peak_s100(b) || (uint64_t)plan.entries_cap * peak_s100(b) < c.frames_per_stream) return SS_ERR_UNSUPPORTED;     // (2^32 entries)
+    Pairs &pr = b->pair;
+    // (a longer pair list grows the series: the buffer is freed first, and hipFree waits for whatever still uses it)
+    HIPCHK(pr.series.ensure((size_t)c.n_streams * plan.entries_cap * p.n_pairs));
+    p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * c.channels; p.n_frames = c.frames_per_stream;
+    p.frames_of = b->ragged_ptr(b->ragged.frames_d);
+    p.series = pr.series.p;
+    p.n_streams = c.n_streams; p.channels = c.channels; p.s100 = peak_s100(b);
+    p.entries_cap = plan.entries_cap; p.stereo = plan.stereo ? 1u : 0u;
+    HIPCHK(ssk::launch_pair_series(p, b->stream));
+    pr.n_pairs = p.n_pairs;
+    for (uint32_t k = 0; k < p.n_pairs; k++) pr.pairs[k] = p.pairs[k];
+    pr.series_done = true;
+    return SS_OK;
+}
+
+int ss_batch_download_pair_series(ss_batch *b, uint32_t stream, ss_pair_entry *out, size_t cap_entries, uint32_t *n_entries)
+{
+    SS_ON_DEVICE(b);
+    if (!b || stream >= b->cfg.n_streams) return SS_ERR_INVALID_ARG;
+    const Pairs &pr = b->pair;
+    if (!pr.series_done) return SS_ERR_INVALID_MODE;
+    const uint64_t n = peak_entries_of(b, stream);
+    if (!out && n) return SS_ERR_INVALID_ARG;
+    if (cap_entries < n) return SS_ERR_CAPACITY;
+    if (n_entries) *n_entries = (uint32_t)n;
+    if (!n) return ss_batch_sync(b);
+    const size_t cap = ssk::plan_peak_series(b->cfg.channels, peak_s100(b), b->cfg.frames_per_stream).entries_cap;
+    return fetch(b, out, reinterpret_cast<const ss_pair_entry *>(pr.series.p + (size_t)stream * cap * pr.n_pairs), (size_t)n * pr.n_pairs);
+}
+
+int ss_batch_pair_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups, const ss_pair_region_config *cfg)
+{
+    SS_ON_DEVICE(b);
+    if (!b || !cfg) return SS_ERR_INVALID_ARG;
+    Pairs &pr = b->pair;
+    if (!pr.series_done) return SS_ERR_INVALID_MODE;
+    if (!(cfg->threshold > -1.0 && cfg->threshold < 1.0) || !(cfg->power_floor >= 0.0)) return SS_ERR_INVALID_ARG;       // (NaN fails the comparisons)
+    if (!cfg->min_run || cfg->reserved) return SS_ERR_INVALID_ARG;
+    uint32_t longest = 0;
+    int rc = check_regions(b, regions, n_regions, n_groups, [b](uint32_t s) { return peak_entries_of(b, s); }, &longest);
+    if (rc) return rc;
+    const size_t NP = pr.n_pairs;
+    if (n_regions * NP > 0x7FFFFFFFull || n_groups * NP > 0x7FFFFFFFull) return SS_ERR_UNSUPPORTED;
+    HIPCHK(pr.results.ensure(n_regions * NP)); HIPCHK(pr.group_results.ensure(n_groups * NP));
+    if ((rc = pr.list.replace(b->stream, regions, n_regions))) return rc;
+    ssk::RegionPairsParams p{};
+    p.series = pr.series.p; p.n_pairs = pr.n_pairs;
+    p.entries_cap = ssk::plan_peak_series(b->cfg.channels, peak_s100(b), b->cfg.frames_per_stream).entries_cap;
+    p.threshold = cfg->threshold; p.power_floor = cfg->power_floor; p.min_run = cfg->min_run;
+    p.regions = pr.list.dev.p; p.results = pr.results.p; p.n_regions = n_regions; p.n_groups = n_groups; p.group_results = pr.group_results.p;
+    HIPCHK(ssk::launch_region_pairs(p, b->stream));
+    pr.list.queued(n_regions, n_groups);
+    pr.list_pairs = pr.n_pairs;
+    return SS_OK;
+}
+
+int ss_batch_download_region_pairs(ss_batch *b, ss_region_pair *out, size_t cap_records)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const Pairs &pr = b->pair;
+    return fetch_records(b, pr.list.done, out, cap_records > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap_records, pr.list.n_regions * pr.list_pairs, pr.results.p);
+}
+
+int ss_batch_download_group_pairs(ss_batch *b, ss_group_pair *out, size_t cap_records)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const Pairs &pr = b->pair;
+    return fetch_records(b, pr.list.done, out, cap_records > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap_records, pr.list.n_groups * pr.list_pairs, pr.group_results.p);
 }
 
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max)

@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_bank_signal_watch.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_pair_series.hip, ss_bank_signal_watch.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -450,6 +450,52 @@ struct SignalScanParams {
     SignalEvent *events;             // [stream][2][max_events]: the silence list, the clip list (max_events == 0: unused)
 };
 hipError_t launch_signal_scan(const SignalScanParams &p, hipStream_t s);
+// Pair series (ss_batch_pair_series; ss_pair_series.hip): per (stream, 100 ms entry, channel pair) the f64 sums of x_a^2, x_b^2 and
+// x_a x_b over the entry's frames in which both samples are finite, from the resident corpus alone — no pass, no tables.  The grid
+// is the peak series' (plan_peak_series' entries_cap).  The records are laid out as ss_channel_pair / ss_pair_entry
+// (include/soundscope_hip.h).
+constexpr uint32_t kMaxPairs = 16;
+struct ChannelPair { uint32_t a, b; };
+struct alignas(16) PairEntry { double s_aa, s_bb, s_ab; uint32_t frames, skipped; };
+static_assert(sizeof(ChannelPair) == 8 && sizeof(PairEntry) == 32 && offsetof(PairEntry, s_ab) == 16 && offsetof(PairEntry, frames) == 24 &&
+              offsetof(PairEntry, skipped) == 28, "pair entry layout");
+// sweep_frames: the frames a workgroup has in flight at a time (256 lanes, four loads each; a 16-byte load holds two stereo frames).
+// It fixes which lane adds which frame, and with that the order of every sum.
+struct PairSeriesPlan { uint32_t sweep_frames, entries_cap; bool stereo; };
+// stereo: two channels and one pair of distinct channels — the form that reads the entry as 16-byte loads
+PairSeriesPlan plan_pair_series(uint32_t channels, uint32_t s100, uint64_t n_frames, const ChannelPair *pairs, uint32_t n_pairs);
+struct PairSeriesParams {
+    const float *pcm;                // [stream][frame][channels] f32, 16-byte aligned
+    uint64_t stream_stride;          // floats between streams
+    uint64_t n_frames;               // frames of a slot
+    const uint64_t *frames_of;       // ragged batches: each stream's own frames (nullable = n_frames for all)
+    PairEntry *series;               // [stream][entries_cap][n_pairs]
+    uint32_t n_streams, channels, s100;
+    uint32_t entries_cap, n_pairs;   // plan_pair_series; 1 .. kMaxPairs
+    uint32_t stereo;                 // plan_pair_series
+    ChannelPair pairs[kMaxPairs];    // a, b < channels (the caller has checked)
+};
+hipError_t launch_pair_series(const PairSeriesParams &p, hipStream_t s);
+// Pair regions (ss_batch_pair_regions), behind a series on the same stream: the entries' sums added in entry order, the entries
+// below the correlation threshold and their runs, and the regions' records added per group in region index order.  The records are
+// laid out as ss_region_pair / ss_group_pair.
+struct RegionPair {
+    double s_aa, s_bb, s_ab; unsigned long long frames, skipped;
+    uint32_t n_active, n_below, first_below, longest_below, longest_below_at, below_runs;
+};
+struct GroupPair { double s_aa, s_bb, s_ab; unsigned long long frames, skipped, n_active, n_below, below_runs; };
+static_assert(sizeof(RegionPair) == 64 && offsetof(RegionPair, frames) == 24 && offsetof(RegionPair, n_active) == 40 &&
+              offsetof(RegionPair, below_runs) == 60 && sizeof(GroupPair) == 64 && offsetof(GroupPair, n_active) == 40, "pair region layouts");
+struct RegionPairsParams {
+    const PairEntry *series; uint32_t entries_cap, n_pairs;
+    double threshold, power_floor; uint32_t min_run;       // ss_pair_region_config (the caller has checked)
+    const LoudnessRegion *regions;   // [n_regions], every one inside its stream's entries (the caller has checked)
+    RegionPair *results;             // [n_regions][n_pairs]
+    uint32_t n_regions, n_groups;
+    GroupPair *group_results;        // [n_groups][n_pairs]
+};
+// reduces every (region, pair) (k_region_pairs), then every (group, pair) over the regions' records (k_group_pairs)
+hipError_t launch_region_pairs(const RegionPairsParams &p, hipStream_t s);
 // gate + LRA on explicit histograms (corpus gate after the all-reduce; handle getters)
 // `peaks` (optional): a handle's readings in one launch (ReadingsExtra above)
 hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, const double *bounds,
