@@ -906,6 +906,82 @@ int ss_meter_bank_signal_watch_reset(ss_meter_bank *m, const uint32_t *streams, 
 int ss_meter_bank_signal_watch(ss_meter_bank *m, ss_stream_watch *streams_out, uint32_t cap_streams,
                                ss_channel_watch *channels_out, size_t cap_records);
 
+/* Pair watch of a bank: the live counterpart of ss_batch_pair_series and ss_batch_pair_regions — are this input's
+ * channels in phase, how is it balanced, what would a mono fold-down lose, and since when is it out of phase — kept on the device
+ * for every stream and channel pair and advanced by every add call, whichever of the six forms it has.  Not in the reference.
+ *  S = s100 = (rate + 5) / 10, as the batch series has it.  Frames and entries of a stream count from that stream's pair-watch reset.
+ *  Entry j covers the stream's frames [j S, (j + 1) S), whichever calls they arrived in.  An entry is complete when its S-th frame
+ *  has arrived; E is the number of complete entries.  The open_frames frames behind the last complete entry belong to no record
+ *  yet: there is no partial tail entry in the live form.  A complete entry's ss_pair_entry for pair (a, b) is, bit for bit, what the
+ *  batch series' general form computes for the same S frames: frame i of the entry belongs to lane i mod 256; a lane adds its frames
+ *  in ascending order from +0 with one fused multiply-add per product; a frame in which x_a or x_b is NaN or infinite adds +0 and is
+ *  counted in `skipped`; the 64 lanes of a wave meet in the xor butterfly at distances 32 .. 1; the four waves are added in wave
+ *  order.  How the material was cut into calls changes no bit of any entry: one call, 10 ms blocks, one frame at a time and ragged
+ *  calls agree, and two banks fed the same calls agree byte for byte.
+ *  Lane state: per (stream, pair) the open entry's 256 lane sums x 3 f64 persist on the device between calls (6 KB per pair); a
+ *  call loads them where open_frames > 0, each lane goes on adding its own frames, and lanes meet only when the entry completes.
+ *  Ring: the newest R = window_entries complete entries per (stream, pair) stay on the device (32 R bytes), 1 <= R <=
+ *  SS_BANK_PAIR_WINDOW_MAX (60 s).
+ *  Record, per (stream, pair), as the state stands after the last add:
+ *  - window: the sums, frames and skipped of the newest window_count = min(R, E) complete entries, added in ascending entry order
+ *    from +0, one rounded f64 addition each: ss_batch_pair_regions' rule for the region [E - window_count, E);
+ *  - total: the same over [0, E), kept as a running sequential sum (each entry added as it completes);
+ *  - n_active, n_below, first_below, longest_below, longest_below_at, below_runs: ss_region_pair's fields for the region [0, E),
+ *    with the ACTIVE and BELOW predicates of the comment above (threshold, power_floor, min_run), stepped once per completed entry;
+ *  - trailing_below: the entries of the run that holds entry E - 1, else 0 — out of phase since then.  "None" is UINT64_MAX.
+ *  The caller forms correlation, balance and mono loss from `window` or `total` as from a region's sums.
+ *  - ss_meter_bank_reset resets the meters, not the pair watch.  A stream given 0 frames in a call keeps its state and records byte
+ *    for byte, and an all-zero call launches nothing.  A non-finite sample touches its own stream's counters only.  The pair watch
+ *    moves nothing else: readings, peaks, histograms, spectra and signal-watch records are byte for byte what they are without it,
+ *    and a bank that never enables it allocates and launches exactly what it did before.  For the PCM forms the sums see the f32
+ *    values the meter sees, ss_pcm_decode's.
+ *  - Cost: one launch per add call (one workgroup per stream walks the stream's frames of that call entry by entry: a long call is
+ *    walked serially), none for a read.
+ *  Status codes, all checked before anything is allocated or queued, so a refused call leaves the previous watch as it was: a or b
+ *  >= channels, n_pairs > 16, pairs == NULL with n_pairs > 0, the default pair on a mono bank, a NaN threshold or |threshold| >= 1, a
+ *  NaN or negative power_floor, min_run == 0, window_entries == 0 or > SS_BANK_PAIR_WINDOW_MAX, a bad stream index:
+ *  SS_ERR_INVALID_ARG; _plan, _reset or either read before _enable: SS_ERR_INVALID_MODE; a `cap` too small: SS_ERR_CAPACITY, with
+ *  nothing written. */
+#define SS_BANK_PAIR_WINDOW_MAX 600
+typedef struct ss_pair_sums {
+    double   s_aa, s_bb, s_ab;    /* the entries' sums added in entry order */
+    uint64_t frames, skipped;
+} ss_pair_sums;                   /* 40 bytes */
+typedef struct ss_pair_watch_config {
+    double   threshold;           /* an entry is BELOW iff its correlation < threshold; -1 < threshold < 1 */
+    double   power_floor;         /* an entry is ACTIVE iff s_aa + s_bb > power_floor * frames (linear power per frame, >= 0) */
+    uint32_t min_run;             /* >= 1: runs of consecutive active BELOW entries at least this long are counted */
+    uint32_t window_entries;      /* R: 1 .. SS_BANK_PAIR_WINDOW_MAX complete entries in the window and the ring */
+} ss_pair_watch_config;           /* 24 bytes */
+typedef struct ss_pair_watch {
+    ss_pair_sums window;          /* the newest window_count complete entries */
+    ss_pair_sums total;           /* every complete entry since the stream's pair-watch reset */
+    uint64_t entries;             /* E: complete entries */
+    uint64_t n_active, n_below;   /* n_below counts active entries only */
+    uint64_t first_below;         /* entry index of the first active BELOW entry; UINT64_MAX if none */
+    uint64_t longest_below;       /* entries of the longest run, of any length; ties go to the lowest entry; 0 if none */
+    uint64_t longest_below_at;    /* entry index of its first entry; UINT64_MAX if none */
+    uint64_t below_runs;          /* runs of at least min_run */
+    uint64_t trailing_below;      /* entries of the run that holds entry E - 1, else 0 */
+    uint32_t open_frames;         /* frames behind the last complete entry: in no record yet */
+    uint32_t window_count;        /* min(R, E) */
+    uint64_t reserved;            /* 0 */
+} ss_pair_watch;                  /* 160 bytes */
+/* cfg != NULL: empty state for every stream (enabling again, with the same or new parameters, starts empty); cfg == NULL: the watch
+ * off, its state freed.  pairs == NULL with n_pairs == 0 is the one pair (0, 1); the call copies `pairs`. */
+int ss_meter_bank_pair_watch_enable(ss_meter_bank *m, const ss_channel_pair *pairs, uint32_t n_pairs, const ss_pair_watch_config *cfg);
+/* *lanes = 256 (frame i of an entry belongs to lane i mod *lanes), the window and the pairs of the watch as enabled */
+int ss_meter_bank_pair_watch_plan(const ss_meter_bank *m, uint32_t *lanes, uint32_t *window_entries, uint32_t *n_pairs);
+/* empties the listed streams' pair watch (streams == NULL: all); the others are untouched */
+int ss_meter_bank_pair_watch_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count);
+/* the records for the state after the last add, [stream][pair]; cap_records counts records.  Waits; no launch (the adds leave the
+ * records behind) and one copy through page-locked memory. */
+int ss_meter_bank_pair_watch(ss_meter_bank *m, ss_pair_watch *out, size_t cap_records);
+/* the ring of one stream: its newest *n_entries = min(R, E) complete entries in ascending order, [entry][pair], the first of them
+ * entry *first_entry (both optional); cap_entries counts entries (records / n_pairs).  Waits; no launch and one copy. */
+int ss_meter_bank_pair_watch_entries(ss_meter_bank *m, uint32_t stream, ss_pair_entry *out, size_t cap_entries,
+                                     uint64_t *first_entry, uint32_t *n_entries);
+
 /* ------------------------------------------------------------------------- *
  *  Multi-GPU: one process per GPU, streams sharded over the ranks, and exactly ONE exchange —
  *  the SUM all-reduce of the two 1000-bin u64 histograms for the corpus-level integrated-LUFS gate

@@ -52,6 +52,8 @@ SYMBOLS = [
     "ss_meter_bank_spectrum_tracked", "ss_meter_bank_spectrum_tracked_columns",
     "ss_meter_bank_signal_watch_enable", "ss_meter_bank_signal_watch_plan", "ss_meter_bank_signal_watch_reset",
     "ss_meter_bank_signal_watch",
+    "ss_meter_bank_pair_watch_enable", "ss_meter_bank_pair_watch_plan", "ss_meter_bank_pair_watch_reset",
+    "ss_meter_bank_pair_watch", "ss_meter_bank_pair_watch_entries",
     "ss_batch_spectrum_stats", "ss_batch_download_spectrum_stats", "ss_batch_corpus_spectrum", "ss_batch_spectrum_stats_plan",
     "ss_batch_loudness_regions", "ss_batch_download_region_results", "ss_batch_download_group_results", "ss_batch_group_histograms",
     "ss_batch_peak_series", "ss_batch_peak_series_plan", "ss_batch_download_peak_series", "ss_batch_peak_regions",
@@ -206,6 +208,20 @@ class RegionPair(C.Structure):
 class GroupPair(C.Structure):
     _fields_ = [("s_aa", C.c_double), ("s_bb", C.c_double), ("s_ab", C.c_double)] + [
         (n, C.c_uint64) for n in ("frames", "skipped", "n_active", "n_below", "below_runs")]
+
+
+class PairSums(C.Structure):               # ss_pair_sums
+    _fields_ = [("s_aa", C.c_double), ("s_bb", C.c_double), ("s_ab", C.c_double), ("frames", C.c_uint64), ("skipped", C.c_uint64)]
+
+
+class PairWatchConfig(C.Structure):        # ss_pair_watch_config
+    _fields_ = [("threshold", C.c_double), ("power_floor", C.c_double), ("min_run", C.c_uint32), ("window_entries", C.c_uint32)]
+
+
+class PairWatch(C.Structure):              # ss_pair_watch
+    _fields_ = [("window", PairSums), ("total", PairSums)] + [(n, C.c_uint64) for n in (
+        "entries", "n_active", "n_below", "first_below", "longest_below", "longest_below_at", "below_runs", "trailing_below")] + [
+        ("open_frames", C.c_uint32), ("window_count", C.c_uint32), ("reserved", C.c_uint64)]
 
 
 class SpectrogramView(C.Structure):
@@ -398,6 +414,12 @@ def _bind(lib):
         "ss_meter_bank_signal_watch_plan": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "ss_meter_bank_signal_watch_reset": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_uint32]),
         "ss_meter_bank_signal_watch": (C.c_int, [vp, C.POINTER(StreamWatch), C.c_uint32, C.POINTER(ChannelWatch), C.c_size_t]),
+        "ss_meter_bank_pair_watch_enable": (C.c_int, [vp, C.POINTER(ChannelPair), C.c_uint32, C.POINTER(PairWatchConfig)]),
+        "ss_meter_bank_pair_watch_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ss_meter_bank_pair_watch_reset": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_uint32]),
+        "ss_meter_bank_pair_watch": (C.c_int, [vp, C.POINTER(PairWatch), C.c_size_t]),
+        "ss_meter_bank_pair_watch_entries": (C.c_int, [vp, C.c_uint32, C.POINTER(PairEntry), C.c_size_t, C.POINTER(C.c_uint64),
+                                                       C.POINTER(C.c_uint32)]),
         "ss_batch_signal_scan": (C.c_int, [vp, C.POINTER(SignalScanConfig)]),
         "ss_batch_signal_scan_plan": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_batch_download_stream_scans": (C.c_int, [vp, C.POINTER(StreamScan), C.c_uint32]),

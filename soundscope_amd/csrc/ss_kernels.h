@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_pair_series.hip, ss_bank_signal_watch.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_pair_series.hip, ss_bank_signal_watch.hip, ss_bank_pair_watch.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -639,6 +639,47 @@ hipError_t launch_bank_signal_watch(const BankWatchParams &p, hipStream_t s);
 // the listed streams' state and records are empty (streams == nullptr: streams 0 .. count - 1)
 hipError_t launch_bank_signal_watch_reset(BankWatchSeq *state, StreamWatch *stream_watches, ChannelWatch *channel_watches,
                                           const uint32_t *streams, uint32_t count, uint32_t channels, hipStream_t s);
+
+// pair watch of a bank (ss_meter_bank_pair_watch*; ss_bank_pair_watch.hip): the batch pair series' entries of everything a stream
+// was given since its pair-watch reset, advanced by one launch per add call.  Per (stream, pair) the device holds
+//   - the open entry's lane sums, [3][kPairWatchLanes] f64 (s_aa, s_bb, s_ab: a wave's 64 lanes read consecutive doubles), valid
+//     where the stream's open_frames > 0, and the frames of the open entry that were skipped so far (one u32);
+//   - the ring of the newest window_entries complete entries, entry j at slot j mod window_entries;
+//   - the record, laid out as ss_pair_watch (include/soundscope_hip.h).  The record IS the running state: its totals, counts,
+//     run fields, entries and open_frames are read at the start of a call and written at its end.
+constexpr uint32_t kPairWatchLanes = 256;
+constexpr uint32_t kPairWatchWindowMax = 600;
+struct PairWatchSums { double s_aa, s_bb, s_ab; unsigned long long frames, skipped; };
+struct PairWatch {
+    PairWatchSums window, total;
+    unsigned long long entries, n_active, n_below, first_below, longest_below, longest_below_at, below_runs, trailing_below;
+    uint32_t open_frames, window_count;
+    unsigned long long reserved;
+};
+static_assert(sizeof(PairWatchSums) == 40 && sizeof(PairWatch) == 160 && offsetof(PairWatch, total) == 40 && offsetof(PairWatch, entries) == 80 &&
+              offsetof(PairWatch, trailing_below) == 136 && offsetof(PairWatch, open_frames) == 144 && offsetof(PairWatch, reserved) == 152,
+              "pair watch layout");
+struct BankPairWatchParams {
+    const float *pcm;                // f32 input of this call, any 4-byte alignment: stream s at pcm + offset_of[s], or pcm + s * stride
+    uint64_t stride;                 // floats between streams (offset_of == nullptr)
+    const uint64_t *offset_of;       // [stream], nullable
+    const uint64_t *frames_of;       // [stream], nullable: every stream gets `frames`; a stream of 0 frames is not touched
+    uint64_t frames;
+    uint32_t n_streams, channels, s100;
+    uint32_t window_entries, n_pairs;// 1 .. kPairWatchWindowMax; 1 .. kMaxPairs
+    double threshold, power_floor; uint32_t min_run;      // ss_pair_watch_config (the caller has checked)
+    double *lanes;                   // [stream][pair][3][kPairWatchLanes]
+    uint32_t *open_skipped;          // [stream][pair]
+    PairEntry *ring;                 // [stream][window_entries][pair]
+    PairWatch *records;              // [stream][pair]
+    ChannelPair pairs[kMaxPairs];    // a, b < channels (the caller has checked)
+};
+// one workgroup per stream walks its frames of this call entry by entry and leaves the state, the ring and the records behind
+hipError_t launch_bank_pair_watch(const BankPairWatchParams &p, hipStream_t s);
+// the listed streams' records are empty (streams == nullptr: streams 0 .. count - 1); open_frames == 0 and entries == 0 make the
+// lane sums and the ring unread
+hipError_t launch_bank_pair_watch_reset(PairWatch *records, uint32_t *open_skipped, const uint32_t *streams, uint32_t count,
+                                        uint32_t n_pairs, hipStream_t s);
 
 // ---- waveform ---------------------------------------------------------------
 struct WaveParams {

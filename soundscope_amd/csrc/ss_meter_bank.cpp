@@ -53,6 +53,19 @@ struct ss_meter_bank {
     ssh::DevBuf<ssk::BankWatchSeq> watch_state;    // [n][channels + 1]
     ssh::DevBuf<unsigned char> watch_rec;  // [n] ssk::StreamWatch, then [n][channels] ssk::ChannelWatch
     ssh::PinBuf<unsigned char> watch_pin;
+    // pair watch (ss_meter_bank_pair_watch_enable): the batch pair series' entries of what every stream was given, advanced by one
+    // launch per add (ssk::BankPairWatchParams).  pair_fed mirrors the frames each stream has had since its pair-watch reset — the
+    // device's entries and open_frames follow from it — so that the ring's read knows which slots hold entries without a copy
+    bool pair_on = false;
+    ss_pair_watch_config pair_cfg{};
+    uint32_t pair_n = 0;                   // pairs
+    ssk::ChannelPair pair_list[ssk::kMaxPairs] = {};
+    ssh::DevBuf<double> pair_lanes;        // [n][pairs][3][256]
+    ssh::DevBuf<uint32_t> pair_open_skipped;   // [n][pairs]
+    ssh::DevBuf<ssk::PairEntry> pair_ring; // [n][window_entries][pairs]
+    ssh::DevBuf<ssk::PairWatch> pair_rec;  // [n][pairs]
+    ssh::PinBuf<unsigned char> pair_pin;   // the records, or one stream's ring
+    std::vector<uint64_t> pair_fed;        // [n]
 };
 
 static_assert(sizeof(ss_meter_reading) == 72 && sizeof(ssk::MeterReading) == sizeof(ss_meter_reading), "ss_meter_reading layout");
@@ -188,6 +201,43 @@ int watch_advance(ss_meter_bank *m, const float *pcm, const uint64_t *offset_of,
     return SS_OK;
 }
 
+// ---- pair watch --------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(ss_pair_sums) == 40 && sizeof(ss_pair_watch_config) == 24 && sizeof(ss_pair_watch) == 160 && sizeof(ssk::PairWatch) == 160,
+              "pair watch record layout");
+static_assert(offsetof(ss_pair_watch, total) == offsetof(ssk::PairWatch, total) && offsetof(ss_pair_watch, entries) == offsetof(ssk::PairWatch, entries) &&
+              offsetof(ss_pair_watch, first_below) == offsetof(ssk::PairWatch, first_below) &&
+              offsetof(ss_pair_watch, trailing_below) == offsetof(ssk::PairWatch, trailing_below) &&
+              offsetof(ss_pair_watch, open_frames) == offsetof(ssk::PairWatch, open_frames) &&
+              offsetof(ss_pair_watch, window_count) == offsetof(ssk::PairWatch, window_count) &&
+              offsetof(ss_pair_watch, reserved) == offsetof(ssk::PairWatch, reserved) && offsetof(ss_pair_sums, frames) == offsetof(ssk::PairWatchSums, frames),
+              "ss_pair_watch layout");
+static_assert(SS_BANK_PAIR_WINDOW_MAX == ssk::kPairWatchWindowMax, "one window maximum");
+
+// the pair watch's launch behind the staging of an add, with watch_advance's arguments
+int pair_watch_advance(ss_meter_bank *m, const float *pcm, const uint64_t *offset_of, uint64_t stride, const uint64_t *frames_of, uint64_t frames)
+{
+    ssk::BankPairWatchParams p{};
+    p.pcm = pcm; p.stride = stride; p.offset_of = offset_of; p.frames_of = frames_of; p.frames = frames;
+    p.n_streams = m->meter.n; p.channels = m->meter.channels; p.s100 = (uint32_t)m->meter.s100;
+    p.window_entries = m->pair_cfg.window_entries; p.n_pairs = m->pair_n;
+    p.threshold = m->pair_cfg.threshold; p.power_floor = m->pair_cfg.power_floor; p.min_run = m->pair_cfg.min_run;
+    p.lanes = m->pair_lanes.p; p.open_skipped = m->pair_open_skipped.p; p.ring = m->pair_ring.p; p.records = m->pair_rec.p;
+    for (uint32_t k = 0; k < m->pair_n; k++) p.pairs[k] = m->pair_list[k];
+    HIPCHK(ssk::launch_bank_pair_watch(p, m->stream));
+    return SS_OK;
+}
+
+// the pair watch off: nothing on the stream still uses its state afterwards
+int pair_watch_drop(ss_meter_bank *m)
+{
+    if (!m->pair_on) return SS_OK;
+    HIPCHK(bank_sync(m));
+    m->pair_on = false;
+    m->pair_lanes.release(); m->pair_open_skipped.release(); m->pair_ring.release(); m->pair_rec.release(); m->pair_pin.release();
+    m->pair_fed.clear();
+    return SS_OK;
+}
+
 // the launches of an add behind its staging.  Stream s's input stands at pcm + offset_of[s] (offset_of null: pcm + s * stride); `arr`:
 // a ragged plan's arrays on the device (null: a uniform call)
 int advance(ss_meter_bank *m, const BankPlan &pl, const uint64_t *arr, const float *pcm, const uint64_t *offset_of, uint64_t stride)
@@ -207,6 +257,11 @@ int advance(ss_meter_bank *m, const BankPlan &pl, const uint64_t *arr, const flo
     if (m->watch_on) {                                                   // one launch for the whole call, not one per piece
         int rc = watch_advance(m, pcm, offset_of, stride, arr, pl.longest);
         if (rc) return rc;
+    }
+    if (m->pair_on) {
+        int rc = pair_watch_advance(m, pcm, offset_of, stride, arr, pl.longest);
+        if (rc) return rc;
+        for (uint32_t s = 0; s < n; s++) m->pair_fed[s] += arr ? pl.arrays[s] : pl.longest;
     }
     const uint64_t piece_frames = 32 * ms.s100;
     const ssk::MeterBankParams q = ms.bank_params();
@@ -794,6 +849,114 @@ int ss_meter_bank_signal_watch(ss_meter_bank *m, ss_stream_watch *streams_out, u
     HIPCHK(bank_sync(m));
     if (streams_out) std::memcpy(streams_out, m->watch_pin.p, sbytes);
     if (channels_out) std::memcpy(channels_out, m->watch_pin.p + sbytes, cbytes);
+    return SS_OK;
+}
+
+int ss_meter_bank_pair_watch_enable(ss_meter_bank *m, const ss_channel_pair *pairs, uint32_t n_pairs, const ss_pair_watch_config *cfg)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!cfg) return pair_watch_drop(m);
+    // ss_batch_pair_series' pair-list refusals (ss_batch.cpp's pair_list_of, on the bank's channel count) and ss_batch_pair_regions'
+    // config refusals, before anything is allocated or queued
+    const uint32_t C = m->meter.channels;
+    ssk::ChannelPair list[ssk::kMaxPairs] = {};
+    uint32_t np = n_pairs;
+    if (n_pairs > ssk::kMaxPairs || (!pairs && n_pairs)) return SS_ERR_INVALID_ARG;
+    if (!pairs || !n_pairs) {                                                      // the default pair needs two channels
+        if (C < 2u) return SS_ERR_INVALID_ARG;
+        list[0].a = 0u; list[0].b = 1u;
+        np = 1u;
+    }
+    for (uint32_t k = 0; pairs && k < n_pairs; k++) {
+        if (pairs[k].a >= C || pairs[k].b >= C) return SS_ERR_INVALID_ARG;
+        list[k].a = pairs[k].a; list[k].b = pairs[k].b;
+    }
+    if (!(cfg->threshold > -1.0 && cfg->threshold < 1.0) || !(cfg->power_floor >= 0.0)) return SS_ERR_INVALID_ARG;        // (NaN fails the comparisons)
+    if (!cfg->min_run || !cfg->window_entries || cfg->window_entries > SS_BANK_PAIR_WINDOW_MAX) return SS_ERR_INVALID_ARG;
+    const size_t n = m->meter.n, R = cfg->window_entries;
+    const bool same = m->pair_on && np == m->pair_n && R == m->pair_cfg.window_entries;
+    if (m->pair_on && !same) {                                                     // another shape: the stream may still use the old state
+        int rc = pair_watch_drop(m);
+        if (rc) return rc;
+    }
+    HIPCHK(m->pair_lanes.ensure(n * np * 3u * ssk::kPairWatchLanes));              // (enabling again with the same shape keeps the allocations)
+    HIPCHK(m->pair_open_skipped.ensure(n * np));
+    HIPCHK(m->pair_ring.ensure(n * R * np));
+    HIPCHK(m->pair_rec.ensure(n * np));
+    const size_t rec_bytes = n * np * sizeof(ssk::PairWatch), ring_bytes = R * np * sizeof(ssk::PairEntry);
+    HIPCHK(m->pair_pin.ensure(rec_bytes > ring_bytes ? rec_bytes : ring_bytes));
+    HIPCHK(ssk::launch_bank_pair_watch_reset(m->pair_rec.p, m->pair_open_skipped.p, nullptr, m->meter.n, np, m->stream));
+    m->pair_cfg = *cfg;
+    m->pair_n = np;
+    for (uint32_t k = 0; k < np; k++) m->pair_list[k] = list[k];
+    m->pair_fed.assign(n, 0);
+    m->pair_on = true;
+    return SS_OK;
+}
+
+int ss_meter_bank_pair_watch_plan(const ss_meter_bank *m, uint32_t *lanes, uint32_t *window_entries, uint32_t *n_pairs)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->pair_on) return SS_ERR_INVALID_MODE;
+    if (lanes) *lanes = ssk::kPairWatchLanes;
+    if (window_entries) *window_entries = m->pair_cfg.window_entries;
+    if (n_pairs) *n_pairs = m->pair_n;
+    return SS_OK;
+}
+
+int ss_meter_bank_pair_watch_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->pair_on) return SS_ERR_INVALID_MODE;
+    if (streams && !count) return SS_OK;                                           // (an empty list: nothing is staged)
+    const uint32_t *dev;
+    int rc = stream_list(m, streams, count, &dev);
+    if (rc) return rc;
+    if (!streams) count = m->meter.n;
+    HIPCHK(ssk::launch_bank_pair_watch_reset(m->pair_rec.p, m->pair_open_skipped.p, dev, count, m->pair_n, m->stream));
+    for (uint32_t i = 0; i < count; i++) m->pair_fed[streams ? streams[i] : i] = 0;
+    return SS_OK;
+}
+
+int ss_meter_bank_pair_watch(ss_meter_bank *m, ss_pair_watch *out, size_t cap_records)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->pair_on) return SS_ERR_INVALID_MODE;
+    if (!out) return SS_ERR_INVALID_ARG;
+    const size_t records = (size_t)m->meter.n * m->pair_n, bytes = records * sizeof(ssk::PairWatch);
+    if (cap_records < records) return SS_ERR_CAPACITY;
+    // the add calls left the records as they stand: no launch, one copy
+    HIPCHK(hipMemcpyAsync(m->pair_pin.p, m->pair_rec.p, bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(bank_sync(m));
+    std::memcpy(out, m->pair_pin.p, bytes);
+    return SS_OK;
+}
+
+int ss_meter_bank_pair_watch_entries(ss_meter_bank *m, uint32_t stream, ss_pair_entry *out, size_t cap_entries, uint64_t *first_entry,
+                                     uint32_t *n_entries)
+{
+    SS_ON_DEVICE(m);
+    if (!m) return null_bank();
+    if (!m->pair_on) return SS_ERR_INVALID_MODE;
+    if (stream >= m->meter.n) return SS_ERR_INVALID_ARG;
+    const uint64_t E = m->pair_fed[stream] / m->meter.s100, R = m->pair_cfg.window_entries;
+    const uint32_t n = (uint32_t)(E < R ? E : R), NP = m->pair_n;
+    if (!out && n) return SS_ERR_INVALID_ARG;
+    if (cap_entries < n) return SS_ERR_CAPACITY;
+    // slots [0, n) hold the newest n entries (n < R: entries 0 .. n - 1 in place; n == R: entry j at slot j mod R): one copy
+    const size_t bytes = (size_t)n * NP * sizeof(ssk::PairEntry);
+    if (n) HIPCHK(hipMemcpyAsync(m->pair_pin.p, m->pair_ring.p + (size_t)stream * R * NP, bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(bank_sync(m));
+    const uint64_t first = E - n;
+    const ssk::PairEntry *ring = reinterpret_cast<const ssk::PairEntry *>(m->pair_pin.p);
+    for (uint32_t j = 0; j < n; j++)
+        std::memcpy(out + (size_t)j * NP, ring + (size_t)((first + j) % R) * NP, (size_t)NP * sizeof(ssk::PairEntry));
+    if (first_entry) *first_entry = first;
+    if (n_entries) *n_entries = n;
     return SS_OK;
 }
 

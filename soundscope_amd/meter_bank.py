@@ -9,6 +9,8 @@ With `enable_spectrum_tracking()` it keeps, per row, an exponentially averaged a
 `track_spectrum()` advances them on each stream's own clock, `tracked_spectrum()` / `tracked_spectrum_columns()` read them.
 With `enable_signal_watch()` every add also advances, per stream, the records `Batch.signal_scan` defines for everything the
 stream was given: silence and since when, clip runs, DC sums and non-finite samples; `signal_watch()` reads them.
+With `enable_pair_watch()` every add also advances, per stream and channel pair, the entries `Batch.pair_series` defines: the sums
+of the newest window and of everything so far, and the runs of entries below a correlation threshold; `pair_watch()` reads them.
 """
 import ctypes as C
 
@@ -16,6 +18,7 @@ import numpy as np
 
 from . import _lib as L
 from .analyzer import _check
+from .batch import PAIR_ENTRY_DTYPE
 
 READING_DTYPE = np.dtype([("momentary", "<f8"), ("shortterm", "<f8"), ("integrated", "<f8"), ("loudness_range", "<f8"),
                           ("true_peak", "<f8", (2,)), ("sample_peak", "<f8", (2,)), ("frames", "<u8")])
@@ -27,6 +30,13 @@ CHANNEL_WATCH_DTYPE = np.dtype([("sum", "<f8"), ("sum_sq", "<f8")] + [(n, "<u8")
     "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs", "trailing_clip",
     "last_clip_frame")])
 assert STREAM_WATCH_DTYPE.itemsize == C.sizeof(L.StreamWatch) == 64 and CHANNEL_WATCH_DTYPE.itemsize == C.sizeof(L.ChannelWatch) == 80
+# ss_pair_watch: `window` and `total` are records with the pair entries' field names, so that batch.pair_correlation, pair_balance_db
+# and pair_mono_loss_db take rec["window"] or rec["total"] directly
+PAIR_SUMS_DTYPE = np.dtype([("s_aa", "<f8"), ("s_bb", "<f8"), ("s_ab", "<f8"), ("frames", "<u8"), ("skipped", "<u8")])
+PAIR_WATCH_DTYPE = np.dtype([("window", PAIR_SUMS_DTYPE), ("total", PAIR_SUMS_DTYPE)] + [(n, "<u8") for n in (
+    "entries", "n_active", "n_below", "first_below", "longest_below", "longest_below_at", "below_runs", "trailing_below")] + [
+    ("open_frames", "<u4"), ("window_count", "<u4"), ("reserved", "<u8")])
+assert PAIR_SUMS_DTYPE.itemsize == C.sizeof(L.PairSums) == 40 and PAIR_WATCH_DTYPE.itemsize == C.sizeof(L.PairWatch) == 160
 
 
 class MeterBank:
@@ -268,3 +278,51 @@ class MeterBank:
         _check(L.lib().ss_meter_bank_signal_watch(self._h, st.ctypes.data_as(C.POINTER(L.StreamWatch)), st.size,
                                                   ch.ctypes.data_as(C.POINTER(L.ChannelWatch)), ch.size))
         return st, ch
+
+    # ---- pair watch (ss_meter_bank_pair_watch*) --------------------------------------------------------------------------------
+    def enable_pair_watch(self, pairs=None, window_s=3.0, threshold=0.0, power_floor=0.0, min_run=1):
+        """Watch, from now on, how the channels of every stream relate: per `pairs` (up to 16 (a, b) channel pairs, None: the one
+        pair (0, 1)) the f64 sums of every complete 100 ms entry as Batch.pair_series defines them, the newest window_s seconds of
+        them (1 .. 600 entries), the totals, and the runs of active entries whose correlation is below `threshold`
+        (Batch.pair_regions' predicates).  Enabling again starts empty."""
+        cfg = L.PairWatchConfig(float(threshold), float(power_floor), int(min_run), int(round(float(window_s) * 10.0)))
+        if pairs is None:
+            _check(L.lib().ss_meter_bank_pair_watch_enable(self._h, None, 0, C.byref(cfg)))
+        else:
+            a = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+            _check(L.lib().ss_meter_bank_pair_watch_enable(self._h, a.ctypes.data_as(C.POINTER(L.ChannelPair)), a.shape[0], C.byref(cfg)))
+
+    def disable_pair_watch(self):
+        """The pair watch off, its device memory freed."""
+        _check(L.lib().ss_meter_bank_pair_watch_enable(self._h, None, 0, None))
+
+    def pair_watch_plan(self):
+        """(lanes, window_entries, n_pairs): frame i of an entry belongs to lane i mod lanes (256); the window in entries; the pairs."""
+        ln, w, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_meter_bank_pair_watch_plan(self._h, C.byref(ln), C.byref(w), C.byref(n)))
+        return ln.value, w.value, n.value
+
+    def reset_pair_watch(self, streams=None):
+        """Empty the listed streams' pair watch (None: all); the others are untouched."""
+        if streams is None:
+            _check(L.lib().ss_meter_bank_pair_watch_reset(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+        _check(L.lib().ss_meter_bank_pair_watch_reset(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+
+    def pair_watch(self):
+        """Records [n_streams, n_pairs] of PAIR_WATCH_DTYPE for everything each stream was given since its pair-watch reset;
+        entry numbers count from there."""
+        out = np.empty((self.n_streams, self.pair_watch_plan()[2]), PAIR_WATCH_DTYPE)
+        _check(L.lib().ss_meter_bank_pair_watch(self._h, out.ctypes.data_as(C.POINTER(L.PairWatch)), out.size))
+        return out
+
+    def pair_watch_entries(self, stream):
+        """(first_entry, entries [n, n_pairs] of batch.PAIR_ENTRY_DTYPE): the ring of one stream, its newest min(window, E) complete
+        entries in ascending order."""
+        _, w, pairs = self.pair_watch_plan()
+        out = np.zeros((w, pairs), PAIR_ENTRY_DTYPE)
+        first, n = C.c_uint64(), C.c_uint32()
+        _check(L.lib().ss_meter_bank_pair_watch_entries(self._h, int(stream), out.ctypes.data_as(C.POINTER(L.PairEntry)), w,
+                                                        C.byref(first), C.byref(n)))
+        return first.value, out[:n.value].copy()
