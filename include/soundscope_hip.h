@@ -684,6 +684,105 @@ int ss_batch_pair_regions(ss_batch *b, const ss_loudness_region *regions, uint32
 /* [region][pair] and [group][pair] of the last list, the pairs those of the series it read; cap_records counts records */
 int ss_batch_download_region_pairs(ss_batch *b, ss_region_pair *out, size_t cap_records);
 int ss_batch_download_group_pairs(ss_batch *b, ss_group_pair *out, size_t cap_records);
+/* Batch gain and PCM export: the batch acts on what it measured — a gain per stream (or a gain curve: ramps, steps, fades) applied
+ * to the resident corpus in one sweep, and the corpus handed back in a delivery format.  Not in the reference.
+ *
+ * Host arithmetic, no device needed.  ss_normalisation_gain is the gain law of a loudness target with a true-peak ceiling:
+ *   - a loudness that is NaN or +-inf: gain_db = 0, gain = 1, limited_by = SS_GAIN_UNMEASURED;
+ *   - else g = target_lufs - loudness_lufs;
+ *   - the ceiling applies when max_true_peak_dbtp is finite and peak_linear is finite and > 0: with the headroom h =
+ *     max_true_peak_dbtp - 20 log10(peak_linear), g > h makes g = h and sets SS_GAIN_LIMITED_PEAK;
+ *   - then g > max_gain_db makes g = max_gain_db (SS_GAIN_LIMITED_MAX) and g < min_gain_db makes g = min_gain_db
+ *     (SS_GAIN_LIMITED_MIN): the clamp comes last, so a positive min_gain_db can break the ceiling, and both bits then show;
+ *   - gain = (float)pow(10, g / 20); where the ceiling bound the result (g is still the headroom) and the rounding to f32 went up,
+ *     gain is the next f32 down, so that gain * peak exceeds the ceiling by no rounding of gain's.
+ * +inf for max_true_peak_dbtp and max_gain_db and -inf for min_gain_db mean "none".  A NaN in a target field or in peak_linear,
+ * min_gain_db > max_gain_db, or t == NULL: SS_ERR_INVALID_ARG.  The three outputs are optional.
+ * ss_gain_envelope is the definition of the gain curve ss_batch_apply_gain follows: `pts` holds ONE stream's n points with strictly
+ * ascending frames (the stream field is not read).  With g_k the gains widened to double and f_k the frames:
+ *   - frame <= f_0: g_0;  frame >= f_(n-1): g_(n-1);
+ *   - f_k <= frame < f_(k+1) otherwise: g_k + (double)(frame - f_k) * d_k, d_k = (g_(k+1) - g_k) / (double)(f_(k+1) - f_k),
+ * every operation rounded on its own (no fused multiply-add).  One point is a constant gain, two points a ramp, two points on
+ * adjacent frames a step, points of gain 0 fades.  n == 0 (or pts == NULL) gives 1.
+ *
+ * ss_batch_apply_gain multiplies the resident f32 corpus IN PLACE: sample x of frame n < F_s (the stream's own length,
+ * ss_batch_set_lengths) in a selected channel of a stream that has at least one point becomes
+ *     y = (float)((double)x * ss_gain_envelope(that stream's points, n))
+ * one rounded f64 multiplication and one round-to-nearest conversion; where the envelope is constant that is the plain f32 product
+ * x * g (the product of two f32 values is exact in f64).  THE OPERATION IS LOSSY, one rounding per sample: keep the source if the
+ * gain may have to be taken back.  RESULTS OF EARLIER PASSES, SERIES AND SCANS DESCRIBE THE CORPUS BEFORE THE CALL: run them again
+ * for the corpus behind it.  Streams without a point, unselected channels and frames at or behind F_s stay byte for byte (the latter
+ * are neither read nor written); in a touched stream a frame whose envelope is exactly 1 may or may not be rewritten (its finite
+ * samples are the same either way, a NaN stays a NaN with an unspecified payload).  NaN in gives NaN out, a finite product that
+ * overflows gives +-inf.  Negative gains (polarity), gain 0 and points at or behind F_s are valid.
+ * `points` lists the streams' points grouped by stream (each stream's points together, the streams in any order), frames strictly
+ * ascending within a stream; the list is copied before the call returns, the work is queued on the batch's stream like the other
+ * follow-up calls, and nothing is waited for.  channel_mask 0 means every channel, else bit c selects channel c.
+ * Per (stream, channel) the call leaves one ss_gain_channel, taken over all frames [0, F_s) of the stream as they are behind the
+ * call (unselected channels of a touched stream are measured as they are; untouched streams read touched = 0, zeros and first_over =
+ * UINT64_MAX): n_over counts |y| >= clip_level, infinities included (clip_level = +inf: nothing is over).  Only integer atomics
+ * meet across workgroups (a maximum of the float's bits, additions, a 64-bit minimum), so two calls on the same bytes leave the
+ * same bytes.  ss_batch_download_gain_stats returns the records of the last call, [stream][channel], and waits for the stream.
+ * ss_batch_apply_gain_plan reports tile_frames, the frames one workgroup sweeps: a tile that lies inside one constant stretch of the
+ * envelope takes the f32 form, any other the f64 form.  A batch that never calls any of this allocates and launches exactly what it
+ * did before.
+ * Status codes, all checked before anything is queued: points == NULL with n_points > 0, cfg == NULL, points not grouped by stream,
+ * frames not strictly ascending within a stream, stream >= n_streams, a NaN or infinite gain, a frame >= 2^52, a mask bit at or
+ * above the channel count, a clip_level that is NaN or <= 0, reserved != 0: SS_ERR_INVALID_ARG; ss_batch_download_gain_stats before
+ * the first call: SS_ERR_INVALID_MODE; a `cap` too small: SS_ERR_CAPACITY.  n_points == 0 is valid: it touches nothing and the
+ * records read all untouched.
+ *
+ * ss_batch_download_pcm is the inverse of ss_batch_upload_pcm, in its layout: `count` slots of frames_per_stream * channels samples
+ * from stream `first` on, converted on the device into a staging buffer of the call's own and copied out; it waits.  Frames at or
+ * behind F_s are written as the format's zero (128 for SS_PCM_U8) and not read.  With scale = 128, 32768, 8388608 or 2^31:
+ *     v = x * scale (exact in f32);  with dither v = v + d, one rounded f32 addition;  q = rint(v), halves to even, saturated to
+ *     [-scale, scale - 1];  NaN gives 0, +-inf saturates;  SS_PCM_U8 stores q + 128.
+ * SS_PCM_F32 copies and SS_PCM_F64 widens; dither is ignored for both.  dither == NULL or kind SS_DITHER_NONE: none.
+ * SS_DITHER_TPDF is counter-based, so any sample's value is reproducible on its own; all of it is u32 arithmetic that wraps:
+ *     mix(v):  v ^= v >> 16;  v *= 0x7FEB352D;  v ^= v >> 15;  v *= 0x846CA68B;  v ^= v >> 16
+ *     i = frame * channels + channel (u64);  k = mix(mix(mix(seed_hi ^ stream) ^ seed_lo) ^ i_hi) ^ i_lo
+ *     u1 = mix(k) >> 8;  u2 = mix(k ^ 0x80000000) >> 8;  d = (float)((int32_t)u1 - (int32_t)u2) * 2^-24
+ * (seed_hi, seed_lo, i_hi, i_lo: the upper and lower 32 bits; stream: the absolute stream index).  d is exact, lies in (-1, 1) and
+ * is triangular: +-1 LSB.  Status codes: an unknown format or dither kind, reserved != 0, first + count beyond the batch, pcm ==
+ * NULL with count > 0: SS_ERR_INVALID_ARG; cap_bytes too small: SS_ERR_CAPACITY. */
+enum { SS_GAIN_LIMITED_PEAK = 1, SS_GAIN_LIMITED_MAX = 2, SS_GAIN_LIMITED_MIN = 4, SS_GAIN_UNMEASURED = 8 };
+enum { SS_DITHER_NONE = 0, SS_DITHER_TPDF = 1 };
+typedef struct ss_normalise_target {
+    double target_lufs;           /* e.g. -23 (broadcast), -14 (streaming) */
+    double max_true_peak_dbtp;    /* the ceiling, e.g. -1; +inf: none */
+    double max_gain_db;           /* +inf: no upper clamp */
+    double min_gain_db;           /* -inf: no lower clamp */
+} ss_normalise_target;            /* 32 bytes */
+typedef struct ss_gain_point {
+    uint64_t frame;               /* < 2^52 */
+    uint32_t stream;
+    float    gain;                /* linear, finite; negative flips the polarity */
+} ss_gain_point;                  /* 16 bytes */
+typedef struct ss_gain_config {
+    uint64_t channel_mask;        /* 0: every channel; else bit c selects channel c */
+    float    clip_level;          /* linear, > 0; +inf: nothing is over */
+    uint32_t reserved;            /* 0 */
+} ss_gain_config;                 /* 16 bytes */
+typedef struct ss_gain_channel {
+    float    sample_peak;         /* the largest finite |y| */
+    uint32_t touched;             /* 1: the stream had a point */
+    uint64_t n_over;              /* samples with |y| >= clip_level, infinities included */
+    uint64_t first_over;          /* the lowest such frame; UINT64_MAX if none */
+    uint64_t n_nonfinite;         /* NaN and +-inf */
+} ss_gain_channel;                /* 32 bytes */
+typedef struct ss_pcm_dither {
+    uint64_t seed;
+    uint32_t kind;                /* SS_DITHER_NONE, SS_DITHER_TPDF */
+    uint32_t reserved;            /* 0 */
+} ss_pcm_dither;                  /* 16 bytes */
+int ss_normalisation_gain(const ss_normalise_target *t, double loudness_lufs, double peak_linear, double *gain_db, float *gain,
+                          uint32_t *limited_by);
+double ss_gain_envelope(const ss_gain_point *pts, uint32_t n, uint64_t frame);
+int ss_batch_apply_gain(ss_batch *b, const ss_gain_point *points, uint32_t n_points, const ss_gain_config *cfg);
+int ss_batch_apply_gain_plan(const ss_batch *b, uint32_t *tile_frames);
+/* [stream][channel]; cap_records counts records */
+int ss_batch_download_gain_stats(ss_batch *b, ss_gain_channel *out, size_t cap_records);
+int ss_batch_download_pcm(ss_batch *b, uint32_t first, uint32_t count, void *pcm, size_t cap_bytes, int format, const ss_pcm_dither *dither);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

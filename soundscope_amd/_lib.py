@@ -65,6 +65,8 @@ SYMBOLS = [
     "ss_batch_spectrum_regions_plan", "ss_region_windows",
     "ss_batch_pair_series", "ss_batch_pair_series_plan", "ss_batch_download_pair_series", "ss_batch_pair_regions",
     "ss_batch_download_region_pairs", "ss_batch_download_group_pairs",
+    "ss_normalisation_gain", "ss_gain_envelope", "ss_batch_apply_gain", "ss_batch_apply_gain_plan", "ss_batch_download_gain_stats",
+    "ss_batch_download_pcm",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -79,6 +81,8 @@ SS_BATCH_LOUDNESS_SERIES = 32
 SS_REGION_NO_GROUP = 0xFFFFFFFF
 SS_SIGNAL_SILENCE, SS_SIGNAL_CLIP = 0, 1
 SS_PCM_U8, SS_PCM_S16, SS_PCM_S24, SS_PCM_S32, SS_PCM_F32, SS_PCM_F64 = 1, 2, 3, 4, 5, 6
+SS_GAIN_LIMITED_PEAK, SS_GAIN_LIMITED_MAX, SS_GAIN_LIMITED_MIN, SS_GAIN_UNMEASURED = 1, 2, 4, 8
+SS_DITHER_NONE, SS_DITHER_TPDF = 0, 1
 SS_GAIN_FIXED, SS_GAIN_REFERENCE = 0, 1
 SS_COMM_RCCL, SS_COMM_HOST_TCP = 0, 1
 SS_TP_ARITH_F16X3, SS_TP_ARITH_F32 = 0, 1
@@ -208,6 +212,27 @@ class RegionPair(C.Structure):
 class GroupPair(C.Structure):
     _fields_ = [("s_aa", C.c_double), ("s_bb", C.c_double), ("s_ab", C.c_double)] + [
         (n, C.c_uint64) for n in ("frames", "skipped", "n_active", "n_below", "below_runs")]
+
+
+class NormaliseTarget(C.Structure):        # ss_normalise_target
+    _fields_ = [("target_lufs", C.c_double), ("max_true_peak_dbtp", C.c_double), ("max_gain_db", C.c_double), ("min_gain_db", C.c_double)]
+
+
+class GainPoint(C.Structure):              # ss_gain_point
+    _fields_ = [("frame", C.c_uint64), ("stream", C.c_uint32), ("gain", C.c_float)]
+
+
+class GainConfig(C.Structure):             # ss_gain_config
+    _fields_ = [("channel_mask", C.c_uint64), ("clip_level", C.c_float), ("reserved", C.c_uint32)]
+
+
+class GainChannel(C.Structure):            # ss_gain_channel
+    _fields_ = [("sample_peak", C.c_float), ("touched", C.c_uint32), ("n_over", C.c_uint64), ("first_over", C.c_uint64),
+                ("n_nonfinite", C.c_uint64)]
+
+
+class PcmDither(C.Structure):              # ss_pcm_dither
+    _fields_ = [("seed", C.c_uint64), ("kind", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PairSums(C.Structure):               # ss_pair_sums
@@ -436,6 +461,12 @@ def _bind(lib):
         "ss_batch_pair_regions": (C.c_int, [vp, C.POINTER(LoudnessRegion), C.c_uint32, C.c_uint32, C.POINTER(PairRegionConfig)]),
         "ss_batch_download_region_pairs": (C.c_int, [vp, C.POINTER(RegionPair), C.c_size_t]),
         "ss_batch_download_group_pairs": (C.c_int, [vp, C.POINTER(GroupPair), C.c_size_t]),
+        "ss_normalisation_gain": (C.c_int, [C.POINTER(NormaliseTarget), C.c_double, C.c_double, f64p, f32p, C.POINTER(C.c_uint32)]),
+        "ss_gain_envelope": (C.c_double, [C.POINTER(GainPoint), C.c_uint32, C.c_uint64]),
+        "ss_batch_apply_gain": (C.c_int, [vp, C.POINTER(GainPoint), C.c_uint32, C.POINTER(GainConfig)]),
+        "ss_batch_apply_gain_plan": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "ss_batch_download_gain_stats": (C.c_int, [vp, C.POINTER(GainChannel), C.c_size_t]),
+        "ss_batch_download_pcm": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_int, C.POINTER(PcmDither)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

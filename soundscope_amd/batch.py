@@ -65,6 +65,73 @@ def pair_mono_loss_db(rec):
         return 10.0 * np.log10((aa + 2.0 * ab + bb) / (2.0 * (aa + bb)))
 
 
+# batch gain (ss_gain_point, ss_gain_channel) and what normalise() hands back per stream
+GAIN_POINT_DTYPE = np.dtype([("frame", np.uint64), ("stream", np.uint32), ("gain", np.float32)])
+GAIN_CHANNEL_DTYPE = np.dtype([("sample_peak", np.float32), ("touched", np.uint32), ("n_over", np.uint64), ("first_over", np.uint64),
+                               ("n_nonfinite", np.uint64)])
+NORMALISE_DTYPE = np.dtype([("loudness", np.float64), ("peak", np.float64), ("gain_db", np.float64), ("gain", np.float32),
+                            ("limited_by", np.uint32)])
+_PCM_DTYPES = {L.SS_PCM_U8: np.uint8, L.SS_PCM_S16: np.int16, L.SS_PCM_S24: np.uint8, L.SS_PCM_S32: np.int32,
+               L.SS_PCM_F32: np.float32, L.SS_PCM_F64: np.float64}
+
+
+def _gain_points(points):
+    """A point list as a contiguous GAIN_POINT_DTYPE array: such an array as it is, else rows (stream, frame, gain)."""
+    if isinstance(points, np.ndarray) and points.dtype == GAIN_POINT_DTYPE:
+        return np.ascontiguousarray(points).reshape(-1)
+    out = np.zeros(len(points), GAIN_POINT_DTYPE)
+    for i, (stream, frame, gain) in enumerate(points):
+        out[i] = (frame, stream, gain)
+    return out
+
+
+def gain_envelope(points, frames):
+    """ss_gain_envelope of ONE stream's points (frames strictly ascending) at every frame of `frames`, as f64: g_0 at or before the
+    first point, g_last at or behind the last, g_k + (frame - f_k) * d_k for f_k <= frame < f_(k+1) with d_k = (g_(k+1) - g_k) /
+    (f_(k+1) - f_k) — numpy rounds every operation on its own, as the library does.  No point: 1."""
+    p, n = _gain_points(points), np.asarray(frames, dtype=np.uint64)
+    if p.size == 0:
+        return np.ones(n.shape, np.float64)
+    f, g = p["frame"], p["gain"].astype(np.float64)
+    out = np.full(n.shape, g[0], np.float64)
+    if f.size > 1:
+        k = np.clip(np.searchsorted(f, n, side="right").astype(np.int64) - 1, 0, f.size - 2)      # f_k <= frame < f_(k+1) where it counts
+        d = (g[1:] - g[:-1]) / (f[1:] - f[:-1]).astype(np.float64)
+        ramp = g[k] + (n - f[k]).astype(np.float64) * d[k]      # (frames in front of f_0 wrap here and are replaced below)
+        out = np.where(n <= f[0], g[0], np.where(n >= f[-1], g[-1], ramp))
+    return out
+
+
+def normalisation_gain(loudness_lufs, peak_linear, target_lufs, max_true_peak_dbtp=np.inf, max_gain_db=np.inf, min_gain_db=-np.inf):
+    """ss_normalisation_gain over arrays: (gain_db f64, gain f32, limited_by u32) for every (loudness, linear peak).  The law: an
+    unmeasured loudness (NaN, +-inf) gives 0 dB and SS_GAIN_UNMEASURED; else target - loudness, cut to the headroom under the
+    ceiling (finite ceiling, finite peak > 0), then clamped to [min_gain_db, max_gain_db]; gain = (f32)10^(dB / 20), one f32 down
+    where the ceiling bound and the rounding went up."""
+    lu, pk = np.broadcast_arrays(np.asarray(loudness_lufs, np.float64), np.asarray(peak_linear, np.float64))
+    t, ceiling, g_max, g_min = float(target_lufs), float(max_true_peak_dbtp), float(max_gain_db), float(min_gain_db)
+    if any(np.isnan(v) for v in (t, ceiling, g_max, g_min)) or np.isnan(pk).any() or g_min > g_max:
+        raise ValueError("normalisation target: NaN, or min_gain_db above max_gain_db")
+    measured = np.isfinite(lu)
+    with np.errstate(all="ignore"):
+        g = t - lu
+        capped = np.isfinite(ceiling) & np.isfinite(pk) & (pk > 0)
+        headroom = ceiling - 20.0 * np.log10(np.where(capped, pk, 1.0))
+        by_peak = measured & capped & (g > headroom)
+        g = np.where(by_peak, headroom, g)
+        by_max = measured & (g > g_max)
+        g = np.where(by_max, g_max, g)
+        by_min = measured & (g < g_min)
+        g = np.where(by_min, g_min, g)
+        g = np.where(measured, g, 0.0)
+        exact = np.power(10.0, g / 20.0)
+        lin = exact.astype(np.float32)
+        down = by_peak & (g == headroom) & (lin.astype(np.float64) > exact)
+        lin = np.where(down, np.nextafter(lin, np.float32(-np.inf)), lin).astype(np.float32)
+    why = (by_peak * L.SS_GAIN_LIMITED_PEAK + by_max * L.SS_GAIN_LIMITED_MAX + by_min * L.SS_GAIN_LIMITED_MIN +
+           ~measured * L.SS_GAIN_UNMEASURED).astype(np.uint32)
+    return g, lin, why
+
+
 class Batch:
     def __init__(self, sample_rate=48000, channels=2, n_streams=1, frames_per_stream=480000,
                  fft_n=4096, hop_frames=1024, flags=L.SS_BATCH_ALL, true_peak_factor=0,
@@ -122,6 +189,7 @@ class Batch:
 
     def run(self):
         _check(L.lib().ss_batch_run(self._h))
+        self._ran = True
 
     def sync(self):
         _check(L.lib().ss_batch_sync(self._h))
@@ -575,6 +643,68 @@ class Batch:
     def group_pairs(self):
         """Per group of the last pair list: a structured array [groups][pairs] of GROUP_PAIR_DTYPE."""
         return self._pair_records(1, GROUP_PAIR_DTYPE, L.GroupPair, L.lib().ss_batch_download_group_pairs)
+
+    # -- batch gain and PCM export: a gain curve per stream applied to the resident corpus, and the corpus in a delivery format
+    def apply_gain(self, points, channel_mask=0, clip_level=1.0):
+        """Queue the sweep that multiplies the resident corpus in place by every stream's gain curve (gain_envelope): `points` is a
+        GAIN_POINT_DTYPE array or rows (stream, frame, gain), grouped by stream, frames strictly ascending.  channel_mask 0: every
+        channel, else bit c selects channel c.  Lossy (one rounding per sample); results of earlier passes and series describe the
+        corpus before the call."""
+        p = _gain_points(points)
+        cfg = L.GainConfig(int(channel_mask), float(clip_level), 0)
+        _check(L.lib().ss_batch_apply_gain(self._h, p.ctypes.data_as(C.POINTER(L.GainPoint)) if p.size else None, p.size, C.byref(cfg)))
+
+    def apply_gain_plan(self):
+        """tile_frames: the frames one workgroup of the sweep covers."""
+        t = C.c_uint32()
+        _check(L.lib().ss_batch_apply_gain_plan(self._h, C.byref(t)))
+        return t.value
+
+    def gain_stats(self):
+        """What the last apply_gain() left, a structured array [n_streams][channels] of GAIN_CHANNEL_DTYPE over every stream's own
+        frames: the largest finite |y|, the samples at or over clip_level and the first such frame, the non-finite samples."""
+        out = np.zeros((int(self.cfg.n_streams), int(self.cfg.channels)), GAIN_CHANNEL_DTYPE)
+        _check(L.lib().ss_batch_download_gain_stats(self._h, out.ctypes.data_as(C.POINTER(L.GainChannel)), out.size))
+        return out
+
+    def download_pcm(self, first, count, format, dither_seed=None):
+        """`count` slots from stream `first` on in a delivery format (L.SS_PCM_*), [count][frames_per_stream][channels] (24-bit: a
+        last axis of the three little-endian bytes); frames behind a stream's own length read the format's zero.  dither_seed: TPDF
+        dither of +-1 LSB from that seed on the integer formats."""
+        shape = (int(count), int(self.cfg.frames_per_stream), int(self.cfg.channels)) + ((3,) if format == L.SS_PCM_S24 else ())
+        out = np.empty(shape, _PCM_DTYPES.get(format, np.uint8))
+        dither = None if dither_seed is None else C.byref(L.PcmDither(int(dither_seed) & 0xFFFFFFFFFFFFFFFF, L.SS_DITHER_TPDF, 0))
+        _check(L.lib().ss_batch_download_pcm(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p), out.nbytes, int(format), dither))
+        return out
+
+    def normalise(self, target_lufs, max_true_peak_dbtp=float("inf"), max_gain_db=float("inf"), min_gain_db=float("-inf"), album=False):
+        """Bring every stream to `target_lufs` under a true-peak ceiling (normalisation_gain) and apply the gains on the device, one
+        constant gain per stream; album: ONE gain for all streams, from the loudness and the peak of all of them pooled.  Needs
+        L.SS_BATCH_LUFS; runs a pass if none has run, then peak_series(), and replaces the peak (album: and loudness) region list.
+        Returns a NORMALISE_DTYPE array [n_streams]: the loudness and linear peak read, gain_db, gain, limited_by."""
+        if not int(self.cfg.flags) & L.SS_BATCH_LUFS:
+            raise ValueError("normalise needs a batch with SS_BATCH_LUFS")
+        n, S = int(self.cfg.n_streams), (int(self.cfg.sample_rate) + 5) // 10
+        if not getattr(self, "_ran", False):
+            self.run()
+        self.peak_series()
+        shapes = [self.stream_shape(s) for s in range(n)]
+        whole = [(s, 0, (int(sh.frames) + S - 1) // S, 0) for s, sh in enumerate(shapes)]          # every entry, the tail's included
+        out = np.zeros(n, NORMALISE_DTYPE)
+        if album:
+            self.loudness_regions([(s, 0, int(sh.n_subblocks), 0) for s, sh in enumerate(shapes)], 1)
+            self.peak_regions(whole, 1)
+            out["loudness"], out["peak"] = self.group_results()[0].integrated_lufs, self.group_peaks()[0].true_peak
+        else:
+            self.peak_regions(whole, 1)
+            out["loudness"] = [r.integrated_lufs for r in self.results()]
+            out["peak"] = [r.true_peak for r in self.region_peaks()]
+        out["gain_db"], out["gain"], out["limited_by"] = normalisation_gain(out["loudness"], out["peak"], target_lufs, max_true_peak_dbtp,
+                                                                            max_gain_db, min_gain_db)
+        points = np.zeros(n, GAIN_POINT_DTYPE)
+        points["stream"], points["gain"] = np.arange(n), out["gain"]
+        self.apply_gain(points)
+        return out
 
     def histograms(self):
         out = np.empty(2000, np.uint64)

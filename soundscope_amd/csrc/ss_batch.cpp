@@ -178,6 +178,15 @@ struct Pairs {
     DevBuf<ssk::GroupPair> group_results;               // [group][list_pairs] records (ss_group_pair)
 };
 
+// apply gain (ss_batch_apply_gain): all of it allocated at the batch's first call and grown by a longer point list, so a batch that
+// never asks holds none of it.  One table per call goes through the stage in one upload: the records [stream][channels] as an
+// untouched batch reads them (the kernel adds to them), then the touched streams, then their segments.
+struct Gain {
+    bool done = false;                          // queued at least once: there is something to download
+    HostStage stage;
+    DevBuf<unsigned char> table;
+};
+
 // spectrogram (ss_batch_spectrogram): all of it allocated at the batch's first call and grown by a larger view, so a batch that
 // never asks holds none of it
 struct Spectrogram {
@@ -236,6 +245,7 @@ struct ss_batch {
     SpectrumRegions spec_regions;
     SignalScan scan;
     Pairs pair;
+    Gain gain;
     Spectrogram spectrogram;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
@@ -1968,6 +1978,182 @@ int ss_batch_download_group_pairs(ss_batch *b, ss_group_pair *out, size_t cap_re
     if (!b) return SS_ERR_INVALID_ARG;
     const Pairs &pr = b->pair;
     return fetch_records(b, pr.list.done, out, cap_records > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap_records, pr.list.n_groups * pr.list_pairs, pr.group_results.p);
+}
+
+// ---- batch gain and PCM export: the gain law and the gain curve (host arithmetic), the sweep, the delivery formats ------------------
+static_assert(sizeof(ss_normalise_target) == 32 && sizeof(ss_gain_point) == 16 && offsetof(ss_gain_point, stream) == 8 && offsetof(ss_gain_point, gain) == 12 &&
+              sizeof(ss_gain_config) == 16 && offsetof(ss_gain_config, clip_level) == 8 && sizeof(ss_pcm_dither) == 16, "gain call layouts");
+static_assert(sizeof(ss_gain_channel) == 32 && sizeof(ssk::GainChannel) == 32 && offsetof(ss_gain_channel, touched) == offsetof(ssk::GainChannel, touched) &&
+              offsetof(ss_gain_channel, n_over) == offsetof(ssk::GainChannel, n_over) && offsetof(ss_gain_channel, first_over) == offsetof(ssk::GainChannel, first_over) &&
+              offsetof(ss_gain_channel, n_nonfinite) == offsetof(ssk::GainChannel, n_nonfinite), "gain channel layout");
+
+int ss_normalisation_gain(const ss_normalise_target *t, double loudness_lufs, double peak_linear, double *gain_db, float *gain, uint32_t *limited_by)
+{
+    if (!t || std::isnan(t->target_lufs) || std::isnan(t->max_true_peak_dbtp) || std::isnan(t->max_gain_db) || std::isnan(t->min_gain_db) ||
+        std::isnan(peak_linear) || t->min_gain_db > t->max_gain_db)
+        return SS_ERR_INVALID_ARG;
+    double g = 0.0;
+    float lin = 1.0f;
+    uint32_t why = 0;
+    if (!std::isfinite(loudness_lufs)) {
+        why = SS_GAIN_UNMEASURED;
+    } else {
+        g = t->target_lufs - loudness_lufs;
+        double headroom = 0.0;
+        if (std::isfinite(t->max_true_peak_dbtp) && std::isfinite(peak_linear) && peak_linear > 0.0) {
+            headroom = t->max_true_peak_dbtp - 20.0 * std::log10(peak_linear);
+            if (g > headroom) { g = headroom; why |= SS_GAIN_LIMITED_PEAK; }
+        }
+        if (g > t->max_gain_db) { g = t->max_gain_db; why |= SS_GAIN_LIMITED_MAX; }
+        if (g < t->min_gain_db) { g = t->min_gain_db; why |= SS_GAIN_LIMITED_MIN; }
+        const double exact = std::pow(10.0, g / 20.0);
+        lin = (float)exact;
+        // the ceiling bound the result: the rounding of the gain must not carry it above
+        if ((why & SS_GAIN_LIMITED_PEAK) && g == headroom && (double)lin > exact) lin = std::nextafterf(lin, -INFINITY);
+    }
+    if (gain_db) *gain_db = g;
+    if (gain) *gain = lin;
+    if (limited_by) *limited_by = why;
+    return SS_OK;
+}
+
+double ss_gain_envelope(const ss_gain_point *pts, uint32_t n, uint64_t frame)
+{
+    if (!pts || !n) return 1.0;
+    if (frame <= pts[0].frame) return (double)pts[0].gain;
+    if (frame >= pts[n - 1].frame) return (double)pts[n - 1].gain;
+    uint32_t lo = 0, hi = n - 1;                                // pts[lo].frame <= frame < pts[hi].frame
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (pts[mid].frame <= frame) lo = mid; else hi = mid;
+    }
+    const double g0 = (double)pts[lo].gain, g1 = (double)pts[lo + 1].gain;
+    const double d = (g1 - g0) / (double)(pts[lo + 1].frame - pts[lo].frame);
+    {
+#pragma clang fp contract(off)                                  // the product is rounded on its own
+        const double step = (double)(frame - pts[lo].frame) * d;
+        return g0 + step;
+    }
+}
+
+// One stream's points as the segments k_apply_gain reads (ssk::GainSegment): what ss_gain_envelope gives, frame for frame.
+//  * [0, f_0]: the constant g_0 (a lone point: the whole stream);
+//  * point k to point k + 1: the ramp from f_k — from f_0 + 1 for k = 0, frame f_0 being the first segment's — which is empty where
+//    f_1 = f_0 + 1; a ramp between equal gains has d = +0 and every value of it is g_k + 0 (which makes +0 of a gain of -0), a constant;
+//  * from the last point on: the constant g_last.
+static void gain_segments(const ss_gain_point *pts, uint32_t n, std::vector<ssk::GainSegment> *out)
+{
+    out->push_back({0ull, ssk::kGainConst, (double)pts[0].gain, 0.0});
+    for (uint32_t k = 0; k + 1 < n; k++) {
+        const uint64_t start = k ? pts[k].frame : pts[0].frame + 1;
+        if (start >= pts[k + 1].frame) continue;
+        const double g0 = (double)pts[k].gain, g1 = (double)pts[k + 1].gain;
+        const double d = (g1 - g0) / (double)(pts[k + 1].frame - pts[k].frame);
+        if (d == 0.0) out->push_back({start, ssk::kGainConst, g0 + 0.0, 0.0});
+        else out->push_back({start, pts[k].frame, g0, d});
+    }
+    if (n > 1) out->push_back({pts[n - 1].frame, ssk::kGainConst, (double)pts[n - 1].gain, 0.0});
+}
+
+int ss_batch_apply_gain_plan(const ss_batch *b, uint32_t *tile_frames)
+{
+    if (!b) return SS_ERR_INVALID_ARG;
+    if (tile_frames) *tile_frames = ssk::kGainTileFrames;
+    return SS_OK;
+}
+
+int ss_batch_apply_gain(ss_batch *b, const ss_gain_point *points, uint32_t n_points, const ss_gain_config *cfg)
+{
+    SS_ON_DEVICE(b);
+    if (!b || !cfg || (!points && n_points)) return SS_ERR_INVALID_ARG;
+    const ss_batch_config &c = b->cfg;
+    const uint32_t C = c.channels;
+    if (!(cfg->clip_level > 0.0f) || cfg->reserved) return SS_ERR_INVALID_ARG;          // (NaN fails the comparison)
+    if (C < 64u && (cfg->channel_mask >> C)) return SS_ERR_INVALID_ARG;
+    // the streams' runs of points: grouped by stream, frames strictly ascending
+    std::vector<ssk::GainStream> touched;
+    std::vector<ssk::GainSegment> segments;
+    {
+        std::vector<bool> seen(c.n_streams, false);
+        for (uint32_t i = 0; i < n_points;) {
+            const uint32_t s = points[i].stream;
+            if (s >= c.n_streams || seen[s]) return SS_ERR_INVALID_ARG;
+            seen[s] = true;
+            uint32_t j = i;
+            for (; j < n_points && points[j].stream == s; j++) {
+                if (!std::isfinite(points[j].gain) || points[j].frame >= (1ull << 52)) return SS_ERR_INVALID_ARG;
+                if (j > i && points[j].frame <= points[j - 1].frame) return SS_ERR_INVALID_ARG;
+            }
+            const uint32_t at = (uint32_t)segments.size();
+            gain_segments(points + i, j - i, &segments);
+            touched.push_back({s, at, (uint32_t)segments.size() - at, 0u});
+            i = j;
+        }
+    }
+    const uint64_t tiles_cap = (c.frames_per_stream + ssk::kGainTileFrames - 1) / ssk::kGainTileFrames;
+    const uint64_t records = (uint64_t)c.n_streams * C;
+    if (touched.size() * tiles_cap > 0x7FFFFFFFull || records > 0xFFFFFFFFull) return SS_ERR_UNSUPPORTED;
+    // the table: records | touched | segments
+    const size_t touched_at = (size_t)records * sizeof(ssk::GainChannel), seg_at = touched_at + touched.size() * sizeof(ssk::GainStream);
+    const size_t bytes = seg_at + segments.size() * sizeof(ssk::GainSegment);
+    Gain &gn = b->gain;
+    HIPCHK(gn.table.ensure(bytes));             // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
+    HIPCHK(gn.stage.take(bytes));
+    unsigned char *h = gn.stage.buf.p;
+    {
+        ssk::GainChannel *rec = reinterpret_cast<ssk::GainChannel *>(h);
+        for (uint64_t i = 0; i < records; i++) rec[i] = {0u, 0u, 0ull, ~0ull, 0ull};
+        for (const ssk::GainStream &t : touched)
+            for (uint32_t ch = 0; ch < C; ch++) rec[(size_t)t.stream * C + ch].touched = 1u;
+        if (!touched.empty()) std::memcpy(h + touched_at, touched.data(), touched.size() * sizeof(ssk::GainStream));
+        if (!segments.empty()) std::memcpy(h + seg_at, segments.data(), segments.size() * sizeof(ssk::GainSegment));
+    }
+    HIPCHK(gn.stage.queue(gn.table.p, bytes, b->stream));
+    ssk::ApplyGainParams p{};
+    p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * C; p.n_frames = c.frames_per_stream;
+    p.frames_of = b->ragged_ptr(b->ragged.frames_d);
+    p.stats = reinterpret_cast<ssk::GainChannel *>(gn.table.p);
+    p.touched = reinterpret_cast<const ssk::GainStream *>(gn.table.p + touched_at);
+    p.segments = reinterpret_cast<const ssk::GainSegment *>(gn.table.p + seg_at);
+    p.channel_mask = cfg->channel_mask ? cfg->channel_mask : (C < 64u ? (1ull << C) - 1ull : ~0ull);
+    p.n_touched = (uint32_t)touched.size(); p.channels = C; p.tiles_cap = (uint32_t)tiles_cap;
+    uint32_t clip_bits;
+    std::memcpy(&clip_bits, &cfg->clip_level, sizeof clip_bits);
+    p.clip_bits = std::isinf(cfg->clip_level) ? 0x7F800001u : clip_bits;
+    p.stereo = C == 2u && p.channel_mask == 3ull ? 1u : 0u;
+    HIPCHK(ssk::launch_apply_gain(p, b->stream));
+    gn.done = true;
+    return SS_OK;
+}
+
+int ss_batch_download_gain_stats(ss_batch *b, ss_gain_channel *out, size_t cap_records)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const Gain &gn = b->gain;
+    return fetch_records(b, gn.done, out, cap_records > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap_records, b->cfg.n_streams * b->cfg.channels,
+                         reinterpret_cast<const ssk::GainChannel *>(gn.table.p));
+}
+
+int ss_batch_download_pcm(ss_batch *b, uint32_t first, uint32_t count, void *pcm, size_t cap_bytes, int format, const ss_pcm_dither *dither)
+{
+    SS_ON_DEVICE(b);
+    const size_t sb = ss_pcm_sample_bytes(format);
+    if (!b || !sb) return SS_ERR_INVALID_ARG;
+    if (dither && (dither->kind > (uint32_t)SS_DITHER_TPDF || dither->reserved)) return SS_ERR_INVALID_ARG;
+    if ((uint64_t)first + count > b->cfg.n_streams || (!pcm && count)) return SS_ERR_INVALID_ARG;
+    const size_t per = b->samples_per_stream(), n = per * count;
+    if (cap_bytes < n * sb) return SS_ERR_CAPACITY;
+    if (!n) return ss_batch_sync(b);
+    // The staging is this call's own, freed behind its wait (ss_batch_upload_pcm's rule); a lane stores four samples as whole words.
+    DevBuf<unsigned char> raw;
+    HIPCHK(raw.alloc(((n + 3) & ~(size_t)3) * sb));
+    ssk::PcmOutParams p{};
+    p.pcm = b->pcm.p; p.per_stream = per; p.n_frames = b->cfg.frames_per_stream; p.frames_of = b->ragged_ptr(b->ragged.frames_d);
+    p.n_samples = n; p.out = raw.p; p.first = first; p.channels = b->cfg.channels; p.format = format;
+    p.tpdf = dither && dither->kind == SS_DITHER_TPDF ? 1u : 0u; p.seed = dither ? dither->seed : 0ull;
+    HIPCHK(ssk::launch_f32_to_pcm(p, b->stream));
+    return fetch(b, static_cast<unsigned char *>(pcm), static_cast<const unsigned char *>(raw.p), n * sb);
 }
 
 int ss_batch_render_waveform(ss_batch *b, uint32_t cols, uint32_t x_min, uint32_t x_max)

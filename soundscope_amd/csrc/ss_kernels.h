@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_pair_series.hip, ss_bank_signal_watch.hip, ss_bank_pair_watch.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_pair_series.hip, ss_apply_gain.hip, ss_bank_signal_watch.hip, ss_bank_pair_watch.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -496,6 +496,48 @@ struct RegionPairsParams {
 };
 // reduces every (region, pair) (k_region_pairs), then every (group, pair) over the regions' records (k_group_pairs)
 hipError_t launch_region_pairs(const RegionPairsParams &p, hipStream_t s);
+// Apply gain (ss_batch_apply_gain; ss_apply_gain.hip): the resident corpus times a gain curve per stream, in place, and per (stream,
+// channel) what the result holds.  The host resolves the caller's points into a segment table per touched stream: segment j covers
+// the frames [start_j, start_(j+1)) (the last one to the stream's end), and its value at frame n is
+//     base == kGainConst:  g            else:  g + (double)(n - base) * d      (ss_gain_envelope, each operation rounded on its own)
+// The first segment of a stream starts at frame 0.  The records are laid out as ss_gain_channel.
+constexpr uint32_t kGainTileFrames = 4096;                       // frames one workgroup sweeps
+constexpr unsigned long long kGainConst = ~0ull;
+struct GainSegment { unsigned long long start, base; double g, d; };
+struct GainStream { uint32_t stream, seg_first, n_seg, reserved; };       // a touched stream: its segments [seg_first, seg_first + n_seg)
+struct GainChannel { uint32_t peak_bits, touched; unsigned long long n_over, first_over, n_nonfinite; };
+static_assert(sizeof(GainSegment) == 32 && sizeof(GainStream) == 16 && sizeof(GainChannel) == 32 && offsetof(GainChannel, n_over) == 8 &&
+              offsetof(GainChannel, first_over) == 16 && offsetof(GainChannel, n_nonfinite) == 24, "gain record layouts");
+struct ApplyGainParams {
+    float *pcm;                      // [stream][frame][channels] f32, 16-byte aligned; read and written
+    uint64_t stream_stride;          // floats between streams
+    uint64_t n_frames;               // frames of a slot
+    const uint64_t *frames_of;       // ragged batches: each stream's own frames (nullable = n_frames for all)
+    const GainStream *touched;       // [n_touched]
+    const GainSegment *segments;
+    GainChannel *stats;              // [stream][channels], initialised by the caller (zeros, first_over = ~0)
+    uint64_t channel_mask;           // bit c: channel c is multiplied (the caller has resolved 0 to all channels)
+    uint32_t n_touched, channels, tiles_cap;      // tiles_cap = ceil(n_frames / kGainTileFrames)
+    uint32_t clip_bits;              // the bits of clip_level; 0x7F800001 (above every |y| that is no NaN) for +inf
+    uint32_t stereo;                 // two channels, both selected, an even stream_stride: the form with 16-byte accesses
+};
+// one workgroup per (touched stream, tile); untouched streams cost nothing
+hipError_t launch_apply_gain(const ApplyGainParams &p, hipStream_t s);
+// f32 corpus -> delivery PCM (ss_batch_download_pcm): samples [0, n_samples) of the slots from `first` on become `format` at out,
+// frames at or behind a stream's own length the format's zero.  out holds n_samples rounded up to a multiple of 4 samples.
+struct PcmOutParams {
+    const float *pcm;                // the batch's input, stream 0
+    uint64_t per_stream;             // samples of a slot (frames_per_stream * channels)
+    uint64_t n_frames;
+    const uint64_t *frames_of;       // nullable
+    uint64_t n_samples;              // count * per_stream
+    unsigned char *out;
+    uint64_t seed;
+    uint32_t first, channels;
+    int format;                      // ss_pcm_format
+    uint32_t tpdf;                   // 1: SS_DITHER_TPDF on the integer formats
+};
+hipError_t launch_f32_to_pcm(const PcmOutParams &p, hipStream_t s);
 // gate + LRA on explicit histograms (corpus gate after the all-reduce; handle getters)
 // `peaks` (optional): a handle's readings in one launch (ReadingsExtra above)
 hipError_t launch_hist_eval(const uint64_t *hist2000, const double *energies, const double *bounds,
