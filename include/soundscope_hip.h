@@ -164,6 +164,23 @@ int ss_analyzer_set_true_peak_arith(ss_analyzer *h, int arith);
  * between add_frames calls — sub-normal values flushed to zero at the end of every internal filter call like the crate
  * does.  Waits for the handle's stream. */
 int ss_inspect_filter_state(ss_analyzer *h, uint32_t channel, double v4[4]);
+/* inspection (tests): how ONE streaming call of `frames` frames to a meter of this shape is launched — the handle's ss_add_samples,
+ * a session tick's loudness call, every stream of a meter bank's add.  Host arithmetic only: no device is touched, and the
+ * answer comes from the functions the launch itself calls.  A call longer than piece_frames is cut into calls of piece_frames
+ * first; the tiles of every form lie on the stream's absolute grid (multiples of tile_frames inside every 100 ms sub-block,
+ * counted from the meter's last reset), not on the call. */
+enum { SS_TD_FORM_ONE_WAVE = 0, SS_TD_FORM_SHARED = 1 };
+typedef struct ss_streaming_plan {
+    uint32_t form;             /* SS_TD_FORM_ONE_WAVE: one wave walks the call; SS_TD_FORM_SHARED: the waves of a workgroup share its tiles */
+    uint32_t waves;            /* 1; shared: 8, or 4 where eight LDS slices do not fit                */
+    uint32_t tile_frames;      /* frames of one tile of that form                                      */
+    uint32_t chunk_frames;     /* frames one lane filters sequentially in a tile of that form         */
+    uint32_t true_peak_factor; /* resolved: 4, 2 or 0 (off)                                            */
+    uint32_t subblock_frames;  /* (rate + 5) / 10                                                      */
+    uint64_t piece_frames;     /* 32 sub-blocks                                                        */
+} ss_streaming_plan;           /* 32 bytes */
+/* true_peak_factor: 0 = ebur128's rule for the rate, or 2 / 4.  SS_ERR_NOMEM for a shape no meter takes, SS_ERR_INVALID_ARG. */
+int ss_td_streaming_plan(uint32_t channels, uint32_t rate, int32_t true_peak_factor, uint64_t frames, ss_streaming_plan *out);
 
 /* ------------------------------------------------------------------------ *
  *  PCM ingest: the step before the path.  The reference decodes a
@@ -1393,6 +1410,9 @@ int ss_session_tick_capture_resident(ss_session *s, double *mid_xy, double *side
 /* lufs = [-100.; 300]; analyzer.reset() */
 int ss_session_restart(ss_session *s);
 int ss_session_lufs_history(ss_session *s, double *out300);
+/* inspection (tests): whether the last tick's spectrum (*spectrum_fused) and its short-term reading (*shortterm_fused) rode the
+ * launch of its loudness call (one launch for the tick); 0 and 0 before the first tick and after a tick without a loudness call */
+int ss_session_last_tick_forms(const ss_session *s, int32_t *spectrum_fused, int32_t *shortterm_fused);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,7 @@ SYMBOLS = [
     "ss_batch_download_region_pairs", "ss_batch_download_group_pairs",
     "ss_normalisation_gain", "ss_gain_envelope", "ss_batch_apply_gain", "ss_batch_apply_gain_plan", "ss_batch_download_gain_stats",
     "ss_batch_download_pcm",
+    "ss_td_streaming_plan", "ss_session_last_tick_forms",
 ]
 
 SS_ABI_VERSION = 2          # include/soundscope_hip.h; checked at load
@@ -87,6 +88,7 @@ SS_GAIN_FIXED, SS_GAIN_REFERENCE = 0, 1
 SS_COMM_RCCL, SS_COMM_HOST_TCP = 0, 1
 SS_TP_ARITH_F16X3, SS_TP_ARITH_F32 = 0, 1
 SS_TD_AUTO, SS_TD_RUN_IN, SS_TD_WHOLE_STREAMS = 0, 1, 2
+SS_TD_FORM_ONE_WAVE, SS_TD_FORM_SHARED = 0, 1
 SS_KERNEL_FFT, SS_KERNEL_TIME_DOMAIN, SS_KERNEL_FINALIZE, SS_KERNEL_WAVEFORM, SS_KERNEL_COUNT = 0, 1, 2, 3, 4
 
 
@@ -262,6 +264,14 @@ class MeterReading(C.Structure):
 
 class SpectrumBallistics(C.Structure):
     _fields_ = [("average_tau_s", C.c_double), ("hold_s", C.c_double), ("decay_db_per_s", C.c_double)]
+
+
+class StreamingPlan(C.Structure):           # ss_streaming_plan
+    _fields_ = [(n, C.c_uint32) for n in ("form", "waves", "tile_frames", "chunk_frames", "true_peak_factor", "subblock_frames")] + [
+        ("piece_frames", C.c_uint64)]
+
+
+assert C.sizeof(StreamingPlan) == 32 and StreamingPlan.piece_frames.offset == 24
 
 
 class BatchLayout(C.Structure):
@@ -467,6 +477,8 @@ def _bind(lib):
         "ss_batch_apply_gain_plan": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "ss_batch_download_gain_stats": (C.c_int, [vp, C.POINTER(GainChannel), C.c_size_t]),
         "ss_batch_download_pcm": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_int, C.POINTER(PcmDither)]),
+        "ss_td_streaming_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint64, C.POINTER(StreamingPlan)]),
+        "ss_session_last_tick_forms": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

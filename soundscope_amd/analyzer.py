@@ -51,6 +51,14 @@ def get_mid_and_side_samples(samples):
     return mid, side
 
 
+def streaming_plan(channels: int, rate: int, frames: int, true_peak_factor: int = 0):
+    """How one streaming call of `frames` frames to a meter of this shape is launched (ss_td_streaming_plan; host arithmetic, no
+    device): an ss_streaming_plan with form, waves, tile_frames, chunk_frames, true_peak_factor, subblock_frames, piece_frames."""
+    out = L.StreamingPlan()
+    _check(L.lib().ss_td_streaming_plan(channels, rate, true_peak_factor, frames, C.byref(out)))
+    return out
+
+
 class Analyzer:
     """`pub struct Analyzer` — default is 2 channels at 44 100 Hz (analyzer.rs:34-45)."""
 

@@ -376,7 +376,7 @@ int ssh::add_samples_impl(ss_analyzer *h, const float *samples, size_t n, bool o
     const uint64_t S = m.s100;
     // pieces of at most 32 sub-blocks so the sub-block ring (96) always holds the
     // 30-block history a short-term block needs
-    const uint64_t piece_frames = 32 * S;
+    const uint64_t piece_frames = MeterStore::piece_frames_for(S);
     uint64_t frames = n / C, done = 0;
     h->change_count++;                                  // (whatever happens below: cached readings are of the past)
     // a tick-sized host buffer goes through an input stage, and the call returns behind its launches (the stage's event tells its
@@ -596,6 +596,24 @@ int ss_inspect_filter_state(ss_analyzer *h, uint32_t channel, double v4[4])
     }
     HIPCHK(hipMemcpyAsync(v4, &h->meter.state.p->v[channel][0], 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return SS_OK;
+}
+
+// host arithmetic only (no SS_ON_DEVICE, no require_device): the rules of MeterStore::build, add_samples_impl and the launch
+static_assert(sizeof(ss_streaming_plan) == 32 && offsetof(ss_streaming_plan, subblock_frames) == 20 && offsetof(ss_streaming_plan, piece_frames) == 24,
+              "ss_streaming_plan layout");
+int ss_td_streaming_plan(uint32_t channels, uint32_t rate, int32_t true_peak_factor, uint64_t frames, ss_streaming_plan *out)
+{
+    if (!out || (true_peak_factor != 0 && true_peak_factor != 2 && true_peak_factor != 4)) return SS_ERR_INVALID_ARG;
+    const int rc = meter_args_ok(channels, rate);
+    if (rc) return rc;
+    const uint32_t S = (rate + 5) / 10;
+    const uint64_t piece = MeterStore::piece_frames_for(S);
+    const ssk::TdRingPlan rp = ssk::td_ring_plan(channels, S, frames < piece ? frames : piece);
+    out->form = rp.shared ? SS_TD_FORM_SHARED : SS_TD_FORM_ONE_WAVE;
+    out->waves = rp.waves; out->tile_frames = rp.tile_frames; out->chunk_frames = rp.chunk_frames;
+    out->true_peak_factor = (uint32_t)MeterStore::true_peak_factor_for(rate, true_peak_factor);
+    out->subblock_frames = S; out->piece_frames = piece;
     return SS_OK;
 }
 

@@ -270,11 +270,13 @@ uint64_t MeterStore::ring_frames_for(uint32_t rate)
     return frames % s ? frames + s - frames % s : frames;
 }
 
+int MeterStore::true_peak_factor_for(uint32_t rate, int tp_cfg) { return tp_cfg ? tp_cfg : sst::true_peak_factor_for_rate(rate); }
+
 int MeterStore::build(uint32_t n_streams, uint32_t channels_, uint32_t rate_, int tp_cfg)
 {
     int rc = meter_args_ok(channels_, rate_);
     if (rc) return rc;
-    const int factor = tp_cfg ? tp_cfg : sst::true_peak_factor_for_rate(rate_);
+    const int factor = true_peak_factor_for(rate_, tp_cfg);
     rc = get_td_tables(rate_, factor, channels_, &td);
     if (rc) return rc;
     rc = get_hist_tables(&hist_energies, &hist_bounds);

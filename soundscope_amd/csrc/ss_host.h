@@ -281,6 +281,10 @@ struct SS_HIDDEN MeterStore {
     DevBuf<uint32_t> counts;             // [n][2]
 
     static uint64_t ring_frames_for(uint32_t rate);
+    // a call is cut into pieces of at most 32 sub-blocks (the 96-slot sub-block ring then always holds a short-term block's thirty)
+    static uint64_t piece_frames_for(uint64_t s100) { return 32 * s100; }
+    // the effective true-peak factor of a meter (tp_cfg 0: the crate's rule for the rate)
+    static int true_peak_factor_for(uint32_t rate, int tp_cfg);
     // EbuR128::new for n streams into a FRESH store: argument checks, tables, geometry, buffers, weights (tp_cfg: the true-peak
     // factor, 0 = the crate's rule for the rate).  Nothing else is touched, so a caller that must keep its meter on failure builds
     // into a local store and moves it in on success.

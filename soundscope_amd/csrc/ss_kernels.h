@@ -303,6 +303,11 @@ uint32_t td_resident_waves_per_cu(uint32_t channels, uint32_t s100, uint32_t hal
 // the longest streaming call (frames) that one wave walks; a longer one is shared by the eight waves of a workgroup (SPLIT), with
 // another chunk length and hence other rounding — the one rule for handles, ticks and every stream of a meter bank
 uint32_t td_ring_tile_frames(uint32_t channels, uint32_t s100);
+// that rule itself: whether a streaming call of n_frames frames is shared (what launch_time_domain asks before it picks a form)
+bool td_ring_call_shared(uint32_t channels, uint32_t s100, uint64_t n_frames);
+// the form launch_time_domain gives a streaming call of n_frames frames, from the functions the launch calls (host arithmetic only)
+struct TdRingPlan { bool shared; uint32_t waves, chunk_frames, tile_frames; };      // waves: of the workgroup that walk ONE stream
+TdRingPlan td_ring_plan(uint32_t channels, uint32_t s100, uint64_t n_frames);
 
 // a handle's readings in one launch: 2 * kMaxChannels floats copied from peaks_src to peaks_dst beside the evaluation of its
 // histograms, then `seq` stored into *flag (host-visible memory: whoever sees the flag sees the evaluation and the peaks)

@@ -128,7 +128,8 @@ int bank_plan(const ss_meter_bank *m, const uint64_t *frames, uint64_t each, boo
     }
     pl->longest = longest;
     if (!longest) return SS_OK;
-    const uint64_t S = ms.s100, piece_frames = 32 * S, tile = ssk::td_ring_tile_frames(C, (uint32_t)S);
+    const uint64_t S = ms.s100, piece_frames = MeterStore::piece_frames_for(S);
+    auto shared = [&](uint64_t take) { return ssk::td_ring_call_shared(C, (uint32_t)S, take); };      // the launch's own form switch
     const size_t n_pieces = (size_t)((longest + piece_frames - 1) / piece_frames);
     if (frames) {
         pl->arrays.assign((2 + n_pieces) * (size_t)n, 0);
@@ -147,7 +148,7 @@ int bank_plan(const ss_meter_bank *m, const uint64_t *frames, uint64_t each, boo
             const uint64_t done = k * piece_frames < f ? k * piece_frames : f, left = f - done;
             const uint64_t take = left < piece_frames ? left : piece_frames;
             if (frames) pl->arrays[pc.take + s] = take; else pc.all = take;
-            if (take > tile) { if (take > pc.max_long) pc.max_long = take; }
+            if (shared(take)) { if (take > pc.max_long) pc.max_long = take; }
             else if (take > pc.max_short) pc.max_short = take;
             const uint64_t fed = m->fed[s] + done;
             pc.gate = pc.gate || (fed + take) / S > fed / S;
@@ -158,7 +159,7 @@ int bank_plan(const ss_meter_bank *m, const uint64_t *frames, uint64_t each, boo
             pl->arrays.resize(pl->arrays.size() + 2 * (size_t)n, 0);
             for (uint32_t s = 0; s < n; s++) {
                 const uint64_t take = pl->arrays[pc.take + s];
-                pl->arrays[(take > tile ? pc.hi : pc.lo) + s] = take;
+                pl->arrays[(shared(take) ? pc.hi : pc.lo) + s] = take;
             }
         }
         pl->pieces.push_back(pc);
@@ -263,7 +264,7 @@ int advance(ss_meter_bank *m, const BankPlan &pl, const uint64_t *arr, const flo
         if (rc) return rc;
         for (uint32_t s = 0; s < n; s++) m->pair_fed[s] += arr ? pl.arrays[s] : pl.longest;
     }
-    const uint64_t piece_frames = 32 * ms.s100;
+    const uint64_t piece_frames = MeterStore::piece_frames_for(ms.s100);
     const ssk::MeterBankParams q = ms.bank_params();
     for (size_t k = 0; k < pl.pieces.size(); k++) {
         const BankPlan::Piece &pc = pl.pieces[k];

@@ -40,6 +40,7 @@ struct ss_session {
     float gain_db = 0.0f;
     uint64_t duration_ms = 0;
     double lufs[SS_LUFS_HISTORY];
+    bool last_fused = false, last_st_fused = false;     // the last tick's TickExtras::fused / st_fused (ss_session_last_tick_forms)
 };
 
 namespace {
@@ -126,6 +127,7 @@ struct TickCore {
     // samples == nullptr: no loudness call this tick (then no short-term reading either); fft == nullptr: no spectrum
     int run(const float *samples, const ssk::FftBatchParams *fft, ss_tick_result *res)
     {
+        s->last_fused = s->last_st_fused = false;
         if (samples) {
             TickExtras extras;
             extras.fft = fft;
@@ -135,6 +137,7 @@ struct TickCore {
             any_launch = res->add_status == SS_OK;
             fft_launched = extras.fused;
             st_launched = extras.st_fused;
+            s->last_fused = extras.fused; s->last_st_fused = extras.st_fused;
         }
         if (fft && !fft_launched) {                     // (no loudness call this tick, or one that could not take the spectrum along)
             HIPCHK(ssk::launch_spectrum(s->fft_plan, *fft, h->stream));
@@ -383,6 +386,14 @@ int ss_session_lufs_history(ss_session *s, double *out300)
     SS_ON_DEVICE(s);
     if (!s || !out300) return SS_ERR_INVALID_ARG;
     std::memcpy(out300, s->lufs, sizeof s->lufs);
+    return SS_OK;
+}
+
+int ss_session_last_tick_forms(const ss_session *s, int32_t *spectrum_fused, int32_t *shortterm_fused)
+{
+    if (!s || !spectrum_fused || !shortterm_fused) return SS_ERR_INVALID_ARG;
+    *spectrum_fused = s->last_fused ? 1 : 0;
+    *shortterm_fused = s->last_st_fused ? 1 : 0;
     return SS_OK;
 }
 

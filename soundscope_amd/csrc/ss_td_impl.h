@@ -703,6 +703,21 @@ static inline uint32_t td_launch_chunk_frames(bool split, bool ring, uint32_t sp
     return td_eight_wave_tiles(split, ring, split_batch) ? td_split_chunk_frames(C, S) : td_chunk_frames(C, S);
 }
 
+// The tiles of a launch and the waves of its workgroups (what td_launch_w launches, and what td_ring_plan reports).
+// SPLIT: eight waves share the call where eight slices fit the LDS (up to 16 channels or so), four otherwise
+// (a batch's streams: four waves each — the grid is n_streams workgroups, and sixteen waves per CU are what the LDS slices allow;
+// split_batch == kTdSplitSegments, a handful of streams cut into short segments: eight, latency is what counts there)
+struct TdLaunchTile { TdTile t; uint32_t nwb, L; };
+static inline TdLaunchTile td_launch_tile(bool split, bool ring, uint32_t split_batch, uint32_t C, uint32_t S, uint32_t halo)
+{
+    TdLaunchTile lt;
+    lt.L = td_launch_chunk_frames(split, ring, split_batch, C, S);
+    lt.nwb = td_eight_wave_tiles(split, ring, split_batch) ? (uint32_t)kTdSplitWaves : (uint32_t)kTdWavesPerBlock;
+    lt.t = td_tile(C, S, lt.L, halo, lt.nwb, split);
+    if (split && lt.t.lds > kTdLdsBytes) lt.t = td_tile(C, S, lt.L, halo, lt.nwb = (uint32_t)kTdWavesPerBlock, split);
+    return lt;
+}
+
 // waves (SPLIT: workgroups) of a launch: one per (stream, segment), the fix-up's without segment 0
 static inline uint64_t td_launch_units(const TdParams &p) { return (uint64_t)p.n_streams * (p.fixup ? p.nseg - 1u : p.nseg); }
 
@@ -711,15 +726,10 @@ static hipError_t td_launch_w(const TdParams &p, hipStream_t s)
 {
     const uint32_t C = p.channels;
     const uint32_t S = p.s100;
-    const bool eight = td_eight_wave_tiles(SPLIT, RING, p.split_batch);
-    const uint32_t L = td_launch_chunk_frames(SPLIT, RING, p.split_batch, C, S);
     const uint32_t halo = WAVE ? p.halo_frames : (uint32_t)kTdHaloFrames;
-    // SPLIT: eight waves share the call where eight slices fit the LDS (up to 16 channels or so), four otherwise
-    // (a batch's streams: four waves each — the grid is n_streams workgroups, and sixteen waves per CU are what the LDS slices allow;
-    // split_batch == kTdSplitSegments, a handful of streams cut into short segments: eight, latency is what counts there)
-    uint32_t nwb = eight ? (uint32_t)kTdSplitWaves : (uint32_t)kTdWavesPerBlock;
-    TdTile t = td_tile(C, S, L, halo, nwb, SPLIT);
-    if (SPLIT && t.lds > kTdLdsBytes) t = td_tile(C, S, L, halo, nwb = (uint32_t)kTdWavesPerBlock, SPLIT);
+    const TdLaunchTile lt = td_launch_tile(SPLIT, RING, p.split_batch, C, S, halo);
+    const uint32_t L = lt.L, nwb = lt.nwb;
+    const TdTile &t = lt.t;
     auto fn = k_time_domain<FACTOR, RING, CT, WAVE, WPS, SPLIT, LATE>;
     static DevicePrep prepared;                     // one per kernel instantiation
     const hipError_t pe = prepare_on_device(prepared, [fn] {
@@ -749,9 +759,10 @@ static hipError_t td_launch_tick(const TdParams &p, const FftBatchParams &fp, hi
     *fused = false;
     const uint32_t C = p.channels;
     const uint32_t S = p.s100;
-    const uint32_t L = td_launch_chunk_frames(true, true, p.split_batch, C, S);
     const uint32_t halo = (uint32_t)kTdHaloFrames;
-    const TdTile t = td_tile(C, S, L, halo, kTdSplitWaves, true);
+    const TdLaunchTile lt = td_launch_tile(true, true, p.split_batch, C, S, halo);      // the shared call's own tiles
+    const uint32_t L = lt.L;
+    const TdTile &t = lt.t;
     const size_t lds = t.lds < (size_t)kFft16kLdsBytes ? (size_t)kFft16kLdsBytes : t.lds;     // (the spectrum's workgroups use the same dynamic block)
     auto fn = k_tick<FACTOR, CT>;
     static DevicePrep prepared;
@@ -765,7 +776,8 @@ static hipError_t td_launch_tick(const TdParams &p, const FftBatchParams &fp, hi
                                    (int)(kTdLdsBytes - a.sharedSizeBytes));
     });
     if (pe != hipSuccess) return pe;
-    if (lds + static_lds.load(std::memory_order_relaxed) > kTdLdsBytes) return hipSuccess;     // not fused: the caller launches both
+    // not fused (the caller launches both): k_tick is eight waves, and the spectrum's static LDS must fit beside the slices
+    if (lt.nwb != (uint32_t)kTdSplitWaves || lds + static_lds.load(std::memory_order_relaxed) > kTdLdsBytes) return hipSuccess;
     const uint32_t fft_blocks = 2;                                      // mid, side
     hipLaunchKernelGGL(fn, dim3(fft_blocks + 1 + (p.st_out ? p.st_blocks : 0u)), dim3(64 * kTdSplitWaves), lds, s, p, L, t.tile_len, t.wave_floats,
                        halo, fp, fft_blocks);
@@ -874,8 +886,7 @@ static hipError_t td_launch_c(const TdParams &p, hipStream_t s, const FftBatchPa
     if constexpr (RING) if (split) {            // (constexpr: the batch side never instantiates these forms)
         // "longer than one tile" is measured with the BATCH's chunk length, not the split launch's own (td_split_chunk_frames)
         const uint32_t C = p.channels, S = p.s100;
-        const uint32_t batch_tile_len = td_ring_tile_frames(C, S);
-        if (p.n_frames > batch_tile_len) {
+        if (td_ring_call_shared(C, S, p.n_frames)) {
             if (RING && tick_fft && p.n_streams == 1) {                 // a tick: the spectrum's workgroups ride the same launch
                 const hipError_t e = p.channels == 2 ? td_launch_tick<FACTOR, 2>(p, *tick_fft, s, fused)
                                                      : td_launch_tick<FACTOR, 0>(p, *tick_fft, s, fused);

@@ -102,7 +102,27 @@ uint32_t td_resident_waves_per_cu(uint32_t C, uint32_t s100, uint32_t halo_frame
 
 uint32_t td_ring_tile_frames(uint32_t C, uint32_t s100)
 {
-    return td_tile(C, s100, td_chunk_frames(C, s100), kTdHaloFrames, kTdWavesPerBlock, false).tile_len;
+#ifndef SS_TUNING       // (development builds read SS_TD_L anew every time)
+    // the last answer, in one word: every streaming launch and every stream of a ragged bank call asks, mostly for one shape
+    static std::atomic<uint64_t> last{0};
+    const uint64_t key = ((uint64_t)C << 56) | ((uint64_t)(s100 & 0xFFFFFFu) << 24);
+    const uint64_t seen = last.load(std::memory_order_relaxed);
+    if (s100 <= 0xFFFFFFu && seen != 0 && (seen & ~0xFFFFFFull) == key) return (uint32_t)(seen & 0xFFFFFFu);
+#endif
+    const uint32_t tile_len = td_tile(C, s100, td_chunk_frames(C, s100), kTdHaloFrames, kTdWavesPerBlock, false).tile_len;
+#ifndef SS_TUNING
+    if (s100 <= 0xFFFFFFu && tile_len <= 0xFFFFFFu) last.store(key | tile_len, std::memory_order_relaxed);
+#endif
+    return tile_len;
+}
+
+bool td_ring_call_shared(uint32_t C, uint32_t s100, uint64_t n_frames) { return n_frames > td_ring_tile_frames(C, s100); }
+
+TdRingPlan td_ring_plan(uint32_t C, uint32_t s100, uint64_t n_frames)
+{
+    const bool shared = td_ring_call_shared(C, s100, n_frames);
+    const TdLaunchTile lt = td_launch_tile(shared, true, kTdSplitNone, C, s100, kTdHaloFrames);
+    return TdRingPlan{shared, shared ? lt.nwb : 1u, lt.L, lt.t.tile_len};
 }
 
 hipError_t launch_time_domain(const TdParams &p, hipStream_t s, const FftBatchParams *tick_fft, bool *tick_fused)

@@ -63,6 +63,12 @@ class _Session:
         """play / seek: `lufs = [-100.; 300]; analyzer.reset()` (tui.rs:1586-1614)."""
         _check(L.lib().ss_session_restart(self._s))
 
+    def last_tick_forms(self):
+        """(spectrum fused, short-term reading fused): whether each rode the last tick's loudness launch."""
+        a, b = C.c_int32(), C.c_int32()
+        _check(L.lib().ss_session_last_tick_forms(self._s, C.byref(a), C.byref(b)))
+        return bool(a.value), bool(b.value)
+
     def _store(self, res):
         self.last = res
         if res.fft_ran:

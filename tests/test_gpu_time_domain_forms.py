@@ -29,6 +29,7 @@ import pytest
 import soundscope_amd as ssa
 from soundscope_amd import _lib as L
 import _f64ref as R
+from _td_plants import STEP_K, burst as _burst, torture as _torture      # (shared with the streaming forms' tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +43,6 @@ SPAN = 12
 TP_REL = 1e-6
 SERIES_LU = 1e-6
 N_TORTURE = 10
-STEP_K = (0, 1, 2, 7, 15, 64, 481, 1999, 4799, 4801)      # frames between a level step and the boundary behind it
 
 Case = collections.namedtuple("Case", "name rate ch ns frames mode flags factor arith geo build e_bound ragged")
 Case.__new__.__defaults__ = (None,)
@@ -123,11 +123,6 @@ CASES = [
 ]
 
 
-def _burst():
-    t = np.arange(SPAN)
-    return np.sin(np.pi / 2 * t + np.pi / 4) * np.hanning(SPAN + 2)[1:-1]
-
-
 def _lengths(case):
     if case.ragged is None:
         return np.full(case.ns, case.frames, np.int64)
@@ -154,20 +149,6 @@ def _positions(case, geo, n, bench=False, end_only=False):
     p += list(range(seg - 64, seg + S)) if bench else list(range(seg + 64, seg + S - 64, 7))
     p = np.unique(np.clip(np.array(p), 0, n - SPAN))
     return p
-
-
-def _torture(rate, n, ch, k, bounds, seed):
-    """DC offset + 7 Hz + noise, its level stepping k frames in front of each boundary"""
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / rate
-    g = np.ones(n)
-    for j, b in enumerate(bounds):
-        if b - k > 0:
-            g[b - k:] = 0.25 if j % 2 == 0 else 1.0
-    x = np.empty((n, ch))
-    for c in range(ch):
-        x[:, c] = g * ((0.45 - 0.1 * c) + 0.2 * np.sin(2 * np.pi * 7 * t + c) + 0.01 * rng.standard_normal(n))
-    return x.astype(np.float32)
 
 
 def _waveform_bins(x, window_s):
