@@ -25,21 +25,17 @@ def _region_rows(regions):
     return np.ascontiguousarray(rows)
 
 
-PEAK_ENTRY_DTYPE = np.dtype([("true_peak", np.float32), ("sample_peak", np.float32),
-                             ("true_peak_frame", np.uint32), ("sample_peak_frame", np.uint32)])
+# The structured arrays' dtypes are the ctypes records' (_lib.py, Python's one definition of what crosses the C ABI).
+PEAK_ENTRY_DTYPE = np.dtype(L.PeakEntry)
 # the signal scan's records (ss_stream_scan, ss_channel_scan, ss_signal_event)
-STREAM_SCAN_DTYPE = np.dtype([(n, np.uint64) for n in ("silent_frames", "leading_silence", "trailing_silence", "longest_silence",
-                                                       "longest_silence_at", "silence_runs", "clip_runs")])
-CHANNEL_SCAN_DTYPE = np.dtype([("sum", np.float64), ("sum_sq", np.float64)] + [(n, np.uint64) for n in (
-    "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs")])
-SIGNAL_EVENT_DTYPE = np.dtype([("first_frame", np.uint64), ("frames", np.uint64), ("channel", np.uint32), ("reserved", np.uint32)])
+STREAM_SCAN_DTYPE = np.dtype(L.StreamScan)
+CHANNEL_SCAN_DTYPE = np.dtype(L.ChannelScan)
+SIGNAL_EVENT_DTYPE = np.dtype(L.SignalEvent)
 SIGNAL_SILENCE, SIGNAL_CLIP = L.SS_SIGNAL_SILENCE, L.SS_SIGNAL_CLIP
 # the pair series' records (ss_pair_entry, ss_region_pair, ss_group_pair)
-_PAIR_SUMS = [("s_aa", np.float64), ("s_bb", np.float64), ("s_ab", np.float64)]
-PAIR_ENTRY_DTYPE = np.dtype(_PAIR_SUMS + [("frames", np.uint32), ("skipped", np.uint32)])
-REGION_PAIR_DTYPE = np.dtype(_PAIR_SUMS + [("frames", np.uint64), ("skipped", np.uint64)] + [(n, np.uint32) for n in (
-    "n_active", "n_below", "first_below", "longest_below", "longest_below_at", "below_runs")])
-GROUP_PAIR_DTYPE = np.dtype(_PAIR_SUMS + [(n, np.uint64) for n in ("frames", "skipped", "n_active", "n_below", "below_runs")])
+PAIR_ENTRY_DTYPE = np.dtype(L.PairEntry)
+REGION_PAIR_DTYPE = np.dtype(L.RegionPair)
+GROUP_PAIR_DTYPE = np.dtype(L.GroupPair)
 
 
 # what a caller reads off pair records (entries, regions or groups: anything with s_aa, s_bb, s_ab), as plain numpy
@@ -66,9 +62,8 @@ def pair_mono_loss_db(rec):
 
 
 # batch gain (ss_gain_point, ss_gain_channel) and what normalise() hands back per stream
-GAIN_POINT_DTYPE = np.dtype([("frame", np.uint64), ("stream", np.uint32), ("gain", np.float32)])
-GAIN_CHANNEL_DTYPE = np.dtype([("sample_peak", np.float32), ("touched", np.uint32), ("n_over", np.uint64), ("first_over", np.uint64),
-                               ("n_nonfinite", np.uint64)])
+GAIN_POINT_DTYPE = np.dtype(L.GainPoint)
+GAIN_CHANNEL_DTYPE = np.dtype(L.GainChannel)
 NORMALISE_DTYPE = np.dtype([("loudness", np.float64), ("peak", np.float64), ("gain_db", np.float64), ("gain", np.float32),
                             ("limited_by", np.uint32)])
 _PCM_DTYPES = {L.SS_PCM_U8: np.uint8, L.SS_PCM_S16: np.int16, L.SS_PCM_S24: np.uint8, L.SS_PCM_S32: np.int32,

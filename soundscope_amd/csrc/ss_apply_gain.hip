@@ -49,9 +49,9 @@ struct GainStat {
             over += __shfl_xor(over, d); bad += __shfl_xor(bad, d);
         }
         if ((threadIdx.x & 63u) == 0u) {
-            if (peak) atomicMax(&rec->peak_bits, peak);
-            if (over) { atomicAdd(&rec->n_over, (unsigned long long)over); atomicMin(&rec->first_over, tile_begin + first); }
-            if (bad) atomicAdd(&rec->n_nonfinite, (unsigned long long)bad);
+            if (peak) atomicMax(reinterpret_cast<uint32_t *>(&rec->sample_peak), peak);      // the bits of a non-negative f32 order as it does
+            if (over) { atomicAdd(atomic_u64(&rec->n_over), (unsigned long long)over); atomicMin(atomic_u64(&rec->first_over), tile_begin + first); }
+            if (bad) atomicAdd(atomic_u64(&rec->n_nonfinite), (unsigned long long)bad);
         }
     }
 };

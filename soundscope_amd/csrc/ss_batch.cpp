@@ -129,7 +129,7 @@ struct Regions {
 // regions' part grown by a longer list), so a batch that never asks holds none of it
 struct Peaks {
     bool series_done = false;                           // queued at least once: there is something to download
-    DevBuf<uint4> series;                               // [stream][entries_cap][channels] records (ss_peak_entry)
+    DevBuf<ss_peak_entry> series;                       // [stream][entries_cap][channels]
     RegionList list;                                    // of the last ss_batch_peak_regions
     DevBuf<ssk::RegionPeaks> results;
     DevBuf<float> ch_true, ch_sample;                   // [region][channels]
@@ -579,16 +579,15 @@ int fetch(ss_batch *b, T *dst, const T *src, size_t count, hipMemcpyKind kind = 
 
 // ---- follow-up calls: behind a pass, on a list of regions; they hand back one record per region, group or stream -----------------
 // The download of n records and its status ladder: no destination for n > 0 records, then the mode, then the capacity; nothing to
-// copy means synchronise.  (The caller has checked b.)  Dev is Out as the kernels name it.
-template <class Out, class Dev>
-int fetch_records(ss_batch *b, bool mode_ok, Out *out, uint32_t cap, uint32_t n, const Dev *src)
+// copy means synchronise.  (The caller has checked b.)
+template <class Rec>
+int fetch_records(ss_batch *b, bool mode_ok, Rec *out, uint32_t cap, uint32_t n, const Rec *src)
 {
-    static_assert(sizeof(Out) == sizeof(Dev), "the records are copied out as they are");
     if (!out && n) return SS_ERR_INVALID_ARG;
     if (!mode_ok) return SS_ERR_INVALID_MODE;
     if (cap < n) return SS_ERR_CAPACITY;
     if (!n) return ss_batch_sync(b);
-    return fetch(b, out, reinterpret_cast<const Out *>(src), n);
+    return fetch(b, out, src, n);
 }
 
 // Every check of a region list, before anything is queued or allocated: a refused call leaves the previous list, its counts and its
@@ -1168,9 +1167,6 @@ int ss_batch_download_subblocks(ss_batch *b, uint32_t stream, double *out, size_
     return fetch(b, out, b->sub.p + (size_t)stream * per, per);
 }
 
-static_assert(sizeof(ss_loudness_extremes) == 24 && sizeof(ssk::LoudnessExtremes) == sizeof(ss_loudness_extremes) &&
-              offsetof(ssk::LoudnessExtremes, at_m) == offsetof(ss_loudness_extremes, max_momentary_at), "extremes layout");
-
 int ss_batch_download_loudness_series(ss_batch *b, uint32_t stream, double *momentary, double *shortterm, size_t cap)
 {
     SS_ON_DEVICE(b);
@@ -1458,14 +1454,6 @@ void ss_spectrogram_column_windows(const ss_spectrogram_view *v, uint32_t t, uin
 }
 
 // ---- loudness regions: gated loudness of time ranges and groups ----------------------------------------------------
-static_assert(sizeof(ss_loudness_region) == 16 && sizeof(ssk::LoudnessRegion) == 16 && offsetof(ssk::LoudnessRegion, group) == offsetof(ss_loudness_region, group),
-              "region layout");
-static_assert(sizeof(ss_region_result) == 48 && sizeof(ssk::RegionResult) == 48 && offsetof(ssk::RegionResult, at_m) == offsetof(ss_region_result, max_momentary_at) &&
-              offsetof(ssk::RegionResult, n_blocks) == offsetof(ss_region_result, n_gating_blocks), "region result layout");
-static_assert(sizeof(ss_group_result) == 32 && sizeof(ssk::GroupResult) == 32 && offsetof(ssk::GroupResult, n_blocks) == offsetof(ss_group_result, n_gating_blocks),
-              "group result layout");
-static_assert(SS_REGION_NO_GROUP == ssk::kRegionNoGroup, "no-group mark");
-
 int ss_batch_loudness_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups)
 {
     SS_ON_DEVICE(b);
@@ -1513,14 +1501,6 @@ int ss_batch_group_histograms(ss_batch *b, uint32_t group, uint64_t *out2000)
 }
 
 // ---- peak series and peak regions: true and sample peak per 100 ms entry, and their maxima over ranges and groups -----------
-static_assert(sizeof(ss_peak_entry) == 16 && sizeof(uint4) == 16 && offsetof(ss_peak_entry, sample_peak) == 4 && offsetof(ss_peak_entry, true_peak_frame) == 8 &&
-              offsetof(ss_peak_entry, sample_peak_frame) == 12, "peak entry layout");
-static_assert(sizeof(ss_region_peaks) == 48 && sizeof(ssk::RegionPeaks) == 48 && offsetof(ssk::RegionPeaks, true_frame) == offsetof(ss_region_peaks, true_peak_frame) &&
-              offsetof(ssk::RegionPeaks, true_channel) == offsetof(ss_region_peaks, true_peak_channel) && offsetof(ssk::RegionPeaks, n_over) == offsetof(ss_region_peaks, n_over) &&
-              offsetof(ssk::RegionPeaks, first_over) == offsetof(ss_region_peaks, first_over), "region peaks layout");
-static_assert(sizeof(ss_group_peaks) == 32 && sizeof(ssk::GroupPeaks) == 32 && offsetof(ssk::GroupPeaks, true_region) == offsetof(ss_group_peaks, true_peak_region) &&
-              offsetof(ssk::GroupPeaks, n_over) == offsetof(ss_group_peaks, n_over), "group peaks layout");
-
 // the series' time grid and tiling: the batch's rate and slot size alone (no pass, no tables)
 static uint32_t peak_s100(const ss_batch *b) { return (b->cfg.sample_rate + 5u) / 10u; }
 static ssk::PeakSeriesPlan batch_peak_plan(const ss_batch *b) { return ssk::plan_peak_series(b->cfg.channels, peak_s100(b), b->cfg.frames_per_stream); }
@@ -1578,7 +1558,7 @@ int ss_batch_download_peak_series(ss_batch *b, uint32_t stream, ss_peak_entry *o
     if (n_entries) *n_entries = (uint32_t)n;
     if (!n) return ss_batch_sync(b);
     const size_t C = b->cfg.channels;
-    return fetch(b, reinterpret_cast<uint4 *>(out), b->peaks.series.p + (size_t)stream * batch_peak_plan(b).entries_cap * C, (size_t)n * C);
+    return fetch(b, out, b->peaks.series.p + (size_t)stream * batch_peak_plan(b).entries_cap * C, (size_t)n * C);
 }
 
 int ss_batch_peak_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups, double ceiling)
@@ -1771,12 +1751,6 @@ int ss_batch_download_group_spectra(ss_batch *b, uint32_t first_group, uint32_t 
 
 // ---- signal scan: silence, clip runs, DC and non-finite samples of every stream, and the lists of the runs --------------------
 static_assert(sizeof(ss_signal_scan_config) == 24, "scan config layout");
-static_assert(sizeof(ss_stream_scan) == 56 && sizeof(ssk::StreamScan) == 56 && offsetof(ssk::StreamScan, longest_silence_at) == offsetof(ss_stream_scan, longest_silence_at) &&
-              offsetof(ssk::StreamScan, clip_runs) == offsetof(ss_stream_scan, clip_runs), "stream scan layout");
-static_assert(sizeof(ss_channel_scan) == 64 && sizeof(ssk::ChannelScan) == 64 && offsetof(ssk::ChannelScan, first_nonfinite) == offsetof(ss_channel_scan, first_nonfinite) &&
-              offsetof(ssk::ChannelScan, longest_clip_at) == offsetof(ss_channel_scan, longest_clip_at) && offsetof(ssk::ChannelScan, clip_runs) == offsetof(ss_channel_scan, clip_runs),
-              "channel scan layout");
-static_assert(sizeof(ss_signal_event) == 24 && sizeof(ssk::SignalEvent) == 24 && offsetof(ssk::SignalEvent, channel) == offsetof(ss_signal_event, channel), "signal event layout");
 
 // the scan's tiling: the batch's channel count and slot size alone (no pass, no tables)
 static ssk::SignalScanPlan batch_scan_plan(const ss_batch *b) { return ssk::plan_signal_scan(b->cfg.channels, b->cfg.frames_per_stream); }
@@ -1832,7 +1806,7 @@ int ss_batch_download_channel_scans(ss_batch *b, ss_channel_scan *out, size_t ca
     if (!b->scan.done) return SS_ERR_INVALID_MODE;
     const size_t n = (size_t)b->cfg.n_streams * b->cfg.channels;
     if (cap_records < n) return SS_ERR_CAPACITY;
-    return fetch(b, out, reinterpret_cast<const ss_channel_scan *>(b->scan.channels.p), n);
+    return fetch(b, out, b->scan.channels.p, n);
 }
 
 int ss_batch_download_signal_events(ss_batch *b, uint32_t stream, int kind, ss_signal_event *out, size_t cap_events, uint32_t *n_events)
@@ -1852,20 +1826,11 @@ int ss_batch_download_signal_events(ss_batch *b, uint32_t stream, int kind, ss_s
     if (n_events) *n_events = n;
     if (!n) return SS_OK;
     const ssk::SignalEvent *src = sc.events.p + ((size_t)stream * 2 + (kind == SS_SIGNAL_CLIP ? 1 : 0)) * sc.cfg.max_events;
-    return fetch(b, out, reinterpret_cast<const ss_signal_event *>(src), n);
+    return fetch(b, out, src, n);
 }
 
 // ---- pair series and pair regions: sums of x_a^2, x_b^2 and x_a x_b per 100 ms entry, and over ranges and groups ------------------
-static_assert(sizeof(ss_channel_pair) == 8 && sizeof(ssk::ChannelPair) == 8 && offsetof(ss_channel_pair, b) == offsetof(ssk::ChannelPair, b), "channel pair layout");
-static_assert(sizeof(ss_pair_entry) == 32 && sizeof(ssk::PairEntry) == 32 && offsetof(ss_pair_entry, s_ab) == offsetof(ssk::PairEntry, s_ab) &&
-              offsetof(ss_pair_entry, frames) == offsetof(ssk::PairEntry, frames) && offsetof(ss_pair_entry, skipped) == offsetof(ssk::PairEntry, skipped), "pair entry layout");
 static_assert(sizeof(ss_pair_region_config) == 24, "pair region config layout");
-static_assert(sizeof(ss_region_pair) == 64 && sizeof(ssk::RegionPair) == 64 && offsetof(ss_region_pair, frames) == offsetof(ssk::RegionPair, frames) &&
-              offsetof(ss_region_pair, n_active) == offsetof(ssk::RegionPair, n_active) && offsetof(ss_region_pair, first_below) == offsetof(ssk::RegionPair, first_below) &&
-              offsetof(ss_region_pair, longest_below_at) == offsetof(ssk::RegionPair, longest_below_at) && offsetof(ss_region_pair, below_runs) == offsetof(ssk::RegionPair, below_runs),
-              "region pair layout");
-static_assert(sizeof(ss_group_pair) == 64 && sizeof(ssk::GroupPair) == 64 && offsetof(ss_group_pair, frames) == offsetof(ssk::GroupPair, frames) &&
-              offsetof(ss_group_pair, n_active) == offsetof(ssk::GroupPair, n_active) && offsetof(ss_group_pair, below_runs) == offsetof(ssk::GroupPair, below_runs), "group pair layout");
 
 // the pair list a call means: the caller's, or the one pair (0, 1); checked against the batch's channels
 static int pair_list_of(const ss_batch *b, const ss_channel_pair *pairs, uint32_t n_pairs, ssk::ChannelPair (&list)[ssk::kMaxPairs], uint32_t *n)
@@ -1880,7 +1845,7 @@ static int pair_list_of(const ss_batch *b, const ss_channel_pair *pairs, uint32_
     }
     for (uint32_t k = 0; k < n_pairs; k++) {
         if (pairs[k].a >= C || pairs[k].b >= C) return SS_ERR_INVALID_ARG;
-        list[k].a = pairs[k].a; list[k].b = pairs[k].b;
+        list[k] = pairs[k];
     }
     *n = n_pairs;
     return SS_OK;
@@ -1935,7 +1900,7 @@ int ss_batch_download_pair_series(ss_batch *b, uint32_t stream, ss_pair_entry *o
     if (n_entries) *n_entries = (uint32_t)n;
     if (!n) return ss_batch_sync(b);
     const size_t cap = ssk::plan_peak_series(b->cfg.channels, peak_s100(b), b->cfg.frames_per_stream).entries_cap;
-    return fetch(b, out, reinterpret_cast<const ss_pair_entry *>(pr.series.p + (size_t)stream * cap * pr.n_pairs), (size_t)n * pr.n_pairs);
+    return fetch(b, out, pr.series.p + (size_t)stream * cap * pr.n_pairs, (size_t)n * pr.n_pairs);
 }
 
 int ss_batch_pair_regions(ss_batch *b, const ss_loudness_region *regions, uint32_t n_regions, uint32_t n_groups, const ss_pair_region_config *cfg)
@@ -1983,9 +1948,6 @@ int ss_batch_download_group_pairs(ss_batch *b, ss_group_pair *out, size_t cap_re
 // ---- batch gain and PCM export: the gain law and the gain curve (host arithmetic), the sweep, the delivery formats ------------------
 static_assert(sizeof(ss_normalise_target) == 32 && sizeof(ss_gain_point) == 16 && offsetof(ss_gain_point, stream) == 8 && offsetof(ss_gain_point, gain) == 12 &&
               sizeof(ss_gain_config) == 16 && offsetof(ss_gain_config, clip_level) == 8 && sizeof(ss_pcm_dither) == 16, "gain call layouts");
-static_assert(sizeof(ss_gain_channel) == 32 && sizeof(ssk::GainChannel) == 32 && offsetof(ss_gain_channel, touched) == offsetof(ssk::GainChannel, touched) &&
-              offsetof(ss_gain_channel, n_over) == offsetof(ssk::GainChannel, n_over) && offsetof(ss_gain_channel, first_over) == offsetof(ssk::GainChannel, first_over) &&
-              offsetof(ss_gain_channel, n_nonfinite) == offsetof(ssk::GainChannel, n_nonfinite), "gain channel layout");
 
 int ss_normalisation_gain(const ss_normalise_target *t, double loudness_lufs, double peak_linear, double *gain_db, float *gain, uint32_t *limited_by)
 {
@@ -2102,7 +2064,7 @@ int ss_batch_apply_gain(ss_batch *b, const ss_gain_point *points, uint32_t n_poi
     unsigned char *h = gn.stage.buf.p;
     {
         ssk::GainChannel *rec = reinterpret_cast<ssk::GainChannel *>(h);
-        for (uint64_t i = 0; i < records; i++) rec[i] = {0u, 0u, 0ull, ~0ull, 0ull};
+        for (uint64_t i = 0; i < records; i++) rec[i] = {0.f, 0u, 0ull, ~0ull, 0ull};
         for (const ssk::GainStream &t : touched)
             for (uint32_t ch = 0; ch < C; ch++) rec[(size_t)t.stream * C + ch].touched = 1u;
         if (!touched.empty()) std::memcpy(h + touched_at, touched.data(), touched.size() * sizeof(ssk::GainStream));

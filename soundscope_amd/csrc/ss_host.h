@@ -10,8 +10,6 @@
 //   ss_comm.cpp         the all-reduce of the corpus histograms (RCCL opened at run time; does not include this header)
 //   ss_tables.cpp       the host-side design of the constant tables (includes ss_tables.h only)
 #pragma once
-#include "../../include/soundscope_hip.h"
-
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,7 +25,7 @@
 #include <vector>
 
 #include "ss_internal.h"
-#include "ss_kernels.h"
+#include "ss_kernels.h"        // (and with it the public header, include/soundscope_hip.h)
 #include "ss_tables.h"
 
 namespace ssh {
@@ -147,9 +145,7 @@ struct HostStage {
 constexpr size_t kPcmReadSlack = 8;
 
 // EbuR128::sample_peak(c) and EbuR128::true_peak(c) = max(true, sample) of channel c, from a host copy of a state's peaks
-// (`block`: TdState::sample_peak | TdState::true_peak, read as one block of 2 * kMaxChannels floats)
-static_assert(offsetof(ssk::TdState, true_peak) == offsetof(ssk::TdState, sample_peak) + sizeof(float) * ssk::kMaxChannels,
-              "sample_peak and true_peak are read as one block");
+// (`block`: TdState::sample_peak | TdState::true_peak, read as one block of 2 * kMaxChannels floats: adjacent, ss_kernels.h)
 inline void peaks_of(const float *block, uint32_t c, double *sample_pk, double *true_pk)
 {
     const float sp = block[c], tp = block[ssk::kMaxChannels + c];

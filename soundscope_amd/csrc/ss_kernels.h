@@ -7,7 +7,53 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/soundscope_hip.h"
+
 namespace ssk {
+
+// The records that cross the C ABI have one definition, the public header's: the kernels write, and the host code copies out, the
+// ss_* structs themselves under these names.  The sizes are the header's "/* N bytes */" comments.
+using LoudnessExtremes = ss_loudness_extremes;
+using LoudnessRegion = ss_loudness_region;
+using RegionResult = ss_region_result;
+using GroupResult = ss_group_result;
+using RegionPeaks = ss_region_peaks;
+using GroupPeaks = ss_group_peaks;
+using StreamScan = ss_stream_scan;
+using ChannelScan = ss_channel_scan;
+using SignalEvent = ss_signal_event;
+using ChannelPair = ss_channel_pair;
+using PairEntry = ss_pair_entry;
+using RegionPair = ss_region_pair;
+using GroupPair = ss_group_pair;
+using GainChannel = ss_gain_channel;
+using MeterReading = ss_meter_reading;
+using StreamWatch = ss_stream_watch;
+using ChannelWatch = ss_channel_watch;
+using PairWatchSums = ss_pair_sums;
+using PairWatch = ss_pair_watch;
+static_assert(sizeof(ss_loudness_extremes) == 24, "ss_loudness_extremes");
+static_assert(sizeof(ss_loudness_region) == 16, "ss_loudness_region");
+static_assert(sizeof(ss_region_result) == 48, "ss_region_result");
+static_assert(sizeof(ss_group_result) == 32, "ss_group_result");
+static_assert(sizeof(ss_peak_entry) == 16, "ss_peak_entry");
+static_assert(sizeof(ss_region_peaks) == 48, "ss_region_peaks");
+static_assert(sizeof(ss_group_peaks) == 32, "ss_group_peaks");
+static_assert(sizeof(ss_stream_scan) == 56, "ss_stream_scan");
+static_assert(sizeof(ss_channel_scan) == 64, "ss_channel_scan");
+static_assert(sizeof(ss_signal_event) == 24, "ss_signal_event");
+static_assert(sizeof(ss_channel_pair) == 8, "ss_channel_pair");
+static_assert(sizeof(ss_pair_entry) == 32, "ss_pair_entry");
+static_assert(sizeof(ss_region_pair) == 64, "ss_region_pair");
+static_assert(sizeof(ss_group_pair) == 64, "ss_group_pair");
+static_assert(sizeof(ss_gain_channel) == 32, "ss_gain_channel");
+static_assert(sizeof(ss_meter_reading) == 72, "ss_meter_reading");
+static_assert(sizeof(ss_stream_watch) == 64, "ss_stream_watch");
+static_assert(sizeof(ss_channel_watch) == 80, "ss_channel_watch");
+static_assert(sizeof(ss_pair_sums) == 40, "ss_pair_sums");
+static_assert(sizeof(ss_pair_watch) == 160, "ss_pair_watch");
+// the records count in uint64_t, HIP's 64-bit atomics take unsigned long long: the one cast of a kernel that adds to a record in place
+__device__ __forceinline__ unsigned long long *atomic_u64(uint64_t *p) { return reinterpret_cast<unsigned long long *>(p); }
 
 // hipFuncSetAttribute applies to the current device only: a launcher prepares its kernel once per device.  The bit of a
 // device is set only AFTER the attribute call has succeeded there, under the launcher's mutex — a second thread on the
@@ -233,6 +279,8 @@ struct TdState {                 // per stream / per handle, device resident
     // time segments (each starting from a zero state) would otherwise not know.
     uint32_t bad_key[kMaxChannels];
 };
+static_assert(offsetof(TdState, true_peak) == offsetof(TdState, sample_peak) + sizeof(float) * kMaxChannels,
+              "sample_peak and true_peak are read as one block (ssh::peaks_of, ReadingsExtra)");
 
 enum TdSplitBatch : uint32_t { kTdSplitNone = 0, kTdSplitStreams = 1, kTdSplitSegments = 2 };    // TdParams::split_batch
 
@@ -342,17 +390,12 @@ hipError_t launch_finalize(const FinalizeParams &p, hipStream_t s);
 __attribute__((visibility("hidden"))) hipError_t launch_finalize_stream(const FinalizeParams &p, hipStream_t s);
 // Momentary / short-term loudness series of every stream of a batch and their maxima (SS_BATCH_LOUDNESS_SERIES), behind
 // launch_finalize on the same stream: p as given there (batches: slot == sub-block index); series[stream][series_stride][2]
-// (momentary, short-term) LUFS, extremes[stream] laid out as ss_loudness_extremes.
-struct LoudnessExtremes { double max_m, max_s; uint32_t at_m, at_s; };
+// (momentary, short-term) LUFS, extremes[stream] an ss_loudness_extremes.
 hipError_t launch_loudness_series(const FinalizeParams &p, double *series, uint64_t series_stride, LoudnessExtremes *extremes,
                                   hipStream_t s);
 // Loudness regions (ss_batch_loudness_regions), behind a pass on the same stream: the gated loudness of runs of one stream's
-// sub-blocks, optionally pooled into groups.  The records are laid out as ss_loudness_region / ss_region_result /
-// ss_group_result (include/soundscope_hip.h).
-constexpr uint32_t kRegionNoGroup = 0xFFFFFFFFu;
-struct LoudnessRegion { uint32_t stream, first_subblock, n_subblocks, group; };
-struct RegionResult { double integrated, lra, max_m, max_s; uint32_t at_m, at_s, n_blocks, n_st_blocks; };
-struct GroupResult { double integrated, lra; unsigned long long n_blocks, n_st_blocks; };
+// sub-blocks, optionally pooled into groups.  The records are ss_loudness_region / ss_region_result / ss_group_result.
+constexpr uint32_t kRegionNoGroup = SS_REGION_NO_GROUP;
 struct RegionGateParams {
     const TdConst *k;
     const double *subblocks; uint64_t sub_stride; uint32_t sub_cap;      // batches: slot == sub-block index
@@ -372,8 +415,8 @@ inline uint32_t region_gate_threads(uint32_t longest) { return longest > kRegion
 // clears the groups, gates every region (k_region_gate) and evaluates every group (k_group_eval): three steps queued on s
 hipError_t launch_region_gate(const RegionGateParams &p, hipStream_t s);
 // Peak series (ss_batch_peak_series; ss_peak_series.hip): per (stream, 100 ms entry, channel) the true and sample peak and the
-// frame of each, from the resident corpus alone — no pass, no tables.  A record is laid out as ss_peak_entry
-// (include/soundscope_hip.h): {f32 true_peak, f32 sample_peak, u32 true_peak_frame, u32 sample_peak_frame}.
+// frame of each, from the resident corpus alone — no pass, no tables.  A record is an ss_peak_entry: {f32 true_peak,
+// f32 sample_peak, u32 true_peak_frame, u32 sample_peak_frame}, stored and loaded by the kernels as one 16-byte word.
 struct PeakSeriesPlan { uint32_t tile_frames, entries_cap; };
 // tile_frames: frames of an entry a workgroup stages at a time; entries_cap = ceil(n_frames / s100): record slots per stream
 PeakSeriesPlan plan_peak_series(uint32_t channels, uint32_t s100, uint64_t n_frames);
@@ -382,7 +425,7 @@ struct PeakSeriesParams {
     uint64_t stream_stride;          // floats between streams
     uint64_t n_frames;               // frames of a slot
     const uint64_t *frames_of;       // ragged batches: each stream's own frames (nullable = n_frames for all)
-    void *series;                    // [stream][entries_cap][channels] records of 16 bytes
+    ss_peak_entry *series;           // [stream][entries_cap][channels]
     uint32_t n_streams, channels, s100;
     uint32_t tile_frames, entries_cap;      // plan_peak_series
     int factor;                      // 4, 2 or 0 (sample peak only)
@@ -390,11 +433,9 @@ struct PeakSeriesParams {
 };
 hipError_t launch_peak_series(const PeakSeriesParams &p, hipStream_t s);
 // Peak regions (ss_batch_peak_regions), behind a series on the same stream: its maxima over runs of one stream's entries, pooled
-// into groups.  The records are laid out as ss_region_peaks / ss_group_peaks.
-struct RegionPeaks { double true_peak, sample_peak; unsigned long long true_frame, sample_frame; uint32_t true_channel, sample_channel, n_over, first_over; };
-struct GroupPeaks { double true_peak, sample_peak; uint32_t true_region, sample_region; unsigned long long n_over; };
+// into groups.  The records are ss_region_peaks / ss_group_peaks.
 struct RegionPeaksParams {
-    const void *series; uint32_t entries_cap, channels, s100;
+    const ss_peak_entry *series; uint32_t entries_cap, channels, s100;
     double ceiling;                  // linear; an entry counts as over when any channel's true peak exceeds it
     const LoudnessRegion *regions;   // [n_regions], every one inside its stream's entries (the caller has checked)
     RegionPeaks *results;            // [n_regions]
@@ -433,10 +474,7 @@ struct alignas(16) SignalTileCarry {     // what k_signal_carry tells k_signal_e
     uint32_t ev_off;                 // qualifying runs of the sequence that end in earlier tiles (at most max_events)
     uint32_t owned;                  // ... that end in this tile (a run belongs to the tile that holds its last frame)
 };
-// the records, laid out as ss_stream_scan / ss_channel_scan / ss_signal_event (include/soundscope_hip.h)
-struct StreamScan { unsigned long long silent_frames, leading_silence, trailing_silence, longest_silence, longest_silence_at, silence_runs, clip_runs; };
-struct ChannelScan { double sum, sum_sq; unsigned long long nonfinite, first_nonfinite, clipped_samples, longest_clip, longest_clip_at, clip_runs; };
-struct SignalEvent { unsigned long long first_frame, frames; uint32_t channel, reserved; };
+// (the records are ss_stream_scan / ss_channel_scan / ss_signal_event)
 struct SignalScanParams {
     const float *pcm;                // [stream][frame][channels] f32, 16-byte aligned
     uint64_t stream_stride;          // floats between streams
@@ -457,13 +495,8 @@ struct SignalScanParams {
 hipError_t launch_signal_scan(const SignalScanParams &p, hipStream_t s);
 // Pair series (ss_batch_pair_series; ss_pair_series.hip): per (stream, 100 ms entry, channel pair) the f64 sums of x_a^2, x_b^2 and
 // x_a x_b over the entry's frames in which both samples are finite, from the resident corpus alone — no pass, no tables.  The grid
-// is the peak series' (plan_peak_series' entries_cap).  The records are laid out as ss_channel_pair / ss_pair_entry
-// (include/soundscope_hip.h).
+// is the peak series' (plan_peak_series' entries_cap).  The records are ss_channel_pair / ss_pair_entry.
 constexpr uint32_t kMaxPairs = 16;
-struct ChannelPair { uint32_t a, b; };
-struct alignas(16) PairEntry { double s_aa, s_bb, s_ab; uint32_t frames, skipped; };
-static_assert(sizeof(ChannelPair) == 8 && sizeof(PairEntry) == 32 && offsetof(PairEntry, s_ab) == 16 && offsetof(PairEntry, frames) == 24 &&
-              offsetof(PairEntry, skipped) == 28, "pair entry layout");
 // sweep_frames: the frames a workgroup has in flight at a time (256 lanes, four loads each; a 16-byte load holds two stereo frames).
 // It fixes which lane adds which frame, and with that the order of every sum.
 struct PairSeriesPlan { uint32_t sweep_frames, entries_cap; bool stereo; };
@@ -483,14 +516,7 @@ struct PairSeriesParams {
 hipError_t launch_pair_series(const PairSeriesParams &p, hipStream_t s);
 // Pair regions (ss_batch_pair_regions), behind a series on the same stream: the entries' sums added in entry order, the entries
 // below the correlation threshold and their runs, and the regions' records added per group in region index order.  The records are
-// laid out as ss_region_pair / ss_group_pair.
-struct RegionPair {
-    double s_aa, s_bb, s_ab; unsigned long long frames, skipped;
-    uint32_t n_active, n_below, first_below, longest_below, longest_below_at, below_runs;
-};
-struct GroupPair { double s_aa, s_bb, s_ab; unsigned long long frames, skipped, n_active, n_below, below_runs; };
-static_assert(sizeof(RegionPair) == 64 && offsetof(RegionPair, frames) == 24 && offsetof(RegionPair, n_active) == 40 &&
-              offsetof(RegionPair, below_runs) == 60 && sizeof(GroupPair) == 64 && offsetof(GroupPair, n_active) == 40, "pair region layouts");
+// ss_region_pair / ss_group_pair.
 struct RegionPairsParams {
     const PairEntry *series; uint32_t entries_cap, n_pairs;
     double threshold, power_floor; uint32_t min_run;       // ss_pair_region_config (the caller has checked)
@@ -505,14 +531,13 @@ hipError_t launch_region_pairs(const RegionPairsParams &p, hipStream_t s);
 // channel) what the result holds.  The host resolves the caller's points into a segment table per touched stream: segment j covers
 // the frames [start_j, start_(j+1)) (the last one to the stream's end), and its value at frame n is
 //     base == kGainConst:  g            else:  g + (double)(n - base) * d      (ss_gain_envelope, each operation rounded on its own)
-// The first segment of a stream starts at frame 0.  The records are laid out as ss_gain_channel.
+// The first segment of a stream starts at frame 0.  The records are ss_gain_channel: the kernel keeps sample_peak as the bits of
+// a non-negative f32, whose unsigned order is the values' order.
 constexpr uint32_t kGainTileFrames = 4096;                       // frames one workgroup sweeps
 constexpr unsigned long long kGainConst = ~0ull;
 struct GainSegment { unsigned long long start, base; double g, d; };
 struct GainStream { uint32_t stream, seg_first, n_seg, reserved; };       // a touched stream: its segments [seg_first, seg_first + n_seg)
-struct GainChannel { uint32_t peak_bits, touched; unsigned long long n_over, first_over, n_nonfinite; };
-static_assert(sizeof(GainSegment) == 32 && sizeof(GainStream) == 16 && sizeof(GainChannel) == 32 && offsetof(GainChannel, n_over) == 8 &&
-              offsetof(GainChannel, first_over) == 16 && offsetof(GainChannel, n_nonfinite) == 24, "gain record layouts");
+static_assert(sizeof(GainSegment) == 32 && sizeof(GainStream) == 16, "gain table layouts");
 struct ApplyGainParams {
     float *pcm;                      // [stream][frame][channels] f32, 16-byte aligned; read and written
     uint64_t stream_stride;          // floats between streams
@@ -573,23 +598,17 @@ struct MeterBankParams {
     uint32_t n_streams, channels;
     uint32_t st_on;                  // 0: thirty sub-blocks are more than the crate's 3 s ring (the short-term reading is NaN)
 };
-// one record per stream, laid out as ss_meter_reading (include/soundscope_hip.h)
-struct MeterReading {
-    double momentary, shortterm, integrated, loudness_range;
-    double true_peak[2], sample_peak[2];
-    uint64_t frames;
-};
 // gating behind a time-domain launch of `frames` frames per stream (frames_of, device memory, nullable: frames_of[s] for stream s
 // instead): stream s's new sub-blocks are [(fed - frames) / S, fed / S), fed = state[s].frames_fed (the streams' phases differ
 // after a selective reset or a ragged add)
 hipError_t launch_meter_bank_gate(const MeterBankParams &p, uint64_t frames, const uint64_t *frames_of, hipStream_t s);
-// every stream's readings into out[stream] (device or mapped host memory)
+// every stream's readings into out[stream] (an ss_meter_reading each; device or mapped host memory)
 hipError_t launch_meter_bank_readings(const MeterBankParams &p, MeterReading *out, hipStream_t s);
 // clears the listed streams' meters (streams == nullptr: streams 0 .. count - 1)
 hipError_t launch_meter_bank_reset(const MeterBankParams &p, const uint32_t *streams, uint32_t count, hipStream_t s);
 
 // meter-bank spectra (ss_fft.hip): every stream's newest 16384 frames, kept in a ring, transformed in one launch
-constexpr uint32_t kBankSpecN = 16384;
+constexpr uint32_t kBankSpecN = SS_BANK_SPECTRUM_N;
 // the column fold of a bank kernel (the rule: ss_chart_dev.h): the tables of ssh::column_tables with stride = n_bins, and the gain
 struct ChartFold {
     const double *pink;              // n_bins f64 pink compensation
@@ -664,9 +683,7 @@ struct alignas(16) BankWatchSeq {
     double sum, sum_sq;              // channel q - 1 (sequence 0: unused): over its finite samples, tile by tile behind the state
     unsigned long long clipped, nonfinite, first_nonfinite, last_clip;   // (~0: none)
 };                                   // 112 bytes
-// the records, laid out as ss_stream_watch / ss_channel_watch (include/soundscope_hip.h): the batch records, then the live fields
-struct StreamWatch { unsigned long long silent_frames, leading_silence, trailing_silence, longest_silence, longest_silence_at, silence_runs, clip_runs, frames; };
-struct ChannelWatch { double sum, sum_sq; unsigned long long nonfinite, first_nonfinite, clipped_samples, longest_clip, longest_clip_at, clip_runs, trailing_clip, last_clip_frame; };
+// (the records are ss_stream_watch / ss_channel_watch: the batch records, then the live fields)
 struct BankWatchParams {
     const float *pcm;                // f32 input of this call, any 4-byte alignment: stream s at pcm + offset_of[s], or pcm + s * stride
     uint64_t stride;                 // floats between streams (offset_of == nullptr)
@@ -692,20 +709,10 @@ hipError_t launch_bank_signal_watch_reset(BankWatchSeq *state, StreamWatch *stre
 //   - the open entry's lane sums, [3][kPairWatchLanes] f64 (s_aa, s_bb, s_ab: a wave's 64 lanes read consecutive doubles), valid
 //     where the stream's open_frames > 0, and the frames of the open entry that were skipped so far (one u32);
 //   - the ring of the newest window_entries complete entries, entry j at slot j mod window_entries;
-//   - the record, laid out as ss_pair_watch (include/soundscope_hip.h).  The record IS the running state: its totals, counts,
+//   - the record, an ss_pair_watch.  The record IS the running state: its totals, counts,
 //     run fields, entries and open_frames are read at the start of a call and written at its end.
 constexpr uint32_t kPairWatchLanes = 256;
-constexpr uint32_t kPairWatchWindowMax = 600;
-struct PairWatchSums { double s_aa, s_bb, s_ab; unsigned long long frames, skipped; };
-struct PairWatch {
-    PairWatchSums window, total;
-    unsigned long long entries, n_active, n_below, first_below, longest_below, longest_below_at, below_runs, trailing_below;
-    uint32_t open_frames, window_count;
-    unsigned long long reserved;
-};
-static_assert(sizeof(PairWatchSums) == 40 && sizeof(PairWatch) == 160 && offsetof(PairWatch, total) == 40 && offsetof(PairWatch, entries) == 80 &&
-              offsetof(PairWatch, trailing_below) == 136 && offsetof(PairWatch, open_frames) == 144 && offsetof(PairWatch, reserved) == 152,
-              "pair watch layout");
+constexpr uint32_t kPairWatchWindowMax = SS_BANK_PAIR_WINDOW_MAX;
 struct BankPairWatchParams {
     const float *pcm;                // f32 input of this call, any 4-byte alignment: stream s at pcm + offset_of[s], or pcm + s * stride
     uint64_t stride;                 // floats between streams (offset_of == nullptr)

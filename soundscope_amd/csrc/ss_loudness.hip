@@ -563,11 +563,11 @@ __global__ __launch_bounds__(1024) void k_region_gate(RegionGateParams p)
     GroupResult *grp = rg.group != kRegionNoGroup ? p.group_results + rg.group : nullptr;
     if (tid == 0) {
         for (int w = 1; w < (nthr >> 6); w++) { max_at(bm, am, red_v[0][w], red_at[0][w]); max_at(bs, as, red_v[1][w], red_at[1][w]); }
-        out->max_m = bm; out->max_s = bs; out->at_m = am; out->at_s = as;
-        out->n_blocks = nb; out->n_st_blocks = ns;
+        out->max_momentary = bm; out->max_shortterm = bs; out->max_momentary_at = am; out->max_shortterm_at = as;
+        out->n_gating_blocks = nb; out->n_st_blocks = ns;
         if (grp) {
-            if (nb) atomicAdd(&grp->n_blocks, (unsigned long long)nb);
-            if (ns) atomicAdd(&grp->n_st_blocks, (unsigned long long)ns);
+            if (nb) atomicAdd(atomic_u64(&grp->n_gating_blocks), (unsigned long long)nb);
+            if (ns) atomicAdd(atomic_u64(&grp->n_st_blocks), (unsigned long long)ns);
         }
     }
     if (grp) {
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(1024) void k_region_gate(RegionGateParams p)
             if (ds) atomicAdd(&gh[kHistBins + i], ds);
         }
     }
-    if (tid < 64) eval_hist(hb, hs, p.hist_energies, bd, &out->integrated, &out->lra);
+    if (tid < 64) eval_hist(hb, hs, p.hist_energies, bd, &out->integrated_lufs, &out->loudness_range);
 }
 
 // One wave per group behind the regions, shaped like k_hist_eval: the group's summed pair and the two tables into LDS, eval_hist
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(64) void k_group_eval(RegionGateParams p)
     stage_tables(tab, p.hist_energies, p.hist_bounds, threadIdx.x, 64, [&](int i) { hb[i] = gh[i]; hs[i] = gh[kHistBins + i]; });
     __syncthreads();
     GroupResult *out = p.group_results + blockIdx.x;
-    eval_hist(hb, hs, tab, tab + kHistBins, &out->integrated, &out->lra);
+    eval_hist(hb, hs, tab, tab + kHistBins, &out->integrated_lufs, &out->loudness_range);
 }
 
 hipError_t launch_region_gate(const RegionGateParams &p, hipStream_t s)

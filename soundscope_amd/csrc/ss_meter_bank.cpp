@@ -68,10 +68,6 @@ struct ss_meter_bank {
     std::vector<uint64_t> pair_fed;        // [n]
 };
 
-static_assert(sizeof(ss_meter_reading) == 72 && sizeof(ssk::MeterReading) == sizeof(ss_meter_reading), "ss_meter_reading layout");
-static_assert(offsetof(ss_meter_reading, true_peak) == offsetof(ssk::MeterReading, true_peak) &&
-              offsetof(ss_meter_reading, frames) == offsetof(ssk::MeterReading, frames), "ss_meter_reading layout");
-
 namespace {
 
 // the stream has been waited for: the staging buffer is free
@@ -168,18 +164,15 @@ int bank_plan(const ss_meter_bank *m, const uint64_t *frames, uint64_t each, boo
 }
 
 // ---- signal watch ------------------------------------------------------------------------------------------------------------------
-static_assert(sizeof(ss_stream_watch) == 64 && sizeof(ssk::StreamWatch) == 64 && sizeof(ss_channel_watch) == 80 && sizeof(ssk::ChannelWatch) == 80,
-              "watch record layout");
 // both records begin with the batch scan's
 static_assert(offsetof(ss_stream_watch, silent_frames) == offsetof(ss_stream_scan, silent_frames) &&
               offsetof(ss_stream_watch, longest_silence_at) == offsetof(ss_stream_scan, longest_silence_at) &&
-              offsetof(ss_stream_watch, clip_runs) == offsetof(ss_stream_scan, clip_runs) && offsetof(ss_stream_watch, frames) == sizeof(ss_stream_scan) &&
-              offsetof(ssk::StreamWatch, frames) == offsetof(ss_stream_watch, frames), "ss_stream_watch begins with ss_stream_scan");
+              offsetof(ss_stream_watch, clip_runs) == offsetof(ss_stream_scan, clip_runs) && offsetof(ss_stream_watch, frames) == sizeof(ss_stream_scan),
+              "ss_stream_watch begins with ss_stream_scan");
 static_assert(offsetof(ss_channel_watch, sum) == offsetof(ss_channel_scan, sum) && offsetof(ss_channel_watch, first_nonfinite) == offsetof(ss_channel_scan, first_nonfinite) &&
               offsetof(ss_channel_watch, longest_clip_at) == offsetof(ss_channel_scan, longest_clip_at) &&
-              offsetof(ss_channel_watch, clip_runs) == offsetof(ss_channel_scan, clip_runs) && offsetof(ss_channel_watch, trailing_clip) == sizeof(ss_channel_scan) &&
-              offsetof(ssk::ChannelWatch, trailing_clip) == offsetof(ss_channel_watch, trailing_clip) &&
-              offsetof(ssk::ChannelWatch, last_clip_frame) == offsetof(ss_channel_watch, last_clip_frame), "ss_channel_watch begins with ss_channel_scan");
+              offsetof(ss_channel_watch, clip_runs) == offsetof(ss_channel_scan, clip_runs) && offsetof(ss_channel_watch, trailing_clip) == sizeof(ss_channel_scan),
+              "ss_channel_watch begins with ss_channel_scan");
 
 ssk::StreamWatch *watch_streams(const ss_meter_bank *m) { return reinterpret_cast<ssk::StreamWatch *>(m->watch_rec.p); }
 ssk::ChannelWatch *watch_channels(const ss_meter_bank *m) { return reinterpret_cast<ssk::ChannelWatch *>(watch_streams(m) + m->meter.n); }
@@ -203,16 +196,7 @@ int watch_advance(ss_meter_bank *m, const float *pcm, const uint64_t *offset_of,
 }
 
 // ---- pair watch --------------------------------------------------------------------------------------------------------------------
-static_assert(sizeof(ss_pair_sums) == 40 && sizeof(ss_pair_watch_config) == 24 && sizeof(ss_pair_watch) == 160 && sizeof(ssk::PairWatch) == 160,
-              "pair watch record layout");
-static_assert(offsetof(ss_pair_watch, total) == offsetof(ssk::PairWatch, total) && offsetof(ss_pair_watch, entries) == offsetof(ssk::PairWatch, entries) &&
-              offsetof(ss_pair_watch, first_below) == offsetof(ssk::PairWatch, first_below) &&
-              offsetof(ss_pair_watch, trailing_below) == offsetof(ssk::PairWatch, trailing_below) &&
-              offsetof(ss_pair_watch, open_frames) == offsetof(ssk::PairWatch, open_frames) &&
-              offsetof(ss_pair_watch, window_count) == offsetof(ssk::PairWatch, window_count) &&
-              offsetof(ss_pair_watch, reserved) == offsetof(ssk::PairWatch, reserved) && offsetof(ss_pair_sums, frames) == offsetof(ssk::PairWatchSums, frames),
-              "ss_pair_watch layout");
-static_assert(SS_BANK_PAIR_WINDOW_MAX == ssk::kPairWatchWindowMax, "one window maximum");
+static_assert(sizeof(ss_pair_watch_config) == 24, "pair watch config layout");
 
 // the pair watch's launch behind the staging of an add, with watch_advance's arguments
 int pair_watch_advance(ss_meter_bank *m, const float *pcm, const uint64_t *offset_of, uint64_t stride, const uint64_t *frames_of, uint64_t frames)
@@ -348,8 +332,6 @@ int bank_reset(ss_meter_bank *m, const uint32_t *streams, uint32_t count)
 }
 
 int null_bank() { return require_device() ? SS_ERR_DEVICE : SS_ERR_INVALID_ARG; }
-
-static_assert(SS_BANK_SPECTRUM_N == ssk::kBankSpecN, "one window length");
 
 uint32_t spec_rows(const ss_meter_bank *m) { return m->meter.channels == 2 ? 2u : m->meter.channels; }
 
@@ -871,7 +853,7 @@ int ss_meter_bank_pair_watch_enable(ss_meter_bank *m, const ss_channel_pair *pai
     }
     for (uint32_t k = 0; pairs && k < n_pairs; k++) {
         if (pairs[k].a >= C || pairs[k].b >= C) return SS_ERR_INVALID_ARG;
-        list[k].a = pairs[k].a; list[k].b = pairs[k].b;
+        list[k] = pairs[k];
     }
     if (!(cfg->threshold > -1.0 && cfg->threshold < 1.0) || !(cfg->power_floor >= 0.0)) return SS_ERR_INVALID_ARG;        // (NaN fails the comparisons)
     if (!cfg->min_run || !cfg->window_entries || cfg->window_entries > SS_BANK_PAIR_WINDOW_MAX) return SS_ERR_INVALID_ARG;

@@ -144,6 +144,9 @@ __global__ __launch_bounds__(kPeakThreads) void k_peak_series(PeakSeriesParams p
     __syncthreads();
     if (threadIdx.x < C) {
         const unsigned long long kt = best[0][threadIdx.x], ks = best[1][threadIdx.x];
+        // the record leaves (and k_region_peaks reads it) as one 16-byte word: x, y, z, w are ss_peak_entry's four fields in order
+        static_assert(offsetof(ss_peak_entry, sample_peak) == 4 && offsetof(ss_peak_entry, true_peak_frame) == 8 &&
+                      offsetof(ss_peak_entry, sample_peak_frame) == 12, "peak entry as a uint4");
         uint4 rec;
         rec.x = (uint32_t)(kt >> 32); rec.y = (uint32_t)(ks >> 32);
         rec.z = 0xFFFFFFFFu - (uint32_t)kt; rec.w = 0xFFFFFFFFu - (uint32_t)ks;
@@ -239,9 +242,9 @@ __global__ __launch_bounds__(256) void k_region_peaks(RegionPeaksParams p)
         RegionPeaks out;
         const bool has_t = top[0] != 0u, has_s = top[1] != 0u;
         out.true_peak = (double)__uint_as_float(top[0]); out.sample_peak = (double)__uint_as_float(top[1]);
-        out.true_frame = has_t ? where[0] >> 6 : ~0ull; out.sample_frame = has_s ? where[1] >> 6 : ~0ull;
-        out.true_channel = has_t ? (uint32_t)(where[0] & 63ull) : 0xFFFFFFFFu;
-        out.sample_channel = has_s ? (uint32_t)(where[1] & 63ull) : 0xFFFFFFFFu;
+        out.true_peak_frame = has_t ? where[0] >> 6 : ~0ull; out.sample_peak_frame = has_s ? where[1] >> 6 : ~0ull;
+        out.true_peak_channel = has_t ? (uint32_t)(where[0] & 63ull) : 0xFFFFFFFFu;
+        out.sample_peak_channel = has_s ? (uint32_t)(where[1] & 63ull) : 0xFFFFFFFFu;
         out.n_over = n_over_s; out.first_over = first_over_s;
         p.results[blockIdx.x] = out;
         if (rg.group != kRegionNoGroup) {
@@ -262,8 +265,8 @@ __global__ __launch_bounds__(256) void k_group_peaks(RegionPeaksParams p)
     const unsigned long long *acc = p.group_acc + (size_t)g * 3;
     GroupPeaks out;
     out.true_peak = (double)__uint_as_float((uint32_t)(acc[0] >> 32)); out.sample_peak = (double)__uint_as_float((uint32_t)(acc[1] >> 32));
-    out.true_region = acc[0] ? 0xFFFFFFFFu - (uint32_t)acc[0] : 0xFFFFFFFFu;
-    out.sample_region = acc[1] ? 0xFFFFFFFFu - (uint32_t)acc[1] : 0xFFFFFFFFu;
+    out.true_peak_region = acc[0] ? 0xFFFFFFFFu - (uint32_t)acc[0] : 0xFFFFFFFFu;
+    out.sample_peak_region = acc[1] ? 0xFFFFFFFFu - (uint32_t)acc[1] : 0xFFFFFFFFu;
     out.n_over = acc[2];
     p.group_results[g] = out;
 }

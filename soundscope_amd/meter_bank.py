@@ -20,23 +20,15 @@ from . import _lib as L
 from .analyzer import _check
 from .batch import PAIR_ENTRY_DTYPE
 
-READING_DTYPE = np.dtype([("momentary", "<f8"), ("shortterm", "<f8"), ("integrated", "<f8"), ("loudness_range", "<f8"),
-                          ("true_peak", "<f8", (2,)), ("sample_peak", "<f8", (2,)), ("frames", "<u8")])
-assert READING_DTYPE.itemsize == C.sizeof(L.MeterReading) == 72
+# the structured arrays' dtypes are the ctypes records' (_lib.py), as batch.py's are
+READING_DTYPE = np.dtype(L.MeterReading)
 # ss_stream_watch / ss_channel_watch: the batch scan's records (batch.STREAM_SCAN_DTYPE / CHANNEL_SCAN_DTYPE), then the live fields
-STREAM_WATCH_DTYPE = np.dtype([(n, "<u8") for n in ("silent_frames", "leading_silence", "trailing_silence", "longest_silence",
-                                                    "longest_silence_at", "silence_runs", "clip_runs", "frames")])
-CHANNEL_WATCH_DTYPE = np.dtype([("sum", "<f8"), ("sum_sq", "<f8")] + [(n, "<u8") for n in (
-    "nonfinite", "first_nonfinite", "clipped_samples", "longest_clip", "longest_clip_at", "clip_runs", "trailing_clip",
-    "last_clip_frame")])
-assert STREAM_WATCH_DTYPE.itemsize == C.sizeof(L.StreamWatch) == 64 and CHANNEL_WATCH_DTYPE.itemsize == C.sizeof(L.ChannelWatch) == 80
+STREAM_WATCH_DTYPE = np.dtype(L.StreamWatch)
+CHANNEL_WATCH_DTYPE = np.dtype(L.ChannelWatch)
 # ss_pair_watch: `window` and `total` are records with the pair entries' field names, so that batch.pair_correlation, pair_balance_db
 # and pair_mono_loss_db take rec["window"] or rec["total"] directly
-PAIR_SUMS_DTYPE = np.dtype([("s_aa", "<f8"), ("s_bb", "<f8"), ("s_ab", "<f8"), ("frames", "<u8"), ("skipped", "<u8")])
-PAIR_WATCH_DTYPE = np.dtype([("window", PAIR_SUMS_DTYPE), ("total", PAIR_SUMS_DTYPE)] + [(n, "<u8") for n in (
-    "entries", "n_active", "n_below", "first_below", "longest_below", "longest_below_at", "below_runs", "trailing_below")] + [
-    ("open_frames", "<u4"), ("window_count", "<u4"), ("reserved", "<u8")])
-assert PAIR_SUMS_DTYPE.itemsize == C.sizeof(L.PairSums) == 40 and PAIR_WATCH_DTYPE.itemsize == C.sizeof(L.PairWatch) == 160
+PAIR_SUMS_DTYPE = np.dtype(L.PairSums)
+PAIR_WATCH_DTYPE = np.dtype(L.PairWatch)
 
 
 class MeterBank:

@@ -18,6 +18,15 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(ss_[a-z0-9_]+)\s*\(", src)))
 
 
+# (field, byte offset) of a ctypes record and of a numpy structured dtype: what the ABI files compare with their literal tables
+def offsets(struct):
+    return [(name, getattr(struct, name).offset) for name, _ in struct._fields_]
+
+
+def dtype_offsets(dt):
+    return [(n, dt.fields[n][1]) for n in dt.names]
+
+
 def test_header_symbols_all_exported():
     lib = ctypes.CDLL(L.LIB_PATH)
     names = declared_symbols()

@@ -11,19 +11,11 @@ import pytest
 
 from soundscope_amd import _lib as L
 from soundscope_amd.batch import GAIN_CHANNEL_DTYPE, GAIN_POINT_DTYPE, gain_envelope, normalisation_gain
-from test_abi import HEADER, build_c_client, declared_symbols
+from test_abi import HEADER, build_c_client, declared_symbols, dtype_offsets, offsets
 
 NEW = ("ss_normalisation_gain", "ss_gain_envelope", "ss_batch_apply_gain", "ss_batch_apply_gain_plan", "ss_batch_download_gain_stats",
        "ss_batch_download_pcm")
 INF = math.inf
-
-
-def offsets(struct):
-    return [(name, getattr(struct, name).offset) for name, _ in struct._fields_]
-
-
-def dtype_offsets(dt):
-    return [(n, dt.fields[n][1]) for n in dt.names]
 
 
 def test_record_layouts():

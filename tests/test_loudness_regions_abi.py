@@ -5,13 +5,9 @@ import os
 import re
 
 from soundscope_amd import _lib as L
-from test_abi import HEADER, build_c_client
+from test_abi import HEADER, build_c_client, offsets
 
 NEW = ("ss_batch_loudness_regions", "ss_batch_download_region_results", "ss_batch_download_group_results", "ss_batch_group_histograms")
-
-
-def offsets(struct):
-    return [(name, getattr(struct, name).offset) for name, _ in struct._fields_]
 
 
 def test_record_layouts():

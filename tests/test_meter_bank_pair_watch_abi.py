@@ -14,9 +14,8 @@ import pytest
 from soundscope_amd import _lib as L
 from soundscope_amd import batch as B
 from soundscope_amd import meter_bank as M
-from test_abi import HEADER, build_c_client, declared_symbols
+from test_abi import HEADER, build_c_client, declared_symbols, offsets
 from test_kernel_resources import HIPCC, _resources
-from test_signal_scan_abi import offsets
 
 NEW = ("ss_meter_bank_pair_watch_enable", "ss_meter_bank_pair_watch_plan", "ss_meter_bank_pair_watch_reset",
        "ss_meter_bank_pair_watch", "ss_meter_bank_pair_watch_entries")

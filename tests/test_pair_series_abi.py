@@ -7,7 +7,7 @@ import re
 import numpy as np
 
 from soundscope_amd import _lib as L
-from test_abi import HEADER, build_c_client, declared_symbols
+from test_abi import HEADER, build_c_client, declared_symbols, dtype_offsets, offsets
 
 NEW = ("ss_batch_pair_series", "ss_batch_pair_series_plan", "ss_batch_download_pair_series", "ss_batch_pair_regions",
        "ss_batch_download_region_pairs", "ss_batch_download_group_pairs")
@@ -15,14 +15,6 @@ SUMS = [("s_aa", 0), ("s_bb", 8), ("s_ab", 16)]
 REGION_TAIL = [("frames", 24), ("skipped", 32), ("n_active", 40), ("n_below", 44), ("first_below", 48), ("longest_below", 52),
                ("longest_below_at", 56), ("below_runs", 60)]
 GROUP_TAIL = [("frames", 24), ("skipped", 32), ("n_active", 40), ("n_below", 48), ("below_runs", 56)]
-
-
-def offsets(struct):
-    return [(name, getattr(struct, name).offset) for name, _ in struct._fields_]
-
-
-def dtype_offsets(dt):
-    return [(n, dt.fields[n][1]) for n in dt.names]
 
 
 def test_record_layouts():

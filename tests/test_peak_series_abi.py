@@ -5,14 +5,10 @@ import ctypes
 import re
 
 from soundscope_amd import _lib as L
-from test_abi import HEADER, build_c_client, declared_symbols
+from test_abi import HEADER, build_c_client, declared_symbols, offsets
 
 NEW = ("ss_batch_peak_series", "ss_batch_peak_series_plan", "ss_batch_download_peak_series", "ss_batch_peak_regions",
        "ss_batch_download_region_peaks", "ss_batch_download_group_peaks", "ss_batch_download_region_channel_peaks")
-
-
-def offsets(struct):
-    return [(name, getattr(struct, name).offset) for name, _ in struct._fields_]
 
 
 def test_record_layouts():

@@ -11,16 +11,12 @@ import pytest
 
 from soundscope_amd import _lib as L
 from soundscope_amd import batch as B
-from test_abi import HEADER, build_c_client, declared_symbols
+from test_abi import HEADER, build_c_client, declared_symbols, offsets
 from test_kernel_resources import HIPCC, _resources
 
 NEW = ("ss_batch_signal_scan", "ss_batch_signal_scan_plan", "ss_batch_download_stream_scans", "ss_batch_download_channel_scans",
        "ss_batch_download_signal_events")
 KERNELS = ["k_signal_tiles", "k_signal_carry", "k_signal_events"]
-
-
-def offsets(struct):
-    return [(name, getattr(struct, name).offset) for name, _ in struct._fields_]
 
 
 def test_record_layouts():
