@@ -10,10 +10,18 @@ all-reduce of the 2x1000-bin u64 histograms when N > 1, issued by the C-ABI libr
   N > 1 : BASELINE config 4 — 8192 streams IN TOTAL sharded over the ranks (strong scaling, SURVEY §8d);
           `--scaling weak` keeps `--streams` per GPU instead.
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W            (plain run)
+         python bench.py --gpus 1 --steps K --warmup W --full     (plain run + every other leg)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
          (torchrun is only the process launcher: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT)
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and no more: set-up, W warm-up steps, the K timed steps (with the per-kernel HIP
+events that ride inside them), --dump-outputs, the line.  `--full` adds, around the very same timed steps, everything else
+the line can carry: the spectrum kernel's traffic floor, the host copy of the corpus gate, the sustained run, the f16x3
+true-peak leg and both modes' errors against an f64 convolution, an overlap mode's separate per-kernel pass, the
+PCIe-inclusive rates, the CPU baseline with its parity check (--no-cpu skips it) and the other configurations
+(--no-extra skips them).  The entries of the line that only `--full` measures are null, or absent, in a plain run.
 """
 import argparse
 import json
@@ -404,7 +412,7 @@ def time_config(ssa, L, rate, channels, streams, frames, fft_n, hop, tp_factor, 
     return res
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed passes (default: a timed region of about 1 s)")
@@ -424,11 +432,20 @@ def main():
     ap.add_argument("--allow-host-fallback", action="store_true",
                     help="N > 1: if the RCCL communicator cannot be created, stage the 16 kB exchange through host memory instead of failing "
                          "(the JSON says which transport ran).  Without this flag a failed RCCL setup ends the run non-zero.")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (and its parity check)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the config 2 / config 5 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure and check everything else the line can carry (traffic floor, host copy of the "
+                         "corpus gate, sustained run, f16x3 true-peak leg, PCIe-inclusive rates, CPU baseline and parity check, the "
+                         "other configurations); off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg (and its parity check)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the config 2 / config 5 lines")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (a fixed seeded sample, at most 64 MB) as "
                          "DIR/<name>.npy, float32 / float64 (rank 0's shard); see dump_outputs")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -506,7 +523,7 @@ def main():
     # the memory system's floor for the spectrum kernel's access pattern on THIS box: its loads and stores alone, same
     # grid / occupancy / addresses, no arithmetic (overwrites the spectra, so it runs before anything is computed)
     io_floor_ms = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             io_floor_ms = b.traffic_floor(5)
         except Exception:
@@ -553,12 +570,13 @@ def main():
     samples_per_step = total_streams * frames * 2
     value = samples_per_step * args.steps / dt
     corpus_i, corpus_lra = b.corpus_gate_read()                 # what the last step left on the device
-    hist[0] = np.concatenate(b.histograms())                    # (all-reduced in place when N > 1)
-    host_i, host_lra = corpus_gate(hist[0])                     # the same gate on the host copy of the histograms
-    if abs(corpus_i - host_i) > 1e-9 or abs(corpus_lra - host_lra) > 1e-9:
-        raise SystemExit(f"device corpus gate {corpus_i, corpus_lra} != host {host_i, host_lra}")
+    if args.full:
+        hist[0] = np.concatenate(b.histograms())                # (all-reduced in place when N > 1)
+        host_i, host_lra = corpus_gate(hist[0])                 # the same gate on the host copy of the histograms
+        if abs(corpus_i - host_i) > 1e-9 or abs(corpus_lra - host_lra) > 1e-9:
+            raise SystemExit(f"device corpus gate {corpus_i, corpus_lra} != host {host_i, host_lra}")
     if args.dump_outputs and rank == 0:
-        # before anything else runs on the batch: the sustained and f16x3 passes below overwrite its results
+        # before anything else runs on the batch: --full's sustained and f16x3 passes below overwrite its results
         n_files, n_bytes = dump_outputs(b, first, (corpus_i, corpus_lra), args.dump_outputs)
         print(f"[bench] wrote {n_files} arrays ({n_bytes / 1e6:.1f} MB) to {args.dump_outputs}", file=sys.stderr, flush=True)
 
@@ -566,12 +584,12 @@ def main():
     # 159-164).  The timed step above runs it at that width (SS_TP_ARITH_F32, the library's default: an f32 fma chain per output —
     # v_pk_fma_f32 on the packed VALU for 2 / 6 / 8 channels since round 6, v_mfma_f32_16x16x4_f32 for other counts).  The SAME step is timed again with the opt-in f16x3 split on the matrix cores
     # (ss_batch_set_true_peak_arith), and both modes' peaks of the timed batch are measured against an f64 polyphase
-    # convolution of the same streams (numpy, independent of the oracle).
+    # convolution of the same streams (numpy, independent of the oracle).  (--full; the mode the step ran in is read either way.)
     if b.true_peak_arith != L.SS_TP_ARITH_F32:
         raise SystemExit("the timed step did not run at the reference's f32 true-peak width")
     tp_arith = None
     sustained = None
-    if comm is None:
+    if args.full and comm is None:
         # a sustained run of the same step (>= 1 s): clocks and thermals of the driver's short headline are otherwise invisible
         n_sus = max(200, int(math.ceil(1.2 / (dt / args.steps))))
         sclk0 = gpu_sclk_mhz(dev)
@@ -624,8 +642,8 @@ def main():
                             "timed batch against an f64 polyphase convolution with the crate's f32 taps (numpy)"}
 
     # per-kernel times of an overlap mode: a separate SEQUENTIAL pass (with two kernels sharing the chip a per-kernel HIP-event time
-    # would not describe either of them); HIP events on the batch's own stream
-    if region is None:
+    # would not describe either of them); HIP events on the batch's own stream.  A run of its own: --full
+    if args.full and region is None:
         b.timing_enable(True)
         region0 = [b.timing_read(k) for k in range(L.SS_KERNEL_COUNT)]
         for _ in range(max(3, min(args.steps, 10))):
@@ -638,14 +656,17 @@ def main():
     if rank == 0:
         # dominant kernel: the spectrum kernel.  Algorithmic bytes per launch:
         # every input f32 once + every retained bin once = 4 B/sample + 4*W*2*nbins per stream.
+        kernels_timed = region is not None       # (a plain run in an overlap mode has no per-kernel times: their pass is --full's)
+        if not kernels_timed:
+            region = [(0.0, 0)] * L.SS_KERNEL_COUNT
         fft_ms, fft_n_launch = region[L.SS_KERNEL_FFT]
         alg_bytes = count * (frames * 2 * 4 + lay.n_windows * lay.fft_channels * lay.n_bins * 4)
         achieved = alg_bytes / (fft_ms / max(fft_n_launch, 1) * 1e-3) / 1e9 if fft_ms > 0 else None
         kernels = {}
         for k in range(L.SS_KERNEL_COUNT):
             ms, n = region[k]
-            kernels[lib.ss_batch_kernel_name(b._h, k).decode()] = round(ms / max(n, 1), 4)
-        seq_ms = sum(kernels.values())
+            kernels[lib.ss_batch_kernel_name(b._h, k).decode()] = round(ms / max(n, 1), 4) if kernels_timed else None
+        seq_ms = sum(kernels.values()) if kernels_timed else None
         traffic, traffic_src = None, None
         tpath = os.path.join(ROOT, "profiles", "fft_hbm_traffic.json")
         if os.path.exists(tpath):        # PMC counters cannot be read inside this run: committed rocprofv3 passes, labelled as such
@@ -666,7 +687,7 @@ def main():
             "metric": "audio samples/s analyzed (48 kHz stereo)", "value": value, "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-            "dtype": "f32 + f64", "data": "synthetic",
+            "dtype": "f32 + f64", "data": "synthetic", "full": bool(args.full),
             "value_f16x3_split": tp_arith["value_f16x3_split"] if tp_arith else None,
             "true_peak_arithmetic": tp_arith,
             "config": {"workload": (f"{total_streams} streams in total (BASELINE config 4) sharded over {world} GPU(s)" if strong
@@ -694,8 +715,9 @@ def main():
                        "sustained": sustained,
                        "corpus_integrated_lufs": corpus_i, "corpus_lra": corpus_lra,
                        "kernel_ms": kernels, "kernel_ms_note": ("HIP events on the batch's stream around every kernel of the K timed steps themselves (ring of event sets, no host "
-                                                              "synchronisation inside the region)" if timed_in_region else "separate sequential pass, HIP events on the batch's stream"),
-                       "sequential_gpu_ms": round(seq_ms, 4),
+                                                              "synchronisation inside the region)" if timed_in_region else "separate sequential pass, HIP events on the batch's stream"
+                                                              if kernels_timed else "not measured: an overlap mode's separate sequential pass runs with --full"),
+                       "sequential_gpu_ms": round(seq_ms, 4) if kernels_timed else None,
                        "step_hbm_frac": step_alg / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
                        "time_domain_kernel": td},
             "roofline": {"bound": "hbm", "kernel": lib.ss_batch_kernel_name(b._h, L.SS_KERNEL_FFT).decode(),
@@ -711,17 +733,18 @@ def main():
         }
         # PCIe-inclusive rate (informational, never `value`): host f32 -> HBM upload of a slice + its share of a pass
         host = None
-        try:
-            k = min(count, 64)
-            host = np.concatenate([b.download_input(i) for i in range(k)])
-            t0 = time.perf_counter()
-            b.upload(0, host)
-            up = time.perf_counter() - t0
-            out["config"]["pcie_inclusive_samples_per_s"] = host.size / (up + dt / args.steps * k / count)
-            out["config"]["h2d_GBps"] = host.nbytes / up / 1e9
-        except Exception:
-            pass
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            try:
+                k = min(count, 64)
+                host = np.concatenate([b.download_input(i) for i in range(k)])
+                t0 = time.perf_counter()
+                b.upload(0, host)
+                up = time.perf_counter() - t0
+                out["config"]["pcie_inclusive_samples_per_s"] = host.size / (up + dt / args.steps * k / count)
+                out["config"]["h2d_GBps"] = host.nbytes / up / 1e9
+            except Exception:
+                pass
+        if args.full and world == 1 and not args.no_cpu:
             cb, check = cpu_baseline(b, args.rate, args.fft_n, args.hop)
             out["cpu_baseline"] = cb
             out["config"]["self_check_vs_oracle"] = check
@@ -746,7 +769,7 @@ def main():
         if io_floor_ms:
             out["roofline"]["io_floor_ms"] = io_floor_ms
             out["roofline"]["kernel_over_io_floor"] = (fft_ms / max(fft_n_launch, 1)) / io_floor_ms
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             b.close()
             extra = []
             if not strong:

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Refresh the judged measurement set on the GPU box (one call): the bench line, the rocprofv3 kernel-trace summary of
-# the SAME bench command, and PMC passes (each counter group in its own rocprofv3 run, no tracing beside --pmc) over
+# Refresh the judged measurement set on an MI355X (one call): the whole bench line (bench.py --full: roofline floor,
+# CPU baseline, self-check, the other configurations), the rocprofv3 kernel-trace summary of the SAME bench command, and PMC passes (each counter group in its own rocprofv3 run, no tracing beside --pmc) over
 # the config 3 probe (tools/perf_probe.py) and the config 5 probe (tools/probe_cfg5.py).
 # usage: tools/profile_round.sh <tag>     (outputs under tools/out/<tag>/; copy what is judged into profiles/)
 # The first run that fails or times out ends the set.
@@ -12,8 +12,8 @@ out=$root/tools/out/$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 if [ "${SKIP_BENCH:-0}" != 1 ]; then        # (SKIP_BENCH=1: the PMC passes only)
-timeout -k 10 600 python $root/bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
-timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- python $root/bench.py --steps 20 --warmup 5 > $out/kt_bench.json 2> $out/kt.err
+timeout -k 10 600 python $root/bench.py --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err
+timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- python $root/bench.py --steps 20 --warmup 5 --full > $out/kt_bench.json 2> $out/kt.err
 db=$(find $out/kt -name '*.db' -print -quit)
 python $root/tools/rocpd_summary.py "$db" $out/kernel_stats.txt
 rm -rf $out/kt

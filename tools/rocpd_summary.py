@@ -2,7 +2,7 @@
 """Summarise a rocprofv3 rocpd SQLite result (kernel trace and/or PMC) as text.
 
 Kernel rows are grouped by (kernel name, grid size), so the launches of different BASELINE configurations inside one
-bench.py process stay apart (config 3's 1024-stream launches vs the config 2 / config 5 extras of the same kernel).
+`bench.py --full` process stay apart (config 3's 1024-stream launches vs the config 2 / config 5 extras of the same kernel).
 For every group two averages are given: over all launches, and over the launches that ran ALONE on the device (no other
 kernel of >= 50 us overlapped them in time) — bench.py's overlapped steps run the spectrum kernel beside the time-domain
 kernel, which stretches both; its per-kernel HIP-event numbers come from the sequential timing pass, i.e. they must
