@@ -800,6 +800,89 @@ int ss_batch_apply_gain_plan(const ss_batch *b, uint32_t *tile_frames);
 /* [stream][channel]; cap_records counts records */
 int ss_batch_download_gain_stats(ss_batch *b, ss_gain_channel *out, size_t cap_records);
 int ss_batch_download_pcm(ss_batch *b, uint32_t first, uint32_t count, void *pcm, size_t cap_bytes, int format, const ss_pcm_dither *dither);
+/* Batch limiter: a look-ahead peak limiter over the resident corpus — the gain a loudness law asks for, applied in the same sweep
+ * that shapes only the transients which would cross the ceiling.  Not in the reference.  Feed-forward: every reduction in it is a
+ * minimum or a sum of integers, so any evaluation order, tiling or prefix scheme gives the same bits.
+ *
+ * For one stream of F frames (its own length), the item's f32 gain g, ceiling > 0 (f32), look-ahead L and hold H in frames,
+ * ONE = 2^30:
+ *  1. Level.  m[n] is an f32 over the SELECTED channels, which are linked: per channel |x[n][c]| (SS_LIMIT_SAMPLE_PEAK) or exactly
+ *     what ss_batch_peak_series computes for that frame (SS_LIMIT_TRUE_PEAK: branch 0 and every interpolated branch, each one f32
+ *     FMA chain, oldest tap first, fmaxf over the branches so that a NaN branch leaves the others standing, x[n] = 0 for n < 0, the
+ *     batch's true_peak_factor rule — at 192 kHz and above there is no interpolation and the two detectors are the same bits).
+ *     m[n] is the largest FINITE value among the selected channels, 0 where none is finite: a sample that is NaN or +-inf is not
+ *     heard.  A = taps - 1 (11 at factor 4, 23 at factor 2) in true-peak mode with an interpolator, else 0.
+ *  2. Required gain.  v = (double)m[n] * (double)fabsf(g), which is exact.  r_q[n] = (uint32)floor((double)ceiling / v * ONE) where
+ *     v is finite and v > (double)ceiling, else ONE: a NaN or infinite level (ss_limit_curve takes any) never moves the gain, and
+ *     non-finite samples pass through as x * g would leave them.
+ *  3. Window minimum.  For any integer k, w_q[k] = min r_q[j] over j in [k - H, k + L + A] and [0, F); ONE over an empty range.
+ *     The gain is already down at frame 0 when a peak lies within L frames of the start, and the A extra frames put every frame
+ *     whose sample enters an over-ceiling interpolated output at or below that output's required gain.
+ *  4. Window sum.  S[n] = sum of w_q[n - j] over j = 0 .. L, a u64 below 2^42; c[n] = (double)S[n] / (double)((L + 1) * ONE), one
+ *     f64 division, so a full sum gives exactly 1.  Every window in the sum contains n, hence c[n] <= r_q[n] / ONE, and
+ *     c[m] <= r_q[n] / ONE for m in [n - A, n].
+ *  5. Output.  y = (float)((double)x * ((double)g * c[n])) for the selected channels of frames [0, F): every operation rounded on
+ *     its own (no fused multiply-add).  Where c[n] = 1 this is the plain f32 product x * g, the bits ss_batch_apply_gain writes for
+ *     one point of gain g, so a separate ss_batch_apply_gain is not needed.
+ * In both detectors every finite |y| <= ceiling holds EXACTLY (floor quantisation, monotone rounding) — in true-peak mode with the
+ * exception of the A frames behind an infinite sample of the same channel, whose value is infinite.  The TRUE peak behind the
+ * call is not bounded by construction — the gain moves inside the interpolator's support; DESIGN.md section 3.3.6 has it measured.
+ * ss_limit_curve is steps 2 to 4 on the host, no device needed: level[0 .. n) are the m[n], `advance` is A; it writes r_q[n], sum[n]
+ * and curve[n] = c[n] where the pointer is not NULL.  NULL cfg, NULL level with n > 0, a NaN or infinite gain, a ceiling that is
+ * NaN, <= 0 or infinite, lookahead or hold above its maximum, advance > 23: SS_ERR_INVALID_ARG (the other config fields are not
+ * read).
+ *
+ * ss_batch_limit rewrites the resident f32 corpus IN PLACE.  THE OPERATION IS LOSSY: keep the source if the result may have to be
+ * taken back.  RESULTS OF EARLIER PASSES, SERIES AND SCANS DESCRIBE THE CORPUS BEFORE THE CALL: run them again for the corpus behind
+ * it.  Streams without an item, unselected channels and frames at or behind F stay byte for byte (the latter are never read); a
+ * NaN stays a NaN with an unspecified payload.  Items name each stream at most once, in any order; the list is copied before the
+ * call returns, the work is queued on the batch's stream like the other follow-up calls, and nothing is waited for.
+ * channel_mask 0 means every channel.  The sweep is two launches per group of streams — the detector writes r_q of the tiles that
+ * hold a frame over the ceiling to a scratch buffer of 4 bytes x frames_per_stream x group_streams (scratch_bytes bounds it, 0: 256
+ * MiB; allocated at the first call, grown only), then the tiles are rewritten — and the groups follow one another when the items
+ * do not fit.  ss_batch_limit_plan reports tile_frames, group_streams and the scratch bytes a call with n_items items would use.
+ * Per stream the call leaves one ss_limit_stream (untouched streams: touched = 0, first_limited = UINT64_MAX, min_sum = (L + 1) *
+ * 2^30) and per (stream, channel) one ss_gain_channel as ss_batch_apply_gain defines it, taken over [0, F) as the corpus stands
+ * behind the call; they are the limiter's own (ss_batch_download_gain_stats keeps returning what the last ss_batch_apply_gain
+ * left).  Only integer atomics meet across workgroups, so two calls on the same bytes leave the same bytes.
+ * Status codes, all checked before anything is queued: cfg == NULL, items == NULL with n_items > 0, a duplicate stream or one >=
+ * n_streams, a NaN or infinite gain, a ceiling that is NaN, <= 0 or infinite, a clip_level that is NaN or <= 0, lookahead or hold
+ * above its maximum, an unknown detector, a mask bit at or above the channel count, reserved != 0: SS_ERR_INVALID_ARG;
+ * ss_batch_download_limit_stats before the first call: SS_ERR_INVALID_MODE; a `cap` too small, a scratch_bytes that cannot hold one
+ * stream: SS_ERR_CAPACITY.  n_items == 0 is valid.  A batch that never calls any of this allocates and launches exactly what it did
+ * before. */
+enum { SS_LIMIT_SAMPLE_PEAK = 0, SS_LIMIT_TRUE_PEAK = 1 };
+#define SS_LIMIT_LOOKAHEAD_MAX 2048
+#define SS_LIMIT_HOLD_MAX      8192
+typedef struct ss_limit_item {
+    uint32_t stream;
+    float    gain;                /* linear, finite; negative flips the polarity */
+} ss_limit_item;                  /* 8 bytes */
+typedef struct ss_limit_config {
+    uint64_t channel_mask;        /* 0: every channel; else bit c selects channel c */
+    float    ceiling;             /* linear, > 0, finite */
+    float    clip_level;          /* of the per-channel records: linear, > 0; +inf: nothing is over */
+    uint32_t lookahead, hold;     /* L and H in frames */
+    uint32_t detector;            /* SS_LIMIT_SAMPLE_PEAK, SS_LIMIT_TRUE_PEAK */
+    uint32_t reserved;            /* 0 */
+    uint64_t scratch_bytes;       /* 0: the default of 256 MiB */
+} ss_limit_config;                /* 40 bytes */
+typedef struct ss_limit_stream {
+    uint64_t n_limited;           /* frames with S[n] < (L + 1) * 2^30 */
+    uint64_t first_limited;       /* the lowest such frame; UINT64_MAX if none */
+    uint64_t min_sum;             /* min S[n]; (L + 1) * 2^30 if none: the lowest gain is min_sum / ((L + 1) * 2^30) */
+    uint32_t touched;             /* 1: the stream had an item */
+    uint32_t reserved;
+} ss_limit_stream;                /* 32 bytes */
+/* host arithmetic; any output may be NULL */
+int ss_limit_curve(const float *level, uint64_t n, float gain, const ss_limit_config *cfg, uint32_t advance,
+                   uint32_t *r_q, uint64_t *sum, double *curve);
+int ss_batch_limit(ss_batch *b, const ss_limit_item *items, uint32_t n_items, const ss_limit_config *cfg);
+int ss_batch_limit_plan(const ss_batch *b, const ss_limit_config *cfg, uint32_t n_items,
+                        uint32_t *tile_frames, uint32_t *group_streams, uint64_t *scratch_bytes);
+/* streams [n_streams] and channels [stream][channel]; either may be NULL; waits */
+int ss_batch_download_limit_stats(ss_batch *b, ss_limit_stream *streams, size_t cap_streams,
+                                  ss_gain_channel *channels, size_t cap_records);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

@@ -67,6 +67,7 @@ SYMBOLS = [
     "ss_batch_download_region_pairs", "ss_batch_download_group_pairs",
     "ss_normalisation_gain", "ss_gain_envelope", "ss_batch_apply_gain", "ss_batch_apply_gain_plan", "ss_batch_download_gain_stats",
     "ss_batch_download_pcm",
+    "ss_limit_curve", "ss_batch_limit", "ss_batch_limit_plan", "ss_batch_download_limit_stats",
     "ss_td_streaming_plan", "ss_session_last_tick_forms",
 ]
 
@@ -84,6 +85,8 @@ SS_SIGNAL_SILENCE, SS_SIGNAL_CLIP = 0, 1
 SS_PCM_U8, SS_PCM_S16, SS_PCM_S24, SS_PCM_S32, SS_PCM_F32, SS_PCM_F64 = 1, 2, 3, 4, 5, 6
 SS_GAIN_LIMITED_PEAK, SS_GAIN_LIMITED_MAX, SS_GAIN_LIMITED_MIN, SS_GAIN_UNMEASURED = 1, 2, 4, 8
 SS_DITHER_NONE, SS_DITHER_TPDF = 0, 1
+SS_LIMIT_SAMPLE_PEAK, SS_LIMIT_TRUE_PEAK = 0, 1
+SS_LIMIT_LOOKAHEAD_MAX, SS_LIMIT_HOLD_MAX = 2048, 8192
 SS_GAIN_FIXED, SS_GAIN_REFERENCE = 0, 1
 SS_COMM_RCCL, SS_COMM_HOST_TCP = 0, 1
 SS_TP_ARITH_F16X3, SS_TP_ARITH_F32 = 0, 1
@@ -235,6 +238,20 @@ class GainChannel(C.Structure):            # ss_gain_channel
 
 class PcmDither(C.Structure):              # ss_pcm_dither
     _fields_ = [("seed", C.c_uint64), ("kind", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LimitItem(C.Structure):              # ss_limit_item
+    _fields_ = [("stream", C.c_uint32), ("gain", C.c_float)]
+
+
+class LimitConfig(C.Structure):            # ss_limit_config
+    _fields_ = [("channel_mask", C.c_uint64), ("ceiling", C.c_float), ("clip_level", C.c_float), ("lookahead", C.c_uint32),
+                ("hold", C.c_uint32), ("detector", C.c_uint32), ("reserved", C.c_uint32), ("scratch_bytes", C.c_uint64)]
+
+
+class LimitStream(C.Structure):            # ss_limit_stream
+    _fields_ = [("n_limited", C.c_uint64), ("first_limited", C.c_uint64), ("min_sum", C.c_uint64), ("touched", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class PairSums(C.Structure):               # ss_pair_sums
@@ -477,6 +494,10 @@ def _bind(lib):
         "ss_batch_apply_gain_plan": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "ss_batch_download_gain_stats": (C.c_int, [vp, C.POINTER(GainChannel), C.c_size_t]),
         "ss_batch_download_pcm": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_int, C.POINTER(PcmDither)]),
+        "ss_limit_curve": (C.c_int, [f32p, C.c_uint64, C.c_float, C.POINTER(LimitConfig), C.c_uint32, C.POINTER(C.c_uint32), u64p, f64p]),
+        "ss_batch_limit": (C.c_int, [vp, C.POINTER(LimitItem), C.c_uint32, C.POINTER(LimitConfig)]),
+        "ss_batch_limit_plan": (C.c_int, [vp, C.POINTER(LimitConfig), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p]),
+        "ss_batch_download_limit_stats": (C.c_int, [vp, C.POINTER(LimitStream), C.c_size_t, C.POINTER(GainChannel), C.c_size_t]),
         "ss_td_streaming_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint64, C.POINTER(StreamingPlan)]),
         "ss_session_last_tick_forms": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     }

@@ -97,6 +97,35 @@ def gain_envelope(points, frames):
     return out
 
 
+# batch limiter (ss_limit_item, ss_limit_stream); the per-channel records are GAIN_CHANNEL_DTYPE
+LIMIT_ITEM_DTYPE = np.dtype(L.LimitItem)
+LIMIT_STREAM_DTYPE = np.dtype(L.LimitStream)
+
+
+def _limit_items(items):
+    """An item list as a contiguous LIMIT_ITEM_DTYPE array: such an array as it is, else rows (stream, gain)."""
+    if isinstance(items, np.ndarray) and items.dtype == LIMIT_ITEM_DTYPE:
+        return np.ascontiguousarray(items).reshape(-1)
+    out = np.zeros(len(items), LIMIT_ITEM_DTYPE)
+    for i, (stream, gain) in enumerate(items):
+        out[i] = (stream, gain)
+    return out
+
+
+def limit_curve(level, gain, ceiling, lookahead, hold, advance=0):
+    """ss_limit_curve: the limiter's gain curve of ONE stream from its frames' levels (f32), on the host — (r_q u32, S u64, c f64)
+    per frame: the required gain floor(ceiling / (level |gain|) 2^30) where the product is finite and over the ceiling (else 2^30),
+    its minimum over [k - hold, k + lookahead + advance] summed over the lookahead + 1 windows that hold the frame, and that sum
+    over (lookahead + 1) 2^30.  lookahead and hold are frames."""
+    m = np.ascontiguousarray(level, dtype=np.float32).reshape(-1)
+    cfg = L.LimitConfig(0, float(ceiling), 1.0, int(lookahead), int(hold), 0, 0, 0)
+    r_q, s, c = np.zeros(m.size, np.uint32), np.zeros(m.size, np.uint64), np.zeros(m.size, np.float64)
+    _check(L.lib().ss_limit_curve(m.ctypes.data_as(C.POINTER(C.c_float)), m.size, float(gain), C.byref(cfg), int(advance),
+                                  r_q.ctypes.data_as(C.POINTER(C.c_uint32)), s.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                  c.ctypes.data_as(C.POINTER(C.c_double))))
+    return r_q, s, c
+
+
 def normalisation_gain(loudness_lufs, peak_linear, target_lufs, max_true_peak_dbtp=np.inf, max_gain_db=np.inf, min_gain_db=-np.inf):
     """ss_normalisation_gain over arrays: (gain_db f64, gain f32, limited_by u32) for every (loudness, linear peak).  The law: an
     unmeasured loudness (NaN, +-inf) gives 0 dB and SS_GAIN_UNMEASURED; else target - loudness, cut to the headroom under the
@@ -672,10 +701,51 @@ class Batch:
         _check(L.lib().ss_batch_download_pcm(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p), out.nbytes, int(format), dither))
         return out
 
-    def normalise(self, target_lufs, max_true_peak_dbtp=float("inf"), max_gain_db=float("inf"), min_gain_db=float("-inf"), album=False):
+    # -- batch limiter: the gain and a look-ahead gain curve that shapes only what would cross the ceiling, in one sweep
+    def _limit_config(self, ceiling, lookahead_s, hold_s, true_peak, channel_mask, clip_level, scratch_bytes):
+        rate = int(self.cfg.sample_rate)
+        frames = [int(round(float(s) * rate)) for s in (lookahead_s, hold_s)]
+        if not 0 <= frames[0] <= L.SS_LIMIT_LOOKAHEAD_MAX or not 0 <= frames[1] <= L.SS_LIMIT_HOLD_MAX:
+            raise ValueError("limiter: a look-ahead of %d or a hold of %d frames is outside [0, %d] / [0, %d]"
+                             % (frames[0], frames[1], L.SS_LIMIT_LOOKAHEAD_MAX, L.SS_LIMIT_HOLD_MAX))
+        return L.LimitConfig(int(channel_mask), float(ceiling), float(clip_level), frames[0], frames[1],
+                             L.SS_LIMIT_TRUE_PEAK if true_peak else L.SS_LIMIT_SAMPLE_PEAK, 0, int(scratch_bytes))
+
+    def limit(self, items, ceiling, lookahead_s=0.0015, hold_s=0.010, true_peak=True, channel_mask=0, clip_level=1.0, scratch_bytes=0):
+        """Queue the limiter's sweep over the resident corpus, in place: `items` is a LIMIT_ITEM_DTYPE array or rows (stream, gain),
+        each stream at most once; a stream's samples become x * gain * c[n] with the gain curve c of limit_curve from the linked
+        level of the selected channels (true_peak: the batch's interpolator, else the samples' magnitudes), so that every finite
+        |y| <= ceiling.  Seconds become frames by round(s * rate); a value beyond the maxima is refused.  Lossy; results of earlier
+        passes and series describe the corpus before the call."""
+        it = _limit_items(items)
+        cfg = self._limit_config(ceiling, lookahead_s, hold_s, true_peak, channel_mask, clip_level, scratch_bytes)
+        _check(L.lib().ss_batch_limit(self._h, it.ctypes.data_as(C.POINTER(L.LimitItem)) if it.size else None, it.size, C.byref(cfg)))
+
+    def limit_plan(self, n_items, ceiling=1.0, lookahead_s=0.0015, hold_s=0.010, true_peak=True, channel_mask=0, clip_level=1.0, scratch_bytes=0):
+        """(tile_frames, group_streams, scratch_bytes) of a limit() call with n_items items: the frames one workgroup sweeps, the
+        streams whose required gains the scratch buffer holds at a time (the sweep runs group after group), and that buffer's bytes."""
+        cfg = self._limit_config(ceiling, lookahead_s, hold_s, true_peak, channel_mask, clip_level, scratch_bytes)
+        t, g, sb = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check(L.lib().ss_batch_limit_plan(self._h, C.byref(cfg), int(n_items), C.byref(t), C.byref(g), C.byref(sb)))
+        return t.value, g.value, sb.value
+
+    def limit_stats(self):
+        """What the last limit() left: (LIMIT_STREAM_DTYPE [n_streams], GAIN_CHANNEL_DTYPE [n_streams][channels]) — the frames whose
+        gain was lowered, the first of them and the lowest window sum per stream, and gain_stats()' records of the corpus behind it."""
+        n = int(self.cfg.n_streams)
+        streams, channels = np.zeros(n, LIMIT_STREAM_DTYPE), np.zeros((n, int(self.cfg.channels)), GAIN_CHANNEL_DTYPE)
+        _check(L.lib().ss_batch_download_limit_stats(self._h, streams.ctypes.data_as(C.POINTER(L.LimitStream)), streams.size,
+                                                     channels.ctypes.data_as(C.POINTER(L.GainChannel)), channels.size))
+        return streams, channels
+
+    def normalise(self, target_lufs, max_true_peak_dbtp=float("inf"), max_gain_db=float("inf"), min_gain_db=float("-inf"), album=False,
+                  limiter=None):
         """Bring every stream to `target_lufs` under a true-peak ceiling (normalisation_gain) and apply the gains on the device, one
         constant gain per stream; album: ONE gain for all streams, from the loudness and the peak of all of them pooled.  Needs
         L.SS_BATCH_LUFS; runs a pass if none has run, then peak_series(), and replaces the peak (album: and loudness) region list.
+        limiter: a dict of limit()'s keywords (lookahead_s, hold_s, true_peak, ...) — the law is then evaluated with no peak ceiling
+        (limited_by never reads SS_GAIN_LIMITED_PEAK) and the one sweep is limit() with those gains under the ceiling
+        10^(max_true_peak_dbtp / 20), which must be finite.
         Returns a NORMALISE_DTYPE array [n_streams]: the loudness and linear peak read, gain_db, gain, limited_by."""
         if not int(self.cfg.flags) & L.SS_BATCH_LUFS:
             raise ValueError("normalise needs a batch with SS_BATCH_LUFS")
@@ -694,8 +764,16 @@ class Batch:
             self.peak_regions(whole, 1)
             out["loudness"] = [r.integrated_lufs for r in self.results()]
             out["peak"] = [r.true_peak for r in self.region_peaks()]
-        out["gain_db"], out["gain"], out["limited_by"] = normalisation_gain(out["loudness"], out["peak"], target_lufs, max_true_peak_dbtp,
+        if limiter is not None and not np.isfinite(max_true_peak_dbtp):
+            raise ValueError("normalise with a limiter needs a finite max_true_peak_dbtp")
+        out["gain_db"], out["gain"], out["limited_by"] = normalisation_gain(out["loudness"], out["peak"], target_lufs,
+                                                                            max_true_peak_dbtp if limiter is None else float("inf"),
                                                                             max_gain_db, min_gain_db)
+        if limiter is not None:
+            items = np.zeros(n, LIMIT_ITEM_DTYPE)
+            items["stream"], items["gain"] = np.arange(n), out["gain"]
+            self.limit(items, 10.0 ** (float(max_true_peak_dbtp) / 20.0), **limiter)
+            return out
         points = np.zeros(n, GAIN_POINT_DTYPE)
         points["stream"], points["gain"] = np.arange(n), out["gain"]
         self.apply_gain(points)

@@ -187,6 +187,16 @@ struct Gain {
     DevBuf<unsigned char> table;
 };
 
+// limiter (ss_batch_limit): all of it allocated at the batch's first call and grown only, so a batch that never asks holds none of it.
+// One table per call: the stream records [stream], the channel records [stream][channels] and the items go through the stage in one
+// upload; the tiles' minima [item][tiles_cap] lie behind them and are the kernels' own.  scratch: the r_q rows of one group of items.
+struct Limit {
+    bool done = false;                          // queued at least once: there is something to download
+    HostStage stage;
+    DevBuf<unsigned char> table;
+    DevBuf<uint32_t> scratch;
+};
+
 // spectrogram (ss_batch_spectrogram): all of it allocated at the batch's first call and grown by a larger view, so a batch that
 // never asks holds none of it
 struct Spectrogram {
@@ -246,6 +256,7 @@ struct ss_batch {
     SignalScan scan;
     Pairs pair;
     Gain gain;
+    Limit limit;
     Spectrogram spectrogram;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
@@ -2095,6 +2106,172 @@ int ss_batch_download_gain_stats(ss_batch *b, ss_gain_channel *out, size_t cap_r
     const Gain &gn = b->gain;
     return fetch_records(b, gn.done, out, cap_records > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap_records, b->cfg.n_streams * b->cfg.channels,
                          reinterpret_cast<const ssk::GainChannel *>(gn.table.p));
+}
+
+// ---- batch limiter: the gain curve (host arithmetic), the plan, the two launches per group of items ---------------------------------
+static_assert(offsetof(ss_limit_item, gain) == 4 && offsetof(ss_limit_config, ceiling) == 8 && offsetof(ss_limit_config, clip_level) == 12 &&
+              offsetof(ss_limit_config, lookahead) == 16 && offsetof(ss_limit_config, detector) == 24 && offsetof(ss_limit_config, scratch_bytes) == 32 &&
+              offsetof(ss_limit_stream, min_sum) == 16 && offsetof(ss_limit_stream, touched) == 24, "limiter call layouts");
+constexpr uint64_t kLimitScratchDefault = 256ull << 20;
+
+// what ss_limit_curve and ss_batch_limit both ask of the gain and of the curve's part of a config
+static bool limit_curve_args_ok(float gain, const ss_limit_config *cfg)
+{
+    return cfg && std::isfinite(gain) && cfg->ceiling > 0.0f && std::isfinite(cfg->ceiling) &&          // (NaN fails the comparison)
+           cfg->lookahead <= SS_LIMIT_LOOKAHEAD_MAX && cfg->hold <= SS_LIMIT_HOLD_MAX;
+}
+
+int ss_limit_curve(const float *level, uint64_t n, float gain, const ss_limit_config *cfg, uint32_t advance, uint32_t *r_q, uint64_t *sum, double *curve)
+{
+    if (!limit_curve_args_ok(gain, cfg) || (!level && n) || advance > 23u) return SS_ERR_INVALID_ARG;
+    if (!n) return SS_OK;
+    const uint64_t L = cfg->lookahead, H = cfg->hold, A = advance, one = ssk::kLimitOne;
+    // step 2
+    std::vector<uint32_t> rq(n);
+    const double ag = std::fabs((double)gain), ceiling = (double)cfg->ceiling;
+    for (uint64_t i = 0; i < n; i++) {
+        const double v = (double)level[i] * ag;
+        rq[i] = std::isfinite(v) && v > ceiling ? (uint32_t)std::floor(ceiling / v * (double)one) : (uint32_t)one;
+    }
+    // step 3: w[i] is w_q of frame k = i - L, the minimum of r_q over [k - H, k + L + A] cut to [0, n) — never empty for these k.
+    // The window's ends only move forward, so a queue of candidates with ascending values holds its minimum in front.
+    std::vector<uint32_t> w(n + L);
+    {
+        std::vector<uint64_t> queue(n);
+        uint64_t head = 0, tail = 0, next = 0;
+        for (uint64_t i = 0; i < n + L; i++) {
+            const uint64_t hi = i + A < n - 1 ? i + A : n - 1, lo = i > L + H ? i - L - H : 0;
+            for (; next <= hi; next++) {
+                while (tail > head && rq[queue[tail - 1]] >= rq[next]) tail--;
+                queue[tail++] = next;
+            }
+            while (queue[head] < lo) head++;
+            w[i] = rq[queue[head]];
+        }
+    }
+    // step 4: S[m] = w[m .. m + L] summed, a sum that slides
+    const uint64_t full = (L + 1) * one;
+    uint64_t s = 0;
+    for (uint64_t i = 0; i <= L; i++) s += w[i];
+    for (uint64_t m = 0; m < n; m++) {
+        if (r_q) r_q[m] = rq[m];
+        if (sum) sum[m] = s;
+        if (curve) curve[m] = (double)s / (double)full;
+        if (m + 1 < n) s = s + w[m + L + 1] - w[m];
+    }
+    return SS_OK;
+}
+
+// every check of a limiter config against the batch, and the detector it means: factor 4, 2 or 0
+static int check_limit_config(const ss_batch *b, const ss_limit_config *cfg, int *factor)
+{
+    if (!cfg || !(cfg->ceiling > 0.0f) || !std::isfinite(cfg->ceiling) || !(cfg->clip_level > 0.0f) || cfg->reserved) return SS_ERR_INVALID_ARG;
+    if (cfg->lookahead > SS_LIMIT_LOOKAHEAD_MAX || cfg->hold > SS_LIMIT_HOLD_MAX || cfg->detector > (uint32_t)SS_LIMIT_TRUE_PEAK) return SS_ERR_INVALID_ARG;
+    const ss_batch_config &c = b->cfg;
+    if (c.channels < 64u && (cfg->channel_mask >> c.channels)) return SS_ERR_INVALID_ARG;
+    *factor = cfg->detector == SS_LIMIT_TRUE_PEAK ? (c.true_peak_factor ? (int)c.true_peak_factor : sst::true_peak_factor_for_rate(c.sample_rate)) : 0;
+    return SS_OK;
+}
+
+static ssk::LimitPlan batch_limit_plan(const ss_batch *b, const ss_limit_config *cfg, uint32_t n_items)
+{
+    return ssk::plan_limit(b->cfg.frames_per_stream, n_items, cfg->scratch_bytes ? cfg->scratch_bytes : kLimitScratchDefault);
+}
+
+int ss_batch_limit_plan(const ss_batch *b, const ss_limit_config *cfg, uint32_t n_items, uint32_t *tile_frames, uint32_t *group_streams, uint64_t *scratch_bytes)
+{
+    if (!b) return SS_ERR_INVALID_ARG;
+    int factor = 0;
+    int rc = check_limit_config(b, cfg, &factor);
+    if (rc) return rc;
+    const ssk::LimitPlan plan = batch_limit_plan(b, cfg, n_items);
+    if (n_items && !plan.group_streams) return SS_ERR_CAPACITY;
+    if (tile_frames) *tile_frames = plan.tile_frames;
+    if (group_streams) *group_streams = plan.group_streams;
+    if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+    return SS_OK;
+}
+
+int ss_batch_limit(ss_batch *b, const ss_limit_item *items, uint32_t n_items, const ss_limit_config *cfg)
+{
+    SS_ON_DEVICE(b);
+    if (!b || (!items && n_items)) return SS_ERR_INVALID_ARG;
+    ssk::LimitParams p{};
+    int rc = check_limit_config(b, cfg, &p.factor);
+    if (rc) return rc;
+    const ss_batch_config &c = b->cfg;
+    const uint32_t C = c.channels;
+    {
+        std::vector<bool> seen(c.n_streams, false);
+        for (uint32_t i = 0; i < n_items; i++) {
+            if (items[i].stream >= c.n_streams || seen[items[i].stream] || !std::isfinite(items[i].gain)) return SS_ERR_INVALID_ARG;
+            seen[items[i].stream] = true;
+        }
+    }
+    const ssk::LimitPlan plan = batch_limit_plan(b, cfg, n_items);
+    if (n_items && !plan.group_streams) return SS_ERR_CAPACITY;
+    const uint64_t records = (uint64_t)c.n_streams * C;
+    if ((uint64_t)n_items * plan.tiles_cap > 0x7FFFFFFFull || records > 0xFFFFFFFFull) return SS_ERR_UNSUPPORTED;
+    if (p.factor) {
+        uint32_t len = 0;
+        rc = ss_inspect_true_peak(p.factor, p.taps, 36, &len);
+        if (rc) return rc;
+        p.advance = len - 1u;
+    }
+    // the table: stream records | channel records | items | the tiles' minima (not uploaded)
+    const size_t ch_at = (size_t)c.n_streams * sizeof(ssk::LimitStream), items_at = ch_at + (size_t)records * sizeof(ssk::GainChannel);
+    const size_t bytes = items_at + (size_t)n_items * sizeof(ssk::LimitItem), min_at = (bytes + 15) & ~(size_t)15;
+    Limit &lm = b->limit;
+    HIPCHK(lm.table.ensure(min_at + (size_t)n_items * plan.tiles_cap * sizeof(uint32_t)));       // (a buffer that grows is freed first: hipFree waits for whatever still uses it)
+    HIPCHK(lm.scratch.ensure((size_t)(plan.scratch_bytes / sizeof(uint32_t))));
+    HIPCHK(lm.stage.take(bytes));
+    unsigned char *h = lm.stage.buf.p;
+    {
+        ssk::LimitStream *ls = reinterpret_cast<ssk::LimitStream *>(h);
+        ssk::GainChannel *rec = reinterpret_cast<ssk::GainChannel *>(h + ch_at);
+        const uint64_t full = ((uint64_t)cfg->lookahead + 1u) * ssk::kLimitOne;
+        for (uint32_t s = 0; s < c.n_streams; s++) ls[s] = {0ull, ~0ull, full, 0u, 0u};
+        for (uint64_t i = 0; i < records; i++) rec[i] = {0.f, 0u, 0ull, ~0ull, 0ull};
+        for (uint32_t i = 0; i < n_items; i++) {
+            ls[items[i].stream].touched = 1u;
+            for (uint32_t ch = 0; ch < C; ch++) rec[(size_t)items[i].stream * C + ch].touched = 1u;
+        }
+        if (n_items) std::memcpy(h + items_at, items, (size_t)n_items * sizeof(ssk::LimitItem));
+    }
+    HIPCHK(lm.stage.queue(lm.table.p, bytes, b->stream));
+    p.pcm = b->pcm.p; p.stream_stride = c.frames_per_stream * C; p.n_frames = c.frames_per_stream;
+    p.frames_of = b->ragged_ptr(b->ragged.frames_d);
+    p.streams = reinterpret_cast<ssk::LimitStream *>(lm.table.p);
+    p.stats = reinterpret_cast<ssk::GainChannel *>(lm.table.p + ch_at);
+    p.items = reinterpret_cast<const ssk::LimitItem *>(lm.table.p + items_at);
+    p.tile_min = reinterpret_cast<uint32_t *>(lm.table.p + min_at);
+    p.scratch = lm.scratch.p;
+    p.channel_mask = cfg->channel_mask ? cfg->channel_mask : (C < 64u ? (1ull << C) - 1ull : ~0ull);
+    p.channels = C; p.tiles_cap = plan.tiles_cap;
+    uint32_t clip_bits;
+    std::memcpy(&clip_bits, &cfg->clip_level, sizeof clip_bits);
+    p.clip_bits = std::isinf(cfg->clip_level) ? 0x7F800001u : clip_bits;
+    p.stereo = C == 2u && p.channel_mask == 3ull ? 1u : 0u;
+    p.lookahead = cfg->lookahead; p.hold = cfg->hold; p.ceiling = cfg->ceiling;
+    for (uint32_t first = 0; first < n_items; first += plan.group_streams) {
+        p.item_first = first; p.n_group = n_items - first < plan.group_streams ? n_items - first : plan.group_streams;
+        HIPCHK(ssk::launch_limit(p, b->stream));
+    }
+    lm.done = true;
+    return SS_OK;
+}
+
+int ss_batch_download_limit_stats(ss_batch *b, ss_limit_stream *streams, size_t cap_streams, ss_gain_channel *channels, size_t cap_records)
+{
+    SS_ON_DEVICE(b);
+    if (!b) return SS_ERR_INVALID_ARG;
+    const Limit &lm = b->limit;
+    if (!lm.done) return SS_ERR_INVALID_MODE;
+    const uint32_t n = b->cfg.n_streams, records = n * b->cfg.channels;
+    if ((streams && cap_streams < n) || (channels && cap_records < records)) return SS_ERR_CAPACITY;
+    if (streams) HIPCHK(hipMemcpyAsync(streams, lm.table.p, (size_t)n * sizeof(ss_limit_stream), hipMemcpyDeviceToHost, b->stream));
+    if (channels) HIPCHK(hipMemcpyAsync(channels, lm.table.p + (size_t)n * sizeof(ss_limit_stream), (size_t)records * sizeof(ss_gain_channel), hipMemcpyDeviceToHost, b->stream));
+    return ss_batch_sync(b);
 }
 
 int ss_batch_download_pcm(ss_batch *b, uint32_t first, uint32_t count, void *pcm, size_t cap_bytes, int format, const ss_pcm_dither *dither)

@@ -1,5 +1,5 @@
 // ss_kernels.h — parameter blocks and launchers of the gfx950 kernels.
-// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_pair_series.hip, ss_apply_gain.hip, ss_bank_signal_watch.hip, ss_bank_pair_watch.hip, ss_util.hip.
+// Host code (ss_host.cpp, ss_analyzer.cpp, ss_batch.cpp, ss_session.cpp, ss_ingest.cpp, ss_meter_bank.cpp) sees only this header; device code lives in ss_fft.hip, ss_time_domain.hip, ss_loudness.hip, ss_spectrum_stats.hip, ss_spectrum_regions.hip, ss_spectrogram.hip, ss_peak_series.hip, ss_signal_scan.hip, ss_pair_series.hip, ss_apply_gain.hip, ss_limiter.hip, ss_bank_signal_watch.hip, ss_bank_pair_watch.hip, ss_util.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -553,6 +553,42 @@ struct ApplyGainParams {
 };
 // one workgroup per (touched stream, tile); untouched streams cost nothing
 hipError_t launch_apply_gain(const ApplyGainParams &p, hipStream_t s);
+// Limiter (ss_batch_limit; ss_limiter.hip): the resident corpus times an item's gain and a look-ahead gain curve, in place.  Per
+// group of items two launches: k_limit_detect leaves every tile's minimum required gain in tile_min and the r_q of the tiles that
+// hold a frame over the ceiling in the group's scratch rows, k_limit_apply rewrites the tiles.  The records are ss_limit_stream and
+// ss_gain_channel, initialised by the caller; the kernels add to them with integer atomics.
+constexpr uint32_t kLimitTileFrames = 4096;                      // frames one workgroup detects, and sweeps
+constexpr uint32_t kLimitOne = 1u << 30;                         // the gain 1 as an integer
+using LimitItem = ss_limit_item;
+using LimitStream = ss_limit_stream;
+static_assert(sizeof(ss_limit_item) == 8 && sizeof(ss_limit_stream) == 32 && sizeof(ss_limit_config) == 40, "limiter records");
+struct LimitPlan { uint32_t tile_frames, tiles_cap, group_streams; uint64_t scratch_bytes; };
+// tiles_cap = ceil(n_frames / tile_frames); group_streams: the items whose scratch rows (4 bytes x n_frames each) fit scratch_bytes
+// together, n_items at most; scratch_bytes: what they take
+LimitPlan plan_limit(uint64_t n_frames, uint32_t n_items, uint64_t scratch_bytes);
+struct LimitParams {
+    float *pcm;                      // [stream][frame][channels] f32, 16-byte aligned; read and written
+    uint64_t stream_stride;          // floats between streams
+    uint64_t n_frames;               // frames of a slot
+    const uint64_t *frames_of;       // ragged batches: each stream's own frames (nullable = n_frames for all)
+    const LimitItem *items;          // [items of the call]
+    uint32_t *tile_min;              // [items of the call][tiles_cap]
+    uint32_t *scratch;               // [group_streams][n_frames]: r_q of the launch's items, row = item - item_first
+    LimitStream *streams;            // [stream], initialised by the caller (zeros, first_limited = ~0, min_sum = (L + 1) 2^30)
+    GainChannel *stats;              // [stream][channels], initialised by the caller (zeros, first_over = ~0)
+    uint64_t channel_mask;           // bit c: channel c is heard and multiplied (the caller has resolved 0 to all channels)
+    uint32_t item_first, n_group;    // this launch's items [item_first, item_first + n_group)
+    uint32_t channels, tiles_cap;    // tiles_cap: plan_limit
+    uint32_t clip_bits;              // the bits of clip_level; 0x7F800001 (above every |y| that is no NaN) for +inf
+    uint32_t stereo;                 // two channels, both selected, an even stream_stride: the form with 16-byte accesses
+    uint32_t lookahead, hold;        // L, H <= the header's maxima
+    uint32_t advance;                // A: taps - 1 where the detector interpolates, else 0
+    float ceiling;                   // > 0, finite
+    int factor;                      // of the detector: 4, 2 or 0 (the sample's magnitude)
+    float taps[36];                  // PeakSeriesParams::taps
+};
+// the detector and the sweep of one group, queued on s in that order
+hipError_t launch_limit(const LimitParams &p, hipStream_t s);
 // f32 corpus -> delivery PCM (ss_batch_download_pcm): samples [0, n_samples) of the slots from `first` on become `format` at out,
 // frames at or behind a stream's own length the format's zero.  out holds n_samples rounded up to a multiple of 4 samples.
 struct PcmOutParams {

@@ -11,57 +11,21 @@
 // registers and forms every branch of every frame as one chain of plain v_fma_f32, oldest tap first.  Value and position travel
 // together as (float bits << 32 | ~frame): every captured value is positive, so the integer order is the float order with ties to
 // the lowest frame, and zero reads "0 at 0xFFFFFFFF".  The lanes' words meet in LDS (ds_max_u64); global memory sees plain 16-byte
-// stores only.
+// stores only.  The tile copy and the interpolator (peak_load_tile, peak_frame_max) live in ss_peak_dev.h, which the limiter's
+// detector shares.
 #include "ss_kernels.h"
+#include "ss_peak_dev.h"
 
 namespace ssk {
 
 namespace {
 
-constexpr uint32_t kPeakThreads = 256;
 constexpr int kPeakRun = 25;                // frames a lane takes at a time: odd, so the lanes of a wave spread over the LDS banks
 constexpr uint32_t kPeakTileFloats = 8192;  // floats of one tile's own frames at most (32 KB of LDS)
 
 __device__ __forceinline__ unsigned long long peak_key(float v, uint32_t frame)
 {
     return (unsigned long long)__float_as_uint(v) << 32 | (0xFFFFFFFFu - frame);
-}
-
-// the tile's floats from the corpus into LDS: sh[i] = corpus[first + i] for lo <= first + i < hi (the stream's own floats that
-// the tile reads), zero elsewhere; `first` may lie in front of lo (history in front of frame 0) and is a multiple of four floats
-__device__ __forceinline__ void peak_load_tile(float *sh, const float *corpus, long long first, long long lo, long long hi, uint32_t n4)
-{
-    for (uint32_t v = threadIdx.x; v < n4; v += kPeakThreads) {
-        const long long g = first + 4ll * v;
-        float4 x;
-        if (g >= lo && g + 4 <= hi) {
-            x = *reinterpret_cast<const float4 *>(corpus + g);
-        } else {
-            x.x = (g >= lo && g < hi) ? corpus[g] : 0.f;
-            x.y = (g + 1 >= lo && g + 1 < hi) ? corpus[g + 1] : 0.f;
-            x.z = (g + 2 >= lo && g + 2 < hi) ? corpus[g + 2] : 0.f;
-            x.w = (g + 3 >= lo && g + 3 < hi) ? corpus[g + 3] : 0.f;
-        }
-        *reinterpret_cast<float4 *>(sh + 4u * v) = x;
-    }
-}
-
-// max over the branches of one frame, the sample itself (branch 0) included: win[0 .. NT - 1] are the frames n - (NT - 1) .. n,
-// every interpolated branch one chain of fused multiply-adds from the oldest tap to the newest.  fmaxf is maxNum: a NaN branch
-// leaves the others standing, and only a frame whose branches are all NaN reads NaN.
-template <int NT, int NB>
-__device__ __forceinline__ float peak_frame_max(const float (&tap)[NB ? NB : 1][NT ? NT : 1], const float *win)
-{
-    constexpr int H = NT ? NT - 1 : 0;
-    float v = fabsf(win[H]);
-#pragma unroll
-    for (int f = 0; f < NB; f++) {
-        float y = 0.f;
-#pragma unroll
-        for (int d = NT - 1; d >= 0; d--) y = __builtin_fmaf(tap[f][d], win[H - d], y);
-        v = fmaxf(v, fabsf(y));
-    }
-    return v;
 }
 
 }  // namespace
