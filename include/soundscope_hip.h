@@ -883,6 +883,64 @@ int ss_batch_limit_plan(const ss_batch *b, const ss_limit_config *cfg, uint32_t 
 /* streams [n_streams] and channels [stream][channel]; either may be NULL; waits */
 int ss_batch_download_limit_stats(ss_batch *b, ss_limit_stream *streams, size_t cap_streams,
                                   ss_gain_channel *channels, size_t cap_records);
+/* Batch resampler: sample-rate conversion of the resident corpus by a rational factor L / M, one batch into another — a centred
+ * Kaiser-windowed-sinc polyphase FIR in f32.  Not in the reference.  Every output sample is ONE chain of fused multiply-adds in a
+ * fixed order, so its bits do not depend on tile, slot, batch size or neighbouring streams; ss_resample_host is that chain with
+ * libm's fmaf — the definition in bits — and needs no device.
+ *
+ * Plan rule (ss_resample_plan_make; all in f64, each operation as written):
+ *   A = attenuation_db, 0 meaning 100; passband, 0 meaning 20000.0 / 22050.0;
+ *   g = gcd(in_rate, out_rate), up = L = out_rate / g, down = M = in_rate / g;
+ *   cutoff = fc = 0.5 * min(1.0, (double)L / (double)M)                       cycles per INPUT sample;
+ *   delta = 2.0 * (1.0 - passband) * fc                                        the transition width: the response is flat up to
+ *       passband x the lower Nyquist and stopped from (2 - passband) x it, so aliasing falls into the transition band only;
+ *   beta = 0.1102 * (A - 8.7);
+ *   taps = T = ceil((A - 7.95) / (14.36 * delta)), rounded up to a multiple of 4.
+ *   Equal rates, a zero rate, A outside [40, 140], passband outside [0.5, 0.99], a NaN, out == NULL: SS_ERR_INVALID_ARG;
+ *   L * T > SS_RESAMPLE_TAPS_MAX (24576 floats, 96 KB: the table and a tile share the 160 KiB of a CU's LDS): SS_ERR_UNSUPPORTED.
+ * Taps (ss_resample_taps; [L][T] f32, computed in f64): tap k of phase p is h(t) at t = j / L input samples, j = (k - T/2 + 1) * L - p:
+ *   h(t) = 2 fc * sinc(2 fc t) * I0(beta * sqrt(max(0, 1 - (2 t / T)^2))) / I0(beta),    sinc(x) = sin(pi x) / (pi x), 1 at 0.
+ *   Where L >= M (2 fc = 1) the sinc is taken on the integer j: exactly 0 where j is a non-zero multiple of L, exactly 1 at j = 0 —
+ *   PHASE 0 OF AN UPSAMPLING TABLE IS THE UNIT IMPULSE IN BITS.  Each phase is scaled to sum 1 in f64, then rounded to f32.
+ *   cap_floats < L * T: SS_ERR_CAPACITY.
+ * Output n of channel c of a stream of F_in frames x:  q = n * M (u64), base = q / L, p = q % L,
+ *   acc = 0;  for k = 0 .. T - 1 in that order:  acc = fmaf(taps[p][k], x[base - T/2 + 1 + k][c], acc);   x outside [0, F_in) is 0.
+ *   The filter is centred: no latency is added.  Non-finite samples follow IEEE through the chain; an output whose T-frame window
+ *   holds none is unaffected.
+ * Length (ss_resample_length): the number of n with n * M < F_in * L, ceil(F_in * L / M); 0 for 0.
+ * ss_resample_host writes outputs [first_out, first_out + n_out) as [n_out][channels]; taps is what ss_resample_taps gave.  A null
+ *   pointer (in: with frames_in > 0; out: with n_out > 0), channels == 0, first_out + n_out beyond the length: SS_ERR_INVALID_ARG.
+ *
+ * ss_batch_resample converts every stream of src, each at its own length (ss_batch_set_lengths respected), into the same slot of
+ * dst and gives dst the lengths ss_resample_length(F_s), exactly as ss_batch_set_lengths(dst, ...) would (a stream of 0 frames
+ * stays 0).  Floats of a dst slot at or behind the output length keep their bytes; src is read only, and no float outside [0, F_s)
+ * of a stream's own slot is read.  Checked before anything is queued or changed: a null pointer, src == dst, different devices,
+ * channel or stream counts, src's rate != in_rate, dst's rate != out_rate, reserved != 0, a plan that ss_resample_plan_make would
+ * not have made from its own rates, attenuation_db and passband: SS_ERR_INVALID_ARG; dst's frames_per_stream below the longest
+ * output: SS_ERR_CAPACITY.  The kernel is queued on dst's stream behind what src's stream holds, and src's stream then waits for
+ * it, so work queued on src later (ss_batch_apply_gain ...) cannot overtake the read; the host waits for what ss_batch_set_lengths
+ * on dst waits for (dst's stream), and the first call of dst with a plan other than its last also copies that plan's table to the
+ * device before it returns: nothing else.  Two calls leave the same bytes.  There is no statistics record: dst is a batch, and its
+ * peak series, signal scan and pass are the statistics.  The taps table of the last plan stays on the device with dst.
+ * ss_batch_resample_plan reports how a call would cut the streams: a workgroup converts tile_out_frames = R * L outputs from
+ * tile_in_frames = R * M inputs and their taps - 1 frames of surroundings. */
+#define SS_RESAMPLE_TAPS_MAX 24576
+typedef struct ss_resample_plan {
+    uint32_t in_rate, out_rate;
+    uint32_t up, down;            /* L = out_rate / g, M = in_rate / g, g = gcd */
+    uint32_t taps;                /* T: taps per phase, a multiple of 4 */
+    uint32_t reserved;            /* 0 */
+    double   attenuation_db;      /* A */
+    double   passband;            /* fraction of the lower Nyquist that is flat */
+    double   beta, cutoff;        /* Kaiser beta; fc in cycles per INPUT sample */
+} ss_resample_plan;               /* 56 bytes */
+int ss_resample_plan_make(uint32_t in_rate, uint32_t out_rate, double attenuation_db, double passband, ss_resample_plan *out);
+int ss_resample_taps(const ss_resample_plan *p, float *taps, size_t cap_floats);
+uint64_t ss_resample_length(const ss_resample_plan *p, uint64_t frames_in);
+int ss_resample_host(const ss_resample_plan *p, const float *taps, const float *in, uint64_t frames_in, uint32_t channels,
+                     uint64_t first_out, uint64_t n_out, float *out);
+int ss_batch_resample(ss_batch *src, ss_batch *dst, const ss_resample_plan *p);
+int ss_batch_resample_plan(const ss_batch *src, const ss_resample_plan *p, uint32_t *tile_out_frames, uint32_t *tile_in_frames);
 /* corpus histograms summed over this batch's streams: 1000 block-energy bins
  * followed by 1000 short-term bins (u64 each).  `_device` copies them into a
  * caller-owned device buffer (e.g. the send buffer of an RCCL all-reduce). */

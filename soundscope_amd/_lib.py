@@ -68,6 +68,7 @@ SYMBOLS = [
     "ss_normalisation_gain", "ss_gain_envelope", "ss_batch_apply_gain", "ss_batch_apply_gain_plan", "ss_batch_download_gain_stats",
     "ss_batch_download_pcm",
     "ss_limit_curve", "ss_batch_limit", "ss_batch_limit_plan", "ss_batch_download_limit_stats",
+    "ss_resample_plan_make", "ss_resample_taps", "ss_resample_length", "ss_resample_host", "ss_batch_resample", "ss_batch_resample_plan",
     "ss_td_streaming_plan", "ss_session_last_tick_forms",
 ]
 
@@ -87,6 +88,7 @@ SS_GAIN_LIMITED_PEAK, SS_GAIN_LIMITED_MAX, SS_GAIN_LIMITED_MIN, SS_GAIN_UNMEASUR
 SS_DITHER_NONE, SS_DITHER_TPDF = 0, 1
 SS_LIMIT_SAMPLE_PEAK, SS_LIMIT_TRUE_PEAK = 0, 1
 SS_LIMIT_LOOKAHEAD_MAX, SS_LIMIT_HOLD_MAX = 2048, 8192
+SS_RESAMPLE_TAPS_MAX = 24576
 SS_GAIN_FIXED, SS_GAIN_REFERENCE = 0, 1
 SS_COMM_RCCL, SS_COMM_HOST_TCP = 0, 1
 SS_TP_ARITH_F16X3, SS_TP_ARITH_F32 = 0, 1
@@ -252,6 +254,12 @@ class LimitConfig(C.Structure):            # ss_limit_config
 class LimitStream(C.Structure):            # ss_limit_stream
     _fields_ = [("n_limited", C.c_uint64), ("first_limited", C.c_uint64), ("min_sum", C.c_uint64), ("touched", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class ResamplePlan(C.Structure):           # ss_resample_plan
+    _fields_ = [("in_rate", C.c_uint32), ("out_rate", C.c_uint32), ("up", C.c_uint32), ("down", C.c_uint32), ("taps", C.c_uint32),
+                ("reserved", C.c_uint32), ("attenuation_db", C.c_double), ("passband", C.c_double), ("beta", C.c_double),
+                ("cutoff", C.c_double)]
 
 
 class PairSums(C.Structure):               # ss_pair_sums
@@ -498,6 +506,12 @@ def _bind(lib):
         "ss_batch_limit": (C.c_int, [vp, C.POINTER(LimitItem), C.c_uint32, C.POINTER(LimitConfig)]),
         "ss_batch_limit_plan": (C.c_int, [vp, C.POINTER(LimitConfig), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p]),
         "ss_batch_download_limit_stats": (C.c_int, [vp, C.POINTER(LimitStream), C.c_size_t, C.POINTER(GainChannel), C.c_size_t]),
+        "ss_resample_plan_make": (C.c_int, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(ResamplePlan)]),
+        "ss_resample_taps": (C.c_int, [C.POINTER(ResamplePlan), f32p, C.c_size_t]),
+        "ss_resample_length": (C.c_uint64, [C.POINTER(ResamplePlan), C.c_uint64]),
+        "ss_resample_host": (C.c_int, [C.POINTER(ResamplePlan), f32p, f32p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, f32p]),
+        "ss_batch_resample": (C.c_int, [vp, vp, C.POINTER(ResamplePlan)]),
+        "ss_batch_resample_plan": (C.c_int, [vp, C.POINTER(ResamplePlan), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "ss_td_streaming_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint64, C.POINTER(StreamingPlan)]),
         "ss_session_last_tick_forms": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     }

@@ -126,6 +126,44 @@ def limit_curve(level, gain, ceiling, lookahead, hold, advance=0):
     return r_q, s, c
 
 
+# batch resampler (ss_resample_plan): the plan rule, the table, the output length and the reference chain are host arithmetic
+def resample_plan(in_rate, out_rate, attenuation_db=0.0, passband=0.0):
+    """ss_resample_plan_make: the L.ResamplePlan of a conversion in_rate -> out_rate (up = L, down = M, taps = T per phase, beta,
+    cutoff); attenuation_db 0 means 100, passband 0 means 20000 / 22050 of the lower Nyquist."""
+    plan = L.ResamplePlan()
+    _check(L.lib().ss_resample_plan_make(int(in_rate), int(out_rate), float(attenuation_db), float(passband), C.byref(plan)))
+    return plan
+
+
+def resample_taps(plan):
+    """ss_resample_taps: the plan's polyphase table [L][T] f32; tap k of phase p weighs input frame base - T/2 + 1 + k."""
+    out = np.zeros((int(plan.up), int(plan.taps)), np.float32)
+    _check(L.lib().ss_resample_taps(C.byref(plan), out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+    return out
+
+
+def resample_length(plan, frames_in):
+    """ss_resample_length: the outputs of a stream of frames_in frames, ceil(frames_in * L / M)."""
+    return int(L.lib().ss_resample_length(C.byref(plan), int(frames_in)))
+
+
+def resample_host(plan, x, channels=1, first_out=0, n_out=None, taps=None):
+    """ss_resample_host: outputs [first_out, first_out + n_out) of ONE stream x ([frames][channels] f32, or flat) on the host, as
+    [n_out][channels] f32 — the definition of Batch.resample_into in bits: one fmaf chain per output over the phase's taps in order."""
+    a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    ch = int(channels)
+    frames = a.size // ch
+    assert frames * ch == a.size
+    t = resample_taps(plan) if taps is None else np.ascontiguousarray(taps, dtype=np.float32)
+    if n_out is None:
+        n_out = resample_length(plan, frames) - int(first_out)
+    out = np.zeros((int(n_out), ch), np.float32)
+    f32p = C.POINTER(C.c_float)
+    _check(L.lib().ss_resample_host(C.byref(plan), t.ctypes.data_as(f32p), a.ctypes.data_as(f32p), frames, ch, int(first_out), int(n_out),
+                                    out.ctypes.data_as(f32p)))
+    return out
+
+
 def normalisation_gain(loudness_lufs, peak_linear, target_lufs, max_true_peak_dbtp=np.inf, max_gain_db=np.inf, min_gain_db=-np.inf):
     """ss_normalisation_gain over arrays: (gain_db f64, gain f32, limited_by u32) for every (loudness, linear peak).  The law: an
     unmeasured loudness (NaN, +-inf) gives 0 dB and SS_GAIN_UNMEASURED; else target - loudness, cut to the headroom under the
@@ -737,6 +775,34 @@ class Batch:
         _check(L.lib().ss_batch_download_limit_stats(self._h, streams.ctypes.data_as(C.POINTER(L.LimitStream)), streams.size,
                                                      channels.ctypes.data_as(C.POINTER(L.GainChannel)), channels.size))
         return streams, channels
+
+    # -- batch resampler: every stream of this batch converted to another rate, into the same slot of another batch
+    def resample_into(self, dst, plan):
+        """Queue the conversion of every stream, each at its own length, into the same slot of `dst` (a batch at plan.out_rate with
+        the same channels and streams, and a slot that holds the longest output): dst gets the lengths resample_length(F_s) as
+        dst.set_lengths() would give them, floats behind them keep their bytes, and every output equals resample_host in bits.
+        Queued on dst's stream behind what this batch's stream holds; work queued on this batch later runs behind the read."""
+        _check(L.lib().ss_batch_resample(self._h, dst._h, C.byref(plan)))
+        dst._ragged = True
+
+    def resample_tiles(self, plan):
+        """(tile_out_frames, tile_in_frames): the outputs one workgroup of resample_into converts and the input frames they span."""
+        o, i = C.c_uint32(), C.c_uint32()
+        _check(L.lib().ss_batch_resample_plan(self._h, C.byref(plan), C.byref(o), C.byref(i)))
+        return o.value, i.value
+
+    def resample(self, out_rate, attenuation_db=0.0, passband=0.0, **batch_kwargs):
+        """A new Batch at out_rate holding this batch's streams converted (resample_plan, resample_into): this batch's other
+        settings unless batch_kwargs (Batch's keywords) says otherwise, and a slot as long as the longest output needs."""
+        cfg = self.cfg
+        plan = resample_plan(int(cfg.sample_rate), out_rate, attenuation_db, passband)
+        longest = max(resample_length(plan, self.stream_shape(s).frames) for s in range(int(cfg.n_streams)))
+        kw = dict(fft_n=int(cfg.fft_n), hop_frames=int(cfg.hop_frames), flags=int(cfg.flags), true_peak_factor=int(cfg.true_peak_factor),
+                  waveform_window=float(cfg.waveform_window), spectrum_columns=int(cfg.spectrum_columns))
+        kw.update(batch_kwargs)
+        dst = Batch(int(out_rate), int(cfg.channels), int(cfg.n_streams), max(1, longest), **kw)
+        self.resample_into(dst, plan)
+        return dst
 
     def normalise(self, target_lufs, max_true_peak_dbtp=float("inf"), max_gain_db=float("inf"), min_gain_db=float("-inf"), album=False,
                   limiter=None):

@@ -197,6 +197,17 @@ struct Limit {
     DevBuf<uint32_t> scratch;
 };
 
+// resampler (ss_batch_resample), held by the DESTINATION batch: the taps table of the last plan on the device and the two events
+// that order the call between the batches' streams — all of it made at the batch's first call, so a batch that never asks holds
+// none of it
+struct Resample {
+    bool have = false;                          // `taps` holds the table of `plan`
+    ss_resample_plan plan{};
+    DevBuf<float> taps;                         // [L][T]
+    hipEvent_t ev_src = nullptr, ev_done = nullptr;
+    ~Resample() { for (hipEvent_t e : {ev_src, ev_done}) if (e) (void)hipEventDestroy(e); }
+};
+
 // spectrogram (ss_batch_spectrogram): all of it allocated at the batch's first call and grown by a larger view, so a batch that
 // never asks holds none of it
 struct Spectrogram {
@@ -257,6 +268,7 @@ struct ss_batch {
     Pairs pair;
     Gain gain;
     Limit limit;
+    Resample resample;
     Spectrogram spectrogram;
     Overlap ov;
     bool corpus_reduced = false;      // this pass's corpus histograms already hold the all-reduced sums
@@ -2272,6 +2284,80 @@ int ss_batch_download_limit_stats(ss_batch *b, ss_limit_stream *streams, size_t 
     if (streams) HIPCHK(hipMemcpyAsync(streams, lm.table.p, (size_t)n * sizeof(ss_limit_stream), hipMemcpyDeviceToHost, b->stream));
     if (channels) HIPCHK(hipMemcpyAsync(channels, lm.table.p + (size_t)n * sizeof(ss_limit_stream), (size_t)records * sizeof(ss_gain_channel), hipMemcpyDeviceToHost, b->stream));
     return ss_batch_sync(b);
+}
+
+// ---- batch resampler: one corpus converted by L / M into another; the host arithmetic is ss_resample_host.cpp's ---------------------------
+// what both entry points ask of a plan: it is the one ss_resample_plan_make makes from the plan's own rates, A and passband
+static bool resample_plan_ok(const ss_resample_plan *p)
+{
+    ss_resample_plan q;
+    if (!p || p->reserved || ss_resample_plan_make(p->in_rate, p->out_rate, p->attenuation_db, p->passband, &q) != SS_OK) return false;
+    return q.up == p->up && q.down == p->down && q.taps == p->taps && q.beta == p->beta && q.cutoff == p->cutoff;
+}
+
+static ssk::ResamplePlan batch_resample_plan(const ss_batch *src, const ss_resample_plan *p)
+{
+    uint32_t form = ssk::kResampleAuto;
+#ifdef SS_TUNING
+    if (const char *e = std::getenv("SS_RESAMPLE_FORM")) form = (uint32_t)std::atoi(e);     // 1 register taps, 2 LDS taps, 3 direct
+#endif
+    return ssk::plan_resample(p->up, p->down, p->taps, src->cfg.channels, form);
+}
+
+int ss_batch_resample_plan(const ss_batch *src, const ss_resample_plan *p, uint32_t *tile_out_frames, uint32_t *tile_in_frames)
+{
+    if (!src || !resample_plan_ok(p) || src->cfg.sample_rate != p->in_rate) return SS_ERR_INVALID_ARG;
+    const ssk::ResamplePlan plan = batch_resample_plan(src, p);
+    if (tile_out_frames) *tile_out_frames = plan.tile_periods * p->up;
+    if (tile_in_frames) *tile_in_frames = plan.tile_periods * p->down;
+    return SS_OK;
+}
+
+int ss_batch_resample(ss_batch *src, ss_batch *dst, const ss_resample_plan *p)
+{
+    SS_ON_DEVICE(dst);
+    if (!src || !dst || src == dst || !resample_plan_ok(p)) return SS_ERR_INVALID_ARG;
+    const ss_batch_config &sc = src->cfg, &dc = dst->cfg;
+    if (src->device != dst->device || sc.channels != dc.channels || sc.n_streams != dc.n_streams || sc.sample_rate != p->in_rate ||
+        dc.sample_rate != p->out_rate)
+        return SS_ERR_INVALID_ARG;
+    std::vector<uint64_t> lengths(sc.n_streams);
+    uint64_t longest = 0;
+    for (uint32_t s = 0; s < sc.n_streams; s++) {
+        lengths[s] = ss_resample_length(p, src->frames_of(s));
+        if (lengths[s] > longest) longest = lengths[s];
+    }
+    if (longest > dc.frames_per_stream) return SS_ERR_CAPACITY;
+    const ssk::ResamplePlan plan = batch_resample_plan(src, p);
+    const uint64_t tile_out = (uint64_t)plan.tile_periods * p->up, tiles_cap = (longest + tile_out - 1) / tile_out;
+    if (tiles_cap * sc.n_streams > 0x7FFFFFFFull) return SS_ERR_UNSUPPORTED;
+    Resample &rs = dst->resample;
+    if (!rs.ev_src) HIPCHK(hipEventCreateWithFlags(&rs.ev_src, hipEventDisableTiming));
+    if (!rs.ev_done) HIPCHK(hipEventCreateWithFlags(&rs.ev_done, hipEventDisableTiming));
+    if (!rs.have || std::memcmp(&rs.plan, p, sizeof *p) != 0) {                 // another plan than the table's: its first call copies the table up
+        std::vector<float> table((size_t)p->up * p->taps);
+        const int rc = ss_resample_taps(p, table.data(), table.size());
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(dst->stream));                              // (an earlier call's kernel may still read the old table)
+        rs.have = false;
+        HIPCHK(rs.taps.upload(table));
+        rs.plan = *p; rs.have = true;
+    }
+    // ---- the first change of dst: a failure above has left it as it was
+    const int rc = ss_batch_set_lengths(dst, lengths.data(), dc.n_streams);
+    if (rc) return rc;
+    if (!tiles_cap) return SS_OK;                               // (every stream is empty)
+    ssk::ResampleParams k{};
+    k.src = src->pcm.p; k.dst = dst->pcm.p; k.taps = rs.taps.p;
+    k.src_stride = sc.frames_per_stream * sc.channels; k.dst_stride = dc.frames_per_stream * dc.channels;
+    k.n_frames = sc.frames_per_stream; k.frames_of = src->ragged_ptr(src->ragged.frames_d);
+    k.n_streams = sc.n_streams; k.channels = sc.channels; k.up = p->up; k.down = p->down; k.n_taps = p->taps;
+    k.tiles_cap = (uint32_t)tiles_cap; k.plan = plan;
+    // dst's stream reads src behind what src's stream holds; src's stream goes on behind the read
+    HIPCHK(Overlap::order(rs.ev_src, src->stream, dst->stream));
+    HIPCHK(ssk::launch_resample(k, dst->stream));
+    HIPCHK(Overlap::order(rs.ev_done, dst->stream, src->stream));
+    return SS_OK;
 }
 
 int ss_batch_download_pcm(ss_batch *b, uint32_t first, uint32_t count, void *pcm, size_t cap_bytes, int format, const ss_pcm_dither *dither)

@@ -9,6 +9,7 @@
 //   ss_meter_bank.cpp   meter banks: many live meters advanced together
 //   ss_comm.cpp         the all-reduce of the corpus histograms (RCCL opened at run time; does not include this header)
 //   ss_tables.cpp       the host-side design of the constant tables (includes ss_tables.h only)
+//   ss_resample_host.cpp  the resampler's plan rule, table and reference chain (includes the public header only)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -589,6 +589,36 @@ struct LimitParams {
 };
 // the detector and the sweep of one group, queued on s in that order
 hipError_t launch_limit(const LimitParams &p, hipStream_t s);
+// Resampler (ss_batch_resample; ss_resample.hip): every stream of one corpus converted by L / M into the same slot of another.
+// One workgroup per (stream, tile of tile_periods * L outputs); output n0 + i of a tile reads phase (i M) % L at the tile's input
+// frame (i M) / L, so the tile's input run is tile_periods * M frames and taps - 1 frames of surroundings.  Three forms, equal in
+// bits (each output is the header's one chain):
+//   kResampleRegTaps   lane <-> output residue n mod L: its phase's taps stay in registers while it walks n, n + L, ...
+//   kResampleLdsTaps   the table in LDS at an odd row stride beside the tile, lane <-> output: any L and T that fit
+//   kResampleDirect    taps and samples from global memory, guarded: whatever fits neither
+enum : uint32_t { kResampleAuto = 0, kResampleRegTaps = 1, kResampleLdsTaps = 2, kResampleDirect = 3 };
+static_assert(sizeof(ss_resample_plan) == 56, "ss_resample_plan");
+struct ResamplePlan {
+    uint32_t form;                   // kResampleRegTaps ...
+    uint32_t tile_periods;           // R: a tile is R * L outputs from R * M inputs
+    uint32_t groups, threads;        // register form: residue groups G (lane = g * L + r), and the workgroup's size
+    uint32_t lds_bytes;
+};
+// form: kResampleAuto, or the form to take where it can run the plan (else the next one down the list above)
+ResamplePlan plan_resample(uint32_t up, uint32_t down, uint32_t taps, uint32_t channels, uint32_t form);
+struct ResampleParams {
+    const float *src;                // [stream][frame][channels] f32, 16-byte aligned; read only
+    float *dst;                      // the same layout at dst_stride
+    const float *taps;               // [L][T] f32, 16-byte aligned
+    uint64_t src_stride, dst_stride; // floats between streams
+    uint64_t n_frames;               // frames of a source slot
+    const uint64_t *frames_of;       // ragged sources: each stream's own frames (nullable = n_frames for all)
+    uint32_t n_streams, channels;
+    uint32_t up, down, n_taps;       // L, M, T
+    uint32_t tiles_cap;              // tiles of the longest output
+    ResamplePlan plan;
+};
+hipError_t launch_resample(const ResampleParams &p, hipStream_t s);
 // f32 corpus -> delivery PCM (ss_batch_download_pcm): samples [0, n_samples) of the slots from `first` on become `format` at out,
 // frames at or behind a stream's own length the format's zero.  out holds n_samples rounded up to a multiple of 4 samples.
 struct PcmOutParams {

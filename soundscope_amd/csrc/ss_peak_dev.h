@@ -11,10 +11,12 @@ namespace {
 constexpr uint32_t kPeakThreads = 256;
 
 // the tile's floats from the corpus into LDS: sh[i] = corpus[first + i] for lo <= first + i < hi (the stream's own floats that
-// the tile reads), zero elsewhere; `first` may lie in front of lo (history in front of frame 0) and is a multiple of four floats
-__device__ __forceinline__ void peak_load_tile(float *sh, const float *corpus, long long first, long long lo, long long hi, uint32_t n4)
+// the tile reads), zero elsewhere; `first` may lie in front of lo (history in front of frame 0) and is a multiple of four floats;
+// threads: the workgroup's size (the resampler's differs)
+__device__ __forceinline__ void peak_load_tile(float *sh, const float *corpus, long long first, long long lo, long long hi, uint32_t n4,
+                                               uint32_t threads = kPeakThreads)
 {
-    for (uint32_t v = threadIdx.x; v < n4; v += kPeakThreads) {
+    for (uint32_t v = threadIdx.x; v < n4; v += threads) {
         const long long g = first + 4ll * v;
         float4 x;
         if (g >= lo && g + 4 <= hi) {
